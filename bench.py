@@ -13,15 +13,22 @@ CHILD process (before any GPU call; never an exec), forwards rank 0's one JSON l
 
 N=1 (default line): BASELINE config 2 (BASELINE.json configs[1]) — Split-MNIST task 0 shape, S=3 hyper-samples, F=10, C=10,
 M=100, D=784, B=512, synthetic data resident in HBM.  One step = zero_grad + VARGP.loss + combine + backward
-+ (N>1: one RCCL all-reduce) + Yogi step, exactly as experiments/vargp.py:29-37 does it.  The same line carries a
-`secondary` object: short runs of the other BASELINE configs (Cfg3 Permuted-MNIST tasks 0 / 1 / 4 / 9, Split-MNIST task 1,
-Cfg4's 64 samples on one GPU = the base of the multi-GPU curve, Cfg5 stress sweep), each with ms_per_step, roofline.frac
-and elbo_rtol_vs_cpu (`--no-secondary` skips them).
++ (N>1: one RCCL all-reduce) + Yogi step, exactly as experiments/vargp.py:29-37 does it.
+A plain run sets up, warms up, times exactly --steps steps and prints the line (metric, value, unit, ms_per_step, ...).
+`--dump-outputs DIR` then also writes what the timed step computes from the seeded start state (its loss terms, the gradients
+and the updated parameters) as DIR/<name>.npy: after the timed steps the start state is restored and the step replayed once,
+so that two runs, or two builds, can be compared output for output (the last of many training steps carries the run-to-run
+rounding of the kernels' float atomics, amplified by the optimiser).
+`--full` adds everything else: the ELBO check against the CPU oracle (elbo_rtol_vs_cpu), the in-step kernel time line, the
+re-launch timings behind `roofline`, the CPU baseline, the exchange timings of N>1 and a `secondary` object: short runs of
+the other BASELINE configs (Cfg3 Permuted-MNIST tasks 0 / 1 / 4 / 9, Split-MNIST task 1, Cfg4's 64 samples on one GPU = the
+base of the multi-GPU curve, Cfg5 stress sweep), each with ms_per_step, roofline.frac and elbo_rtol_vs_cpu (`--no-secondary`
+skips them).
 N>1 (default, `scaling: "weak"`): every rank evaluates the metric's own config-2 ELBO + gradient on ITS OWN 3 hyper-samples
 (same minibatch, rank-sliced global noise), ONE exchange sums the flat [grads | kl_u | nll] buffer, every rank takes the same Yogi
 step: an optimizer step over 3N hyper-samples.  The unit of the N=1 line is one ELBO + gradient over 3 hyper-samples x 10 classes;
 an N-rank step processes N of them, so `value` = N x optimizer steps / s (`optimizer_steps_per_s` is in the line as well), directly
-comparable with the N=1 line.  The same line's `secondary` carries BASELINE config 4 as north_star states it -- a FIXED total of 64
+comparable with the N=1 line.  With --full the line's `secondary` carries BASELINE config 4 as north_star states it -- a FIXED total of 64
 hyper-samples x 10 classes split over the N ranks (`smnist_s64`, STRONG scaling, uneven shards if 64 % N != 0; value = global
 steps / s, base = `secondary.smnist_s64` of the N=1 line) -- and config 2's 30 (sample, class) problems class-sharded over the
 ranks (`smnist_pairs`).  `--scaling strong` makes config 4 the headline of the N>1 line instead.
@@ -85,11 +92,31 @@ def make_model(device, seed=0):
     return gp, xall[:B].to(device), yall[:B].to(device)
 
 
-def stress(args, device, cpu=True, n=None):
+def dump_outputs(out_dir, arrays, budget_bytes=64 << 20, sample=1 << 20):
+    """Write {name: tensor} as out_dir/<name>.npy (float32 / float64).  Should they exceed `budget_bytes` in all, every array
+    larger than `sample` elements is replaced by a fixed, seeded sample of that many of its elements (flattened, indices
+    sorted; the same indices on every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for k, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[k] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    if sum(a.nbytes for a in host.values()) > budget_bytes:
+        for k, a in host.items():
+            if a.size > sample:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, sample, replace=False))
+                host[k] = a.reshape(-1)[idx]
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+
+
+def stress(args, device, cpu=True, n=None, dump=None):
     """BASELINE config 5: N=1e6, D=784, M=2048, C=10, S=1.  One ELBO evaluation WITH its gradient over all N points,
     K_uf built tile by tile in HBM (VARGP.elbo_tiled -> vargp_elbo_tn_begin/_tile/_end: kernel matrix of the inducing
     points and its n=2048 factorisation once, forward + partial backward per tile), then the forward-only predictive sweep.
-    `value` = data points per second of the ELBO+gradient sweep.  -> the result dict."""
+    `value` = data points per second of the ELBO+gradient sweep.  The check against the CPU oracle runs with --full only;
+    dump: directory for the sweep's outputs (its ELBO terms and gradients).  -> the result dict."""
     from vargp_amd import _lib, ops
     from vargp_amd.kernels import RBFKernel
     from vargp_amd.likelihoods import MulticlassSoftmax
@@ -101,7 +128,7 @@ def stress(args, device, cpu=True, n=None):
     z = torch.stack([x[c * m:(c + 1) * m] + 0.01 * torch.randn(m, D, device=device) for c in range(C)])
     gp = VARGP(z.cpu(), RBFKernel(D), MulticlassSoftmax(n_f=F_), n_var_samples=1).to(device)
     ops.set_cholesky_error_mode('defer')
-    rtol, rtol_on = stress_elbo_check(gp, x, y)
+    rtol, rtol_on = stress_elbo_check(gp, x, y) if args.full else (None, None)
     # ---- ELBO + gradient sweep ------------------------------------------------------------------------------------
     gp.elbo_tiled(x[:2 * tile], y[:2 * tile], tile, beta=BETA)                      # warm-up (two tiles)
     torch.cuda.synchronize()
@@ -113,6 +140,9 @@ def stress(args, device, cpu=True, n=None):
     dt = time.perf_counter() - t0
     _lib.prof_enable(False)
     kern_ms, kern_n = _lib.prof_read('rbf_kuf_gemm')
+    if dump:
+        dump_outputs(dump, dict({k: v.double() for k, v in zip(('kl_hypers', 'kl_u', 'nll'), out)},
+                                **{'grad.' + k: p.grad for k, p in gp.named_parameters() if p.grad is not None}))
     finite = all(torch.isfinite(v).item() for v in out) and all(bool(torch.isfinite(p.grad).all()) for p in gp.parameters())
     flops = 2.0 * C * m * tile * D
     avg_s = kern_ms / max(kern_n, 1) * 1e-3
@@ -501,11 +531,13 @@ SECONDARY = ['smnist_s64', 'smnist_s32', 'smnist_s16', 'smnist_s8', 'smnist_t1',
 
 
 def run_workload(name, args, device, world, rank, use_dist, steps, warmup, primary=True, kern_n=100):
-    """One ELBO-step workload: build the model, check it against the CPU oracle, capture, time `steps` steps, time the dominant
-    kernels.  -> result dict (rank 0) or None.  primary: the line's top-level fields incl. the CPU baseline."""
+    """One ELBO-step workload: build the model, capture, time `steps` steps; with --full also check it against the CPU oracle
+    and time the dominant kernels.  -> result dict (rank 0) or None.  primary: the line's top-level fields incl. the CPU
+    baseline (--full) and the outputs of --dump-outputs."""
     global S, M, N_PREV
     from vargp_amd import _lib, ops
     from vargp_amd.train import ElboTrainer, split_samples
+    full = args.full
     S, M, N_PREV = (WORKLOADS[name][k] for k in ('S', 'M', 'n_prev'))
     strong = bool(WORKLOADS[name].get('strong'))
     pairs = bool(WORKLOADS[name].get('pairs')) and world > 1      # (one rank: the plain Cfg2 step)
@@ -518,8 +550,8 @@ def run_workload(name, args, device, world, rank, use_dist, steps, warmup, prima
     ops.set_cholesky_error_mode('defer')
     ops.reset_linalg_errors()
     gp, x, y = make_model(device)
-    rtol, rtol_on = elbo_check(gp, x, y) if rank == 0 else (None, None)
-    p0 = snapshot(gp) if rank == 0 and primary else None     # the CPU baseline runs the same (initial) model
+    rtol, rtol_on = elbo_check(gp, x, y) if rank == 0 and full else (None, None)
+    p0 = snapshot(gp) if rank == 0 and primary and full else None     # the CPU baseline runs the same (initial) model
     shards = None
     if pairs:        # every rank builds the whole model; the trainer takes its rectangle of the (S, C) grid
         from vargp_amd.train import split_pairs
@@ -563,6 +595,8 @@ def run_workload(name, args, device, world, rank, use_dist, steps, warmup, prima
         run = trainer.step_graph
     else:
         run = lambda: trainer.step(x, y)
+    # --dump-outputs: the state the timed run starts from (seeded parameters, optimiser state, noise counter), see below
+    start = trainer._snapshot_state() if primary and args.dump_outputs else None
     # The CPU oracle (ELBO check above, cpu_baseline of the previous workload) leaves its OpenMP workers spinning for ~200 ms
     # after their last parallel region; on a box whose CPU quota they exhaust, the launching thread is starved and a short timed
     # region (30 steps = 18 ms) picks up a 20 ms stall (seen as mean = 2 x median on smnist_t1 in the default line only).  Let
@@ -598,11 +632,23 @@ def run_workload(name, args, device, world, rank, use_dist, steps, warmup, prima
     median_ms = per_step[len(per_step) // 2]
     final_loss = [v.item() for v in out]     # read now: the re-launches below include the kernel that resets the accumulators
     finite = all(v == v and abs(v) != float('inf') for v in final_loss)
-    # The exchange, measured two ways (outside the timed region): in place -- hipEvents around the collective of `n_comm` more
-    # steps (includes waiting for the slowest rank) -- and isolated -- the same collective back to back after a barrier.
+    if start is not None:
+        # What the timed step computes from the seeded inputs: the start state is restored and the timed step replayed once;
+        # the caller receives the loss terms, the gradients and the parameters the optimiser step left.  (The last of the
+        # timed steps is not reproducible: the kernels' float atomics round differently from run to run, and a few hundred
+        # optimiser steps amplify that from 1e-6 after one step to 1e-2.)  Written before anything below runs more steps.
+        trainer._restore_state(start)
+        out1 = run()
+        sync()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dict({k: v.double() for k, v in zip(('kl_hypers', 'kl_u', 'nll'), out1)},
+                                                 **{'grad.' + k: p.grad for k, p in gp.named_parameters() if p.grad is not None},
+                                                 **{'param.' + k: p for k, p in gp.named_parameters()}))
+    # The exchange, measured two ways (outside the timed region, --full): in place -- hipEvents around the collective of `n_comm`
+    # more steps (includes waiting for the slowest rank) -- and isolated -- the same collective back to back after a barrier.
     comm_us = comm_iso_us = None
     seen = ranks_seen(world, rank, device) if use_dist else [0]
-    if use_dist:
+    if use_dist and full:
         n_comm = max(5, min(steps, 50))
         trainer.comm_events = []
         for _ in range(n_comm):
@@ -628,7 +674,7 @@ def run_workload(name, args, device, world, rank, use_dist, steps, warmup, prima
     #   t0_bwdmat_gemm_kernel (P_uf = W_uf x beside the adjoint chains of the factorisations).
     block_prog = bool(gp._use_block_program(B))      # which native program runs this model (vargp.py)
     timeline = []
-    if use_graph and not block_prog and not args.no_timeline and not use_dist:       # (several ranks: the exchange sits inside the step)
+    if full and use_graph and not block_prog and not args.no_timeline and not use_dist:   # (several ranks: the exchange sits inside the step)
         try:
             # (the stamps of the LAST step of a launch are read back: of the K-step graph when that is what was timed)
             timeline = step_timeline(trainer.step_graph_k if unroll > 1 else run, 1e3 * median_ms, burst=1 if unroll > 1 else 4)
@@ -636,10 +682,11 @@ def run_workload(name, args, device, world, rank, use_dist, steps, warmup, prima
             print(f'[bench] step timeline failed ({type(e).__name__}: {e})', file=sys.stderr)
     _lib.prof_enable(False)
     _lib.prof_read('')
-    _lib.prof_remember(True)
-    trainer.step(x, y)
-    sync()
-    _lib.prof_remember(False)
+    if full:
+        _lib.prof_remember(True)
+        trainer.step(x, y)
+        sync()
+        _lib.prof_remember(False)
     kernels = {}
     # (config 2 over several ranks: this rank's part of the S x C problems -- a class range, or whole samples when world <= S)
     share = ((trainer.rect[1] - trainer.rect[0]) * (trainer.rect[3] - trainer.rect[2]) / float(S * C)) if pairs else 1.0
@@ -672,7 +719,7 @@ def run_workload(name, args, device, world, rank, use_dist, steps, warmup, prima
                       ('tn_chol_bwd3', S * C * Mt * Mt * Mt / 3.0, 'gemm_kernel gK = T^T tril(Smat T), lower triangle mirrored '
                        '(both factors lower triangular: S*C*Mt^3/3 flop)')]
     for tag, fl, desc in candidates:
-        if args.no_replay:
+        if args.no_replay or not full:
             break
         try:
             kernels[tag] = (_lib.prof_replay(tag, kern_n), fl, desc)
@@ -781,6 +828,8 @@ def run_workload(name, args, device, world, rank, use_dist, steps, warmup, prima
                                  traffic=measured_traffic(dom) if cfg2 else None,
                                  counters_from=_latest_profile('traffic')[1] if cfg2 else None,
                                  counters_commit=(_latest_profile('traffic')[0] or {}).get('commit') if cfg2 else None))
+        if not full:         # no kernel was timed on its own
+            res['roofline'] = None
         # whole step against the same roof: SURVEY 8(d) algorithmic flop of the step / wall time of the step
         step_flop = 3.0 * survey_flops_fwd(s_total if strong else (S if pairs else S * world), C, M, N_PREV, B, D, F_)
         res['step_flop'] = step_flop
@@ -789,7 +838,7 @@ def run_workload(name, args, device, world, rank, use_dist, steps, warmup, prima
         if timeline:
             res['timeline'] = [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items()} for r in timeline]
             res['timeline_sum_us'] = dict(spans=sum(r['span_us'] for r in timeline), gaps=sum(r['gap_before_us'] for r in timeline))
-        if N_PREV > 0:
+        if N_PREV > 0 and full:
             res['roofline_others'] = [dict(kernel=dsc, avg_us=us, achieved=fl / (us * 1e-6) / 1e12,
                                            frac=fl / (us * 1e-6) / 1e12 / MFMA_F32_PEAK_TFLOPS)
                                       for t, (us, fl, dsc) in kernels.items() if t != dom and us == us and fl > 0]
@@ -807,7 +856,7 @@ def run_workload(name, args, device, world, rank, use_dist, steps, warmup, prima
                 res['roofline_others'] = [dict(kernel=dsc, avg_us=us, achieved=fl / (us * 1e-6) / 1e12,
                                                frac=fl / (us * 1e-6) / 1e12 / MFMA_F32_PEAK_TFLOPS)
                                           for t, (us, fl, dsc) in kernels.items() if t not in (dom, gtag) and us == us and fl > 0]
-        if world == 1 and primary and not args.no_cpu_baseline and cfg2:
+        if world == 1 and primary and full and not args.no_cpu_baseline and cfg2:
             res['cpu_baseline'] = cpu_baseline(p0, x, y)
     # hand the workspaces back before the next workload (12 GB at Permuted-MNIST task 9)
     del trainer, run, out
@@ -908,6 +957,12 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: the ELBO check against the CPU oracle, the kernel time line and re-launch timings '
+                         '(roofline), the CPU baseline, the exchange timings and the other BASELINE configs (`secondary`)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed step computes from the seeded start state (loss terms, '
+                         'gradients, updated parameters; the start state is restored and the step replayed once) as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--eager', action='store_true', help='do not replay the step from a captured hipGraph')
     ap.add_argument('--workload', default=None, choices=sorted(WORKLOADS) + ['stress'],
@@ -933,6 +988,8 @@ def main():
     ap.add_argument('--dry-run', action='store_true',
                     help='start the ranks, create the process group, all-gather the rank ids, print a line and exit')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.gpus > 1 and 'RANK' not in os.environ and 'WORLD_SIZE' not in os.environ:
         self_launch(args.gpus)                   # does not return
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -963,7 +1020,7 @@ def main():
             dist.init_process_group('nccl', device_id=device)
 
     if args.workload == 'stress':
-        print(json.dumps(stress(args, device, cpu=not args.no_cpu_baseline)))
+        print(json.dumps(stress(args, device, cpu=args.full and not args.no_cpu_baseline, dump=args.dump_outputs)))
         return
     # (the ranks are counted right after the group is up, so that a failing run still reports who took part)
     seen0 = ranks_seen(world, rank, device) if use_dist else [0]
@@ -976,7 +1033,7 @@ def main():
                                   config=dict(workload=args.workload))))
             sys.stdout.flush()
         raise
-    if world > 1 and default_line and not args.no_secondary and os.environ.get('VARGP_BENCH_PAIRS', '1') != '0':
+    if world > 1 and default_line and args.full and not args.no_secondary and os.environ.get('VARGP_BENCH_PAIRS', '1') != '0':
         # several GPUs, besides the headline: (1) BASELINE config 4 as north_star states it -- a FIXED 64 hyper-samples x 10 classes,
         # whole samples per rank (strong scaling; skipped when it IS the headline); (2) the metric's config 2 -- 3 samples x 10
         # classes -- class-sharded over the same ranks (train.split_pairs).  Every rank runs them; a failure is reported inside the
@@ -1005,7 +1062,7 @@ def main():
             res['optimizer_steps_per_s_headline'] = res.get('optimizer_steps_per_s')
             res['value_strong_fixed_64_samples'] = sec.get('smnist_s64', {}).get('value')
             res['value_strong_cfg2_30_problems'] = sec.get('smnist_pairs', {}).get('value')
-    if rank == 0 and world == 1 and default_line and not args.no_secondary and not use_dist:
+    if rank == 0 and world == 1 and default_line and args.full and not args.no_secondary and not use_dist:
         # short, driver-timed runs of the other BASELINE configs in the same line (their own step counts are stated)
         t_start = time.perf_counter()
         sec = {}

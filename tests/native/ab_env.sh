@@ -7,7 +7,7 @@ for W in $WL; do
   for E in "$@"; do
     [ "$E" = "-" ] && E=""
     echo -n "== $W [$E] "
-    env $E python3 $R/bench.py --workload $W --no-cpu-baseline --no-secondary --no-timeline --no-replay --steps ${STEPS:-100} --warmup 10 2>&1 | tail -1 | python3 -c "
+    env $E python3 $R/bench.py --full --workload $W --no-cpu-baseline --no-secondary --no-timeline --no-replay --steps ${STEPS:-100} --warmup 10 2>&1 | tail -1 | python3 -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read())

@@ -1,6 +1,6 @@
 #!/bin/bash
 # env-knob experiments on the two GEMM-carrying launches at S = 8 (spans from the in-graph stamps)
-run() { echo "== $1"; env $1 python bench.py --workload smnist_s8 --steps 100 --warmup 20 --no-replay 2>/dev/null | python -c "
+run() { echo "== $1"; env $1 python bench.py --full --workload smnist_s8 --steps 100 --warmup 20 --no-replay 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('  steps/s %.1f  ms %.4f' % (d['value'], d['ms_per_step']))

@@ -9,7 +9,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 
-args = argparse.Namespace(eager=False, no_replay=False, no_cpu_baseline=True, comm='allreduce', stress_n=1000000)
+args = argparse.Namespace(eager=False, no_replay=False, no_cpu_baseline=True, comm='allreduce', stress_n=1000000, full=True,
+                          dump_outputs=None, unroll=0, no_timeline=False)
 dev = torch.device('cuda', 0)
 torch.cuda.set_device(0)
 seq = sys.argv[1].split(',')

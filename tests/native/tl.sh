@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 for E in "$@"; do
   [ "$E" = "-" ] && E=""
   echo "== [$E]"
-  env $E python3 $R/bench.py --no-cpu-baseline --no-secondary --steps ${STEPS:-200} --warmup 20 2>&1 | tail -1 | python3 -c "
+  env $E python3 $R/bench.py --full --no-cpu-baseline --no-secondary --steps ${STEPS:-200} --warmup 20 2>&1 | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('value %.1f  ms %.4f  rtol %.2g' % (d['value'], d['ms_per_step'], d.get('elbo_rtol_vs_cpu') or -1))
