@@ -1113,6 +1113,8 @@ extern "C" int vargp_elbo_tn_begin(const vargp_elbo_tn_desc* d, vargp_stream_t s
   int rc = check_tn(d, "elbo_tn_begin", true);
   if (rc) return rc;
   VARGP_REQUIRE(d->D > kRbfDirectD, "elbo_tn_begin: the tiled ELBO needs D > %d (MFMA distance path)", kRbfDirectD);
+  // (refused here, before any launch, and not only by the first tile: see vargp_elbo_tn_tile)
+  VARGP_REQUIRE(d->forward_only || d->C <= 16, "elbo_tn_begin: more than 16 classes is not supported by the tiled ELBO");
   hipStream_t st = as_stream(stream);
   const int S = d->S, C = d->C, M = d->M, D = d->D, B = d->B, F = d->F, nblk = d->nblk, SC = S * C;
   const bool fwd_only = d->forward_only != 0;      // predictive sweep (VARGP.predict(x, tile=)): no accumulators
