@@ -165,6 +165,23 @@ int vargp_softmax_predict(const float* mu, const float* var, const float* eps, f
                           int C, int B, vargp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Independent multi-output Gaussian likelihood (reference: GaussianLikelihood, var_gp/likelihoods.py:66-110), closed form.
+ *   mu, var [S, C, B]; obs_log_var [C]; y [C, B] with class stride ldy = B, or one target row [B] shared by every output
+ *   (ldy = 0: the reference's y.unsqueeze(0).unsqueeze(-1) broadcast).  With v = var + exp(obs_log_var[c]), r = y - mu:
+ *   nll = sum_b mean_{s,c} [ 1/2 log(2 pi v) + 1/2 r^2 / v ]                         (likelihoods.py:92-107)
+ * fwd WRITES *nll (no accumulation).  bwd, seed = d total / d nll (device, 1 float), n = S C:
+ *   gmu = -seed r / (v n),  gvar = seed (1/v - r^2/v^2) / (2 n)   [S, C, B]
+ *   g_obs_log_var[c] = exp(obs_log_var[c]) sum_{s,b} gvar[s, c, b]                   [C]
+ * and, with nll != NULL, also writes the (unseeded) value, so a training step needs one launch.  Deterministic: no float
+ * atomics, every sum in a fixed order (same inputs -> bitwise identical outputs).
+ */
+int vargp_gauss_nll_fwd(const float* mu, const float* var, const float* y, int64_t ldy, const float* obs_log_var, float* nll,
+                        int S, int C, int B, vargp_stream_t stream);
+int vargp_gauss_nll_bwd(const float* mu, const float* var, const float* y, int64_t ldy, const float* obs_log_var,
+                        const float* seed, float* gmu, float* gvar, float* g_obs_log_var, float* nll, int S, int C, int B,
+                        vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Yogi optimiser step, fused over one flat parameter buffer (reference call site:
  * experiments/vargp.py:23,37 -> torch_optimizer.Yogi; algorithm from Zaheer et al. 2018).
  * bias1/bias2 = 1 - beta^t; if `step` (device pointer to the step count t as a float) is not NULL

@@ -525,6 +525,104 @@ def elbo_tn(kernel, z, u_mean, u_tril_vec, x, y, eps_theta, eps_f, prog, z_all, 
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# GaussianLikelihood models (regression, var_gp/likelihoods.py:66-110) on either program: the program's forward with
+# ext_lik stops at the predictive moments and the KL, the closed-form Gaussian nll and its seeded gradients are one
+# launch each (csrc/gauss_lik.hip), and the program's backward takes those gradients from its likelihood buffers
+# ----------------------------------------------------------------------------------------------------------------
+_Y_DUMMY = {}
+
+
+def y_dummy(device):
+    """The block program needs a non-NULL label pointer to evaluate the KL under ext_lik; it never reads it."""
+    dev = torch.device(device)
+    t = _Y_DUMMY.get(dev)
+    if t is None:
+        t = _Y_DUMMY[dev] = torch.zeros(1, dtype=torch.int64, device=dev)
+    return t
+
+
+def lik_views(prog):
+    """prog.lik_buffers(), looked up once per program (the views stay valid for the program's lifetime)."""
+    v = getattr(prog, '_lik_views', None)
+    if v is None:
+        v = prog._lik_views = prog.lik_buffers()
+    return v
+
+
+def gauss_forward(prog, y, obs_log_var):
+    """After a program forward with ext_lik: the Gaussian nll of its moments into prog.scalars[2], completing the
+    (kl_hypers, kl_u, nll) triple.  -> (y as the kernels read it, its class stride)."""
+    mu, var, _, _ = lik_views(prog)
+    S, C, B = mu.shape
+    yt, ldy = ops.gauss_target(y, C, B)
+    ops.gauss_nll_fwd(mu, var, yt, ldy, obs_log_var, prog.scalars[2:])
+    return yt, ldy
+
+
+class _ElboGauss(Function):
+    """VARGP.loss of a GaussianLikelihood model on a native program (T0Program or TnProgram) as ONE autograd node with six
+    differentiable inputs: the five of _ElboT0 / _ElboTn and the likelihood's obs_log_var."""
+
+    @staticmethod
+    def forward(ctx, log_mean, log_logvar, z, u_mean, u_tril_vec, obs_log_var, x, y, eps_theta, prior_log_mean,
+                prior_log_logvar, map_est, prog, z_all, rk_all, eps_u):
+        args = [t.contiguous() if t is not None else None
+                for t in (log_mean, log_logvar, prior_log_mean, prior_log_logvar, z, u_mean, u_tril_vec)]
+        eps_theta = None if eps_theta is None else eps_theta.contiguous()
+        if isinstance(prog, TnProgram):
+            prog.forward(*args, z_all, rk_all, x.contiguous(), y_dummy(x.device), eps_theta, None, ext_lik=True,
+                         eps_u=None if eps_u is None else eps_u.contiguous())
+        else:
+            prog.forward(*args, x.contiguous(), None, eps_theta, None, ext_lik=True)
+        olv = obs_log_var.detach().contiguous()
+        yt, ctx.ldy = gauss_forward(prog, y, olv)
+        scal = prog.scalars.clone()
+        # the workspace belongs to this node until its backward has run or the node has died (as _ElboTn)
+        prog._gen += 1
+        prog.busy = True
+        weakref.finalize(ctx, _release, prog, prog._gen)
+        ctx.gen = prog._gen
+        ctx.prog = prog
+        ctx.map_est = map_est
+        ctx.shapes = (log_mean.shape, z.shape, u_mean.shape, u_tril_vec.shape)
+        ctx.save_for_backward(yt, olv)
+        return scal[0], scal[1], scal[2]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_klh, g_klu, g_nll):
+        prog = ctx.prog
+        if prog._gen != ctx.gen:
+            raise RuntimeError(_REUSED)
+        if getattr(ctx, 'ran', False):
+            prog.rerun_forward()             # second backward of a retained graph: the moments are evaluated again
+        ctx.ran = True
+        yt, olv = ctx.saved_tensors
+        seeds = torch.stack([g_klh.reshape(()), g_klu.reshape(()), g_nll.reshape(())]).float()
+        dev = seeds.device
+        mu, var, gmu, gvar = lik_views(prog)
+        g_olv = torch.empty_like(olv)
+        ops.gauss_nll_bwd(mu, var, yt, ctx.ldy, olv, seeds[2:], gmu, gvar, g_olv)
+        sh_mean, sh_z, sh_um, sh_uv = ctx.shapes
+        g_mean, g_logvar = torch.empty(sh_mean, device=dev), torch.empty(sh_mean, device=dev)
+        g_z, g_um, g_uv = torch.empty(sh_z, device=dev), torch.empty(sh_um, device=dev), torch.empty(sh_uv, device=dev)
+        prog.backward(seeds, g_mean, g_logvar, g_z, g_um, g_uv)       # (ext_lik: seeds[2] is not read)
+        _release(prog, ctx.gen)
+        return (g_mean, None if ctx.map_est else g_logvar, g_z, g_um, g_uv, g_olv) + (None,) * 10
+
+
+def elbo_t0_gauss(kernel, z, u_mean, u_tril_vec, obs_log_var, x, y, eps_theta, prog):
+    """-> (kl_hypers, kl_u, nll) of VARGP.loss for a first-task GaussianLikelihood model on the first-task program."""
+    return _ElboGauss.apply(kernel.log_mean, kernel.log_logvar, z, u_mean, u_tril_vec, obs_log_var, x, y, eps_theta,
+                            kernel.prior_log_mean, kernel.prior_log_logvar, bool(kernel.map_est), prog, None, None, None)
+
+
+def elbo_tn_gauss(kernel, z, u_mean, u_tril_vec, obs_log_var, x, y, eps_theta, prog, z_all, rk_all, eps_u=None):
+    """-> (kl_hypers, kl_u, nll) of VARGP.loss for a GaussianLikelihood model on the block program (eps_u: ep_var_mean = False)."""
+    return _ElboGauss.apply(kernel.log_mean, kernel.log_logvar, z, u_mean, u_tril_vec, obs_log_var, x, y, eps_theta,
+                            kernel.prior_log_mean, kernel.prior_log_logvar, bool(kernel.map_est), prog, z_all, rk_all, eps_u)
+
+# ----------------------------------------------------------------------------------------------------------------
 # VARGP.loss on a native program WITHOUT an autograd graph: lazy terms (vargp_amd/lazy.py)
 # ----------------------------------------------------------------------------------------------------------------
 _RING = 8

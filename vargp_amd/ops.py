@@ -562,6 +562,60 @@ def softmax_predict(mu, var, eps):
     return probs
 
 
+
+def gauss_target(y, C, B):
+    """A regression target as the Gaussian kernels read it: (fp32 contiguous tensor, class stride ldy) -- (C, B) -> ldy = B,
+    (B,) -> ldy = 0 (one row shared by every output: the reference's y.unsqueeze(0).unsqueeze(-1) broadcast)."""
+    y = y.detach().to(torch.float32).contiguous()
+    if y.dim() == 1:
+        assert y.shape[0] == B, (tuple(y.shape), C, B)
+        return y, 0
+    assert tuple(y.shape) == (C, B), (tuple(y.shape), C, B)
+    return y, B
+
+
+def gauss_nll_fwd(mu, var, y, ldy, obs_log_var, out):
+    """Writes the Gaussian nll of mu, var (S, C, B) contiguous into the one-float device tensor `out`."""
+    S, C, B = mu.shape
+    check(lib().vargp_gauss_nll_fwd(ptr(mu), ptr(var), ptr(y), ldy, ptr(obs_log_var), ptr(out), S, C, B, stream_ptr()),
+          'vargp_gauss_nll_fwd')
+
+
+def gauss_nll_bwd(mu, var, y, ldy, obs_log_var, seed, gmu, gvar, g_obs_log_var, nll=None):
+    """Seeded gradients of the Gaussian nll into gmu, gvar (S, C, B) and g_obs_log_var (C,); with `nll`, the value too."""
+    S, C, B = mu.shape
+    check(lib().vargp_gauss_nll_bwd(ptr(mu), ptr(var), ptr(y), ldy, ptr(obs_log_var), ptr(seed), ptr(gmu), ptr(gvar),
+                                    ptr(g_obs_log_var), ptr(nll), S, C, B, stream_ptr()), 'vargp_gauss_nll_bwd')
+
+
+class _GaussNll(Function):
+    @staticmethod
+    def forward(ctx, mu, var, y, obs_log_var):
+        require_device(mu, var, y, obs_log_var)
+        mu, var, obs_log_var = mu.contiguous(), var.contiguous(), obs_log_var.contiguous()
+        S, C, B = mu.shape
+        assert var.shape == mu.shape and obs_log_var.shape == (C,), (mu.shape, var.shape, obs_log_var.shape)
+        yt, ldy = gauss_target(y, C, B)
+        nll = torch.empty((), dtype=torch.float32, device=mu.device)
+        gauss_nll_fwd(mu, var, yt, ldy, obs_log_var, nll)
+        ctx.save_for_backward(mu, var, yt, obs_log_var)
+        ctx.ldy = ldy
+        return nll
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        mu, var, yt, obs_log_var = ctx.saved_tensors
+        gmu, gvar, golv = torch.empty_like(mu), torch.empty_like(var), torch.empty_like(obs_log_var)
+        gauss_nll_bwd(mu, var, yt, ctx.ldy, obs_log_var, g.float().contiguous(), gmu, gvar, golv)
+        return gmu, gvar, None, golv
+
+
+def gauss_nll(mu, var, y, obs_log_var):
+    """sum_b mean_{s,c} -log N(y | mu, var + exp(obs_log_var[c]))  (GaussianLikelihood.loss, likelihoods.py:92-107);
+    y (C, B) or (B,).  Differentiable in mu, var and obs_log_var."""
+    return _GaussNll.apply(mu, var, y, obs_log_var)
+
 # ------------------------------------------------------------------------------------------------
 # variational hyper-parameters
 # ------------------------------------------------------------------------------------------------

@@ -20,7 +20,11 @@ import torch
 import torch.distributed as dist
 
 from . import noise
+from .likelihoods import is_gaussian, n_f
 from .optim import Yogi
+
+_GAUSS_REFUSED = ('{} is not available for GaussianLikelihood models: it assumes integer class labels or the softmax '
+                  'likelihood.  Train them on one GPU with step() / capture() + step_graph()')
 
 
 def split_samples(total, world):
@@ -70,6 +74,11 @@ class ElboTrainer:
         # force_exchange: take the multi-rank path (all-reduce of the flat buffer, two-graph capture) with one rank too --
         # a smoke test of that path where only one GPU is available (bench.py, VARGP_BENCH_FORCE_DIST=1)
         self.multi = self.world > 1 or (bool(force_exchange) and dist.is_available() and dist.is_initialized())
+        # GaussianLikelihood (regression) models: one GPU only -- every multi-rank route exchanges softmax terms or labels
+        self.gauss = bool(gp is not None and is_gaussian(getattr(gp, 'likelihood', None)))
+        if self.gauss and (self.multi or shards is not None):
+            raise NotImplementedError(_GAUSS_REFUSED.format('a multi-rank (sample-parallel, class-sharded or force_exchange) '
+                                                            'trainer'))
         self.params = list(params) if params is not None else [p for p in gp.parameters() if p.requires_grad]
         n = sum(p.numel() for p in self.params)
         dev = self.params[0].device
@@ -152,7 +161,8 @@ class ElboTrainer:
         self._bump = None
         # native noise: the program draws eps_theta / eps_f itself (Philox keyed by noise_seed, device-side step
         # counter): no randn launches, and ranks see slices of one global draw by construction
-        self.native_noise = bool(native_noise) and self._t0 and not self.class_split
+        # (GaussianLikelihood models: the program runs with ext_lik, which takes eps_theta from the caller -- noise.draw)
+        self.native_noise = bool(native_noise) and self._t0 and not self.class_split and not self.gauss
         # ep_var_mean = False models with earlier tasks draw eps_u -- and with it eps_theta / eps_f -- from the torch generator
         # (noise.draw) on every step, native noise or not: the captures below must register that generator
         self._draws_u = bool(is_model and gp.prev_params and gp.var_mean_mask != 1.0)
@@ -220,6 +230,8 @@ class ElboTrainer:
         a kernel boundary inside a graph, so K steps per launch shave that off K - 1 of every K steps.  The K steps read K
         static minibatch slots (`step_graph_k(xs, ys)` with xs (K, B, D), ys (K, B); without arguments the slots keep what they
         hold -- initially K copies of x, y); noise and optimiser step counts advance on the device as in the one-step graph."""
+        if self.gauss:
+            raise NotImplementedError(_GAUSS_REFUSED.format('capture_unrolled'))
         assert self.graph is not None and not self.multi and k >= 2 and x.size(0) == self._sx.size(0)
         self._k = int(k)
         self._sxk = x.unsqueeze(0).repeat(k, *([1] * x.dim())).contiguous()
@@ -252,6 +264,8 @@ class ElboTrainer:
         epoch's full batches with ceil(full batches / K) graph launches and no other launch at all (the per-step form: two
         index_select launches + one graph launch per step).  -> self, or None when the
         trainer cannot (no device step counter, several ranks): the caller keeps `step_graph_gather`."""
+        if self.gauss:
+            raise NotImplementedError(_GAUSS_REFUSED.format('capture_epoch'))
         if self.graph is None or self.multi or self._bump is None or not self._t0:
             return None
         from ._lib import check, lib, ptr, stream_ptr
@@ -384,6 +398,8 @@ class ElboTrainer:
     def step_graph_gather(self, data, targets, idx):
         """Replay the captured step on the minibatch data[idx], targets[idx] (device-resident data set, idx a device index
         tensor of the captured batch size): gathered straight into the graph's static inputs, no host copy."""
+        if self.gauss:
+            raise NotImplementedError(_GAUSS_REFUSED.format('step_graph_gather'))
         self._select_capture(idx.numel())
         torch.index_select(data, 0, idx, out=self._sx)
         torch.index_select(targets, 0, idx, out=self._sy)
@@ -443,8 +459,9 @@ class ElboTrainer:
             eps_theta = eps_f = None
         else:
             eps_theta, eps_f = gp.draw_t0_noise(x)
-            eps_theta, eps_f = None if eps_theta is None else eps_theta.contiguous(), eps_f.contiguous()
-        shape = T0Program.shape_of(S, gp.z, x, gp.likelihood.n_f)
+            eps_theta = None if eps_theta is None else eps_theta.contiguous()
+            eps_f = None if eps_f is None else eps_f.contiguous()     # (None: GaussianLikelihood)
+        shape = T0Program.shape_of(S, gp.z, x, n_f(gp.likelihood))
         self._tn = bool(gp._use_block_program(x.size(0)))
         if self._tn:
             shape = shape + (len(gp.prev_params) + 1,)
@@ -459,6 +476,8 @@ class ElboTrainer:
         if key not in self._seeds:
             self._seeds[key] = torch.tensor([self.beta * w, w, scale * w], dtype=torch.float32, device=x.device)
         packed = gp._tn_operands() if self._tn else ()
+        if self.gauss:
+            return self._gauss_fwd_bwd(x, y, eps_theta, eps_u, packed, key, defer_hyper)
         # (first-task program: forward and backward are issued back to back here and nll is read after both, so the
         # likelihood may be left to the backward's tile kernel -- one launch less)
         extra = dict(eps_u=eps_u) if self._tn else dict(defer_softmax=os.environ.get('VARGP_DEFER_SOFTMAX', '1') != '0')
@@ -476,6 +495,31 @@ class ElboTrainer:
         self._prog.backward(self._seeds[key], gbuf(kern.log_mean), gbuf(kern.log_logvar), gbuf(gp.z), gbuf(gp.u_mean),
                             gbuf(gp.u_tril_vec), defer_hyper=defer_hyper)
         return scal
+
+    def _gauss_fwd_bwd(self, x, y, eps_theta, eps_u, packed, key, defer_hyper):
+        """_t0_fwd_bwd of a GaussianLikelihood model: the program forward with ext_lik (moments + KL), ONE Gaussian launch
+        (nll into scalars[2], the seeded d nll / d (mu, var) into the program's likelihood buffers, d nll / d obs_log_var
+        into its .grad), the program backward."""
+        from . import fused, ops
+        gp, kern, prog = self.gp, self.gp.kernel, self._prog
+        y_arg = fused.y_dummy(x.device) if self._tn else None
+        extra = dict(eps_u=eps_u) if self._tn else {}
+        scal = prog.forward(kern.log_mean.detach(), kern.log_logvar.detach(), kern.prior_log_mean, kern.prior_log_logvar,
+                            gp.z.detach(), gp.u_mean.detach(), gp.u_tril_vec.detach(), *packed, x, y_arg, eps_theta, None,
+                            bump=self._bump, ext_lik=True, **extra)
+        mu, var, gmu, gvar = fused.lik_views(prog)
+        S, C, B = mu.shape
+        yt, ldy = ops.gauss_target(y, C, B)
+        olv = gp.likelihood.obs_log_var
+        seeds = self._seeds[key]
+        ops.gauss_nll_bwd(mu, var, yt, ldy, olv.detach(), seeds[2:], gmu, gvar, self._gbuf(olv), nll=scal[2:])
+        self._prog.backward(seeds, self._gbuf(kern.log_mean), self._gbuf(kern.log_logvar), self._gbuf(gp.z),
+                            self._gbuf(gp.u_mean), self._gbuf(gp.u_tril_vec), defer_hyper=defer_hyper)
+        return scal
+
+    def _gbuf(self, t):
+        """t.grad, or (a tensor that is frozen / not among the optimiser's parameters) a scratch buffer allocated once."""
+        return t.grad if t.grad is not None else self._scratch(t)
 
     def _local_part(self, x, y):
         """This rank's share: gradients of w_r (beta kl_h + kl_u_r + (N/B) nll_r) accumulated into the flat buffer, whose
@@ -540,7 +584,7 @@ class ElboTrainer:
         St, Ct = self.grid
         gp = self.gp
         if gp is not None and hasattr(gp, 'kernel'):
-            D1, F_ = gp.kernel.log_mean.shape[0], gp.likelihood.n_f
+            D1, F_ = gp.kernel.log_mean.shape[0], n_f(gp.likelihood)
         else:
             D1, F_ = self._pair_dims
         eps_theta = noise.draw('eps_theta', (St, D1), x.device)
@@ -571,7 +615,7 @@ class ElboTrainer:
         assert self._t0, 'class-sharded steps need a native program (RBFKernel, ep_var_mean=True) or pair_fns'
         x = x.contiguous()
         tn = bool(gp._use_block_program(B))
-        shape = (Sl, Cl, gp.M, gp.z.size(-1), B, gp.likelihood.n_f) + ((len(gp.prev_params) + 1,) if tn else ())
+        shape = (Sl, Cl, gp.M, gp.z.size(-1), B, n_f(gp.likelihood)) + ((len(gp.prev_params) + 1,) if tn else ())
         if self._prog is None or self._prog.shape != shape:
             if shape not in self._progs:
                 self._progs[shape] = (TnProgram if tn else T0Program)(*shape, x.device, kern.map_est)

@@ -22,7 +22,7 @@ import torch.nn as nn
 from . import fused, gp_utils, noise, ops
 from .gp_utils import vec2tril, mat2trilvec, cholesky, rev_cholesky, gp_cond, block_joint, linear_marginal_diag
 from .kernels import RBFKernel, DeepRBFKernel
-from .likelihoods import MulticlassSoftmax
+from .likelihoods import MulticlassSoftmax, is_gaussian, n_f
 from .ops import LOWER
 
 
@@ -149,7 +149,7 @@ class VARGP(nn.Module):
         (two losses combined before one backward), a spare of the same shape is used -- cached too, never re-allocated per
         step."""
         S = 1 if self.kernel.map_est else self.n_v
-        shape = (S, self.z.size(0), self.M, self.z.size(-1), B, self.likelihood.n_f, len(self.prev_params) + 1)
+        shape = (S, self.z.size(0), self.M, self.z.size(-1), B, n_f(self.likelihood), len(self.prev_params) + 1)
         prog = self._tn_progs.get(shape)
         if prog is None:
             prog = self._tn_progs[shape] = fused.TnProgram(*shape, self.z.device, self.kernel.map_est)
@@ -165,7 +165,7 @@ class VARGP(nn.Module):
         """The (cached) first-task program of this shape for `loss` as an autograd node: descriptor + ~120 MB workspace are
         built once per shape, not per call; a spare while a loss whose backward has not run yet owns the first one."""
         S = 1 if self.kernel.map_est else self.n_v
-        shape = (S, self.z.size(0), self.M, self.z.size(-1), B, self.likelihood.n_f)
+        shape = (S, self.z.size(0), self.M, self.z.size(-1), B, n_f(self.likelihood))
         prog = self._t0_progs.get(shape)
         if prog is not None and prog.ws.device != self.z.device:
             prog = None
@@ -183,7 +183,7 @@ class VARGP(nn.Module):
         """The forward-only program (predictive moments, no gradient buffers): one per model, carved for the widest batch
         asked for so far; narrower batches (the ragged last one of a sweep) run on it through the tile calls."""
         S = 1 if self.kernel.map_est else self.n_v
-        key = (S, self.z.size(0), self.M, self.z.size(-1), self.likelihood.n_f, len(self.prev_params) + 1)
+        key = (S, self.z.size(0), self.M, self.z.size(-1), n_f(self.likelihood), len(self.prev_params) + 1)
         if exact:
             # D <= 32 (the direct distance form) has no tile mode: one small program per batch size, kept -- an accuracy sweep
             # with a ragged last batch would otherwise free and re-carve the single workspace twice per data set
@@ -278,17 +278,21 @@ class VARGP(nn.Module):
 
     def draw_t0_noise(self, x):
         """(eps_theta, eps_f) of one first-task step: the hyper-parameter noise of RBFKernel.sample_hypers
-        (kernels.py:66-67; None under map_est) and the likelihood noise (likelihoods.py:26)."""
+        (kernels.py:66-67; None under map_est) and the likelihood noise (likelihoods.py:26; None for the Gaussian
+        likelihood, which draws none)."""
         kern = self.kernel
         S = 1 if kern.map_est else self.n_v
         eps_theta = None if kern.map_est else noise.draw('eps_theta', (S, kern.log_mean.shape[0]), x.device)
+        if is_gaussian(self.likelihood):
+            return eps_theta, None
         eps_f = noise.draw('eps_f', (S, self.likelihood.n_f, self.z.size(0), x.size(0)), x.device)
         return eps_theta, eps_f
 
     # -- lazy route (lazy.py) ---------------------------------------------------------------------------------------------------
     def _lazy_ok(self):
-        """The five parameters are plain trainable leaves without hooks: the program's backward may write their .grad itself."""
-        if not (self.lazy_loss and torch.is_grad_enabled()):
+        """The five parameters are plain trainable leaves without hooks: the program's backward may write their .grad itself.
+        Not for a GaussianLikelihood model: its sixth trainable tensor (obs_log_var) takes the autograd-node route."""
+        if not (self.lazy_loss and torch.is_grad_enabled()) or is_gaussian(self.likelihood):
             return False
         k = self.kernel
         ps = (k.log_mean, self.z, self.u_mean, self.u_tril_vec) + (() if k.map_est else (k.log_logvar,))
@@ -335,6 +339,16 @@ class VARGP(nn.Module):
         native_t0 = not self.prev_params and self.fused_first_task and type(self.kernel) is RBFKernel and not block
         if (native_t0 or block) and self._lazy_ok():
             return fused.elbo_lazy(self, x, y, block)
+        if is_gaussian(self.likelihood) and (native_t0 or block):
+            # regression: the same programs with the likelihood left to the caller (ext_lik) and the closed-form Gaussian
+            # nll between forward and backward (fused._ElboGauss)
+            eps_theta, _ = self.draw_t0_noise(x)
+            lik = self.likelihood.obs_log_var
+            if block:
+                return fused.elbo_tn_gauss(self.kernel, self.z, self.u_mean, self.u_tril_vec, lik, x, y, eps_theta,
+                                           self._tn_program(x.size(0)), *self._tn_operands(), eps_u=self.draw_u_noise(x))
+            return fused.elbo_t0_gauss(self.kernel, self.z, self.u_mean, self.u_tril_vec, lik, x, y, eps_theta,
+                                       self._t0_program(x.size(0)))
         if not self.prev_params and self.fused_first_task and type(self.kernel) is RBFKernel and not block:
             # first task: the native program (csrc/elbo_t0.hip) as one autograd node
             return fused.elbo_t0(self.kernel, self.z, self.u_mean, self.u_tril_vec, x, y, *self.draw_t0_noise(x),
@@ -363,6 +377,9 @@ class VARGP(nn.Module):
         Injected noise (noise.inject: eps_theta (S, D+1), eps_f (S, F, C, N)) is honoured; otherwise the program draws its
         own (counter-based generator keyed by `noise_seed`)."""
         assert self._tn_applicable() and (not self.prev_params or self.var_mean_mask == 1.0)
+        if is_gaussian(self.likelihood):
+            raise NotImplementedError('elbo_tiled: the tiled sweep evaluates the softmax likelihood of integer labels; '
+                                      'GaussianLikelihood models train through loss() or ElboTrainer')
         kern = self.kernel
         S = 1 if kern.map_est else self.n_v
         prog = self._tn_program(int(tile))       # honours a pending backward of VARGP.loss on the same shape
@@ -384,9 +401,11 @@ class VARGP(nn.Module):
         return scal[0].clone(), scal[1].clone(), scal[2].clone()
 
     def predict(self, x, tile=None):
-        """Class probabilities (B, C)  (vargp.py:196-198).  With `tile`, a large x is swept in blocks of
-        `tile` points that share ONE hyper-sample and ONE set of x-independent factors (K_uu, its Cholesky
-        / inverse, Lz^-1 m, Lz^-1 L_S): the same result as a single call on all of x, in bounded memory."""
+        """Class probabilities (B, C)  (vargp.py:196-198); for a GaussianLikelihood model the predictive means (S, C, B).
+        With `tile`, a large x is swept in blocks of `tile` points that share ONE hyper-sample and ONE set of x-independent
+        factors (K_uu, its Cholesky / inverse, Lz^-1 m, Lz^-1 L_S): the same result as a single call on all of x, in bounded
+        memory."""
+        cat_dim = -1 if is_gaussian(self.likelihood) else 0          # blocks along B: last dim of (S, C, B), first of (B, C)
         if tile is None or x.size(0) <= tile:
             pred_mu, pred_var = self(x)
             return self.likelihood.predict(pred_mu, pred_var)
@@ -402,8 +421,9 @@ class VARGP(nn.Module):
             out = []
             for i in range(0, x.size(0), tile):
                 mu, var = prog.sweep_moments(x[i:i + tile].contiguous())
-                out.append(self.likelihood.predict(mu, var))
-            return torch.cat(out, dim=0)
+                p = self.likelihood.predict(mu, var)
+                out.append(p.clone() if p is mu else p)      # (the Gaussian mean is a view the next tile overwrites)
+            return torch.cat(out, dim=cat_dim)
         theta = self.kernel.sample_hypers(self.n_v)
         if self.prev_params:
             _, _, mu_leq_t, S_leq_t, z_leq_t = self.compute_q(theta)
@@ -417,7 +437,7 @@ class VARGP(nn.Module):
             xt = x[i:i + tile]
             mu, var, _ = gp_utils.marginal_apply(prep, self.kernel.compute(theta, z_leq_t, xt), Kxx_diag)
             out.append(self.likelihood.predict(mu, var))
-        return torch.cat(out, dim=0)
+        return torch.cat(out, dim=cat_dim)
 
     @staticmethod
     def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None,
