@@ -19,11 +19,11 @@ real autograd tensor (one node over the five parameters whose backward is the sa
 (`__torch_function__`), multiplication by tensors or other terms, `backward(gradient=...)`, `.grad_fn`, ...  `.item()`,
 `float()`, `.detach()`, `.cpu()`, `.tolist()` read the device scalars (one sync), without autograd.
 """
-import weakref
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
+
+from .fused import _claim, _release, _verify          # who owns a program's workspace (no native call at import)
 
 _NUM = (int, float)
 
@@ -38,18 +38,13 @@ class PendingForward:
         self.params = params                    # (log_mean, log_logvar or None, z, u_mean, u_tril_vec): the leaves
         self.done = False
         self.retained = False                   # the last backward asked for retain_graph: a further one re-evaluates the forward
-        prog._gen += 1
-        self.gen = prog._gen
-        prog.busy = True
-        weakref.finalize(self, _release, prog, prog._gen)
+        self.gen = _claim(prog, self)
 
     def run_backward(self, coefs, retain=False):
         """d total / d (kl_hypers, kl_u, nll) = coefs (host floats) -> gradients into the parameters' .grad.  A second call is
         legal after `retain=True` (loss.backward(retain_graph=True), as in autograd): the program's forward is re-evaluated on
-        the same operands and noise (fused.T0Program.rerun_forward) and the workspace stays with this forward until it dies."""
-        if self.prog._gen != self.gen:
-            from .fused import _REUSED
-            raise RuntimeError(_REUSED)
+        the same operands and noise (fused._Program.rerun_forward) and the workspace stays with this forward until it dies."""
+        _verify(self.prog, self.gen)
         if self.done:
             if not self.retained:
                 raise RuntimeError('Trying to backward through the graph a second time (VARGP.loss on the native program: the '
@@ -75,11 +70,6 @@ class PendingForward:
             _release(self.prog, self.gen)
 
 
-def _release(prog, gen):
-    if prog._gen == gen:
-        prog.busy = False
-
-
 class _Materialise(Function):
     """The three scalars of a pending forward as real autograd tensors (fallback for everything ElboTerm does not do itself)."""
 
@@ -94,9 +84,7 @@ class _Materialise(Function):
     @once_differentiable
     def backward(ctx, g0, g1, g2):
         fwd = ctx.fwd
-        if fwd.prog._gen != fwd.gen:
-            from .fused import _REUSED
-            raise RuntimeError(_REUSED)
+        _verify(fwd.prog, fwd.gen)
         if fwd.done:
             fwd.prog.rerun_forward()             # retained graph, second backward (autograd itself has let it through)
         fwd.done = True

@@ -93,10 +93,7 @@ class ElboTrainer:
         self._shard = (torch.zeros(self._flat_store.numel() // self.world, dtype=torch.float32, device=dev)
                        if comm == 'rsag' else None)
         self.comm_events = None            # list -> exchange() appends one (start, end) event pair per call (bench.py)
-        off = 0
-        for p in self.params:
-            p.grad = self.flat[off:off + p.numel()].view_as(p)
-            off += p.numel()
+        self._attach_flat_grads()
         self.scalars = self.flat[n:]
         self.optim = optimizer if optimizer is not None else Yogi(self.params, lr=lr)
         if callable(self.optim) and not hasattr(self.optim, 'step'):
@@ -198,10 +195,7 @@ class ElboTrainer:
         torch.cuda.current_stream().wait_stream(side)
         self._restore_state(snap)
         self.graph = torch.cuda.CUDAGraph()
-        if noise._shard is not None and not (self._t0 and self.native_noise and not self._draws_u):
-            # the composed (t > 0) path draws its noise from the shared torch generator inside the captured region;
-            # the first-task program has its own counter-based generator and needs no generator bookkeeping per replay
-            self.graph.register_generator_state(noise._shard[2])
+        self._register_generator(self.graph)
         if not self.multi:
             with torch.cuda.graph(self.graph):
                 self._sout = self.step(self._sx, self._sy)
@@ -225,6 +219,12 @@ class ElboTrainer:
         self._captured[int(x.size(0))] = (self.graph, self.graph_opt, self._sx, self._sy, self._sout, getattr(self, 'graph_mid', None))
         return self
 
+    def _register_generator(self, graph):
+        """The composed (t > 0) path draws its noise from the shared torch generator inside the captured region: the graph must
+        know that generator.  (The native programs have their own counter-based generator and need no bookkeeping per replay.)"""
+        if noise._shard is not None and not (self._t0 and self.native_noise and not self._draws_u):
+            graph.register_generator_state(noise._shard[2])
+
     def capture_unrolled(self, x, y, k):
         """K consecutive steps in ONE hipGraph (one GPU only; after `capture`): a graph launch costs a few microseconds more than
         a kernel boundary inside a graph, so K steps per launch shave that off K - 1 of every K steps.  The K steps read K
@@ -238,8 +238,7 @@ class ElboTrainer:
         self._syk = y.unsqueeze(0).repeat(k, *([1] * y.dim())).contiguous()
         snap = self._snapshot_state()
         self.graph_k = torch.cuda.CUDAGraph()
-        if noise._shard is not None and not (self._t0 and self.native_noise and not self._draws_u):
-            self.graph_k.register_generator_state(noise._shard[2])
+        self._register_generator(self.graph_k)
         with torch.cuda.graph(self.graph_k, pool=self.graph.pool()):
             for i in range(k):
                 self._soutk = self.step(self._sxk[i], self._syk[i])
@@ -447,10 +446,40 @@ class ElboTrainer:
                 and has(k.log_mean) and (bool(k.map_est) or has(k.log_logvar))
                 and os.environ.get('VARGP_DEFER_HYPER', '1') != '0')
 
+    def _attach_flat_grads(self):
+        """(Re-)attach the gradient views of the flat buffer."""
+        if self.params[0].grad is None or self.params[0].grad.data_ptr() != self.flat.data_ptr():
+            off = 0
+            for p in self.params:
+                p.grad = self.flat[off:off + p.numel()].view_as(p)
+                off += p.numel()
+
+    def _program_for(self, shape, block):
+        """Make the program of this shape (created on first use, then kept: see `_progs`) the current one."""
+        if self._prog is None or self._prog.shape != shape:
+            if shape not in self._progs:
+                from .fused import T0Program, TnProgram
+                prog = self._progs[shape] = (TnProgram if block else T0Program)(*shape, self.gp.z.device, self.gp.kernel.map_est)
+                if self.native_noise:
+                    prog.set_rng(self.noise_seed, self._rng_counter,
+                                 self.rank * shape[0] if self.sample_offset is None else self.sample_offset)
+            self._prog = self._progs[shape]
+        self._tn = block
+        return self._prog
+
+    def _gbuf(self, t):
+        """t.grad, or (a tensor that is frozen / not among the optimiser's parameters: the program still writes all five
+        gradients) a scratch buffer allocated once -- keyed by the tensor itself, which holds a reference."""
+        if t.grad is not None:
+            return t.grad
+        if t not in self._scratch_grads:
+            self._scratch_grads[t] = torch.empty_like(t)
+        return self._scratch_grads[t]
+
     def _t0_fwd_bwd(self, x, y, scale, w, defer_hyper=False):
-        """Native first-task program: scalars (kl_hypers, kl_u, nll) of this rank's samples, and the gradient of
+        """Native program: scalars (kl_hypers, kl_u, nll) of this rank's samples, and the gradient of
         w * (beta kl_hypers + kl_u + scale nll) written into every p.grad."""
-        from .fused import T0Program, TnProgram
+        from .fused import T0Program, y_dummy
         gp, kern = self.gp, self.gp.kernel
         x, y = x.contiguous(), y.contiguous()
         S = 1 if kern.map_est else (gp.n_v if self.shards is None else self.rect[1] - self.rect[0])
@@ -461,75 +490,46 @@ class ElboTrainer:
             eps_theta, eps_f = gp.draw_t0_noise(x)
             eps_theta = None if eps_theta is None else eps_theta.contiguous()
             eps_f = None if eps_f is None else eps_f.contiguous()     # (None: GaussianLikelihood)
-        shape = T0Program.shape_of(S, gp.z, x, n_f(gp.likelihood))
-        self._tn = bool(gp._use_block_program(x.size(0)))
-        if self._tn:
-            shape = shape + (len(gp.prev_params) + 1,)
-        if self._prog is None or self._prog.shape != shape:
-            if shape not in self._progs:
-                self._progs[shape] = (TnProgram if self._tn else T0Program)(*shape, x.device, kern.map_est)
-                if self.native_noise:
-                    self._progs[shape].set_rng(self.noise_seed, self._rng_counter,
-                                               self.rank * S if self.sample_offset is None else self.sample_offset)
-            self._prog = self._progs[shape]
+        tn = bool(gp._use_block_program(x.size(0)))
+        shape = T0Program.shape_of(S, gp.z, x, n_f(gp.likelihood)) + ((len(gp.prev_params) + 1,) if tn else ())
+        prog = self._program_for(shape, tn)
         key = (scale, w)
         if key not in self._seeds:
             self._seeds[key] = torch.tensor([self.beta * w, w, scale * w], dtype=torch.float32, device=x.device)
-        packed = gp._tn_operands() if self._tn else ()
+        seeds = self._seeds[key]
+        packed = gp._tn_operands() if tn else ()
+        extra = dict(eps_u=eps_u) if tn else {}
         if self.gauss:
-            return self._gauss_fwd_bwd(x, y, eps_theta, eps_u, packed, key, defer_hyper)
-        # (first-task program: forward and backward are issued back to back here and nll is read after both, so the
-        # likelihood may be left to the backward's tile kernel -- one launch less)
-        extra = dict(eps_u=eps_u) if self._tn else dict(defer_softmax=os.environ.get('VARGP_DEFER_SOFTMAX', '1') != '0')
-        scal = self._prog.forward(kern.log_mean.detach(), kern.log_logvar.detach(), kern.prior_log_mean,
-                                  kern.prior_log_logvar, gp.z.detach(), gp.u_mean.detach(), gp.u_tril_vec.detach(), *packed,
-                                  x, y, eps_theta, eps_f, bump=self._bump, **extra)
-        # (a tensor that is frozen / not among the optimiser's parameters has no .grad: the program still writes all five
-        # gradients, those into scratch)
-        def gbuf(t):
-            if t.grad is not None:
-                return t.grad
-            if t not in self._scratch_grads:          # keyed by the tensor itself: holds a reference, allocated once
-                self._scratch_grads[t] = torch.empty_like(t)
-            return self._scratch_grads[t]
-        self._prog.backward(self._seeds[key], gbuf(kern.log_mean), gbuf(kern.log_logvar), gbuf(gp.z), gbuf(gp.u_mean),
-                            gbuf(gp.u_tril_vec), defer_hyper=defer_hyper)
+            # the likelihood is ours (ext_lik: moments + KL only); the block program still wants a label pointer
+            labels, extra['ext_lik'] = (y_dummy(x.device) if tn else None), True
+        else:
+            labels = y
+            if not tn:
+                # forward and backward are issued back to back here and nll is read after both, so the likelihood may be
+                # left to the backward's tile kernel -- one launch less
+                extra['defer_softmax'] = os.environ.get('VARGP_DEFER_SOFTMAX', '1') != '0'
+        scal = prog.forward(*gp._operands(), *packed, x, labels, eps_theta, eps_f, bump=self._bump, **extra)
+        if self.gauss:
+            self._gauss_lik(prog, y, seeds, scal)
+        prog.backward(seeds, *map(self._gbuf, (kern.log_mean, kern.log_logvar, gp.z, gp.u_mean, gp.u_tril_vec)),
+                      defer_hyper=defer_hyper)
         return scal
 
-    def _gauss_fwd_bwd(self, x, y, eps_theta, eps_u, packed, key, defer_hyper):
-        """_t0_fwd_bwd of a GaussianLikelihood model: the program forward with ext_lik (moments + KL), ONE Gaussian launch
-        (nll into scalars[2], the seeded d nll / d (mu, var) into the program's likelihood buffers, d nll / d obs_log_var
-        into its .grad), the program backward."""
+    def _gauss_lik(self, prog, y, seeds, scal):
+        """Between the forward and the backward of a GaussianLikelihood model's step: ONE launch -- nll into scalars[2], the
+        seeded d nll / d (mu, var) into the program's likelihood buffers, d nll / d obs_log_var into its .grad."""
         from . import fused, ops
-        gp, kern, prog = self.gp, self.gp.kernel, self._prog
-        y_arg = fused.y_dummy(x.device) if self._tn else None
-        extra = dict(eps_u=eps_u) if self._tn else {}
-        scal = prog.forward(kern.log_mean.detach(), kern.log_logvar.detach(), kern.prior_log_mean, kern.prior_log_logvar,
-                            gp.z.detach(), gp.u_mean.detach(), gp.u_tril_vec.detach(), *packed, x, y_arg, eps_theta, None,
-                            bump=self._bump, ext_lik=True, **extra)
         mu, var, gmu, gvar = fused.lik_views(prog)
         S, C, B = mu.shape
         yt, ldy = ops.gauss_target(y, C, B)
-        olv = gp.likelihood.obs_log_var
-        seeds = self._seeds[key]
+        olv = self.gp.likelihood.obs_log_var
         ops.gauss_nll_bwd(mu, var, yt, ldy, olv.detach(), seeds[2:], gmu, gvar, self._gbuf(olv), nll=scal[2:])
-        self._prog.backward(seeds, self._gbuf(kern.log_mean), self._gbuf(kern.log_logvar), self._gbuf(gp.z),
-                            self._gbuf(gp.u_mean), self._gbuf(gp.u_tril_vec), defer_hyper=defer_hyper)
-        return scal
-
-    def _gbuf(self, t):
-        """t.grad, or (a tensor that is frozen / not among the optimiser's parameters) a scratch buffer allocated once."""
-        return t.grad if t.grad is not None else self._scratch(t)
 
     def _local_part(self, x, y):
         """This rank's share: gradients of w_r (beta kl_h + kl_u_r + (N/B) nll_r) accumulated into the flat buffer, whose
         tail carries w_r kl_u_r and w_r nll_r  (w_r = S_r / S; 1 / world for equal shards)."""
         scale = (self.n_total if self.n_total is not None else x.size(0)) / x.size(0)
-        if self.params[0].grad is None or self.params[0].grad.data_ptr() != self.flat.data_ptr():
-            off = 0
-            for p in self.params:                      # (re-)attach the gradient views of the flat buffer
-                p.grad = self.flat[off:off + p.numel()].view_as(p)
-                off += p.numel()
+        self._attach_flat_grads()
         if self.class_split:
             self._pair_part1(x, y)
             self.gather_moments()
@@ -593,15 +593,10 @@ class ElboTrainer:
 
     def _pair_part1(self, x, y):
         """Moments and KL of this rank's (sample, class) rectangle -> the send block."""
-        from .fused import T0Program, TnProgram
         self._pair_setup(x)
         s0, s1, c0, c1 = self.rect
         Sl, Cl, B = s1 - s0, c1 - c0, x.size(0)
-        if self.params[0].grad is None or self.params[0].grad.data_ptr() != self.flat.data_ptr():
-            off = 0
-            for p in self.params:
-                p.grad = self.flat[off:off + p.numel()].view_as(p)
-                off += p.numel()
+        self._attach_flat_grads()
         self.flat.zero_()                           # the program / autograd writes this rank's class rows only
         eps_theta, self._eps_f = self._pair_noise(x)
         th = eps_theta[s0:s1].contiguous()
@@ -616,17 +611,12 @@ class ElboTrainer:
         x = x.contiguous()
         tn = bool(gp._use_block_program(B))
         shape = (Sl, Cl, gp.M, gp.z.size(-1), B, n_f(gp.likelihood)) + ((len(gp.prev_params) + 1,) if tn else ())
-        if self._prog is None or self._prog.shape != shape:
-            if shape not in self._progs:
-                self._progs[shape] = (TnProgram if tn else T0Program)(*shape, x.device, kern.map_est)
-            self._prog = self._progs[shape]
-        self._tn = tn
-        packed = tuple(t[c0:c1] for t in gp._tn_operands()) if tn else ()
-        self._pair_scal = self._prog.forward(kern.log_mean.detach(), kern.log_logvar.detach(), kern.prior_log_mean,
-                                             kern.prior_log_logvar, gp.z.detach()[c0:c1], gp.u_mean.detach()[c0:c1],
-                                             gp.u_tril_vec.detach()[c0:c1], *packed, x, y.contiguous(),
-                                             None if kern.map_est else th, None, bump=self._bump, ext_lik=True)
-        mu, var, _, _ = self._prog.lik_buffers()
+        prog = self._program_for(shape, tn)
+        ops7 = gp._operands()
+        rows = tuple(t[c0:c1] for t in ops7[4:] + (gp._tn_operands() if tn else ()))       # this rank's classes of z, u_mean, ...
+        self._pair_scal = prog.forward(*ops7[:4], *rows, x, y.contiguous(), None if kern.map_est else th, None,
+                                       bump=self._bump, ext_lik=True)
+        mu, var, _, _ = prog.lik_buffers()
         self._send[:Sl * Cl, 0].copy_(mu.view(Sl * Cl, B))
         self._send[:Sl * Cl, 1].copy_(var.view(Sl * Cl, B))
 
@@ -671,13 +661,8 @@ class ElboTrainer:
         if key not in self._seeds:
             self._seeds[key] = torch.tensor([self.beta * self.w_h, self.w_kl, 0.0], dtype=torch.float32, device=x.device)
         g = lambda t: t.grad[c0:c1]
-        self._prog.backward(self._seeds[key], kern.log_mean.grad, kern.log_logvar.grad if kern.log_logvar.grad is not None
-                            else self._scratch(kern.log_logvar), g(gp.z), g(gp.u_mean), g(gp.u_tril_vec))
+        self._prog.backward(self._seeds[key], kern.log_mean.grad, self._gbuf(kern.log_logvar), g(gp.z), g(gp.u_mean),
+                            g(gp.u_tril_vec))
         torch.mul(self._pair_scal[1], self.w_kl, out=self.scalars[0])
         torch.mul(self._nll, self.w_h, out=self.scalars[1])
         return self._pair_scal[0], self.scalars[0], self.scalars[1]
-
-    def _scratch(self, t):
-        if t not in self._scratch_grads:
-            self._scratch_grads[t] = torch.empty_like(t)
-        return self._scratch_grads[t]

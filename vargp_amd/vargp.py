@@ -144,40 +144,33 @@ class VARGP(nn.Module):
                 self._tn_ops = fused.pack_tn_operands(prev, self.z.size(0), self.M, self.z.size(-1), dev)
         return self._tn_ops
 
-    def _tn_program(self, B):
-        """The (cached) training program of this shape.  While a loss() whose backward has not run yet owns its workspace
-        (two losses combined before one backward), a spare of the same shape is used -- cached too, never re-allocated per
-        step."""
-        S = 1 if self.kernel.map_est else self.n_v
-        shape = (S, self.z.size(0), self.M, self.z.size(-1), B, n_f(self.likelihood), len(self.prev_params) + 1)
-        prog = self._tn_progs.get(shape)
-        if prog is None:
-            prog = self._tn_progs[shape] = fused.TnProgram(*shape, self.z.device, self.kernel.map_est)
-        elif prog.busy:
-            spares = self._tn_spares.setdefault(shape, [])
-            prog = next((q for q in spares if not q.busy), None)
-            if prog is None:
-                prog = fused.TnProgram(*shape, self.z.device, self.kernel.map_est)
-                spares.append(prog)
-        return prog
-
-    def _t0_program(self, B):
-        """The (cached) first-task program of this shape for `loss` as an autograd node: descriptor + ~120 MB workspace are
-        built once per shape, not per call; a spare while a loss whose backward has not run yet owns the first one."""
+    def _program(self, B, block):
+        """The (cached) training program of this shape (block: csrc/elbo_tn.hip, otherwise csrc/elbo_t0.hip): descriptor +
+        ~120 MB workspace are built once per shape, not per call.  While a loss() whose backward has not run yet owns its
+        workspace (two losses combined before one backward), a spare of the same shape is used -- cached too, never
+        re-allocated per step."""
         S = 1 if self.kernel.map_est else self.n_v
         shape = (S, self.z.size(0), self.M, self.z.size(-1), B, n_f(self.likelihood))
-        prog = self._t0_progs.get(shape)
-        if prog is not None and prog.ws.device != self.z.device:
-            prog = None
-        if prog is None:
-            prog = self._t0_progs[shape] = fused.T0Program(*shape, self.z.device, self.kernel.map_est)
+        cls, progs, spares = fused.T0Program, self._t0_progs, self._t0_spares
+        if block:
+            shape, cls, progs, spares = shape + (len(self.prev_params) + 1,), fused.TnProgram, self._tn_progs, self._tn_spares
+        dev = self.z.device
+        prog = progs.get(shape)
+        if prog is None or prog.ws.device != dev:
+            prog = progs[shape] = cls(*shape, dev, self.kernel.map_est)
         elif prog.busy:
-            spares = self._t0_spares.setdefault(shape, [])
-            prog = next((q for q in spares if not q.busy and q.ws.device == self.z.device), None)
+            pool = spares.setdefault(shape, [])
+            prog = next((q for q in pool if not q.busy and q.ws.device == dev), None)
             if prog is None:
-                prog = fused.T0Program(*shape, self.z.device, self.kernel.map_est)
-                spares.append(prog)
+                prog = cls(*shape, dev, self.kernel.map_est)
+                pool.append(prog)
         return prog
+
+    def _tn_program(self, B):
+        return self._program(B, True)
+
+    def _t0_program(self, B):
+        return self._program(B, False)
 
     def _tn_eval_program(self, B, exact=False):
         """The forward-only program (predictive moments, no gradient buffers): one per model, carved for the widest batch
@@ -206,10 +199,13 @@ class VARGP(nn.Module):
         self._tn_progs, self._tn_spares, self._tn_eval, self._tn_eval_exact = {}, {}, None, {}
         self._t0_progs, self._t0_spares = {}, {}
 
-    def _tn_args(self):
+    def _operands(self, detach=True):
+        """What every native program reads of the model: (log_mean, log_logvar, prior_log_mean, prior_log_logvar, z, u_mean,
+        u_tril_vec) -- detached for the program calls, the parameters themselves as inputs of the autograd node."""
         k = self.kernel
-        return (k.log_mean.detach(), k.log_logvar.detach(), k.prior_log_mean, k.prior_log_logvar, self.z.detach().contiguous(),
-                self.u_mean.detach().contiguous(), self.u_tril_vec.detach().contiguous(), *self._tn_operands())
+        ps = (k.log_mean, k.log_logvar, self.z, self.u_mean, self.u_tril_vec)
+        log_mean, log_logvar, z, u_mean, u_tril_vec = [p.detach() for p in ps] if detach else ps
+        return log_mean, log_logvar, k.prior_log_mean, k.prior_log_logvar, z, u_mean, u_tril_vec
 
     def forward(self, x, loss_cache=False):
         """x (B, D) -> pred_mu, pred_var (S, C, B); fills `loss_cache` with the KL ingredients if it is
@@ -222,10 +218,10 @@ class VARGP(nn.Module):
             # (D <= 32, the direct distance form, has no tile mode: exact-shape program)
             prog = self._tn_eval_program(x.size(0), exact=self.z.size(-1) <= 32)
             if prog.shape[4] == x.size(0):
-                prog.forward(*self._tn_args(), x.contiguous(), None, eps_theta, None)
+                prog.forward(*self._operands(), *self._tn_operands(), x.contiguous(), None, eps_theta, None)
                 mu, var = prog.moments()
             else:                                  # narrower than the program: x-independent part + one moments-only tile
-                prog.sweep_begin(*self._tn_args(), eps_theta)
+                prog.sweep_begin(*self._operands(), *self._tn_operands(), eps_theta)
                 mu, var = prog.sweep_moments(x.contiguous())
             return mu.clone(), var.clone()
         theta = self.kernel.sample_hypers(self.n_v)
@@ -312,15 +308,7 @@ class VARGP(nn.Module):
         k = self.kernel
         ps = (k.log_mean, k.log_logvar, self.z, self.u_mean, self.u_tril_vec)
         if self._gbufs is None or self._gbufs[0][2].device != self.z.device or self._gbufs[0][2].shape != self.z.shape:
-            sets = []
-            for _ in range(2):
-                offs, tot = [], 0
-                for p in ps:
-                    offs.append(tot)
-                    tot += (p.numel() + 63) // 64 * 64
-                flat = torch.empty(tot, dtype=torch.float32, device=self.z.device)
-                sets.append([flat[o:o + p.numel()].view_as(p) for o, p in zip(offs, ps)])
-            self._gbufs = sets
+            self._gbufs = [fused._flat_views([p.shape for p in ps], self.z.device) for _ in range(2)]
         return self._gbufs
 
     def draw_u_noise(self, x):
@@ -335,29 +323,19 @@ class VARGP(nn.Module):
     def loss(self, x, y):
         """(kl_hypers, kl_u, nll); the caller combines beta*kl_hypers + kl_u + (N/B)*nll
         (vargp.py:177-194, experiments/vargp.py:34)."""
-        block = self._use_block_program(x.size(0))
-        native_t0 = not self.prev_params and self.fused_first_task and type(self.kernel) is RBFKernel and not block
-        if (native_t0 or block) and self._lazy_ok():
-            return fused.elbo_lazy(self, x, y, block)
-        if is_gaussian(self.likelihood) and (native_t0 or block):
-            # regression: the same programs with the likelihood left to the caller (ext_lik) and the closed-form Gaussian
-            # nll between forward and backward (fused._ElboGauss)
-            eps_theta, _ = self.draw_t0_noise(x)
-            lik = self.likelihood.obs_log_var
-            if block:
-                return fused.elbo_tn_gauss(self.kernel, self.z, self.u_mean, self.u_tril_vec, lik, x, y, eps_theta,
-                                           self._tn_program(x.size(0)), *self._tn_operands(), eps_u=self.draw_u_noise(x))
-            return fused.elbo_t0_gauss(self.kernel, self.z, self.u_mean, self.u_tril_vec, lik, x, y, eps_theta,
-                                       self._t0_program(x.size(0)))
-        if not self.prev_params and self.fused_first_task and type(self.kernel) is RBFKernel and not block:
-            # first task: the native program (csrc/elbo_t0.hip) as one autograd node
-            return fused.elbo_t0(self.kernel, self.z, self.u_mean, self.u_tril_vec, x, y, *self.draw_t0_noise(x),
-                                 prog=self._t0_program(x.size(0)))
-        if block:
-            # later tasks: the block-structured program (csrc/elbo_tn.hip) as one autograd node
+        B = x.size(0)
+        block = self._use_block_program(B)                      # csrc/elbo_tn.hip; otherwise, first task: csrc/elbo_t0.hip
+        if block or (not self.prev_params and self.fused_first_task and type(self.kernel) is RBFKernel):
+            lazy = self._lazy_ok()
+            prog, packed = self._program(B, block), (self._tn_operands() if block else ())
+            if lazy:
+                return fused.elbo_lazy(self, x, y, prog, packed)
+            # one autograd node.  Regression: the same programs with the likelihood left to the caller (ext_lik) and the
+            # closed-form Gaussian nll between forward and backward, obs_log_var as a sixth differentiable input
             eps_theta, eps_f = self.draw_t0_noise(x)
-            return fused.elbo_tn(self.kernel, self.z, self.u_mean, self.u_tril_vec, x, y, eps_theta, eps_f,
-                                 self._tn_program(x.size(0)), *self._tn_operands(), eps_u=self.draw_u_noise(x))
+            return fused.elbo_node(self._operands(detach=False), self.kernel.map_est, x, y, eps_theta, eps_f, prog, packed,
+                                   eps_u=self.draw_u_noise(x),
+                                   obs_log_var=self.likelihood.obs_log_var if is_gaussian(self.likelihood) else None)
         loss_cache = dict()
         pred_mu, pred_var = self(x, loss_cache=loss_cache)
         nll = self.likelihood.loss(pred_mu, pred_var, y)
@@ -395,7 +373,7 @@ class VARGP(nn.Module):
         params = [kern.log_mean, kern.log_logvar, self.z, self.u_mean, self.u_tril_vec]
         grads = [torch.empty_like(p) for p in params]
         seeds = torch.tensor([beta, 1.0, scale], dtype=torch.float32, device=x.device)
-        scal = prog.tiled_step(*self._tn_args(), x.contiguous(), y.contiguous(), seeds, grads, eps_theta, eps_f)
+        scal = prog.tiled_step(*self._operands(), *self._tn_operands(), x.contiguous(), y.contiguous(), seeds, grads, eps_theta, eps_f)
         for p, g in zip(params, grads):
             p.grad = g
         return scal[0].clone(), scal[1].clone(), scal[2].clone()
@@ -417,7 +395,7 @@ class VARGP(nn.Module):
             kern = self.kernel
             eps_theta = None if kern.map_est else noise.draw('eps_theta', (self.n_v, kern.log_mean.shape[0]), x.device)
             prog = self._tn_eval_program(int(tile))
-            prog.sweep_begin(*self._tn_args(), None if eps_theta is None else eps_theta.contiguous())
+            prog.sweep_begin(*self._operands(), *self._tn_operands(), None if eps_theta is None else eps_theta.contiguous())
             out = []
             for i in range(0, x.size(0), tile):
                 mu, var = prog.sweep_moments(x[i:i + tile].contiguous())
