@@ -51,14 +51,15 @@ class JsonlLogger:
 def train(task_id, train_set, val_set, test_set, ep_var_mean=True, map_est_hypers=False, dkl=False,
           epochs=1, M=20, n_f=10, n_var_samples=3, batch_size=512, lr=1e-2, beta=1.0,
           eval_interval=10, patience=20, prev_params=None, logger=None, device=None, graph=False, seed=None,
-          retrain=False, eval_shared_hypers=False, dataloader=False):
+          retrain=False, eval_shared_hypers=False, dataloader=False, kernel='rbf'):
     if retrain:      # the variant of experiments/vargp_retrain.py:14-19 (earlier tasks' inducing parameters re-optimised)
         from vargp_amd.vargp_retrain import VARGPRetrain
+        assert kernel == 'rbf', '--retrain builds its model with the RBF kernel'
         gp = VARGPRetrain.create_clf(train_set, M=M, n_f=n_f, n_var_samples=n_var_samples, prev_params=prev_params).to(device)
         graph = False
     else:
         gp = VARGP.create_clf(train_set, M=M, n_f=n_f, n_var_samples=n_var_samples, prev_params=prev_params,
-                              ep_var_mean=ep_var_mean, map_est_hypers=map_est_hypers, dkl=dkl).to(device)
+                              ep_var_mean=ep_var_mean, map_est_hypers=map_est_hypers, dkl=dkl, kernel=kernel).to(device)
     stopper = EarlyStopper(patience=patience)
     N = len(train_set)
     # the program's counter-based noise generator is keyed by the run's seed (the reference draws from the torch global
@@ -184,7 +185,7 @@ def toy(args):
         toy_test.filter_by_class(range(2 * t + 2))
         sd = train(t, toy_train, toy_val, toy_test, epochs=args.epochs, M=args.M, lr=args.lr, beta=args.beta,
                    batch_size=args.batch_size, ep_var_mean=args.ep_var_mean, map_est_hypers=args.map_est_hypers,
-                   dkl=args.dkl, prev_params=prev_params, logger=logger, device=device, patience=-1,
+                   dkl=args.dkl, kernel=args.kernel, prev_params=prev_params, logger=logger, device=device, patience=-1,
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed, retrain=args.retrain,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader)
         prev_params.append(sd)
@@ -209,7 +210,7 @@ def split_mnist(args):
         mnist_test.filter_by_class(range(2 * t + 2))
         sd = train(t, mnist_train, mnist_val, mnist_test, epochs=args.epochs, M=args.M, lr=args.lr, beta=args.beta,
                    batch_size=args.batch_size, ep_var_mean=args.ep_var_mean, map_est_hypers=args.map_est_hypers,
-                   dkl=args.dkl, prev_params=prev_params, logger=logger, device=device,
+                   dkl=args.dkl, kernel=args.kernel, prev_params=prev_params, logger=logger, device=device,
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader)
         prev_params.append(sd)
@@ -237,7 +238,7 @@ def permuted_mnist(args):
         mnist_test[-1].set_task(tasks[t])
         sd = train(t, mnist_train, ConcatDataset(mnist_val), ConcatDataset(mnist_test), epochs=args.epochs, M=args.M,
                    lr=args.lr, beta=args.beta, batch_size=args.batch_size, ep_var_mean=args.ep_var_mean,
-                   map_est_hypers=args.map_est_hypers, dkl=args.dkl, prev_params=prev_params, logger=logger,
+                   map_est_hypers=args.map_est_hypers, dkl=args.dkl, kernel=args.kernel, prev_params=prev_params, logger=logger,
                    device=device, eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader)
         prev_params.append(sd)
@@ -263,6 +264,8 @@ def main(argv=None):
         sp.add_argument('--ep_var_mean', type=lambda v: str(v).lower() not in ('0', 'false'), default=True)
         sp.add_argument('--map_est_hypers', type=lambda v: str(v).lower() not in ('0', 'false'), default=False)
         sp.add_argument('--dkl', type=lambda v: str(v).lower() not in ('0', 'false'), default=False)
+        sp.add_argument('--kernel', choices=('rbf', 'matern12', 'matern32', 'matern52'), default='rbf',
+                        help='covariance function (not stored in checkpoints: give it again when reloading one)')
         sp.add_argument('--seed', type=int, default=None)
         sp.add_argument('--eval_interval', type=int, default=10)
         sp.add_argument('--log_dir', default=os.path.join('runs', f'{name}-{int(time.time())}'))

@@ -86,6 +86,23 @@ int vargp_rbf_gram_bwd(const float* theta, const float* X, const float* Y, const
                        vargp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Matern / ARD kernel matrix, nu = nu2 / 2 with nu2 = 1, 3 or 5 (anything else is an error).  Arguments, layouts, the three
+ * Y cases and `accumulate` exactly as for the RBF entries above.  With d2 the same scaled squared distance, clamped at 0
+ * (the inner-product form can come out slightly negative), and r = sqrt(d2):
+ *   K / gamma^2 = exp(-r) | (1 + sqrt3 r) exp(-sqrt3 r) | (1 + sqrt5 r + 5 r^2 / 3) exp(-sqrt5 r);
+ *   for Y = NULL the diagonal is exactly gamma^2.
+ * Backward: the derivative of nu = 1/2 with respect to d2, -exp(-r) / (2 r), is DEFINED as 0 where d2 <= 0 (coincident points
+ * contribute nothing to gX, gY and the lengthscale part of gtheta); the other two are finite there.  The backward recomputes
+ * d2 from X and Y (nothing is carried over from the forward call but K), so its workspace is the larger one.
+ */
+size_t vargp_matern_workspace_bytes(int S, int C, int M, int N, int D, int backward);
+int vargp_matern_gram_fwd(const float* theta, const float* X, const float* Y, float* K, int S, int C, int M, int N, int D,
+                          int y_shared, int nu2, void* ws, size_t ws_bytes, vargp_stream_t stream);
+int vargp_matern_gram_bwd(const float* theta, const float* X, const float* Y, const float* K, const float* gK, float* gX,
+                          float* gY, float* gtheta, int S, int C, int M, int N, int D, int y_shared, int nu2, int accumulate,
+                          void* ws, size_t ws_bytes, vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Batched Cholesky with jitter + explicit inverse factor (reference: gp_utils.cholesky,
  * var_gp/gp_utils.py:5-11, and every torch.triangular_solve(., Lz) that consumes it).
  *   A[nbatch, n, n] symmetric (lower triangle read);  L = chol(A + eps I) lower, zeros above;

@@ -80,6 +80,10 @@ _SIGNATURES = {
     'vargp_rbf_gram_fwd': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     'vargp_rbf_gram_bwd': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P,
                                    c_size_t, _P]),
+    'vargp_matern_workspace_bytes': (c_size_t, [c_int] * 6),
+    'vargp_matern_gram_fwd': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
+    'vargp_matern_gram_bwd': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P,
+                                      c_size_t, _P]),
     'vargp_chol_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'vargp_chol_inv_fwd': (c_int, [_P, c_float, _P, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
     'vargp_chol_inv_bwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),

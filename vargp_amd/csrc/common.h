@@ -184,6 +184,48 @@ class SideFork {
 
 int launch_gemm(const GemmParams& p, int transA, int transB, int nbatch, bool rbf, hipStream_t st,
                 const char* tag = "bgemm");
+
+// Epilogues of a distance product (gemm_body's EPI, the split-K combine pass and the direct small-D kernel): what becomes of
+// an entry's scaled squared distance d2 = na + nb - 2 x.y, given g2 = gamma^2.  off(): any entry; diag(): the entries (i, i)
+// of a product of a point set with itself, whose distance is zero by definition and not by arithmetic.
+enum DistEpi { kEpiPlain = 0, kEpiRbf = 1, kEpiMatern12, kEpiMatern32, kEpiMatern52, kEpiDist2 };
+struct EpiRbf {
+  static __device__ __forceinline__ float off(float g2, float d2) { return g2 * expf(-0.5f * d2); }
+  static __device__ __forceinline__ float diag(float g2) { return g2; }
+};
+// Matern, nu = NU2 / 2, r = sqrt(max(d2, 0)) (the GEMM form of d2 can come out slightly negative):
+//   k = g2 exp(-r) | g2 (1 + sqrt3 r) exp(-sqrt3 r) | g2 (1 + sqrt5 r + 5 r^2 / 3) exp(-sqrt5 r)
+template <int NU2>
+__device__ __forceinline__ float matern_k(float g2, float d2) {
+  static_assert(NU2 == 1 || NU2 == 3 || NU2 == 5, "Matern: nu = 1/2, 3/2 or 5/2");
+  d2 = fmaxf(d2, 0.f);
+  const float a = sqrtf((float)NU2 * d2);
+  if constexpr (NU2 == 1) return g2 * expf(-a);
+  else if constexpr (NU2 == 3) return g2 * (1.f + a) * expf(-a);
+  else return g2 * (1.f + a + (5.f / 3.f) * d2) * expf(-a);
+}
+// -2 dk/dd2, the weight of gK in the backward (the RBF's is K itself): g2 exp(-r) / r, DEFINED as 0 where d2 <= 0 |
+// 3 g2 exp(-sqrt3 r) | (5/3) g2 (1 + sqrt5 r) exp(-sqrt5 r) -- the last two are finite at r = 0 and never divide by r
+template <int NU2>
+__device__ __forceinline__ float matern_w(float g2, float d2) {
+  static_assert(NU2 == 1 || NU2 == 3 || NU2 == 5, "Matern: nu = 1/2, 3/2 or 5/2");
+  d2 = fmaxf(d2, 0.f);
+  const float a = sqrtf((float)NU2 * d2);
+  if constexpr (NU2 == 1) return d2 > 0.f ? g2 * expf(-a) / a : 0.f;
+  else if constexpr (NU2 == 3) return 3.f * g2 * expf(-a);
+  else return (5.f / 3.f) * g2 * (1.f + a) * expf(-a);
+}
+template <int NU2>
+struct EpiMatern {
+  static __device__ __forceinline__ float off(float g2, float d2) { return matern_k<NU2>(g2, d2); }
+  static __device__ __forceinline__ float diag(float g2) { return g2; }
+};
+struct EpiDist2 {    // the clamped distance itself (the Matern backward recomputes it)
+  static __device__ __forceinline__ float off(float, float d2) { return fmaxf(d2, 0.f); }
+  static __device__ __forceinline__ float diag(float) { return 0.f; }
+};
+// launch_gemm with the epilogue named by a DistEpi (rbf == true is kEpiRbf, false kEpiPlain)
+int launch_gemm_epi(const GemmParams& p, int transA, int transB, int nbatch, int epi, hipStream_t st, const char* tag = "bgemm");
 int launch_gemm_pair(const GemmParams& p0, int nbatch0, const GemmParams& p1, int nbatch1, int transA, int transB,
                      bool rbf, hipStream_t st, const char* tag0, const char* tag1);
 int launch_gemm_pair2(const GemmParams& p0, int tA0, int tB0, int nbatch0, const GemmParams& p1, int tA1, int tB1,
@@ -294,6 +336,10 @@ int launch_chol_nn_gemm(const float* A, int lda, int64_t sA, float eps, float* L
 int rbf_prep_norm_launch(const float* theta, const float* x, int64_t xrows, const float* y, int64_t yrows, float* w,
                          float* g2, float* na, float* nb, int S, int D, int64_t Dp, hipStream_t st, float* ys = nullptr,
                          float* xs = nullptr);
+
+// the backward's finalisation of one side (rbf.hip: rbf_final_kernel), shared by every kernel built on d2
+int rbf_final_launch(const float* x, const float* R, const float* P, const float* theta, float* g, float* gtheta, int64_t rows,
+                     int D, int64_t Dp, int S, float kappa, int accumulate, hipStream_t st);
 
 int chol_inv_bwd_first(const float* T, const float* gT, int nbatch, int n, void* ws, size_t ws_bytes,
                        const GemmParams* other, int oA, int oB, int onb, hipStream_t st);

@@ -276,8 +276,10 @@ constexpr int cmax(int a, int b) { return a > b ? a : b; }
 // the 64 x 64 x 64 tiles of the small batched products: Cfg2 step 197 -> 193.5 us, Split-MNIST t = 1 1754 -> 1794 steps/s);
 // the 128-row tiles of the throughput-bound products lose occupancy to the extra live registers (S = 64: 314 -> 301 steps/s) and
 // keep the compiler's schedule.
+// EPI (RBF products only): what the epilogue makes of an entry's scaled squared distance (common.h: EpiRbf, the default --
+// K = g2 exp(-d2 / 2) --, the Matern family, or the clamped distance itself).
 template <int BM, int BN, int BK, bool AKC, bool BKC, bool VEC, bool RBF, bool SCALED = true, int NT = 256,
-          bool PIN = (BM == 64 && BN == 64)>
+          bool PIN = (BM == 64 && BN == 64), class EPI = EpiRbf>
 __device__ __forceinline__ void gemm_body(const GemmParams& p, const int tile_id_, const int batch_id_, const int split_id_,
                                           float* __restrict__ lds) {
   // The workgroup's tile / batch / split indices are wave-uniform, but they come out of integer divisions that the
@@ -559,7 +561,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, const int tile_id
           float v;
           if constexpr (RBF) {
             const float d2 = nar[r] + nbc - 2.f * acc[a][c][r];
-            v = (p.same_xy && row == col) ? g2 : g2 * expf(-0.5f * d2);
+            v = (p.same_xy && row == col) ? EPI::diag(g2) : EPI::off(g2, d2);
           } else {
             v = p.alpha * acc[a][c][r];
             if (D && row < p.M && col < p.N) v += p.beta * D[(int64_t)row * p.ldd + col];
@@ -604,7 +606,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, const int tile_id
           for (int r = 0; r < 16; ++r) {
             const int row = m0 + wm0 + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * lh;
             const float d2 = nar[r] + nbc - 2.f * acc[a][c][r];
-            v[r] = (p.same_xy && row == col) ? g2 : g2 * expf(-0.5f * d2);
+            v[r] = (p.same_xy && row == col) ? EPI::diag(g2) : EPI::off(g2, d2);
           }
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
@@ -630,7 +632,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, const int tile_id
           for (int r = 0; r < 16; ++r) {
             const int row = m0 + wm0 + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * lh;
             const float d2 = nar[r] + nbc - 2.f * acc[a][c][r];
-            const float v = (p.same_xy && row == col) ? g2 : g2 * expf(-0.5f * d2);
+            const float v = (p.same_xy && row == col) ? EPI::diag(g2) : EPI::off(g2, d2);
             float* dst = (row < p.M && col < p.N) ? &C[(int64_t)row * p.ldc + col] : &g_gemm_trash[tid];
             *dst = v;
           }
@@ -717,7 +719,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, const int tile_id
               v = acc[a][c][r];               // partial inner product; rbf_combine_kernel finishes the job
             } else {
               const float d2 = na[row] + nbc - 2.f * acc[a][c][r];
-              v = (p.same_xy && row == col) ? g2 : g2 * expf(-0.5f * d2);
+              v = (p.same_xy && row == col) ? EPI::diag(g2) : EPI::off(g2, d2);
             }
           } else {
             v = p.alpha * acc[a][c][r];
@@ -993,6 +995,16 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmParams p) {
   gemm_body<BM, BN, BK, AKC, BKC, VEC, RBF, SCALED>(p, id % (int)gridDim.x, id / (int)gridDim.x, blockIdx.z, lds);
 }
 
+// distance products with one of the other epilogues (common.h: DistEpi); the RBF instantiations above keep their names and code
+template <int BM, int BN, int BK, bool VEC, bool SCALED, class EPI>
+__global__ __launch_bounds__(256) void gemm_dist_kernel(const GemmParams p) {
+  __shared__ __attribute__((aligned(16))) float lds[gemm_lds_floats<BM, BN, BK, true, true>()];
+  const int lin = (int)(blockIdx.y * gridDim.x + blockIdx.x), total = (int)(gridDim.x * gridDim.y);
+  const int id = p.xcd_remap ? xcd_remap(lin, total) : lin;
+  gemm_body<BM, BN, BK, true, true, VEC, true, SCALED, 256, (BM == 64 && BN == 64), EPI>(p, id % (int)gridDim.x, id / (int)gridDim.x,
+                                                                                         blockIdx.z, lds);
+}
+
 // the same with eight waves per workgroup (two per SIMD on the same tile: gemm_body's NT = 512), plain products only
 template <int BM, int BN, int BK, bool AKC, bool BKC>
 __global__ __launch_bounds__(512) void gemm_kernel_w8(const GemmParams p) {
@@ -1057,10 +1069,27 @@ static void dispatch_layout(const GemmParams& p, int transA, int transB, dim3 gr
   }
 }
 
+template <int BM, int BN, int BK, class EPI>
+static void dispatch_dist(const GemmParams& p, bool vec, dim3 grid, hipStream_t st) {
+  if (vec) {
+    if (p.kscale) hipLaunchKernelGGL((gemm_dist_kernel<BM, BN, BK, true, true, EPI>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((gemm_dist_kernel<BM, BN, BK, true, false, EPI>), grid, dim3(256), 0, st, p);
+  } else {
+    if (p.kscale) hipLaunchKernelGGL((gemm_dist_kernel<BM, BN, BK, false, true, EPI>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((gemm_dist_kernel<BM, BN, BK, false, false, EPI>), grid, dim3(256), 0, st, p);
+  }
+}
+
+// epi: a DistEpi (kEpiPlain: plain product, kEpiRbf: the fused RBF epilogue, else one of the other distance epilogues)
 template <int BM, int BN, int BK>
-static void dispatch_tile(const GemmParams& p, int transA, int transB, int nbatch, bool rbf, bool vec, hipStream_t st) {
+static void dispatch_tile(const GemmParams& p, int transA, int transB, int nbatch, int epi, bool vec, hipStream_t st) {
   dim3 grid(cdiv(p.M, BM) * cdiv(p.N, BN), nbatch, p.splitk > 1 ? p.splitk : 1);
-  if (rbf) {
+  const bool rbf = epi == kEpiRbf;
+  if (epi == kEpiMatern12) dispatch_dist<BM, BN, BK, EpiMatern<1>>(p, vec, grid, st);
+  else if (epi == kEpiMatern32) dispatch_dist<BM, BN, BK, EpiMatern<3>>(p, vec, grid, st);
+  else if (epi == kEpiMatern52) dispatch_dist<BM, BN, BK, EpiMatern<5>>(p, vec, grid, st);
+  else if (epi == kEpiDist2) dispatch_dist<BM, BN, BK, EpiDist2>(p, vec, grid, st);
+  else if (rbf) {
     if (vec) dispatch_layout<BM, BN, BK, true, true>(p, 0, 1, grid, st);
     else dispatch_layout<BM, BN, BK, false, true>(p, 0, 1, grid, st);
   } else {
@@ -1559,10 +1588,14 @@ int launch_bwdmat_gemm(const BwdMatArgs& a, int first, int nmat, const GemmParam
 static int g_tile_force = 0;   // vargp_tune_gemm_tile (measurement only)
 
 int launch_gemm(const GemmParams& p, int transA, int transB, int nbatch, bool rbf, hipStream_t st, const char* tag) {
+  return launch_gemm_epi(p, transA, transB, nbatch, rbf ? kEpiRbf : kEpiPlain, st, tag);
+}
+
+int launch_gemm_epi(const GemmParams& p, int transA, int transB, int nbatch, int epi, hipStream_t st, const char* tag) {
   if (p.M <= 0 || p.N <= 0 || nbatch <= 0) return VARGP_OK;
   if (prof_remembering() && strcmp(tag, "replay") != 0) {
     const GemmParams pc = p;
-    prof_remember(tag, [pc, transA, transB, nbatch, rbf](hipStream_t s) { launch_gemm(pc, transA, transB, nbatch, rbf, s, "replay"); });
+    prof_remember(tag, [pc, transA, transB, nbatch, epi](hipStream_t s) { launch_gemm_epi(pc, transA, transB, nbatch, epi, s, "replay"); });
   }
   static const int nofast = [] { const char* e = getenv("VARGP_GEMM_NOFAST"); return e ? atoi(e) : 0; }();   // tuning aid
   const_cast<GemmParams&>(p).nofast = nofast;
@@ -1601,14 +1634,14 @@ int launch_gemm(const GemmParams& p, int transA, int transB, int nbatch, bool rb
   static const int tric64 = [] { const char* e = getenv("VARGP_GEMM_TRIC64"); return e ? atoi(e) : 1; }();   // tuning aid
   const bool tri = p.triA != 0 || p.triB != 0 || (tric64 && p.triC != 0);
   const bool pad64_less = round_up(p.M, 64) < round_up(p.M, 128);
-  if (force == 1) dispatch_tile<128, 128, 16>(p, transA, transB, nbatch, rbf, vec, st);
-  else if (force == 2) dispatch_tile<128, 64, 32>(p, transA, transB, nbatch, rbf, vec, st);
-  else if (force == 3) dispatch_tile<64, 64, 64>(p, transA, transB, nbatch, rbf, vec, st);
+  if (force == 1) dispatch_tile<128, 128, 16>(p, transA, transB, nbatch, epi, vec, st);
+  else if (force == 2) dispatch_tile<128, 64, 32>(p, transA, transB, nbatch, epi, vec, st);
+  else if (force == 3) dispatch_tile<64, 64, 64>(p, transA, transB, nbatch, epi, vec, st);
   // (a transposed A, e.g. V2 = T^T P, is the exception: 400 x 512 x 400 b100 123 vs 136 us with 128 x 64 x 32)
-  else if (t12864 >= 384 && tri && pad64_less && transA == 0) dispatch_tile<64, 64, 64>(p, transA, transB, nbatch, rbf, vec, st);
-  else if (t128 >= 512 && !tri && p.M >= 1024 && p.N >= 1024) dispatch_tile<128, 128, 16>(p, transA, transB, nbatch, rbf, vec, st);
-  else if (t12864 >= 384 && p.M > 64) dispatch_tile<128, 64, 32>(p, transA, transB, nbatch, rbf, vec, st);
-  else dispatch_tile<64, 64, 64>(p, transA, transB, nbatch, rbf, vec, st);
+  else if (t12864 >= 384 && tri && pad64_less && transA == 0) dispatch_tile<64, 64, 64>(p, transA, transB, nbatch, epi, vec, st);
+  else if (t128 >= 512 && !tri && p.M >= 1024 && p.N >= 1024) dispatch_tile<128, 128, 16>(p, transA, transB, nbatch, epi, vec, st);
+  else if (t12864 >= 384 && p.M > 64) dispatch_tile<128, 64, 32>(p, transA, transB, nbatch, epi, vec, st);
+  else dispatch_tile<64, 64, 64>(p, transA, transB, nbatch, epi, vec, st);
   return check_launch("bgemm");
 }
 

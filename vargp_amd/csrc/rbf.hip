@@ -265,6 +265,13 @@ int rbf_prep_norm_launch(const float* theta, const float* x, int64_t xrows, cons
   return check_launch("rbf_prep_norm");
 }
 
+int rbf_final_launch(const float* x, const float* R, const float* P, const float* theta, float* g, float* gtheta, int64_t rows,
+                     int D, int64_t Dp, int S, float kappa, int accumulate, hipStream_t st) {
+  hipLaunchKernelGGL(rbf_final_kernel, dim3(cdiv(D, 64), cdiv(rows, RPB)), dim3(256), 0, st, x, R, P, theta, g, gtheta, rows, D,
+                     Dp, S, kappa, accumulate);
+  return check_launch("rbf_final");
+}
+
 int rbf_direct_launch(const float* X, const float* Y, const float* w, const float* g2, float* K, int64_t ldk, int S,
                       int C, int M, int N, int D, int64_t Dp, int y_shared, hipStream_t st) {
   const int64_t total = (int64_t)S * C * M * N;

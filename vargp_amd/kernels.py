@@ -29,6 +29,11 @@ class RBFKernel(nn.Module):
         Returns (S, ...batch, M, N)  (kernels.py:24-56).  A `y` that is an expand() of one (N, D)
         block over the batch dims (how the reference feeds the minibatch, vargp.py:106) is consumed
         without materialising the copies."""
+        return self._compute(ops.rbf_gram, kern_samples, x, y)
+
+    @staticmethod
+    def _compute(gram, kern_samples, x, y):
+        """compute() around one of the gram ops (theta, X (C, M, D), Y, y_shared) -> (S, C, M, N)."""
         batch = x.shape[:-2]
         M, D = x.shape[-2:]
         X = x.reshape(-1, M, D)
@@ -39,7 +44,7 @@ class RBFKernel(nn.Module):
                 Y, shared = y[(0,) * (y.dim() - 2)], True
             else:
                 Y = y.expand(*batch, N, D).reshape(-1, N, D)
-        K = ops.rbf_gram(kern_samples, X, Y, shared)
+        K = gram(kern_samples, X, Y, shared)
         return K.reshape(kern_samples.shape[0], *batch, M, K.shape[-1])
 
     def compute_diag(self, kern_samples):
@@ -58,6 +63,23 @@ class RBFKernel(nn.Module):
         if self.map_est:
             return torch.tensor(0.0, device=self.log_mean.device)
         return ops.hyper_kl(self.log_mean, self.log_logvar, self.prior_log_mean, self.prior_log_logvar)
+
+
+class MaternKernel(RBFKernel):
+    """Matern kernel, nu in {1/2, 3/2, 5/2}, on the RBF's scaled distance r = |(x - y) / lengthscale|:
+    gamma^2 exp(-r), gamma^2 (1 + sqrt3 r) exp(-sqrt3 r), gamma^2 (1 + sqrt5 r + 5 r^2 / 3) exp(-sqrt5 r).
+    Same hyper-parameters, priors and state dict as RBFKernel (`nu` is a constructor argument, not state); the kernel
+    matrices come from `vargp_matern_gram_{fwd,bwd}`.  Models with this kernel run the composed per-op route."""
+
+    def __init__(self, in_size, nu=2.5, prior_log_mean=None, prior_log_logvar=None, map_est=False):
+        if nu not in (0.5, 1.5, 2.5):
+            raise ValueError(f'MaternKernel: nu must be 0.5, 1.5 or 2.5, got {nu!r}')
+        super().__init__(in_size, prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar, map_est=map_est)
+        self.nu = float(nu)
+
+    def compute(self, kern_samples, x, y=None):
+        nu = self.nu
+        return self._compute(lambda th, X, Y, shared: ops.matern_gram(th, X, Y, shared, nu), kern_samples, x, y)
 
 
 class DeepRBFKernel(RBFKernel):

@@ -21,9 +21,12 @@ import torch.nn as nn
 
 from . import fused, gp_utils, noise, ops
 from .gp_utils import vec2tril, mat2trilvec, cholesky, rev_cholesky, gp_cond, block_joint, linear_marginal_diag
-from .kernels import RBFKernel, DeepRBFKernel
+from .kernels import RBFKernel, DeepRBFKernel, MaternKernel
 from .likelihoods import MulticlassSoftmax, is_gaussian, n_f
 from .ops import LOWER
+
+
+_KERNEL_NU = {'rbf': None, 'matern12': 0.5, 'matern32': 1.5, 'matern52': 2.5}   # create_clf(kernel=)
 
 
 class VARGP(nn.Module):
@@ -419,10 +422,15 @@ class VARGP(nn.Module):
 
     @staticmethod
     def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None,
-                   ep_var_mean=True, map_est_hypers=False, dkl=False):
+                   ep_var_mean=True, map_est_hypers=False, dkl=False, kernel='rbf'):
         """Factory used by the experiment driver (vargp.py:200-243): inducing points at random data
         points per class, hyper-prior = previous task's hyper-posterior (popped from prev_params[-1],
-        which is mutated like the reference does)."""
+        which is mutated like the reference does).  kernel: 'rbf' (the reference's), or 'matern12' / 'matern32' /
+        'matern52' (MaternKernel; not with dkl).  The name is not part of a checkpoint: give it again on reload."""
+        if kernel not in _KERNEL_NU:
+            raise ValueError(f'create_clf: kernel must be one of {sorted(_KERNEL_NU)}, got {kernel!r}')
+        if dkl and kernel != 'rbf':
+            raise ValueError('create_clf: dkl=True needs kernel="rbf" (DeepRBFKernel has no Matern head)')
         N = len(dataset)
         out_size = torch.unique(dataset.targets).size(0)
         z = torch.stack([dataset[torch.randperm(N)[:M]][0] for _ in range(out_size)])
@@ -437,13 +445,16 @@ class VARGP(nn.Module):
                 for k in [k for k in p if k.startswith('kernel')]:
                     p.pop(k)
         if dkl:
-            kernel = DeepRBFKernel(z.size(-1), prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
-                                   map_est=map_est_hypers)
+            kern = DeepRBFKernel(z.size(-1), prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
+                                 map_est=map_est_hypers)
             if phi_params:
-                kernel.phi.load_state_dict(phi_params)
+                kern.phi.load_state_dict(phi_params)
+        elif kernel != 'rbf':
+            kern = MaternKernel(z.size(-1), nu=_KERNEL_NU[kernel], prior_log_mean=prior_log_mean,
+                                prior_log_logvar=prior_log_logvar, map_est=map_est_hypers)
         else:
-            kernel = RBFKernel(z.size(-1), prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
-                               map_est=map_est_hypers)
+            kern = RBFKernel(z.size(-1), prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
+                             map_est=map_est_hypers)
         likelihood = MulticlassSoftmax(n_f=n_f)
-        return VARGP(z, kernel, likelihood, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean,
+        return VARGP(z, kern, likelihood, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean,
                      prev_params=prev_params)
