@@ -51,7 +51,7 @@ class JsonlLogger:
 def train(task_id, train_set, val_set, test_set, ep_var_mean=True, map_est_hypers=False, dkl=False,
           epochs=1, M=20, n_f=10, n_var_samples=3, batch_size=512, lr=1e-2, beta=1.0,
           eval_interval=10, patience=20, prev_params=None, logger=None, device=None, graph=False, seed=None,
-          retrain=False, eval_shared_hypers=False, dataloader=False, kernel='rbf'):
+          retrain=False, eval_shared_hypers=False, dataloader=False, kernel='rbf', native_kernel=False):
     if retrain:      # the variant of experiments/vargp_retrain.py:14-19 (earlier tasks' inducing parameters re-optimised)
         from vargp_amd.vargp_retrain import VARGPRetrain
         assert kernel == 'rbf', '--retrain builds its model with the RBF kernel'
@@ -59,7 +59,8 @@ def train(task_id, train_set, val_set, test_set, ep_var_mean=True, map_est_hyper
         graph = False
     else:
         gp = VARGP.create_clf(train_set, M=M, n_f=n_f, n_var_samples=n_var_samples, prev_params=prev_params,
-                              ep_var_mean=ep_var_mean, map_est_hypers=map_est_hypers, dkl=dkl, kernel=kernel).to(device)
+                              ep_var_mean=ep_var_mean, map_est_hypers=map_est_hypers, dkl=dkl, kernel=kernel,
+                              native_kernel=native_kernel).to(device)
     stopper = EarlyStopper(patience=patience)
     N = len(train_set)
     # the program's counter-based noise generator is keyed by the run's seed (the reference draws from the torch global
@@ -185,7 +186,7 @@ def toy(args):
         toy_test.filter_by_class(range(2 * t + 2))
         sd = train(t, toy_train, toy_val, toy_test, epochs=args.epochs, M=args.M, lr=args.lr, beta=args.beta,
                    batch_size=args.batch_size, ep_var_mean=args.ep_var_mean, map_est_hypers=args.map_est_hypers,
-                   dkl=args.dkl, kernel=args.kernel, prev_params=prev_params, logger=logger, device=device, patience=-1,
+                   dkl=args.dkl, kernel=args.kernel, native_kernel=args.native_kernel, prev_params=prev_params, logger=logger, device=device, patience=-1,
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed, retrain=args.retrain,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader)
         prev_params.append(sd)
@@ -210,7 +211,7 @@ def split_mnist(args):
         mnist_test.filter_by_class(range(2 * t + 2))
         sd = train(t, mnist_train, mnist_val, mnist_test, epochs=args.epochs, M=args.M, lr=args.lr, beta=args.beta,
                    batch_size=args.batch_size, ep_var_mean=args.ep_var_mean, map_est_hypers=args.map_est_hypers,
-                   dkl=args.dkl, kernel=args.kernel, prev_params=prev_params, logger=logger, device=device,
+                   dkl=args.dkl, kernel=args.kernel, native_kernel=args.native_kernel, prev_params=prev_params, logger=logger, device=device,
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader)
         prev_params.append(sd)
@@ -238,14 +239,14 @@ def permuted_mnist(args):
         mnist_test[-1].set_task(tasks[t])
         sd = train(t, mnist_train, ConcatDataset(mnist_val), ConcatDataset(mnist_test), epochs=args.epochs, M=args.M,
                    lr=args.lr, beta=args.beta, batch_size=args.batch_size, ep_var_mean=args.ep_var_mean,
-                   map_est_hypers=args.map_est_hypers, dkl=args.dkl, kernel=args.kernel, prev_params=prev_params, logger=logger,
+                   map_est_hypers=args.map_est_hypers, dkl=args.dkl, kernel=args.kernel, native_kernel=args.native_kernel, prev_params=prev_params, logger=logger,
                    device=device, eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader)
         prev_params.append(sd)
     logger.close()
 
 
-def main(argv=None):
+def parse_args(argv=None):
     defaults = {   # reference defaults: experiments/vargp.py:76-78,107-109,143-145
         'toy': dict(epochs=5000, M=20, lr=1e-2, beta=1.0),
         's-mnist': dict(epochs=500, M=60, lr=3e-3, beta=10.0),
@@ -266,6 +267,9 @@ def main(argv=None):
         sp.add_argument('--dkl', type=lambda v: str(v).lower() not in ('0', 'false'), default=False)
         sp.add_argument('--kernel', choices=('rbf', 'matern12', 'matern32', 'matern52'), default='rbf',
                         help='covariance function (not stored in checkpoints: give it again when reloading one)')
+        sp.add_argument('--native_kernel', action='store_true',
+                        help='run a Matern model on the native block ELBO program instead of the composed per-op route '
+                             '(needs --kernel matern12 / matern32 / matern52 and no --dkl; not stored in checkpoints)')
         sp.add_argument('--seed', type=int, default=None)
         sp.add_argument('--eval_interval', type=int, default=10)
         sp.add_argument('--log_dir', default=os.path.join('runs', f'{name}-{int(time.time())}'))
@@ -289,6 +293,14 @@ def main(argv=None):
         if name == 'p-mnist':
             sp.add_argument('--n_tasks', type=int, default=10)
     args = ap.parse_args(argv)
+    if args.native_kernel and (args.kernel == 'rbf' or args.dkl or getattr(args, 'retrain', False)):
+        ap.error('--native_kernel selects the native route of a Matern kernel: it needs --kernel matern12 / matern32 / matern52 '
+                 'and neither --dkl nor --retrain')
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     {'toy': toy, 's-mnist': split_mnist, 's_mnist': split_mnist, 'p-mnist': permuted_mnist,
      'p_mnist': permuted_mnist}[args.cmd](args)
 

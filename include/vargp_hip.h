@@ -335,7 +335,16 @@ typedef struct vargp_elbo_tn_desc {
    * right behind the blocked factorisation, before the products that consume it */
   int32_t* info_host;
   void* info_event;
+  /* The stationary kernel that builds K(z_<=t) and K_uf: 0 = RBF (a zero-initialised descriptor is the program described
+   * above), 1 | 3 | 5 = Matern with nu = 1/2, 3/2, 5/2 on the same scaled distance (same hyper-parameters).  The reference has
+   * no Matern kernel: this replaces kernels.MaternKernel.compute of this package on the composed per-op route
+   * (vargp_matern_gram_fwd / _bwd), with the same definition entry by entry (d2 clamped at 0, exactly gamma^2 on the diagonal
+   * of K(z, z), the nu = 1/2 derivative defined as 0 where d2 <= 0).  Every entry below that takes the descriptor returns
+   * VARGP_EINVAL for any other value.  The workspace sizes do not depend on it. */
+  int32_t kernel_nu2;
 } vargp_elbo_tn_desc;
+/* sizeof(vargp_elbo_tn_desc) as the library was compiled (bindings check their mirror of the struct against it) */
+size_t vargp_elbo_tn_desc_bytes(void);
 size_t vargp_elbo_tn_workspace_bytes(int S, int C, int M, int D, int B, int F, int nblk);
 /* Workspace of a program that only ever evaluates predictive moments (VARGP.forward / predict, var_gp/vargp.py:115-131,
  * 196-198: no likelihood, no KL, no backward): none of the gradient buffers.  Set d->forward_only = 1. */

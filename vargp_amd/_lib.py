@@ -67,6 +67,7 @@ class ElboTnDesc(Structure):
         ('forward_only', c_int32), ('defer_hyper', c_int32), ('ext_lik', c_int32),
         ('eps_u', c_void_p), ('n_v', c_int32), ('no_var_mean', c_int32),
         ('info_host', c_void_p), ('info_event', c_void_p),
+        ('kernel_nu2', c_int32),
     ]
 
 
@@ -121,6 +122,7 @@ _SIGNATURES = {
     'vargp_bias_act_bwd': (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, _P]),
     'vargp_elbo_tn_workspace_bytes': (c_size_t, [c_int] * 7),
     'vargp_elbo_tn_workspace_bytes_fwd': (c_size_t, [c_int] * 7),
+    'vargp_elbo_tn_desc_bytes': (c_size_t, []),
     'vargp_elbo_tn_fwd': (c_int, [POINTER(ElboTnDesc), _P]),
     'vargp_elbo_tn_bwd': (c_int, [POINTER(ElboTnDesc)] + [_P] * 7),
     'vargp_elbo_tn_begin': (c_int, [POINTER(ElboTnDesc), _P]),

@@ -312,6 +312,9 @@ int rbf_splitk(int M, int N, int K, int nbatch);
 constexpr int kRbfDirectD = 32;   // D <= this: kernel matrices from the direct (no-cancellation) distance form
 int rbf_direct_launch(const float* X, const float* Y, const float* w, const float* g2, float* K, int64_t ldk, int S,
                       int C, int M, int N, int D, int64_t Dp, int y_shared, hipStream_t st);
+// the same with a Matern / distance epilogue (matern.hip; epi: kEpiMatern12 / 32 / 52 / kEpiDist2), K dense [S, C, M, N]
+int matern_direct_launch(const float* X, const float* Y, const float* w, const float* g2, float* K, int S, int C, int M, int N,
+                         int D, int64_t Dp, int y_shared, int epi, hipStream_t st);
 int rbf_gram_fwd_impl(const float* theta, const float* X, const float* Y, float* K, int S, int C, int M, int N, int D,
                       int y_shared, void* ws, size_t ws_bytes, int sym_out, hipStream_t st);
 int rbf_gram_bwd_impl(const float* theta, const float* X, const float* Y, const float* K, const float* gK, float* gX,

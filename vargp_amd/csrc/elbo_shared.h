@@ -208,14 +208,30 @@ struct GvecArgs {
 //                  2 sum W into gtheta[s, D]
 //   next nuu     : K_uu, one wave per row: Wuu = W + W^T, r_uu = its row sums, sum Wuu (= 2 sum W) into gtheta[s, D]
 //   rest         : the packed-Cholesky-vector gradient (t0_gvec_role), which only shares the launch
-static __global__ __launch_bounds__(256) void t0_w_kernel(const float* __restrict__ RK, float* __restrict__ gRK,
-                                                   const float* __restrict__ Kuu, const float* __restrict__ gKuu,
-                                                   float* __restrict__ Wuu, float* __restrict__ r_uu,
-                                                   float* __restrict__ r_uf, float* __restrict__ c_uf,
-                                                   float* __restrict__ gtheta, int S, int C, int M, int B, int D, int NR,
-                                                   int LD, int gx, int gy, int nuf, int nuu, const float* __restrict__ vec,
-                                                   const float* __restrict__ Lu, const float* __restrict__ seeds,
-                                                   float* __restrict__ gvec, int sym_guu) {
+// NU2 = 0: the RBF (t0_w_kernel).  NU2 = 1 | 3 | 5 (t0_w_matern_kernel, block program only): the weight of gK is
+// -2 g2 dk/dd2 = matern_w<NU2>(g2, d2) instead of K, with d2 read from D2uf (laid out as the K_uf block of RK: same row stride and
+// offset) and D2uu (as Kuu); gtheta[s, D] still takes 2 sum gK o K.  D2uf / D2uu == NULL (NU2 = 1 only, a measuring aid):
+// d2 = log(K / g2)^2, the inverse of k = g2 exp(-sqrt d2).
+template <int NU2>
+__device__ __forceinline__ float t0_w_weight(const float* __restrict__ D2, int64_t off, float k, float g) {
+  if constexpr (NU2 == 0) return k;
+  else {
+    float d2 = 0.f;
+    if (D2) d2 = D2[off];
+    else if constexpr (NU2 == 1) { const float a = logf(k / g); d2 = a * a; }
+    return matern_w<NU2>(g, d2);
+  }
+}
+template <int NU2>
+__device__ __forceinline__ void t0_w_body(const float* __restrict__ RK, float* __restrict__ gRK,
+                                          const float* __restrict__ Kuu, const float* __restrict__ gKuu,
+                                          float* __restrict__ Wuu, float* __restrict__ r_uu,
+                                          float* __restrict__ r_uf, float* __restrict__ c_uf,
+                                          float* __restrict__ gtheta, int S, int C, int M, int B, int D, int NR,
+                                          int LD, int gx, int gy, int nuf, int nuu, const float* __restrict__ vec,
+                                          const float* __restrict__ Lu, const float* __restrict__ seeds,
+                                          float* __restrict__ gvec, int sym_guu, const float* __restrict__ D2uf,
+                                          const float* __restrict__ D2uu, const float* __restrict__ g2) {
   __shared__ float red[4];
   // block order: the packed-vector gradient first (long per-thread loops: started early they finish under the rest),
   // then K_uu, then K_uf
@@ -235,6 +251,8 @@ static __global__ __launch_bounds__(256) void t0_w_kernel(const float* __restric
     const bool cok = col < B;
     const int cc = cok ? col : B - 1;
     const int rend = min(kWRows, CM - row0);
+    float gam = 0.f, ks = 0.f;                                 // (Matern) gamma^2 of the sample, sum gK o K
+    if constexpr (NU2 != 0) gam = g2[s];
     if ((B & 3) == 0 && (kWRows & 3) == 0) {
       // 16 bytes per lane: the block's 256 columns are one float4 per lane, wave w takes the rows w, w + 4, ... of the block.
       // Per thread kWRows / 4 pairs of loads and one store each instead of kWRows pairs of scalar ones, and one wave
@@ -259,6 +277,12 @@ static __global__ __launch_bounds__(256) void t0_w_kernel(const float* __restric
         const int rr = wv + 4 * q;
         const bool ok = c4ok && rr < rend;
         float4 v = make_float4(kv4[q].x * gv4[q].x, kv4[q].y * gv4[q].y, kv4[q].z * gv4[q].z, kv4[q].w * gv4[q].w);
+        if constexpr (NU2 != 0) {
+          const int64_t off = (s * CM + row0 + min(rr, rend - 1)) * LD + NR + c4c;
+          if (ok) ks += (v.x + v.y) + (v.z + v.w);
+          v = make_float4(gv4[q].x * t0_w_weight<NU2>(D2uf, off, kv4[q].x, gam), gv4[q].y * t0_w_weight<NU2>(D2uf, off + 1, kv4[q].y, gam),
+                          gv4[q].z * t0_w_weight<NU2>(D2uf, off + 2, kv4[q].z, gam), gv4[q].w * t0_w_weight<NU2>(D2uf, off + 3, kv4[q].w, gam));
+        }
         if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (ok) *reinterpret_cast<float4*>(gRK + (s * CM + row0 + rr) * LD + NR + c4) = v;
         cs4.x += v.x; cs4.y += v.y; cs4.z += v.z; cs4.w += v.w;
@@ -269,7 +293,9 @@ static __global__ __launch_bounds__(256) void t0_w_kernel(const float* __restric
       __syncthreads();
       const float csum = (cred[0][threadIdx.x] + cred[1][threadIdx.x]) + (cred[2][threadIdx.x] + cred[3][threadIdx.x]);
       if (col < B) atomicAdd(&c_uf[s * B + col], csum);
-      const float tot = block_sum<256>(col < B ? csum : 0.f, red);
+      float mine = col < B ? csum : 0.f;
+      if constexpr (NU2 != 0) mine = ks;
+      const float tot = block_sum<256>(mine, red);
       if (threadIdx.x == 0) atomicAdd(&gtheta[s * (D + 1) + D], 2.f * tot);
       return;
     }
@@ -285,14 +311,19 @@ static __global__ __launch_bounds__(256) void t0_w_kernel(const float* __restric
 #pragma unroll
     for (int rr = 0; rr < kWRows; ++rr) {
       const bool ok = cok && rr < rend;
-      const float v = ok ? kv[rr] * gv[rr] : 0.f;
+      float v = ok ? kv[rr] * gv[rr] : 0.f;
+      if constexpr (NU2 != 0) {
+        ks += v;
+        const int64_t off = (s * CM + row0 + min(rr, rend - 1)) * LD + NR + cc;
+        v = ok ? gv[rr] * t0_w_weight<NU2>(D2uf, off, kv[rr], gam) : 0.f;
+      }
       if (ok) gRK[(s * CM + row0 + rr) * LD + NR + col] = v;
       csum += v;
       const float rs = wave_sum(v);
       if (lane == 0 && rs != 0.f) atomicAdd(&r_uf[s * CM + row0 + rr], rs);
     }
     if (cok) atomicAdd(&c_uf[s * B + col], csum);
-    const float tot = block_sum<256>(csum, red);
+    const float tot = block_sum<256>(NU2 != 0 ? ks : csum, red);
     if (threadIdx.x == 0) atomicAdd(&gtheta[s * (D + 1) + D], 2.f * tot);
     return;
   }
@@ -308,7 +339,8 @@ static __global__ __launch_bounds__(256) void t0_w_kernel(const float* __restric
   // before its stores
   constexpr int RW = kUuRows / 4;
   const int wv = threadIdx.x >> 6;
-  float acc[RW], dsum = 0.f;
+  float acc[RW], dsum = 0.f, gam = 0.f;
+  if constexpr (NU2 != 0) gam = g2[b / C];
 #pragma unroll
   for (int r = 0; r < RW; ++r) acc[r] = 0.f;
   for (int j0 = 0; j0 < M; j0 += 128) {
@@ -332,12 +364,18 @@ static __global__ __launch_bounds__(256) void t0_w_kernel(const float* __restric
         const int j = j0 + 64 * h + lane;
         if (i < i1 && j < M) {
           // sym_guu: gK_uu is symmetric (it comes out of the Cholesky backward), so W + W^T = 2 W: no transposed reads
-          const float v = sym_guu ? 2.f * kv[r][h] * gv[r][h] : kv[r][h] * gv[r][h] + kt[r][h] * gt[r][h];
+          float v = sym_guu ? 2.f * kv[r][h] * gv[r][h] : kv[r][h] * gv[r][h] + kt[r][h] * gt[r][h];
           // the diagonal counts for gamma only (K_ii = gamma^2: see rbf_w_self_kernel, rbf.hip)
           const bool dg = i == j;
+          if constexpr (NU2 != 0) {      // dsum = sum gK o K over every entry; d2 is symmetric: one weight for both mirrored entries
+            dsum += v;
+            v = (sym_guu ? 2.f * gv[r][h] : gv[r][h] + gt[r][h]) *
+                t0_w_weight<NU2>(D2uu ? D2uu + b * M * M : nullptr, (int64_t)i * M + j, kv[r][h], gam);
+          } else {
+            dsum += dg ? v : 0.f;
+          }
           Wuu[b * M * M + (int64_t)i * M + j] = dg ? 0.f : v;
           acc[r] += dg ? 0.f : v;
-          dsum += dg ? v : 0.f;
         }
       }
     }
@@ -348,13 +386,37 @@ static __global__ __launch_bounds__(256) void t0_w_kernel(const float* __restric
     const float a = wave_sum(acc[r]);
     if (i < i1) {
       if (lane == 0) r_uu[b * M + i] = a;
-      tot += a;
+      if constexpr (NU2 == 0) tot += a;
     }
   }
   tot += wave_sum(dsum);
   // every lane of a wave holds the wave's total: count it once
   const float t = block_sum<256>(lane == 0 ? tot : 0.f, red);
   if (threadIdx.x == 0) atomicAdd(&gtheta[(b / C) * (D + 1) + D], t);
+}
+
+static __global__ __launch_bounds__(256) void t0_w_kernel(const float* __restrict__ RK, float* __restrict__ gRK,
+                                                   const float* __restrict__ Kuu, const float* __restrict__ gKuu,
+                                                   float* __restrict__ Wuu, float* __restrict__ r_uu,
+                                                   float* __restrict__ r_uf, float* __restrict__ c_uf,
+                                                   float* __restrict__ gtheta, int S, int C, int M, int B, int D, int NR,
+                                                   int LD, int gx, int gy, int nuf, int nuu, const float* __restrict__ vec,
+                                                   const float* __restrict__ Lu, const float* __restrict__ seeds,
+                                                   float* __restrict__ gvec, int sym_guu) {
+  t0_w_body<0>(RK, gRK, Kuu, gKuu, Wuu, r_uu, r_uf, c_uf, gtheta, S, C, M, B, D, NR, LD, gx, gy, nuf, nuu, vec, Lu, seeds, gvec,
+               sym_guu, nullptr, nullptr, nullptr);
+}
+// the Matern weight (block program): no packed-vector role (gridDim.x == nuf + nuu)
+template <int NU2>
+static __global__ __launch_bounds__(256) void t0_w_matern_kernel(const float* __restrict__ Kuf, float* __restrict__ gKuf,
+                                                          const float* __restrict__ Kuu, const float* __restrict__ gKuu,
+                                                          float* __restrict__ Wuu, float* __restrict__ r_uu,
+                                                          float* __restrict__ r_uf, float* __restrict__ c_uf,
+                                                          float* __restrict__ gtheta, int S, int C, int M, int B, int D,
+                                                          int gx, int gy, int nuf, int nuu, const float* __restrict__ D2uf,
+                                                          const float* __restrict__ D2uu, const float* __restrict__ g2) {
+  t0_w_body<NU2>(Kuf, gKuf, Kuu, gKuu, Wuu, r_uu, r_uf, c_uf, gtheta, S, C, M, B, D, 0, B, gx, gy, nuf, nuu, nullptr, nullptr,
+                 nullptr, nullptr, 1, D2uf, D2uu, g2);
 }
 
 // minibatch side of the lengthscale gradient: gtheta[s, d] += w_sd sum_b x_bd^2 c_uf[s, b]; block (bx, by) = 64 columns of D x

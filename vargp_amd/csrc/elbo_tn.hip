@@ -19,6 +19,7 @@
 // Gradients reach theta (through both kernel matrices), the current z (last M rows of each class), u_mean, u_tril_vec.
 #include "common.h"
 #include "elbo_shared.h"
+#include <string.h>
 
 namespace vargp {
 
@@ -641,8 +642,93 @@ __global__ void tn_kl_bwd_kernel(const float* __restrict__ QPs, float* __restric
   if (col == 0 || (col >= 4 && col - 4 <= i && col < 4 + M)) gQPs[off] += g * QPs[off];
 }
 
+// kernel_nu2 of the descriptor: 0 = RBF, 1 | 3 | 5 = Matern nu = 1/2, 3/2, 5/2 (include/vargp_hip.h)
+static bool tn_nu2_ok(int nu2) { return nu2 == 0 || nu2 == 1 || nu2 == 3 || nu2 == 5; }
+static int tn_epi(int nu2) { return nu2 == 1 ? kEpiMatern12 : nu2 == 3 ? kEpiMatern32 : nu2 == 5 ? kEpiMatern52 : kEpiRbf; }
+#define TN_REQUIRE_NU2(d, who) \
+  VARGP_REQUIRE(tn_nu2_ok((d)->kernel_nu2), "%s: kernel_nu2 = %d (0: RBF; 1, 3 or 5: Matern nu = 1/2, 3/2, 5/2)", who, (d)->kernel_nu2)
+
+// a kernel matrix of the program: launch_gemm with the descriptor's epilogue (the RBF launch is the one it always was)
+static int tn_gram_gemm(const GemmParams& p, int nbatch, int nu2, hipStream_t st, const char* rbf_tag, const char* matern_tag) {
+  if (nu2 == 0) return launch_gemm(p, 0, 1, nbatch, true, st, rbf_tag);
+  return launch_gemm_epi(p, 0, 1, nbatch, tn_epi(nu2), st, matern_tag);
+}
+
+// Matern backward: W = gK o (-2 g2 dk/dd2) needs the scaled squared distances, which K does not give back.  They are
+// RECOMPUTED here -- the forward's two distance products once more with the epilogue EpiDist2 (operands, norms and tile choice
+// are the forward's, still in the workspace; 0 on the diagonal of K_all) -- into buffers that are dead by now: d2_uf into gP
+// (consumed by the gK_uf product), d2_all into the Cholesky backward's scratch.  No workspace beyond the RBF program's, and
+// nothing of the forward is overwritten (a second backward on the same forward stays legal).  DESIGN.md section 9 has the
+// measurement against the alternatives.  uf / uu: which of the two this call needs (the tiled ELBO: uf per tile, uu at the end).
+static int tn_matern_d2(const vargp_elbo_tn_desc* d, const TnWs& o, const float* x, int B, bool uf, bool uu, float* d2uf, float* d2uu,
+                        hipStream_t st) {
+  const int S = d->S, C = d->C, D = d->D, Mt = o.Mt, SC = S * C;
+  const int64_t MtMt = (int64_t)Mt * Mt, MtB = (int64_t)Mt * B, zrows = (int64_t)C * Mt;
+  int rc;
+  if (D <= kRbfDirectD) {
+    if (uu) { rc = matern_direct_launch(d->z_all, nullptr, o.w, o.g2, d2uu, S, C, Mt, Mt, D, o.Dp, 0, kEpiDist2, st); if (rc) return rc; }
+    if (uf) { rc = matern_direct_launch(d->z_all, x, o.w, o.g2, d2uf, S, C, Mt, B, D, o.Dp, 1, kEpiDist2, st); if (rc) return rc; }
+    return VARGP_OK;
+  }
+  if (uu) {
+    GemmParams p0{};
+    p0.A = o.zs; p0.B = d->z_all; p0.C = d2uu;
+    p0.M = Mt; p0.N = Mt; p0.K = D; p0.lda = D; p0.ldb = D; p0.ldc = Mt;
+    p0.nb1 = C; p0.nb2 = 1;
+    p0.sA[0] = zrows * D; p0.sA[1] = (int64_t)Mt * D; p0.sB[1] = (int64_t)Mt * D;
+    p0.sC[0] = C * MtMt; p0.sC[1] = MtMt;
+    p0.alpha = 1.f;
+    p0.kscale = nullptr; p0.ks_ld = o.Dp; p0.g2 = o.g2;
+    p0.na = o.na; p0.sNa[0] = zrows; p0.sNa[1] = Mt;
+    p0.nbv = o.na; p0.sNb[0] = zrows; p0.sNb[1] = Mt;
+    p0.same_xy = 1; p0.triC = 2; p0.symout = 1;
+    rc = launch_gemm_epi(p0, 0, 1, SC, kEpiDist2, st, "matern_kuu_d2_gemm");
+    if (rc) return rc;
+  }
+  if (uf) {
+    GemmParams pf{};
+    pf.A = d->z_all; pf.B = o.xs; pf.C = d2uf;
+    pf.M = C * Mt; pf.N = B; pf.K = D; pf.lda = D; pf.ldb = D; pf.ldc = B;
+    pf.nb1 = 1; pf.nb2 = 1;
+    pf.sB[0] = (int64_t)B * D;
+    pf.sC[0] = (int64_t)C * MtB;
+    pf.alpha = 1.f;
+    pf.kscale = nullptr; pf.ks_ld = o.Dp; pf.g2 = o.g2;
+    pf.na = o.na; pf.sNa[0] = zrows;
+    pf.nbv = o.nb; pf.sNb[0] = B;
+    rc = launch_gemm_epi(pf, 0, 1, S, kEpiDist2, st, "matern_kuf_d2_gemm");
+    if (rc) return rc;
+  }
+  return VARGP_OK;
+}
+
+// the W pass of either kernel (elbo_shared.h): nuf blocks of the K_uf role (0: none), nuu of the K_all role (0: none)
+static void tn_w_launch(int nu2, const TnWs& o, int S, int C, int B, int D, int gx, int gy, int nuf, int nuu, const float* seeds,
+                        const float* d2uf, const float* d2uu, hipStream_t st) {
+  const dim3 grid(nuf + nuu), blk(256);
+  const int Mt = o.Mt;
+  if (nu2 == 0)
+    hipLaunchKernelGGL(t0_w_kernel, grid, blk, 0, st, o.Kuf, o.gKuf, o.Kall, o.gK, o.Wuu, o.r_uu, o.r_uf, o.c_uf, o.gtheta, S, C, Mt, B, D,
+                       0, B, gx, gy, nuf, nuu, (const float*)nullptr, (const float*)nullptr, seeds, (float*)nullptr, 1);
+  else if (nu2 == 1)
+    hipLaunchKernelGGL(t0_w_matern_kernel<1>, grid, blk, 0, st, o.Kuf, o.gKuf, o.Kall, o.gK, o.Wuu, o.r_uu, o.r_uf, o.c_uf, o.gtheta, S, C,
+                       Mt, B, D, gx, gy, nuf, nuu, d2uf, d2uu, o.g2);
+  else if (nu2 == 3)
+    hipLaunchKernelGGL(t0_w_matern_kernel<3>, grid, blk, 0, st, o.Kuf, o.gKuf, o.Kall, o.gK, o.Wuu, o.r_uu, o.r_uf, o.c_uf, o.gtheta, S, C,
+                       Mt, B, D, gx, gy, nuf, nuu, d2uf, d2uu, o.g2);
+  else
+    hipLaunchKernelGGL(t0_w_matern_kernel<5>, grid, blk, 0, st, o.Kuf, o.gKuf, o.Kall, o.gK, o.Wuu, o.r_uu, o.r_uf, o.c_uf, o.gtheta, S, C,
+                       Mt, B, D, gx, gy, nuf, nuu, d2uf, d2uu, o.g2);
+}
+// measuring aid: VARGP_TN_D2=invert takes d2 of a nu = 1/2 program from K itself instead of recomputing it
+static bool tn_d2_invert(int nu2) {
+  static const int inv = [] { const char* e = getenv("VARGP_TN_D2"); return (e && strcmp(e, "invert") == 0) ? 1 : 0; }();
+  return inv && nu2 == 1;
+}
+
 static int check_tn(const vargp_elbo_tn_desc* d, const char* who, bool tiled = false) {
   VARGP_REQUIRE(d, "%s: null descriptor", who);
+  TN_REQUIRE_NU2(d, who);
   VARGP_REQUIRE(d->S > 0 && d->C > 0 && d->M > 0 && d->D > 0 && d->B > 0 && d->F > 0 && d->nblk > 0, "%s: bad dims", who);
   VARGP_REQUIRE(d->log_mean && d->z && d->u_mean && d->u_tril_vec && d->z_all && d->rk_all && d->x && d->scalars && d->info &&
                     d->ws, "%s: null pointer", who);
@@ -688,6 +774,8 @@ extern "C" size_t vargp_elbo_tn_workspace_bytes(int S, int C, int M, int D, int 
   return carve_tn(nullptr, S, C, M, D, B, F, nblk).bytes + 256;
 }
 
+extern "C" size_t vargp_elbo_tn_desc_bytes(void) { return sizeof(vargp_elbo_tn_desc); }
+
 extern "C" size_t vargp_elbo_tn_workspace_bytes_fwd(int S, int C, int M, int D, int B, int F, int nblk) {
   return carve_tn(nullptr, S, C, M, D, B, F, nblk, true).bytes + 256;
 }
@@ -695,6 +783,7 @@ extern "C" size_t vargp_elbo_tn_workspace_bytes_fwd(int S, int C, int M, int D, 
 
 extern "C" int vargp_elbo_tn_moments(const vargp_elbo_tn_desc* d, float** mu, float** var) {
   VARGP_REQUIRE(d && d->ws && mu && var, "elbo_tn_moments: null pointer");
+  TN_REQUIRE_NU2(d, "elbo_tn_moments");
   const TnWs o = carve_tn(d->ws, d->S, d->C, d->M, d->D, d->B, d->F, d->nblk, d->forward_only != 0);
   *mu = o.mu; *var = o.var;
   return VARGP_OK;
@@ -702,6 +791,7 @@ extern "C" int vargp_elbo_tn_moments(const vargp_elbo_tn_desc* d, float** mu, fl
 
 extern "C" int vargp_elbo_tn_lik_buffers(const vargp_elbo_tn_desc* d, float** mu, float** var, float** gmu, float** gvar) {
   VARGP_REQUIRE(d && d->ws && !d->forward_only, "elbo_tn_lik_buffers: null pointer / forward_only program");
+  TN_REQUIRE_NU2(d, "elbo_tn_lik_buffers");
   const TnWs o = carve_tn(d->ws, d->S, d->C, d->M, d->D, d->B, d->F, d->nblk, false);
   if (mu) *mu = o.mu;
   if (var) *var = o.var;
@@ -752,10 +842,13 @@ extern "C" int vargp_elbo_tn_fwd(const vargp_elbo_tn_desc* d, vargp_stream_t str
   GemmParams pf{};       // K_uf = rbf(z_all, x): the classes' inducing points are just more rows of one [C*Mt, D] x [D, B] product
   rc = rbf_prep_norm_launch(o.theta, d->z_all, zrows, d->x, B, o.w, o.g2, o.na, o.nb, S, D, o.Dp, st, o.xs, o.zs);
   if (rc) return rc;
+  const int nu2 = d->kernel_nu2;
   if (!mfma) {           // small input dimension: direct (cancellation-free) distances
-    rc = rbf_direct_launch(d->z_all, nullptr, o.w, o.g2, o.Kall, Mt, S, C, Mt, Mt, D, o.Dp, 0, st);
+    rc = nu2 ? matern_direct_launch(d->z_all, nullptr, o.w, o.g2, o.Kall, S, C, Mt, Mt, D, o.Dp, 0, tn_epi(nu2), st)
+             : rbf_direct_launch(d->z_all, nullptr, o.w, o.g2, o.Kall, Mt, S, C, Mt, Mt, D, o.Dp, 0, st);
     if (rc) return rc;
-    rc = rbf_direct_launch(d->z_all, d->x, o.w, o.g2, o.Kuf, B, S, C, Mt, B, D, o.Dp, 1, st);
+    rc = nu2 ? matern_direct_launch(d->z_all, d->x, o.w, o.g2, o.Kuf, S, C, Mt, B, D, o.Dp, 1, tn_epi(nu2), st)
+             : rbf_direct_launch(d->z_all, d->x, o.w, o.g2, o.Kuf, B, S, C, Mt, B, D, o.Dp, 1, st);
     if (rc) return rc;
     kuf_done = true;
   } else {
@@ -772,7 +865,7 @@ extern "C" int vargp_elbo_tn_fwd(const vargp_elbo_tn_desc* d, vargp_stream_t str
     static const int ksym = [] { const char* e = getenv("VARGP_TN_KSYM"); return e ? atoi(e) : 1; }();   // tuning aid
     p0.same_xy = 1;
     if (ksym) { p0.triC = 2; p0.symout = 1; }
-    rc = launch_gemm(p0, 0, 1, SC, true, st, "rbf_kuu_gemm");
+    rc = tn_gram_gemm(p0, SC, nu2, st, "rbf_kuu_gemm", "matern_kuu_gemm");
     if (rc) return rc;
     pf.A = d->z_all; pf.B = o.xs; pf.C = o.Kuf;
     pf.M = C * Mt; pf.N = B; pf.K = D; pf.lda = D; pf.ldb = D; pf.ldc = B;
@@ -791,7 +884,9 @@ extern "C" int vargp_elbo_tn_fwd(const vargp_elbo_tn_desc* d, vargp_stream_t str
   constexpr int kMaxSlices = 24;   // one slice per pivot chain up to Mt = 2400
   GemmParams slices[kMaxSlices];
   int nsl = 0, consumed = 0;
-  if (!kuf_done) {
+  // (Matern: the merged factorisation + GEMM kernels carry the RBF epilogue only, so K_uf is launched by itself behind the
+  //  factorisation instead of beside its pivot chains)
+  if (!kuf_done && nu2 == 0) {
     const int npanel = Mt <= 100 ? 1 : cdiv(Mt, 100);
     nsl = std::min(std::min(npanel, kMaxSlices), std::max(1, (int)(zrows / 128)));
     const int64_t per = round_up(cdiv(zrows, nsl), 64);
@@ -814,7 +909,7 @@ extern "C" int vargp_elbo_tn_fwd(const vargp_elbo_tn_desc* d, vargp_stream_t str
   }
   if (!kuf_done) {
     if (consumed == 0) {
-      rc = launch_gemm(pf, 0, 1, S, true, st, "rbf_kuf_gemm");
+      rc = tn_gram_gemm(pf, S, nu2, st, "rbf_kuf_gemm", "matern_kuf_gemm");
       if (rc) return rc;
     } else {
       for (int i = consumed; i < nsl; ++i) {
@@ -1041,9 +1136,14 @@ extern "C" int vargp_elbo_tn_bwd(const vargp_elbo_tn_desc* d, const float* seeds
   {
     const int gx = cdiv(B, 256), gy = cdiv(zrows, kWRows), nuf = gx * gy * S;
     const int nuu = SC * cdiv(Mt, kUuRows);
-    hipLaunchKernelGGL(t0_w_kernel, dim3(nuf + nuu), dim3(256), 0, st, o.Kuf, o.gKuf, o.Kall, o.gK, o.Wuu, o.r_uu, o.r_uf,
-                       o.c_uf, o.gtheta, S, C, Mt, B, D, 0, B, gx, gy, nuf, nuu, (const float*)nullptr, (const float*)nullptr,
-                       seeds, (float*)nullptr, 1);
+    const int nu2 = d->kernel_nu2;
+    float *d2uf = nullptr, *d2uu = nullptr;
+    if (nu2 && !tn_d2_invert(nu2)) {
+      d2uf = o.gP; d2uu = Smat;
+      rc = tn_matern_d2(d, o, d->x, B, true, true, d2uf, d2uu, st);
+      if (rc) return rc;
+    }
+    tn_w_launch(nu2, o, S, C, B, D, gx, gy, nuf, nuu, seeds, d2uf, d2uu, st);
   }
   {
     GemmParams p0{}, p1{};
@@ -1164,7 +1264,7 @@ extern "C" int vargp_elbo_tn_begin(const vargp_elbo_tn_desc* d, vargp_stream_t s
     p0.na = o.na; p0.sNa[0] = zrows; p0.sNa[1] = Mt;
     p0.nbv = o.na; p0.sNb[0] = zrows; p0.sNb[1] = Mt;
     p0.same_xy = 1; p0.triC = 2; p0.symout = 1;
-    rc = launch_gemm(p0, 0, 1, SC, true, st, "rbf_kuu_gemm");
+    rc = tn_gram_gemm(p0, SC, d->kernel_nu2, st, "rbf_kuu_gemm", "matern_kuu_gemm");
     if (rc) return rc;
   }
   rc = chol_inv_fwd_impl(o.Kall, d->jitter, o.LL, o.TT, nullptr, d->info, SC, Mt, o.chol, o.chol_bytes, false, st);
@@ -1190,6 +1290,7 @@ extern "C" int vargp_elbo_tn_begin(const vargp_elbo_tn_desc* d, vargp_stream_t s
 extern "C" int vargp_elbo_tn_tile(const vargp_elbo_tn_desc* d, const float* seeds, const float* x, const int64_t* y,
                                   const float* eps_f_in, int Bt, vargp_stream_t stream) {
   VARGP_REQUIRE(d && x && d->ws && Bt > 0 && Bt <= d->B, "elbo_tn_tile: bad arguments");
+  TN_REQUIRE_NU2(d, "elbo_tn_tile");
   const bool moments_only = y == nullptr;          // predictive sweep: mu, var (S, C, Bt) of this tile, nothing else
   VARGP_REQUIRE(moments_only || seeds, "elbo_tn_tile: seeds missing");
   VARGP_REQUIRE(moments_only || !d->forward_only, "elbo_tn_tile: a forward_only program takes y == NULL tiles only");
@@ -1224,7 +1325,7 @@ extern "C" int vargp_elbo_tn_tile(const vargp_elbo_tn_desc* d, const float* seed
     pf.kscale = nullptr; pf.ks_ld = o.Dp; pf.g2 = o.g2;      // pre-scaled B operand
     pf.na = o.na; pf.sNa[0] = zrows;
     pf.nbv = o.nb; pf.sNb[0] = B;
-    rc = launch_gemm(pf, 0, 1, S, true, st, "rbf_kuf_gemm");
+    rc = tn_gram_gemm(pf, S, d->kernel_nu2, st, "rbf_kuf_gemm", "matern_kuf_gemm");
     if (rc) return rc;
   }
   {
@@ -1298,8 +1399,14 @@ extern "C" int vargp_elbo_tn_tile(const vargp_elbo_tn_desc* d, const float* seed
   }
   {   // W_uf = gK_uf o K_uf in place, row sums (accumulating over the tiles), column sums (this tile's)
     const int gx = cdiv(B, 256), gy = cdiv(zrows, kWRows), nuf = gx * gy * S;
-    hipLaunchKernelGGL(t0_w_kernel, dim3(nuf), dim3(256), 0, st, o.Kuf, o.gKuf, o.Kall, o.gK, o.Wuu, o.r_uu, o.r_uf, o.c_uf, o.gtheta,
-                       S, C, Mt, B, D, 0, B, gx, gy, nuf, 0, (const float*)nullptr, (const float*)nullptr, seeds, (float*)nullptr, 1);
+    const int nu2 = d->kernel_nu2;
+    float* d2uf = nullptr;      // (Matern) this tile's d2_uf into gP, dead since the gK_uf product; the tile's x o w is still in xs
+    if (nu2 && !tn_d2_invert(nu2)) {
+      d2uf = o.gP;
+      rc = tn_matern_d2(d, o, x, B, true, false, d2uf, nullptr, st);
+      if (rc) return rc;
+    }
+    tn_w_launch(nu2, o, S, C, B, D, gx, gy, nuf, 0, seeds, d2uf, nullptr, st);
     GemmParams p1{};
     p1.A = o.gKuf; p1.B = x; p1.C = o.Puf; p1.D = o.Puf;
     p1.M = C * Mt; p1.N = D; p1.K = B; p1.lda = B; p1.ldb = D; p1.ldc = D; p1.ldd = D;
@@ -1319,6 +1426,7 @@ extern "C" int vargp_elbo_tn_tile(const vargp_elbo_tn_desc* d, const float* seed
 extern "C" int vargp_elbo_tn_end(const vargp_elbo_tn_desc* d, const float* seeds, float* g_log_mean, float* g_log_logvar,
                                  float* g_z, float* g_u_mean, float* g_u_tril_vec, vargp_stream_t stream) {
   VARGP_REQUIRE(d && d->ws && seeds && g_log_mean && g_log_logvar && g_z && g_u_mean && g_u_tril_vec, "elbo_tn_end: null pointer");
+  TN_REQUIRE_NU2(d, "elbo_tn_end");
   hipStream_t st = as_stream(stream);
   const int S = d->S, C = d->C, M = d->M, D = d->D, F = d->F, nblk = d->nblk, SC = S * C;
   const TnWs o = carve_tn(d->ws, S, C, M, D, d->B, F, nblk);
@@ -1365,9 +1473,14 @@ extern "C" int vargp_elbo_tn_end(const vargp_elbo_tn_desc* d, const float* seeds
   }
   {   // K_all: W + W^T = 2 gK o K, its row sums; the W.z product; the inducing-point side of the finalisation
     const int nuu = SC * cdiv(Mt, kUuRows);
-    hipLaunchKernelGGL(t0_w_kernel, dim3(nuu), dim3(256), 0, st, o.Kuf, o.gKuf, o.Kall, o.gK, o.Wuu, o.r_uu, o.r_uf, o.c_uf, o.gtheta,
-                       S, C, Mt, d->B, D, 0, d->B, 1, 1, 0, nuu, (const float*)nullptr, (const float*)nullptr, seeds,
-                       (float*)nullptr, 1);
+    const int nu2 = d->kernel_nu2;
+    float* d2uu = nullptr;      // (Matern) d2_all into the Cholesky backward's scratch, dead since gK was written
+    if (nu2 && !tn_d2_invert(nu2)) {
+      d2uu = Smat;
+      rc = tn_matern_d2(d, o, nullptr, d->B, false, true, nullptr, d2uu, st);
+      if (rc) return rc;
+    }
+    tn_w_launch(nu2, o, S, C, d->B, D, 1, 1, 0, nuu, seeds, nullptr, d2uu, st);
     GemmParams p0{};
     p0.A = o.Wuu; p0.B = d->z_all; p0.C = o.Puu;
     p0.M = Mt; p0.N = D; p0.K = Mt; p0.lda = Mt; p0.ldb = D; p0.ldc = D;

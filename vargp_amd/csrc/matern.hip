@@ -161,6 +161,19 @@ __global__ __launch_bounds__(256) void matern_w_self_kernel(const float* __restr
   if (threadIdx.x == 0) atomicAdd(&gtheta[(b / Cb) * (D + 1) + D], 2.f * t);
 }
 
+// the direct form for a caller that has run the pre-pass itself (the block ELBO program, elbo_tn.hip): out [S, C, M, N], dense
+int matern_direct_launch(const float* X, const float* Y, const float* w, const float* g2, float* out, int S, int C, int M, int N,
+                         int D, int64_t Dp, int y_shared, int epi, hipStream_t st) {
+  const int64_t total = (int64_t)S * C * M * N;
+  const dim3 grid(cdiv(total, 256)), blk(256);
+  if (epi == kEpiMatern12) hipLaunchKernelGGL(matern_direct_kernel<EpiMatern<1>>, grid, blk, 0, st, X, Y, w, g2, out, C, M, N, D, Dp, y_shared, total);
+  else if (epi == kEpiMatern32) hipLaunchKernelGGL(matern_direct_kernel<EpiMatern<3>>, grid, blk, 0, st, X, Y, w, g2, out, C, M, N, D, Dp, y_shared, total);
+  else if (epi == kEpiMatern52) hipLaunchKernelGGL(matern_direct_kernel<EpiMatern<5>>, grid, blk, 0, st, X, Y, w, g2, out, C, M, N, D, Dp, y_shared, total);
+  else if (epi == kEpiDist2) hipLaunchKernelGGL(matern_direct_kernel<EpiDist2>, grid, blk, 0, st, X, Y, w, g2, out, C, M, N, D, Dp, y_shared, total);
+  else VARGP_REQUIRE(false, "matern_direct_launch: epilogue %d", epi);
+  return check_launch("matern_gram(direct)");
+}
+
 // The distance product of one call with the epilogue `epi` (a DistEpi other than kEpiPlain / kEpiRbf) into out[S, C, M, N]:
 // vargp_rbf_gram_fwd's sequence -- pre-pass, then the direct kernel, the fused GEMM, or split-K partials + combine pass.
 template <class EPI>

@@ -301,16 +301,26 @@ def pack_tn_operands(prev, C, M, D, device):
 
 
 class TnProgram(_Program):
-    """`vargp_elbo_tn_*` for fixed (S, C, M, D, B, F, nblk).  `forward(y=None)` evaluates the predictive moments only."""
+    """`vargp_elbo_tn_*` for fixed (S, C, M, D, B, F, nblk).  `forward(y=None)` evaluates the predictive moments only.
+    kernel_nu2: kernels.native_code of the model's kernel (0: RBF; 1 | 3 | 5: Matern) -- a property of the program like its
+    shape (`key`: what callers cache programs under, so an RBF and a Matern model of equal shape never share one)."""
     _Desc = ElboTnDesc
     _C = dict(ws='vargp_elbo_tn_workspace_bytes', ws_fwd='vargp_elbo_tn_workspace_bytes_fwd', fwd='vargp_elbo_tn_fwd',
               bwd='vargp_elbo_tn_bwd', lik_buffers='vargp_elbo_tn_lik_buffers', hyper_desc='vargp_elbo_tn_hyper_desc')
 
-    def __init__(self, S, C, M, D, B, F, nblk, device, map_est=False, forward_only=False):
+    def __init__(self, S, C, M, D, B, F, nblk, device, map_est=False, forward_only=False, kernel_nu2=0):
         # forward_only: predictive moments only (VARGP.forward / predict): none of the gradient buffers is carved
         self.forward_only = bool(forward_only)
+        if kernel_nu2 not in (0, 1, 3, 5):
+            raise ValueError(f'TnProgram: kernel_nu2 must be 0 (RBF) or 1, 3, 5 (Matern), got {kernel_nu2!r}')
+        self.kernel_nu2 = int(kernel_nu2)
+        # (the workspace does not depend on the kernel: the Matern backward recomputes d2 into buffers that are dead by then)
         super().__init__((S, C, M, D, B, F, nblk), S * C, device, map_est, ws='ws_fwd' if self.forward_only else 'ws',
-                         nblk=nblk, forward_only=int(self.forward_only))
+                         nblk=nblk, forward_only=int(self.forward_only), kernel_nu2=self.kernel_nu2)
+
+    @property
+    def key(self):
+        return self.shape + (self.kernel_nu2,)
 
     def moments(self, Bt=None):
         """(mu, var) (S, C, B) of the last forward (or (S, C, Bt) of the last moments-only tile): views into the workspace."""

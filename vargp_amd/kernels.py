@@ -68,18 +68,32 @@ class RBFKernel(nn.Module):
 class MaternKernel(RBFKernel):
     """Matern kernel, nu in {1/2, 3/2, 5/2}, on the RBF's scaled distance r = |(x - y) / lengthscale|:
     gamma^2 exp(-r), gamma^2 (1 + sqrt3 r) exp(-sqrt3 r), gamma^2 (1 + sqrt5 r + 5 r^2 / 3) exp(-sqrt5 r).
-    Same hyper-parameters, priors and state dict as RBFKernel (`nu` is a constructor argument, not state); the kernel
-    matrices come from `vargp_matern_gram_{fwd,bwd}`.  Models with this kernel run the composed per-op route."""
+    Same hyper-parameters, priors and state dict as RBFKernel (`nu` and `native` are constructor arguments, not state);
+    `compute` builds the kernel matrices with `vargp_matern_gram_{fwd,bwd}`.  native=False (the default): a model with this
+    kernel runs the composed per-op route.  native=True: it runs the block ELBO program (csrc/elbo_tn.hip with the Matern
+    epilogues, `native_code`), like an RBFKernel model on that program."""
 
-    def __init__(self, in_size, nu=2.5, prior_log_mean=None, prior_log_logvar=None, map_est=False):
+    def __init__(self, in_size, nu=2.5, prior_log_mean=None, prior_log_logvar=None, map_est=False, native=False):
         if nu not in (0.5, 1.5, 2.5):
             raise ValueError(f'MaternKernel: nu must be 0.5, 1.5 or 2.5, got {nu!r}')
         super().__init__(in_size, prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar, map_est=map_est)
         self.nu = float(nu)
+        self.native = bool(native)
 
     def compute(self, kern_samples, x, y=None):
         nu = self.nu
         return self._compute(lambda th, X, Y, shared: ops.matern_gram(th, X, Y, shared, nu), kern_samples, x, y)
+
+
+def native_code(kernel):
+    """Which kernel epilogue of the native ELBO programs a model with `kernel` runs on (vargp_elbo_tn_desc.kernel_nu2):
+    0 for exactly RBFKernel, 1 | 3 | 5 (= 2 nu) for exactly MaternKernel built with native=True, None for anything else
+    (DeepRBFKernel, subclasses, native=False): the composed per-op route.  The one place that decides the route."""
+    if type(kernel) is RBFKernel:
+        return 0
+    if type(kernel) is MaternKernel and kernel.native:
+        return int(round(2 * kernel.nu))
+    return None
 
 
 class DeepRBFKernel(RBFKernel):

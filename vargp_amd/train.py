@@ -20,6 +20,7 @@ import torch
 import torch.distributed as dist
 
 from . import noise
+from .kernels import native_code
 from .likelihoods import is_gaussian, n_f
 from .optim import Yogi
 
@@ -150,7 +151,7 @@ class ElboTrainer:
         # decided per batch shape in _t0_fwd_bwd, exactly as VARGP.loss routes -- `_tn` describes the most recent step
         self._tn = bool(is_model and gp._use_block_program())                                             # csrc/elbo_tn.hip
         self._t0 = bool(is_model and not gp.prev_params and gp.fused_first_task
-                        and type(gp.kernel).__name__ == 'RBFKernel') or self._tn                           # csrc/elbo_t0.hip
+                        and native_code(gp.kernel) == 0) or self._tn                                      # csrc/elbo_t0.hip
         # one program (descriptor + workspace) PER SHAPE, never freed: a captured hipGraph holds raw pointers into the
         # program it was captured with, and the ragged last minibatch of an epoch runs eagerly through another shape
         self._progs, self._prog, self._seeds, self._own_grads, self._scratch_grads = {}, None, {}, None, {}
@@ -459,7 +460,8 @@ class ElboTrainer:
         if self._prog is None or self._prog.shape != shape:
             if shape not in self._progs:
                 from .fused import T0Program, TnProgram
-                prog = self._progs[shape] = (TnProgram if block else T0Program)(*shape, self.gp.z.device, self.gp.kernel.map_est)
+                kw = dict(kernel_nu2=native_code(self.gp.kernel)) if block else {}     # (one model, one kernel: not in the key)
+                prog = self._progs[shape] = (TnProgram if block else T0Program)(*shape, self.gp.z.device, self.gp.kernel.map_est, **kw)
                 if self.native_noise:
                     prog.set_rng(self.noise_seed, self._rng_counter,
                                  self.rank * shape[0] if self.sample_offset is None else self.sample_offset)

@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from . import fused, gp_utils, noise, ops
 from .gp_utils import vec2tril, mat2trilvec, cholesky, rev_cholesky, gp_cond, block_joint, linear_marginal_diag
-from .kernels import RBFKernel, DeepRBFKernel, MaternKernel
+from .kernels import RBFKernel, DeepRBFKernel, MaternKernel, native_code
 from .likelihoods import MulticlassSoftmax, is_gaussian, n_f
 from .ops import LOWER
 
@@ -122,7 +122,7 @@ class VARGP(nn.Module):
         return self.M > 104 or n_v * self.z.size(0) * ntile > int(os.environ.get('VARGP_T0_UNITS', self.T0_TILE_UNITS_MAX))
 
     def _tn_applicable(self):
-        return (self.fused_tasks and type(self.kernel) is RBFKernel and self.z.is_cuda
+        return (self.fused_tasks and native_code(self.kernel) is not None and self.z.is_cuda
                 and all(p['z'].shape[-2] == self.M for p in self.prev_params))
 
     def _use_block_program(self, B=None):
@@ -136,7 +136,8 @@ class VARGP(nn.Module):
             # tn_nm_* kernels (csrc/elbo_tn.hip), for up to 16 samples
             n_v = 1 if self.kernel.map_est else self.n_v
             return self.var_mean_mask == 1.0 or (self.var_mean_mask == 0.0 and n_v <= 16)
-        return self.fused_first_task and self.first_task_as_block(B)
+        # (csrc/elbo_t0.hip is RBF-only: a native Matern first-task model is always the one-block case of the block program)
+        return self.fused_first_task and (native_code(self.kernel) != 0 or self.first_task_as_block(B))
 
     def _tn_operands(self):
         """z_all (C, Mt, D), rk_all (C, nblk, M, NR): earlier tasks packed once, the last block is the program's scratch."""
@@ -154,18 +155,20 @@ class VARGP(nn.Module):
         re-allocated per step."""
         S = 1 if self.kernel.map_est else self.n_v
         shape = (S, self.z.size(0), self.M, self.z.size(-1), B, n_f(self.likelihood))
-        cls, progs, spares = fused.T0Program, self._t0_progs, self._t0_spares
+        cls, progs, spares, kw = fused.T0Program, self._t0_progs, self._t0_spares, {}
         if block:
             shape, cls, progs, spares = shape + (len(self.prev_params) + 1,), fused.TnProgram, self._tn_progs, self._tn_spares
+            kw = dict(kernel_nu2=native_code(self.kernel))
         dev = self.z.device
-        prog = progs.get(shape)
+        key = shape + tuple(kw.values())                 # (block programs: the kernel is part of the key, fused.TnProgram.key)
+        prog = progs.get(key)
         if prog is None or prog.ws.device != dev:
-            prog = progs[shape] = cls(*shape, dev, self.kernel.map_est)
+            prog = progs[key] = cls(*shape, dev, self.kernel.map_est, **kw)
         elif prog.busy:
-            pool = spares.setdefault(shape, [])
+            pool = spares.setdefault(key, [])
             prog = next((q for q in pool if not q.busy and q.ws.device == dev), None)
             if prog is None:
-                prog = cls(*shape, dev, self.kernel.map_est)
+                prog = cls(*shape, dev, self.kernel.map_est, **kw)
                 pool.append(prog)
         return prog
 
@@ -180,6 +183,7 @@ class VARGP(nn.Module):
         asked for so far; narrower batches (the ragged last one of a sweep) run on it through the tile calls."""
         S = 1 if self.kernel.map_est else self.n_v
         key = (S, self.z.size(0), self.M, self.z.size(-1), n_f(self.likelihood), len(self.prev_params) + 1)
+        kw = dict(map_est=self.kernel.map_est, forward_only=True, kernel_nu2=native_code(self.kernel))
         if exact:
             # D <= 32 (the direct distance form) has no tile mode: one small program per batch size, kept -- an accuracy sweep
             # with a ragged last batch would otherwise free and re-carve the single workspace twice per data set
@@ -187,14 +191,13 @@ class VARGP(nn.Module):
             if prog is None or prog.ws.device != self.z.device:
                 if len(self._tn_eval_exact) >= 8:
                     self._tn_eval_exact.clear()
-                prog = self._tn_eval_exact[key + (B,)] = fused.TnProgram(*key[:4], B, *key[4:], self.z.device,
-                                                                         self.kernel.map_est, forward_only=True)
+                prog = self._tn_eval_exact[key + (B,)] = fused.TnProgram(*key[:4], B, *key[4:], self.z.device, **kw)
             return prog
         prog = self._tn_eval
         if (prog is None or prog.shape[4] < B or (prog.shape[:4] + prog.shape[5:]) != key
                 or prog.ws.device != self.z.device):
             self._tn_eval = None          # release the old workspace before carving the wider one
-            prog = self._tn_eval = fused.TnProgram(*key[:4], B, *key[4:], self.z.device, self.kernel.map_est, forward_only=True)
+            prog = self._tn_eval = fused.TnProgram(*key[:4], B, *key[4:], self.z.device, **kw)
         return prog
 
     def release_programs(self):
@@ -328,7 +331,7 @@ class VARGP(nn.Module):
         (vargp.py:177-194, experiments/vargp.py:34)."""
         B = x.size(0)
         block = self._use_block_program(B)                      # csrc/elbo_tn.hip; otherwise, first task: csrc/elbo_t0.hip
-        if block or (not self.prev_params and self.fused_first_task and type(self.kernel) is RBFKernel):
+        if block or (not self.prev_params and self.fused_first_task and native_code(self.kernel) == 0):
             lazy = self._lazy_ok()
             prog, packed = self._program(B, block), (self._tn_operands() if block else ())
             if lazy:
@@ -422,15 +425,20 @@ class VARGP(nn.Module):
 
     @staticmethod
     def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None,
-                   ep_var_mean=True, map_est_hypers=False, dkl=False, kernel='rbf'):
+                   ep_var_mean=True, map_est_hypers=False, dkl=False, kernel='rbf', native_kernel=False):
         """Factory used by the experiment driver (vargp.py:200-243): inducing points at random data
         points per class, hyper-prior = previous task's hyper-posterior (popped from prev_params[-1],
         which is mutated like the reference does).  kernel: 'rbf' (the reference's), or 'matern12' / 'matern32' /
-        'matern52' (MaternKernel; not with dkl).  The name is not part of a checkpoint: give it again on reload."""
+        'matern52' (MaternKernel; not with dkl).  native_kernel=True: the Matern model runs the native block program
+        (MaternKernel(native=True)); an error with 'rbf' or dkl, which have no such choice.  Neither is part of a checkpoint:
+        give them again on reload."""
         if kernel not in _KERNEL_NU:
             raise ValueError(f'create_clf: kernel must be one of {sorted(_KERNEL_NU)}, got {kernel!r}')
         if dkl and kernel != 'rbf':
             raise ValueError('create_clf: dkl=True needs kernel="rbf" (DeepRBFKernel has no Matern head)')
+        if native_kernel and (dkl or kernel == 'rbf'):
+            raise ValueError('create_clf: native_kernel=True selects the native route of a Matern kernel (kernel="matern12" / '
+                             '"matern32" / "matern52", dkl=False); the RBF kernel is always native, DeepRBFKernel never')
         N = len(dataset)
         out_size = torch.unique(dataset.targets).size(0)
         z = torch.stack([dataset[torch.randperm(N)[:M]][0] for _ in range(out_size)])
@@ -451,7 +459,7 @@ class VARGP(nn.Module):
                 kern.phi.load_state_dict(phi_params)
         elif kernel != 'rbf':
             kern = MaternKernel(z.size(-1), nu=_KERNEL_NU[kernel], prior_log_mean=prior_log_mean,
-                                prior_log_logvar=prior_log_logvar, map_est=map_est_hypers)
+                                prior_log_logvar=prior_log_logvar, map_est=map_est_hypers, native=bool(native_kernel))
         else:
             kern = RBFKernel(z.size(-1), prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
                              map_est=map_est_hypers)
