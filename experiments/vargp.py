@@ -51,16 +51,18 @@ class JsonlLogger:
 def train(task_id, train_set, val_set, test_set, ep_var_mean=True, map_est_hypers=False, dkl=False,
           epochs=1, M=20, n_f=10, n_var_samples=3, batch_size=512, lr=1e-2, beta=1.0,
           eval_interval=10, patience=20, prev_params=None, logger=None, device=None, graph=False, seed=None,
-          retrain=False, eval_shared_hypers=False, dataloader=False, kernel='rbf', native_kernel=False):
+          retrain=False, eval_shared_hypers=False, dataloader=False, kernel='rbf', native_kernel=False,
+          likelihood='softmax', link='probit'):
     if retrain:      # the variant of experiments/vargp_retrain.py:14-19 (earlier tasks' inducing parameters re-optimised)
         from vargp_amd.vargp_retrain import VARGPRetrain
         assert kernel == 'rbf', '--retrain builds its model with the RBF kernel'
-        gp = VARGPRetrain.create_clf(train_set, M=M, n_f=n_f, n_var_samples=n_var_samples, prev_params=prev_params).to(device)
+        gp = VARGPRetrain.create_clf(train_set, M=M, n_f=n_f, n_var_samples=n_var_samples, prev_params=prev_params,
+                                     likelihood=likelihood, link=link).to(device)
         graph = False
     else:
         gp = VARGP.create_clf(train_set, M=M, n_f=n_f, n_var_samples=n_var_samples, prev_params=prev_params,
                               ep_var_mean=ep_var_mean, map_est_hypers=map_est_hypers, dkl=dkl, kernel=kernel,
-                              native_kernel=native_kernel).to(device)
+                              native_kernel=native_kernel, likelihood=likelihood, link=link).to(device)
     stopper = EarlyStopper(patience=patience)
     N = len(train_set)
     # the program's counter-based noise generator is keyed by the run's seed (the reference draws from the torch global
@@ -186,7 +188,8 @@ def toy(args):
         toy_test.filter_by_class(range(2 * t + 2))
         sd = train(t, toy_train, toy_val, toy_test, epochs=args.epochs, M=args.M, lr=args.lr, beta=args.beta,
                    batch_size=args.batch_size, ep_var_mean=args.ep_var_mean, map_est_hypers=args.map_est_hypers,
-                   dkl=args.dkl, kernel=args.kernel, native_kernel=args.native_kernel, prev_params=prev_params, logger=logger, device=device, patience=-1,
+                   dkl=args.dkl, kernel=args.kernel, native_kernel=args.native_kernel, likelihood=args.likelihood,
+                   link=args.link, prev_params=prev_params, logger=logger, device=device, patience=-1,
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed, retrain=args.retrain,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader)
         prev_params.append(sd)
@@ -211,7 +214,8 @@ def split_mnist(args):
         mnist_test.filter_by_class(range(2 * t + 2))
         sd = train(t, mnist_train, mnist_val, mnist_test, epochs=args.epochs, M=args.M, lr=args.lr, beta=args.beta,
                    batch_size=args.batch_size, ep_var_mean=args.ep_var_mean, map_est_hypers=args.map_est_hypers,
-                   dkl=args.dkl, kernel=args.kernel, native_kernel=args.native_kernel, prev_params=prev_params, logger=logger, device=device,
+                   dkl=args.dkl, kernel=args.kernel, native_kernel=args.native_kernel, likelihood=args.likelihood,
+                   link=args.link, prev_params=prev_params, logger=logger, device=device,
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader)
         prev_params.append(sd)
@@ -239,7 +243,8 @@ def permuted_mnist(args):
         mnist_test[-1].set_task(tasks[t])
         sd = train(t, mnist_train, ConcatDataset(mnist_val), ConcatDataset(mnist_test), epochs=args.epochs, M=args.M,
                    lr=args.lr, beta=args.beta, batch_size=args.batch_size, ep_var_mean=args.ep_var_mean,
-                   map_est_hypers=args.map_est_hypers, dkl=args.dkl, kernel=args.kernel, native_kernel=args.native_kernel, prev_params=prev_params, logger=logger,
+                   map_est_hypers=args.map_est_hypers, dkl=args.dkl, kernel=args.kernel, native_kernel=args.native_kernel, likelihood=args.likelihood,
+                   link=args.link, prev_params=prev_params, logger=logger,
                    device=device, eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader)
         prev_params.append(sd)
@@ -270,6 +275,11 @@ def parse_args(argv=None):
         sp.add_argument('--native_kernel', action='store_true',
                         help='run a Matern model on the native block ELBO program instead of the composed per-op route '
                              '(needs --kernel matern12 / matern32 / matern52 and no --dkl; not stored in checkpoints)')
+        sp.add_argument('--likelihood', choices=('softmax', 'bernoulli'), default='softmax',
+                        help="classification likelihood: the reference's Monte-Carlo softmax, or independent one-vs-rest "
+                             'Bernoulli outputs (deterministic 20-node Gauss-Hermite rule; not stored in checkpoints)')
+        sp.add_argument('--link', choices=('probit', 'logit'), default='probit',
+                        help='link function of --likelihood bernoulli')
         sp.add_argument('--seed', type=int, default=None)
         sp.add_argument('--eval_interval', type=int, default=10)
         sp.add_argument('--log_dir', default=os.path.join('runs', f'{name}-{int(time.time())}'))
@@ -296,6 +306,9 @@ def parse_args(argv=None):
     if args.native_kernel and (args.kernel == 'rbf' or args.dkl or getattr(args, 'retrain', False)):
         ap.error('--native_kernel selects the native route of a Matern kernel: it needs --kernel matern12 / matern32 / matern52 '
                  'and neither --dkl nor --retrain')
+    if args.graph and args.likelihood == 'bernoulli':
+        ap.error('--graph with --likelihood bernoulli: the epoch graphs (capture_epoch / step_graph_gather) run the softmax '
+                 'likelihood inside the native program and refuse a Bernoulli model; train it without --graph')
     return args
 
 

@@ -199,6 +199,32 @@ int vargp_gauss_nll_bwd(const float* mu, const float* var, const float* y, int64
                         vargp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Independent-output Bernoulli likelihood: binary, multi-label and one-vs-rest classification.  Not in the reference.
+ *   p(t | f) = Lambda(s f), s = 2 t - 1; link 0: Lambda = Phi (probit), link 1: Lambda = logistic (logit).
+ *   mu, var [S, C, B].  Exactly one of `t` and `labels` is non-NULL:
+ *     t       float targets in {0, 1}, [C, B] with row stride ldt, or one row [B] shared by every output (ldt = 0);
+ *     labels  int64 [B] class indices read as one-vs-rest, t[c, b] = (labels[b] == c); a label outside [0, C) matches no output
+ *             (every output of that point is a negative) -- label values are not checked.
+ *   With the 20-node Gauss-Hermite rule (x_k, w_k = numpy.polynomial.hermite.hermgauss(20), w^_k = w_k / sqrt(pi)), which is the
+ *   definition of the expected log-likelihood and not an approximation left open:
+ *     ell[s,c,b] = sum_k w^_k log Lambda(s_cb (mu + sqrt(2 var) x_k)),     nll = - sum_b sum_c mean_s ell   (SUM over outputs)
+ * fwd WRITES *nll.  bwd, seed = d total / d nll (device, 1 float): gmu, gvar [S, C, B] = seed * the exact derivatives of that
+ * sum; with nll != NULL it also writes the (unseeded) value, bit-equal to fwd's, so a training step needs one call.
+ * predict: probs[B, C] = mean_s P(t = 1) -- probit: Phi(mu / sqrt(1 + var)); logit: the same rule on the logistic function.  The
+ * rows are NOT normalised over the outputs.
+ * ws: vargp_bernoulli_workspace_bytes(S, C, B) bytes of device scratch, used inside the call only (per-workgroup partial
+ * values; may be NULL in bwd when nll is NULL).  Deterministic: no float atomics, every sum in a fixed order.
+ */
+size_t vargp_bernoulli_workspace_bytes(int S, int C, int B);
+int vargp_bernoulli_nll_fwd(const float* mu, const float* var, const float* t, int64_t ldt, const int64_t* labels, int link,
+                            float* nll, int S, int C, int B, float* ws, size_t ws_bytes, vargp_stream_t stream);
+int vargp_bernoulli_nll_bwd(const float* mu, const float* var, const float* t, int64_t ldt, const int64_t* labels, int link,
+                            const float* seed, float* gmu, float* gvar, float* nll, int S, int C, int B, float* ws,
+                            size_t ws_bytes, vargp_stream_t stream);
+int vargp_bernoulli_predict(const float* mu, const float* var, int link, float* probs, int S, int C, int B,
+                            vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Yogi optimiser step, fused over one flat parameter buffer (reference call site:
  * experiments/vargp.py:23,37 -> torch_optimizer.Yogi; algorithm from Zaheer et al. 2018).
  * bias1/bias2 = 1 - beta^t; if `step` (device pointer to the step count t as a float) is not NULL

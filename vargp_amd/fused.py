@@ -10,7 +10,7 @@ likelihood), the backward ~20.  This module holds
     calls.  Everything the two share (operand binding, the Cholesky-status protocol, backward, re-evaluation) is written
     once in `_Program`; a subclass names its C entry points and adds the operands only it has;
   * `_claim` / `_verify` / `_release` — who owns a program's workspace between a forward and its backward;
-  * `elbo_node()` — a program as ONE autograd node (softmax or Gaussian likelihood), which is what `VARGP.loss` returns
+  * `elbo_node()` — a program as ONE autograd node (softmax or an external likelihood), which is what `VARGP.loss` returns
     into the reference's training loop (`loss.backward()`, experiments/vargp.py:34-35) when the lazy route is off;
   * `elbo_lazy()` — the same without an autograd graph (lazy.py), the default.
 `train.ElboTrainer` drives a persistent program directly (no autograd graph, gradients written straight into the
@@ -398,9 +398,10 @@ class TnProgram(_Program):
 
 
 # ----------------------------------------------------------------------------------------------------------------
-# GaussianLikelihood models (regression, var_gp/likelihoods.py:66-110) on either program: the program's forward with
-# ext_lik stops at the predictive moments and the KL, the closed-form Gaussian nll and its seeded gradients are one
-# launch each (csrc/gauss_lik.hip), and the program's backward takes those gradients from its likelihood buffers
+# External likelihoods (likelihoods.is_external: GaussianLikelihood -- regression, var_gp/likelihoods.py:66-110 -- and
+# BernoulliLikelihood) on either program: the program's forward with ext_lik stops at the predictive moments and the KL, the
+# likelihood's value and its seeded gradients are one call each (likelihood.ext_value / ext_backward over lik_views(prog):
+# csrc/gauss_lik.hip, csrc/bernoulli_lik.hip), and the program's backward takes those gradients from its likelihood buffers
 # ----------------------------------------------------------------------------------------------------------------
 _Y_DUMMY = {}
 
@@ -422,43 +423,33 @@ def lik_views(prog):
     return v
 
 
-def gauss_forward(prog, y, obs_log_var):
-    """After a program forward with ext_lik: the Gaussian nll of its moments into prog.scalars[2], completing the
-    (kl_hypers, kl_u, nll) triple.  -> (y as the kernels read it, its class stride)."""
-    mu, var, _, _ = lik_views(prog)
-    S, C, B = mu.shape
-    yt, ldy = ops.gauss_target(y, C, B)
-    ops.gauss_nll_fwd(mu, var, yt, ldy, obs_log_var, prog.scalars[2:])
-    return yt, ldy
-
-
 # ----------------------------------------------------------------------------------------------------------------
 # VARGP.loss on a native program as ONE autograd node
 # ----------------------------------------------------------------------------------------------------------------
 class _Elbo(Function):
-    """Differentiable inputs: the program's operands (VARGP._operands order; the two prior tensors get no gradient) and, for
-    a GaussianLikelihood model, obs_log_var (None: the softmax likelihood inside the program).  `packed` = (z_all, rk_all) on
-    the block program, () on the first-task program."""
+    """Differentiable inputs: the program's operands (VARGP._operands order; the two prior tensors get no gradient) and an
+    external likelihood's own parameter (lik.ext_param(): GaussianLikelihood's obs_log_var; None otherwise).  lik: the
+    external likelihood (None: the softmax likelihood inside the program).  `packed` = (z_all, rk_all) on the block program,
+    () on the first-task program."""
 
     @staticmethod
-    def forward(ctx, log_mean, log_logvar, prior_log_mean, prior_log_logvar, z, u_mean, u_tril_vec, obs_log_var, x, y,
-                eps_theta, eps_f, map_est, prog, packed, eps_u):
+    def forward(ctx, log_mean, log_logvar, prior_log_mean, prior_log_logvar, z, u_mean, u_tril_vec, lik_param, x, y,
+                eps_theta, eps_f, map_est, prog, packed, eps_u, lik):
         c = lambda t: None if t is None else t.contiguous()
-        gauss = obs_log_var is not None
+        ext = lik is not None
         if prog is None:         # no cached program handed in: a workspace of this node's own
             S = 1 if map_est else eps_theta.shape[0]
             prog = T0Program(*T0Program.shape_of(S, z, x, eps_f.shape[1]), z.device, map_est)
-        labels = c(y) if not gauss else y_dummy(x.device) if packed else None
+        labels = c(y) if not ext else y_dummy(x.device) if packed else None
         prog.forward(*map(c, (log_mean, log_logvar, prior_log_mean, prior_log_logvar, z, u_mean, u_tril_vec)), *packed,
-                     c(x), labels, c(eps_theta), c(eps_f), ext_lik=gauss, **(dict(eps_u=c(eps_u)) if packed else {}))
-        if gauss:                # the closed-form nll between the program's forward and backward
-            olv = obs_log_var.detach().contiguous()
-            yt, ctx.ldy = gauss_forward(prog, y, olv)
-            ctx.save_for_backward(yt, olv)
+                     c(x), labels, c(eps_theta), c(eps_f), ext_lik=ext, **(dict(eps_u=c(eps_u)) if packed else {}))
+        if ext:                  # the likelihood's value between the program's forward and backward
+            ctx.target = lik.ext_target(y, z.shape[0], x.shape[0])
+            lik.ext_value(prog, ctx.target)
         scal = prog.scalars.clone()          # the program's scalars are overwritten by its next forward
         # grad mode is always off inside Function.forward, so the node's lifetime is the signal for ownership
         ctx.gen = _claim(prog, ctx)
-        ctx.prog, ctx.map_est, ctx.gauss = prog, map_est, gauss
+        ctx.prog, ctx.map_est, ctx.lik = prog, map_est, lik
         ctx.shapes = (log_mean.shape, log_mean.shape, z.shape, u_mean.shape, u_tril_vec.shape)
         return scal[0], scal[1], scal[2]
 
@@ -471,23 +462,20 @@ class _Elbo(Function):
             prog.rerun_forward()             # second backward of a retained graph: the forward is evaluated again
         ctx.ran = True
         seeds = torch.stack([g_klh.reshape(()), g_klu.reshape(()), g_nll.reshape(())]).float()
-        g_olv = None
-        if ctx.gauss:
-            yt, olv = ctx.saved_tensors
-            mu, var, gmu, gvar = lik_views(prog)
-            g_olv = torch.empty_like(olv)
-            ops.gauss_nll_bwd(mu, var, yt, ctx.ldy, olv, seeds[2:], gmu, gvar, g_olv)
+        g_lik = ctx.lik.ext_backward(prog, ctx.target, seeds[2:]) if ctx.lik is not None else None
         g_mean, g_logvar, g_z, g_um, g_uv = _flat_views(ctx.shapes, seeds.device)
         prog.backward(seeds, g_mean, g_logvar, g_z, g_um, g_uv)       # (ext_lik: seeds[2] is not read)
         _release(prog, ctx.gen)              # (a later loss() may take the workspace: a further backward of THIS node then raises)
-        return (g_mean, None if ctx.map_est else g_logvar, None, None, g_z, g_um, g_uv, g_olv) + (None,) * 8
+        return (g_mean, None if ctx.map_est else g_logvar, None, None, g_z, g_um, g_uv, g_lik) + (None,) * 9
 
 
-def elbo_node(operands, map_est, x, y, eps_theta, eps_f, prog=None, packed=(), eps_u=None, obs_log_var=None):
+def elbo_node(operands, map_est, x, y, eps_theta, eps_f, prog=None, packed=(), eps_u=None, likelihood=None):
     """-> (kl_hypers, kl_u, nll) of VARGP.loss as ONE autograd node.  operands: VARGP._operands(detach=False); `prog`: the
     (cached, not busy) program of this shape -- None: a first-task program of the node's own; packed: VARGP._tn_operands() on
-    the block program; eps_u: ep_var_mean = False; obs_log_var: GaussianLikelihood models (eps_f is then None)."""
-    return _Elbo.apply(*operands, obs_log_var, x, y, eps_theta, eps_f, bool(map_est), prog, tuple(packed), eps_u)
+    the block program; eps_u: ep_var_mean = False; likelihood: an external likelihood (GaussianLikelihood, BernoulliLikelihood;
+    eps_f is then None)."""
+    lik_param = likelihood.ext_param() if likelihood is not None else None
+    return _Elbo.apply(*operands, lik_param, x, y, eps_theta, eps_f, bool(map_est), prog, tuple(packed), eps_u, likelihood)
 
 
 # ----------------------------------------------------------------------------------------------------------------

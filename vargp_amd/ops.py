@@ -663,6 +663,104 @@ def gauss_nll(mu, var, y, obs_log_var):
     y (C, B) or (B,).  Differentiable in mu, var and obs_log_var."""
     return _GaussNll.apply(mu, var, y, obs_log_var)
 
+
+# ------------------------------------------------------------------------------------------------
+# Bernoulli likelihood (independent outputs; csrc/bernoulli_lik.hip -- not in the reference)
+# ------------------------------------------------------------------------------------------------
+BERNOULLI_LINKS = {'probit': 0, 'logit': 1}
+
+
+def bernoulli_link(link):
+    if link not in BERNOULLI_LINKS:
+        raise ValueError(f'link must be one of {sorted(BERNOULLI_LINKS)}, got {link!r}')
+    return BERNOULLI_LINKS[link]
+
+
+def bernoulli_target(y, C, B):
+    """A classification target as the Bernoulli kernels read it -> (t, ldt, labels), exactly one of t / labels not None:
+      int64 (B,)               class indices read as one-vs-rest, t[c, b] = (y[b] == c): (None, 0, y) -- no one-hot tensor
+                               (a label outside [0, C) matches no output; values are not checked);
+      float / bool (C, B)      per-output targets in {0, 1}: (fp32 tensor, B, None);
+      float / bool (B,)        one row shared by every output: (fp32 tensor, 0, None).
+    Other integer dtypes are refused (cast to int64 for class indices, to float for 0 / 1 targets)."""
+    if not torch.is_tensor(y):
+        raise TypeError(f'bernoulli_target: a tensor is needed, got {type(y).__name__}')
+    y = y.detach()
+    if y.dtype == torch.int64:
+        if tuple(y.shape) != (B,):
+            raise ValueError(f'bernoulli_target: int64 class indices must have shape ({B},), got {tuple(y.shape)}; '
+                             'per-output 0 / 1 targets are float or bool')
+        return None, 0, y.contiguous()
+    if not (y.dtype.is_floating_point or y.dtype == torch.bool):
+        raise TypeError(f'bernoulli_target: int64 class indices or float / bool 0 / 1 targets, got {y.dtype}')
+    if tuple(y.shape) == (B,):
+        return y.to(torch.float32).contiguous(), 0, None
+    if tuple(y.shape) == (C, B):
+        return y.to(torch.float32).contiguous(), B, None
+    raise ValueError(f'bernoulli_target: targets must have shape ({C}, {B}) or ({B},), got {tuple(y.shape)}')
+
+
+def _bernoulli_ws(S, C, B, device):
+    return scratch(lib().vargp_bernoulli_workspace_bytes(S, C, B), device)
+
+
+def bernoulli_nll_fwd(mu, var, t, ldt, labels, link, out):
+    """Writes the Bernoulli nll of mu, var (S, C, B) contiguous into the one-float device tensor `out`; (t, ldt, labels) from
+    bernoulli_target, link 0 (probit) / 1 (logit)."""
+    S, C, B = mu.shape
+    ws = _bernoulli_ws(S, C, B, mu.device)
+    check(lib().vargp_bernoulli_nll_fwd(ptr(mu), ptr(var), ptr(t), ldt, ptr(labels), link, ptr(out), S, C, B, ptr(ws),
+                                        ws.numel() * 4, stream_ptr()), 'vargp_bernoulli_nll_fwd')
+
+
+def bernoulli_nll_bwd(mu, var, t, ldt, labels, link, seed, gmu, gvar, nll=None):
+    """Seeded gradients of the Bernoulli nll into gmu, gvar (S, C, B); with `nll`, the value too (bit-equal to the forward's)."""
+    S, C, B = mu.shape
+    ws = _bernoulli_ws(S, C, B, mu.device) if nll is not None else None
+    check(lib().vargp_bernoulli_nll_bwd(ptr(mu), ptr(var), ptr(t), ldt, ptr(labels), link, ptr(seed), ptr(gmu), ptr(gvar),
+                                        ptr(nll), S, C, B, ptr(ws), ws.numel() * 4 if ws is not None else 0, stream_ptr()),
+          'vargp_bernoulli_nll_bwd')
+
+
+def bernoulli_predict(mu, var, link='probit'):
+    """probs (B, C) = mean_s P(t = 1) of mu, var (S, C, B); not normalised over the outputs."""
+    require_device(mu, var)
+    mu, var = mu.contiguous(), var.contiguous()
+    S, C, B = mu.shape
+    probs = torch.empty(B, C, dtype=torch.float32, device=mu.device)
+    check(lib().vargp_bernoulli_predict(ptr(mu), ptr(var), bernoulli_link(link), ptr(probs), S, C, B, stream_ptr()),
+          'vargp_bernoulli_predict')
+    return probs
+
+
+class _BernoulliNll(Function):
+    @staticmethod
+    def forward(ctx, mu, var, y, link):
+        require_device(mu, var, y)
+        mu, var = mu.contiguous(), var.contiguous()
+        S, C, B = mu.shape
+        assert var.shape == mu.shape and mu.dtype == torch.float32 and var.dtype == torch.float32, (mu.shape, var.shape, mu.dtype, var.dtype)
+        t, ldt, labels = bernoulli_target(y, C, B)
+        nll = torch.empty((), dtype=torch.float32, device=mu.device)
+        bernoulli_nll_fwd(mu, var, t, ldt, labels, link, nll)
+        ctx.save_for_backward(mu, var, t, labels)
+        ctx.ldt, ctx.link = ldt, link
+        return nll
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        mu, var, t, labels = ctx.saved_tensors
+        gmu, gvar = torch.empty_like(mu), torch.empty_like(var)
+        bernoulli_nll_bwd(mu, var, t, ctx.ldt, labels, ctx.link, g.float().contiguous(), gmu, gvar)
+        return gmu, gvar, None, None
+
+
+def bernoulli_nll(mu, var, y, link='probit'):
+    """- sum_b sum_c mean_s E_{f ~ N(mu, var)} log Lambda((2 t - 1) f) by the 20-node Gauss-Hermite rule
+    (BernoulliLikelihood.loss); y as bernoulli_target takes it.  Differentiable in mu and var."""
+    return _BernoulliNll.apply(mu, var, y, bernoulli_link(link))
+
 # ------------------------------------------------------------------------------------------------
 # variational hyper-parameters
 # ------------------------------------------------------------------------------------------------

@@ -21,11 +21,11 @@ import torch.distributed as dist
 
 from . import noise
 from .kernels import native_code
-from .likelihoods import is_gaussian, n_f
+from .likelihoods import is_external, n_f
 from .optim import Yogi
 
-_GAUSS_REFUSED = ('{} is not available for GaussianLikelihood models: it assumes integer class labels or the softmax '
-                  'likelihood.  Train them on one GPU with step() / capture() + step_graph()')
+_EXT_REFUSED = ('{} is not available for {} models: it assumes integer class labels and the softmax likelihood inside the '
+                'program.  Train them on one GPU with step() / capture() + step_graph()')
 
 
 def split_samples(total, world):
@@ -75,11 +75,11 @@ class ElboTrainer:
         # force_exchange: take the multi-rank path (all-reduce of the flat buffer, two-graph capture) with one rank too --
         # a smoke test of that path where only one GPU is available (bench.py, VARGP_BENCH_FORCE_DIST=1)
         self.multi = self.world > 1 or (bool(force_exchange) and dist.is_available() and dist.is_initialized())
-        # GaussianLikelihood (regression) models: one GPU only -- every multi-rank route exchanges softmax terms or labels
-        self.gauss = bool(gp is not None and is_gaussian(getattr(gp, 'likelihood', None)))
-        if self.gauss and (self.multi or shards is not None):
-            raise NotImplementedError(_GAUSS_REFUSED.format('a multi-rank (sample-parallel, class-sharded or force_exchange) '
-                                                            'trainer'))
+        # external likelihoods (GaussianLikelihood, BernoulliLikelihood): one GPU only -- every multi-rank route exchanges
+        # softmax terms or labels
+        self.ext = bool(gp is not None and is_external(getattr(gp, 'likelihood', None)))
+        if self.ext and (self.multi or shards is not None):
+            raise NotImplementedError(self._refused('a multi-rank (sample-parallel, class-sharded or force_exchange) trainer'))
         self.params = list(params) if params is not None else [p for p in gp.parameters() if p.requires_grad]
         n = sum(p.numel() for p in self.params)
         dev = self.params[0].device
@@ -159,8 +159,8 @@ class ElboTrainer:
         self._bump = None
         # native noise: the program draws eps_theta / eps_f itself (Philox keyed by noise_seed, device-side step
         # counter): no randn launches, and ranks see slices of one global draw by construction
-        # (GaussianLikelihood models: the program runs with ext_lik, which takes eps_theta from the caller -- noise.draw)
-        self.native_noise = bool(native_noise) and self._t0 and not self.class_split and not self.gauss
+        # (external likelihoods: the program runs with ext_lik, which takes eps_theta from the caller -- noise.draw)
+        self.native_noise = bool(native_noise) and self._t0 and not self.class_split and not self.ext
         # ep_var_mean = False models with earlier tasks draw eps_u -- and with it eps_theta / eps_f -- from the torch generator
         # (noise.draw) on every step, native noise or not: the captures below must register that generator
         self._draws_u = bool(is_model and gp.prev_params and gp.var_mean_mask != 1.0)
@@ -173,6 +173,9 @@ class ElboTrainer:
         if self._t0 and isinstance(self.optim, Yogi) and len(self.optim.param_groups) == 1:
             self.optim.external_step = True
             self._bump = self.optim.step_counter(dev)
+
+    def _refused(self, what):
+        return _EXT_REFUSED.format(what, type(self.gp.likelihood).__name__)
 
     # -- hipGraph capture of the step --------------------------------------------------------------
     def capture(self, x, y, warmup=3):
@@ -231,8 +234,8 @@ class ElboTrainer:
         a kernel boundary inside a graph, so K steps per launch shave that off K - 1 of every K steps.  The K steps read K
         static minibatch slots (`step_graph_k(xs, ys)` with xs (K, B, D), ys (K, B); without arguments the slots keep what they
         hold -- initially K copies of x, y); noise and optimiser step counts advance on the device as in the one-step graph."""
-        if self.gauss:
-            raise NotImplementedError(_GAUSS_REFUSED.format('capture_unrolled'))
+        if self.ext:
+            raise NotImplementedError(self._refused('capture_unrolled'))
         assert self.graph is not None and not self.multi and k >= 2 and x.size(0) == self._sx.size(0)
         self._k = int(k)
         self._sxk = x.unsqueeze(0).repeat(k, *([1] * x.dim())).contiguous()
@@ -264,8 +267,8 @@ class ElboTrainer:
         epoch's full batches with ceil(full batches / K) graph launches and no other launch at all (the per-step form: two
         index_select launches + one graph launch per step).  -> self, or None when the
         trainer cannot (no device step counter, several ranks): the caller keeps `step_graph_gather`."""
-        if self.gauss:
-            raise NotImplementedError(_GAUSS_REFUSED.format('capture_epoch'))
+        if self.ext:
+            raise NotImplementedError(self._refused('capture_epoch'))
         if self.graph is None or self.multi or self._bump is None or not self._t0:
             return None
         from ._lib import check, lib, ptr, stream_ptr
@@ -398,8 +401,8 @@ class ElboTrainer:
     def step_graph_gather(self, data, targets, idx):
         """Replay the captured step on the minibatch data[idx], targets[idx] (device-resident data set, idx a device index
         tensor of the captured batch size): gathered straight into the graph's static inputs, no host copy."""
-        if self.gauss:
-            raise NotImplementedError(_GAUSS_REFUSED.format('step_graph_gather'))
+        if self.ext:
+            raise NotImplementedError(self._refused('step_graph_gather'))
         self._select_capture(idx.numel())
         torch.index_select(data, 0, idx, out=self._sx)
         torch.index_select(targets, 0, idx, out=self._sy)
@@ -491,7 +494,7 @@ class ElboTrainer:
         else:
             eps_theta, eps_f = gp.draw_t0_noise(x)
             eps_theta = None if eps_theta is None else eps_theta.contiguous()
-            eps_f = None if eps_f is None else eps_f.contiguous()     # (None: GaussianLikelihood)
+            eps_f = None if eps_f is None else eps_f.contiguous()     # (None: an external likelihood)
         tn = bool(gp._use_block_program(x.size(0)))
         shape = T0Program.shape_of(S, gp.z, x, n_f(gp.likelihood)) + ((len(gp.prev_params) + 1,) if tn else ())
         prog = self._program_for(shape, tn)
@@ -501,7 +504,7 @@ class ElboTrainer:
         seeds = self._seeds[key]
         packed = gp._tn_operands() if tn else ()
         extra = dict(eps_u=eps_u) if tn else {}
-        if self.gauss:
+        if self.ext:
             # the likelihood is ours (ext_lik: moments + KL only); the block program still wants a label pointer
             labels, extra['ext_lik'] = (y_dummy(x.device) if tn else None), True
         else:
@@ -511,21 +514,16 @@ class ElboTrainer:
                 # left to the backward's tile kernel -- one launch less
                 extra['defer_softmax'] = os.environ.get('VARGP_DEFER_SOFTMAX', '1') != '0'
         scal = prog.forward(*gp._operands(), *packed, x, labels, eps_theta, eps_f, bump=self._bump, **extra)
-        if self.gauss:
-            self._gauss_lik(prog, y, seeds, scal)
+        if self.ext:
+            # between the forward and the backward: ONE call -- nll into scalars[2], the seeded d nll / d (mu, var) into the
+            # program's likelihood buffers, the gradient of the likelihood's own parameter (obs_log_var) into its .grad
+            lik = gp.likelihood
+            own = lik.ext_param()
+            lik.ext_backward(prog, lik.ext_target(y, shape[1], shape[4]), seeds[2:], nll=scal[2:],
+                             grad=None if own is None else self._gbuf(own))
         prog.backward(seeds, *map(self._gbuf, (kern.log_mean, kern.log_logvar, gp.z, gp.u_mean, gp.u_tril_vec)),
                       defer_hyper=defer_hyper)
         return scal
-
-    def _gauss_lik(self, prog, y, seeds, scal):
-        """Between the forward and the backward of a GaussianLikelihood model's step: ONE launch -- nll into scalars[2], the
-        seeded d nll / d (mu, var) into the program's likelihood buffers, d nll / d obs_log_var into its .grad."""
-        from . import fused, ops
-        mu, var, gmu, gvar = fused.lik_views(prog)
-        S, C, B = mu.shape
-        yt, ldy = ops.gauss_target(y, C, B)
-        olv = self.gp.likelihood.obs_log_var
-        ops.gauss_nll_bwd(mu, var, yt, ldy, olv.detach(), seeds[2:], gmu, gvar, self._gbuf(olv), nll=scal[2:])
 
     def _local_part(self, x, y):
         """This rank's share: gradients of w_r (beta kl_h + kl_u_r + (N/B) nll_r) accumulated into the flat buffer, whose

@@ -22,11 +22,20 @@ import torch.nn as nn
 from . import fused, gp_utils, noise, ops
 from .gp_utils import vec2tril, mat2trilvec, cholesky, rev_cholesky, gp_cond, block_joint, linear_marginal_diag
 from .kernels import RBFKernel, DeepRBFKernel, MaternKernel, native_code
-from .likelihoods import MulticlassSoftmax, is_gaussian, n_f
+from .likelihoods import BernoulliLikelihood, MulticlassSoftmax, is_external, is_gaussian, n_f
 from .ops import LOWER
 
 
 _KERNEL_NU = {'rbf': None, 'matern12': 0.5, 'matern32': 1.5, 'matern52': 2.5}   # create_clf(kernel=)
+
+
+def make_clf_likelihood(likelihood, n_f, link='probit'):
+    """create_clf(likelihood=, link=) -> the likelihood module; ValueError for an unknown name or link."""
+    if likelihood == 'softmax':
+        return MulticlassSoftmax(n_f=n_f)
+    if likelihood == 'bernoulli':
+        return BernoulliLikelihood(link=link)
+    raise ValueError(f"create_clf: likelihood must be 'softmax' or 'bernoulli', got {likelihood!r}")
 
 
 class VARGP(nn.Module):
@@ -280,12 +289,12 @@ class VARGP(nn.Module):
 
     def draw_t0_noise(self, x):
         """(eps_theta, eps_f) of one first-task step: the hyper-parameter noise of RBFKernel.sample_hypers
-        (kernels.py:66-67; None under map_est) and the likelihood noise (likelihoods.py:26; None for the Gaussian
-        likelihood, which draws none)."""
+        (kernels.py:66-67; None under map_est) and the likelihood noise (likelihoods.py:26; None for an external
+        likelihood -- Gaussian, Bernoulli -- which draws none)."""
         kern = self.kernel
         S = 1 if kern.map_est else self.n_v
         eps_theta = None if kern.map_est else noise.draw('eps_theta', (S, kern.log_mean.shape[0]), x.device)
-        if is_gaussian(self.likelihood):
+        if is_external(self.likelihood):
             return eps_theta, None
         eps_f = noise.draw('eps_f', (S, self.likelihood.n_f, self.z.size(0), x.size(0)), x.device)
         return eps_theta, eps_f
@@ -293,8 +302,9 @@ class VARGP(nn.Module):
     # -- lazy route (lazy.py) ---------------------------------------------------------------------------------------------------
     def _lazy_ok(self):
         """The five parameters are plain trainable leaves without hooks: the program's backward may write their .grad itself.
-        Not for a GaussianLikelihood model: its sixth trainable tensor (obs_log_var) takes the autograd-node route."""
-        if not (self.lazy_loss and torch.is_grad_enabled()) or is_gaussian(self.likelihood):
+        Not for a model with an external likelihood (GaussianLikelihood and its sixth trainable tensor obs_log_var,
+        BernoulliLikelihood): the likelihood runs between the program's forward and backward on the autograd-node route."""
+        if not (self.lazy_loss and torch.is_grad_enabled()) or is_external(self.likelihood):
             return False
         k = self.kernel
         ps = (k.log_mean, self.z, self.u_mean, self.u_tril_vec) + (() if k.map_est else (k.log_logvar,))
@@ -336,12 +346,12 @@ class VARGP(nn.Module):
             prog, packed = self._program(B, block), (self._tn_operands() if block else ())
             if lazy:
                 return fused.elbo_lazy(self, x, y, prog, packed)
-            # one autograd node.  Regression: the same programs with the likelihood left to the caller (ext_lik) and the
-            # closed-form Gaussian nll between forward and backward, obs_log_var as a sixth differentiable input
+            # one autograd node.  External likelihoods (Gaussian, Bernoulli): the same programs with the likelihood left to the
+            # caller (ext_lik), its value between forward and backward, its own parameter (obs_log_var) as a sixth input
             eps_theta, eps_f = self.draw_t0_noise(x)
             return fused.elbo_node(self._operands(detach=False), self.kernel.map_est, x, y, eps_theta, eps_f, prog, packed,
                                    eps_u=self.draw_u_noise(x),
-                                   obs_log_var=self.likelihood.obs_log_var if is_gaussian(self.likelihood) else None)
+                                   likelihood=self.likelihood if is_external(self.likelihood) else None)
         loss_cache = dict()
         pred_mu, pred_var = self(x, loss_cache=loss_cache)
         nll = self.likelihood.loss(pred_mu, pred_var, y)
@@ -361,9 +371,9 @@ class VARGP(nn.Module):
         Injected noise (noise.inject: eps_theta (S, D+1), eps_f (S, F, C, N)) is honoured; otherwise the program draws its
         own (counter-based generator keyed by `noise_seed`)."""
         assert self._tn_applicable() and (not self.prev_params or self.var_mean_mask == 1.0)
-        if is_gaussian(self.likelihood):
+        if is_external(self.likelihood):
             raise NotImplementedError('elbo_tiled: the tiled sweep evaluates the softmax likelihood of integer labels; '
-                                      'GaussianLikelihood models train through loss() or ElboTrainer')
+                                      f'{type(self.likelihood).__name__} models train through loss() or ElboTrainer')
         kern = self.kernel
         S = 1 if kern.map_est else self.n_v
         prog = self._tn_program(int(tile))       # honours a pending backward of VARGP.loss on the same shape
@@ -385,7 +395,8 @@ class VARGP(nn.Module):
         return scal[0].clone(), scal[1].clone(), scal[2].clone()
 
     def predict(self, x, tile=None):
-        """Class probabilities (B, C)  (vargp.py:196-198); for a GaussianLikelihood model the predictive means (S, C, B).
+        """Class probabilities (B, C)  (vargp.py:196-198; BernoulliLikelihood: per-output P(t = 1), not normalised over the
+        outputs); for a GaussianLikelihood model the predictive means (S, C, B).
         With `tile`, a large x is swept in blocks of `tile` points that share ONE hyper-sample and ONE set of x-independent
         factors (K_uu, its Cholesky / inverse, Lz^-1 m, Lz^-1 L_S): the same result as a single call on all of x, in bounded
         memory."""
@@ -425,13 +436,16 @@ class VARGP(nn.Module):
 
     @staticmethod
     def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None,
-                   ep_var_mean=True, map_est_hypers=False, dkl=False, kernel='rbf', native_kernel=False):
+                   ep_var_mean=True, map_est_hypers=False, dkl=False, kernel='rbf', native_kernel=False,
+                   likelihood='softmax', link='probit'):
         """Factory used by the experiment driver (vargp.py:200-243): inducing points at random data
         points per class, hyper-prior = previous task's hyper-posterior (popped from prev_params[-1],
         which is mutated like the reference does).  kernel: 'rbf' (the reference's), or 'matern12' / 'matern32' /
         'matern52' (MaternKernel; not with dkl).  native_kernel=True: the Matern model runs the native block program
-        (MaternKernel(native=True)); an error with 'rbf' or dkl, which have no such choice.  Neither is part of a checkpoint:
-        give them again on reload."""
+        (MaternKernel(native=True)); an error with 'rbf' or dkl, which have no such choice.  likelihood: 'softmax' (the
+        reference's MulticlassSoftmax(n_f)) or 'bernoulli' (BernoulliLikelihood(link), the integer labels read as one-vs-rest
+        targets; n_f is then unused), with any kernel choice.  None of these is part of a checkpoint: give them again on reload."""
+        lik = make_clf_likelihood(likelihood, n_f, link)
         if kernel not in _KERNEL_NU:
             raise ValueError(f'create_clf: kernel must be one of {sorted(_KERNEL_NU)}, got {kernel!r}')
         if dkl and kernel != 'rbf':
@@ -463,6 +477,5 @@ class VARGP(nn.Module):
         else:
             kern = RBFKernel(z.size(-1), prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
                              map_est=map_est_hypers)
-        likelihood = MulticlassSoftmax(n_f=n_f)
-        return VARGP(z, kern, likelihood, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean,
+        return VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean,
                      prev_params=prev_params)

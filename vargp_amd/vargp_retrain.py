@@ -16,7 +16,6 @@ import torch.nn as nn
 from . import gp_utils, noise, ops
 from .gp_utils import vec2tril, rev_cholesky, linear_marginal_diag
 from .kernels import RBFKernel
-from .likelihoods import MulticlassSoftmax
 from .ops import LOWER
 
 _HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
@@ -172,9 +171,12 @@ class VARGPRetrain(nn.Module):
         return self.likelihood.predict(pred_mu, pred_var)
 
     @staticmethod
-    def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None):
+    def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None, likelihood='softmax', link='probit'):
         """Factory (vargp_retrain.py:239-267): inducing points at random data points per class, hyper-prior = the last
-        task's hyper-posterior (popped from prev_params, which is mutated like the reference does)."""
+        task's hyper-posterior (popped from prev_params, which is mutated like the reference does).  likelihood / link: as
+        VARGP.create_clf."""
+        from .vargp import make_clf_likelihood
+        lik = make_clf_likelihood(likelihood, n_f, link)
         N = len(dataset)
         out_size = torch.unique(dataset.targets).size(0)
         z = torch.stack([dataset[torch.randperm(N)[:M]][0] for _ in range(out_size)])
@@ -186,4 +188,4 @@ class VARGPRetrain(nn.Module):
                 for k in [k for k in p if k.startswith('kernel')]:
                     p.pop(k)
         kernel = RBFKernel(z.size(-1), prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar)
-        return VARGPRetrain(z, kernel, MulticlassSoftmax(n_f=n_f), n_var_samples=n_var_samples, prev_params=prev_params)
+        return VARGPRetrain(z, kernel, lik, n_var_samples=n_var_samples, prev_params=prev_params)
