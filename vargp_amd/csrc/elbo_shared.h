@@ -119,6 +119,23 @@ static __global__ void t0_hyper_bwd_kernel(const float* __restrict__ mean, const
   glogvar[d] = gv;
 }
 
+// that step as data (include/vargp_hip.h: vargp_hyper_grad_desc) for either program: d its descriptor, o its carved workspace,
+// eps_theta the noise the forward used (given or drawn)
+template <class Desc, class Ws>
+static void hyper_grad_desc_fill(const Desc* d, const Ws& o, const float* eps_theta, const float* seeds, vargp_hyper_grad_desc* out) {
+  out->log_mean = d->log_mean; out->log_logvar = d->log_logvar;
+  out->prior_log_mean = d->prior_log_mean; out->prior_log_logvar = d->prior_log_logvar;
+  out->eps_theta = eps_theta;
+  out->gtheta = o.gtheta; out->g2 = o.g2; out->gkd = o.gkd; out->seeds = seeds;
+  out->S = d->S; out->C = d->C; out->D1 = d->D + 1; out->map_est = d->map_est;
+}
+// ... and as the last launch of a backward
+static void hyper_bwd_launch(const vargp_hyper_grad_desc& h, float* g_log_mean, float* g_log_logvar, hipStream_t st) {
+  hipLaunchKernelGGL(t0_hyper_bwd_kernel, dim3(cdiv(h.D1, 256)), dim3(256), 0, st, h.log_mean, h.log_logvar, h.prior_log_mean,
+                     h.prior_log_logvar, h.eps_theta, h.gtheta, h.g2, h.gkd, h.seeds, g_log_mean, g_log_logvar, h.S, h.C, h.D1,
+                     h.map_est);
+}
+
 // K-splits for the products with few output tiles and a long K: about 4 slabs of 64 per workgroup (measured best)
 static int ksplit(int K) {
   static const int per = [] { const char* e = getenv("VARGP_KSPLIT_PER"); return e ? atoi(e) : 256; }();   // tuning aid

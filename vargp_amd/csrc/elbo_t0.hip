@@ -1398,10 +1398,11 @@ extern "C" int vargp_elbo_t0_bwd(const vargp_elbo_t0_desc* d, const float* seeds
                          o.Puu, o.Puf, o.w, g_z, o.gtheta, zrows, (int64_t)B, D, o.Dp, S, nzy, gv);
     }
   }
-  if (!d->defer_hyper)
-    hipLaunchKernelGGL(t0_hyper_bwd_kernel, dim3(cdiv(D + 1, 256)), dim3(256), 0, st, d->log_mean, d->log_logvar,
-                       d->prior_log_mean, d->prior_log_logvar, eps_theta, o.gtheta, o.g2, o.gkd, seeds, g_log_mean,
-                       g_log_logvar, S, C, D + 1, d->map_est);
+  if (!d->defer_hyper) {
+    vargp_hyper_grad_desc h;
+    hyper_grad_desc_fill(d, o, eps_theta, seeds, &h);
+    hyper_bwd_launch(h, g_log_mean, g_log_logvar, st);
+  }
   return check_launch("elbo_t0_bwd");
 }
 
@@ -1410,10 +1411,6 @@ extern "C" int vargp_elbo_t0_hyper_desc(const vargp_elbo_t0_desc* d, const float
   if (rc) return rc;
   VARGP_REQUIRE(seeds && out, "elbo_t0_hyper_desc: null pointer");
   const T0Ws o = carve_t0(d->ws, d->S, d->C, d->M, d->D, d->B, d->F);
-  out->log_mean = d->log_mean; out->log_logvar = d->log_logvar;
-  out->prior_log_mean = d->prior_log_mean; out->prior_log_logvar = d->prior_log_logvar;
-  out->eps_theta = (d->eps_f == nullptr && !d->ext_lik) ? o.eps_theta : d->eps_theta;
-  out->gtheta = o.gtheta; out->g2 = o.g2; out->gkd = o.gkd; out->seeds = seeds;
-  out->S = d->S; out->C = d->C; out->D1 = d->D + 1; out->map_est = d->map_est;
+  hyper_grad_desc_fill(d, o, (d->eps_f == nullptr && !d->ext_lik) ? o.eps_theta : d->eps_theta, seeds, out);
   return VARGP_OK;
 }

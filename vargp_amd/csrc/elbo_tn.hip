@@ -642,65 +642,12 @@ __global__ void tn_kl_bwd_kernel(const float* __restrict__ QPs, float* __restric
   if (col == 0 || (col >= 4 && col - 4 <= i && col < 4 + M)) gQPs[off] += g * QPs[off];
 }
 
+
 // kernel_nu2 of the descriptor: 0 = RBF, 1 | 3 | 5 = Matern nu = 1/2, 3/2, 5/2 (include/vargp_hip.h)
 static bool tn_nu2_ok(int nu2) { return nu2 == 0 || nu2 == 1 || nu2 == 3 || nu2 == 5; }
 static int tn_epi(int nu2) { return nu2 == 1 ? kEpiMatern12 : nu2 == 3 ? kEpiMatern32 : nu2 == 5 ? kEpiMatern52 : kEpiRbf; }
 #define TN_REQUIRE_NU2(d, who) \
   VARGP_REQUIRE(tn_nu2_ok((d)->kernel_nu2), "%s: kernel_nu2 = %d (0: RBF; 1, 3 or 5: Matern nu = 1/2, 3/2, 5/2)", who, (d)->kernel_nu2)
-
-// a kernel matrix of the program: launch_gemm with the descriptor's epilogue (the RBF launch is the one it always was)
-static int tn_gram_gemm(const GemmParams& p, int nbatch, int nu2, hipStream_t st, const char* rbf_tag, const char* matern_tag) {
-  if (nu2 == 0) return launch_gemm(p, 0, 1, nbatch, true, st, rbf_tag);
-  return launch_gemm_epi(p, 0, 1, nbatch, tn_epi(nu2), st, matern_tag);
-}
-
-// Matern backward: W = gK o (-2 g2 dk/dd2) needs the scaled squared distances, which K does not give back.  They are
-// RECOMPUTED here -- the forward's two distance products once more with the epilogue EpiDist2 (operands, norms and tile choice
-// are the forward's, still in the workspace; 0 on the diagonal of K_all) -- into buffers that are dead by now: d2_uf into gP
-// (consumed by the gK_uf product), d2_all into the Cholesky backward's scratch.  No workspace beyond the RBF program's, and
-// nothing of the forward is overwritten (a second backward on the same forward stays legal).  DESIGN.md section 9 has the
-// measurement against the alternatives.  uf / uu: which of the two this call needs (the tiled ELBO: uf per tile, uu at the end).
-static int tn_matern_d2(const vargp_elbo_tn_desc* d, const TnWs& o, const float* x, int B, bool uf, bool uu, float* d2uf, float* d2uu,
-                        hipStream_t st) {
-  const int S = d->S, C = d->C, D = d->D, Mt = o.Mt, SC = S * C;
-  const int64_t MtMt = (int64_t)Mt * Mt, MtB = (int64_t)Mt * B, zrows = (int64_t)C * Mt;
-  int rc;
-  if (D <= kRbfDirectD) {
-    if (uu) { rc = matern_direct_launch(d->z_all, nullptr, o.w, o.g2, d2uu, S, C, Mt, Mt, D, o.Dp, 0, kEpiDist2, st); if (rc) return rc; }
-    if (uf) { rc = matern_direct_launch(d->z_all, x, o.w, o.g2, d2uf, S, C, Mt, B, D, o.Dp, 1, kEpiDist2, st); if (rc) return rc; }
-    return VARGP_OK;
-  }
-  if (uu) {
-    GemmParams p0{};
-    p0.A = o.zs; p0.B = d->z_all; p0.C = d2uu;
-    p0.M = Mt; p0.N = Mt; p0.K = D; p0.lda = D; p0.ldb = D; p0.ldc = Mt;
-    p0.nb1 = C; p0.nb2 = 1;
-    p0.sA[0] = zrows * D; p0.sA[1] = (int64_t)Mt * D; p0.sB[1] = (int64_t)Mt * D;
-    p0.sC[0] = C * MtMt; p0.sC[1] = MtMt;
-    p0.alpha = 1.f;
-    p0.kscale = nullptr; p0.ks_ld = o.Dp; p0.g2 = o.g2;
-    p0.na = o.na; p0.sNa[0] = zrows; p0.sNa[1] = Mt;
-    p0.nbv = o.na; p0.sNb[0] = zrows; p0.sNb[1] = Mt;
-    p0.same_xy = 1; p0.triC = 2; p0.symout = 1;
-    rc = launch_gemm_epi(p0, 0, 1, SC, kEpiDist2, st, "matern_kuu_d2_gemm");
-    if (rc) return rc;
-  }
-  if (uf) {
-    GemmParams pf{};
-    pf.A = d->z_all; pf.B = o.xs; pf.C = d2uf;
-    pf.M = C * Mt; pf.N = B; pf.K = D; pf.lda = D; pf.ldb = D; pf.ldc = B;
-    pf.nb1 = 1; pf.nb2 = 1;
-    pf.sB[0] = (int64_t)B * D;
-    pf.sC[0] = (int64_t)C * MtB;
-    pf.alpha = 1.f;
-    pf.kscale = nullptr; pf.ks_ld = o.Dp; pf.g2 = o.g2;
-    pf.na = o.na; pf.sNa[0] = zrows;
-    pf.nbv = o.nb; pf.sNb[0] = B;
-    rc = launch_gemm_epi(pf, 0, 1, S, kEpiDist2, st, "matern_kuf_d2_gemm");
-    if (rc) return rc;
-  }
-  return VARGP_OK;
-}
 
 // the W pass of either kernel (elbo_shared.h): nuf blocks of the K_uf role (0: none), nuu of the K_all role (0: none)
 static void tn_w_launch(int nu2, const TnWs& o, int S, int C, int B, int D, int gx, int gy, int nuf, int nuu, const float* seeds,
@@ -766,6 +713,325 @@ static GemmParams blk_gemm(const float* A, int lda, const int64_t (&sA)[3], cons
   return p;
 }
 
+// one plain product of the program: operands, transpositions, batch count, profiling tag
+struct TnGemm {
+  GemmParams p;
+  int tA, tB, nbatch;
+  const char* tag;
+  TnGemm& onto_c() {      // accumulate: D = C, beta = 1
+    p.D = p.C; p.ldd = p.ldc; p.beta = 1.f;
+    for (int i = 0; i < 3; ++i) p.sD[i] = p.sC[i];
+    return *this;
+  }
+};
+
+// What every entry point of the program shares: descriptor, carved workspace, stream, derived sizes -- and, as members, the
+// description of each launch, ONCE: the GemmParams of a product, or a kernel launch with its grid and arguments, as a function of
+// what differs between callers (the width B and the x of the minibatch or tile, output and epilogue of a distance product,
+// overwrite or accumulate, which roles of a multi-role kernel run).  Which launches run, in what order and which of them share
+// one: the entry points below.
+struct Tn {
+  const vargp_elbo_tn_desc* d;
+  TnWs o;
+  hipStream_t st;
+  int S, C, M, D, F, nblk, SC, Mt, NRs, nu2;
+  int64_t MtMt, MtN, zrows;
+  int64_t sQ[3], sRK[3], sTd[3];      // (s, c, block) strides of QPs / gQPs, of rk_all and of the diagonal blocks of T / gT
+
+  Tn(const vargp_elbo_tn_desc* d_, bool fwd_only, vargp_stream_t stream)
+      : d(d_), o(carve_tn(d_->ws, d_->S, d_->C, d_->M, d_->D, d_->B, d_->F, d_->nblk, fwd_only)), st(as_stream(stream)),
+        S(d_->S), C(d_->C), M(d_->M), D(d_->D), F(d_->F), nblk(d_->nblk), SC(d_->S * d_->C), Mt(o.Mt), NRs(o.NRs),
+        nu2(d_->kernel_nu2), MtMt((int64_t)o.Mt * o.Mt), MtN((int64_t)o.Mt * o.NRs), zrows((int64_t)d_->C * o.Mt),
+        sQ{C * MtN, MtN, (int64_t)M * NRs}, sRK{0, (int64_t)nblk * M * NRs, (int64_t)M * NRs},
+        sTd{C * MtMt, MtMt, (int64_t)M * Mt + M} {}
+
+  float* rk_last() const { return d->rk_all + (int64_t)(nblk - 1) * M * NRs; }      // the current task's block of rk_all
+  float* Smat() const { return reinterpret_cast<float*>(o.chol); }                  // scratch of the Cholesky backward
+
+  int run(const TnGemm& g) const { return launch_gemm(g.p, g.tA, g.tB, g.nbatch, false, st, g.tag); }
+  int run_pair(const TnGemm& a, const TnGemm& b, const char* tag) const {
+    return launch_gemm_pair2(a.p, a.tA, a.tB, a.nbatch, b.p, b.tA, b.tB, b.nbatch, st, tag);
+  }
+  TnGemm flat(const float* A, int lda, int64_t sA, const float* B, int ldb, int64_t sB, float* Cm, int ldc, int64_t sC, int m, int n,
+              int k, int tA, int tB, const char* tag) const {
+    return TnGemm{flat_gemm(A, lda, sA, B, ldb, sB, Cm, ldc, sC, m, n, k), tA, tB, SC, tag};
+  }
+
+  // ---- forward ------------------------------------------------------------------------------------------------------
+  // zero_count: floats zeroed from gmu on (the softmax-gradient accumulators; 0: none).  native_theta / native_f: the noise the
+  // generator draws here (the tiled ELBO draws the likelihood's per tile)
+  void prologue(int64_t zero_count, bool native_theta, bool native_f) const {
+    TnProArgs a{};
+    a.mean = d->log_mean; a.logvar = d->log_logvar; a.pmean = d->prior_log_mean; a.plogvar = d->prior_log_logvar;
+    a.eps_theta = d->eps_theta; a.vec = d->u_tril_vec; a.u_mean = d->u_mean; a.z = d->z;
+    a.theta = o.theta; a.g2 = o.g2; a.kd = o.kd; a.scalars = d->scalars; a.bump = d->bump;
+    a.rk_last = rk_last(); a.z_all = d->z_all;
+    a.info = d->info; a.ninfo = SC;
+    a.zero_begin = o.gmu; a.zero_count = zero_count;
+    a.S = S; a.C = C; a.M = M; a.D = D; a.Mt = Mt; a.NRs = NRs; a.nblk = nblk; a.map_est = d->map_est;
+    a.nzero_blocks = (int)std::min<int64_t>(64, cdiv(zero_count, 1024));
+    if (native_theta) {
+      a.native = 1; a.seed = d->rng_seed; a.rng_counter = d->rng_counter;
+      a.g0_theta = (int64_t)d->rng_sample_offset * (D + 1);
+      a.eps_theta_out = o.eps_theta;
+    }
+    if (native_f) {
+      const int64_t per_sample_f = (int64_t)F * C * d->B;
+      a.g0_f = (int64_t)d->rng_sample_offset * per_sample_f;
+      a.n_f = S * per_sample_f;
+      a.eps_f_out = o.eps_f;
+      a.nrng_blocks = (int)std::min<int64_t>(512, cdiv(a.n_f + 7, 1024));
+    }
+    a.npack_blocks = cdiv((int64_t)C * M * NRs, 256);
+    const int grid = 1 + S + a.nzero_blocks + a.nrng_blocks + a.npack_blocks + cdiv((int64_t)C * M * D, 256);
+    hipLaunchKernelGGL(tn_prologue_kernel, dim3(grid), dim3(256), 0, st, a);
+  }
+
+  // The two distance products (D > kRbfDirectD) over ALL inducing points, earlier tasks + current; out: K itself, or the d2 of
+  // the Matern backward.  Operands pre-scaled by the norm pass (zs = z_all o w, xs = x o w): no per-k scaling in the main loop.
+  // K_all (S, C, Mt, Mt): tiles touching the lower triangle, mirrored (the matrix is symmetric)
+  GemmParams kall_gemm(float* out) const {
+    GemmParams p{};
+    p.A = o.zs; p.B = d->z_all; p.C = out;
+    p.M = Mt; p.N = Mt; p.K = D; p.lda = D; p.ldb = D; p.ldc = Mt;
+    p.nb1 = C; p.nb2 = 1;
+    p.sA[0] = zrows * D; p.sA[1] = (int64_t)Mt * D; p.sB[1] = (int64_t)Mt * D;
+    p.sC[0] = C * MtMt; p.sC[1] = MtMt;
+    p.alpha = 1.f;
+    p.kscale = nullptr; p.ks_ld = o.Dp; p.g2 = o.g2;
+    p.na = o.na; p.sNa[0] = zrows; p.sNa[1] = Mt;
+    p.nbv = o.na; p.sNb[0] = zrows; p.sNb[1] = Mt;
+    p.same_xy = 1; p.triC = 2; p.symout = 1;
+    return p;
+  }
+  // K_uf (S, C, Mt, B) of the x whose x o w is in xs: the classes' inducing points are just more rows of one [C*Mt, D] x [D, B]
+  // product
+  GemmParams kuf_gemm(float* out, int B) const {
+    GemmParams p{};
+    p.A = d->z_all; p.B = o.xs; p.C = out;
+    p.M = C * Mt; p.N = B; p.K = D; p.lda = D; p.ldb = D; p.ldc = B;
+    p.nb1 = 1; p.nb2 = 1;
+    p.sB[0] = (int64_t)B * D;
+    p.sC[0] = (int64_t)C * Mt * B;
+    p.alpha = 1.f;
+    p.kscale = nullptr; p.ks_ld = o.Dp; p.g2 = o.g2;
+    p.na = o.na; p.sNa[0] = zrows;
+    p.nbv = o.nb; p.sNb[0] = B;
+    return p;
+  }
+  // launch of one of them (uf: kuf_gemm or a row slice of it) with the epilogue epi: tn_epi(nu2) for the kernel matrix (the RBF
+  // launch is the one it always was), kEpiDist2 for d2
+  int gram(const GemmParams& p, bool uf, int epi) const {
+    const int nbatch = uf ? S : SC;
+    if (epi == kEpiRbf) return launch_gemm(p, 0, 1, nbatch, true, st, uf ? "rbf_kuf_gemm" : "rbf_kuu_gemm");
+    if (epi == kEpiDist2) return launch_gemm_epi(p, 0, 1, nbatch, epi, st, uf ? "matern_kuf_d2_gemm" : "matern_kuu_d2_gemm");
+    return launch_gemm_epi(p, 0, 1, nbatch, epi, st, uf ? "matern_kuf_gemm" : "matern_kuu_gemm");
+  }
+
+  // [a_i | . | H_i] = T_ii [m_i | 0 | Lu_i] for every (s, c, block i)
+  TnGemm small_gemm() const {
+    TnGemm g{blk_gemm(o.TT, Mt, sTd, d->rk_all, NRs, sRK, o.QPs, NRs, sQ, M, NRs, M, C, nblk), 0, 0, SC * nblk, "tn_small_gemm"};
+    g.p.triA = 1;
+    return g;
+  }
+  // P = T K_uf
+  TnGemm p_gemm(int B) const {
+    TnGemm g = flat(o.TT, Mt, MtMt, o.Kuf, B, (int64_t)Mt * B, o.P, B, (int64_t)Mt * B, Mt, B, Mt, 0, 0, "tn_p_gemm");
+    g.p.triA = 1;
+    return g;
+  }
+  // V2 = T^T P  (= K'^-1 K_uf: the eps term of the variance)
+  TnGemm v2_gemm(int B) const {
+    TnGemm g = flat(o.TT, Mt, MtMt, o.P, B, (int64_t)Mt * B, o.V2, B, (int64_t)Mt * B, Mt, B, Mt, 1, 0, "tn_v2_gemm");
+    g.p.triA = 2;
+    return g;
+  }
+  // W_i = H_i^T P_i
+  TnGemm w_gemm(int B) const {
+    const int64_t MtB = (int64_t)Mt * B, sP[3] = {C * MtB, MtB, (int64_t)M * B};
+    TnGemm g{blk_gemm(o.QPs + 4, NRs, sQ, o.P, B, sP, o.W, B, sP, M, B, M, C, nblk), 1, 0, SC * nblk, "tn_w_gemm"};
+    g.p.triA = 2;
+    return g;
+  }
+  // mu, var of B columns (moments) and / or the KL of the current task into *kl_u (NULL: no KL role); rng_counter (nullable) is
+  // stepped: this call's noise has been drawn; a_term = 0: without the KL's mean term (ep_var_mean = False)
+  void pdiag_kl(int B, bool moments, float* kl_u, uint32_t* rng_counter, int a_term) const {
+    const bool narrow = moments && cdiv(B, 64) * SC < 512;
+    const int nbx = cdiv(B, narrow ? 32 : 64), npd = moments ? nbx * SC : 0, nkx = cdiv(M, kTnKlRows);
+    hipLaunchKernelGGL(narrow ? tn_pdiag_kl_kernel<32> : tn_pdiag_kl_kernel<64>, dim3(npd + (kl_u ? nkx * SC : 0)), dim3(256), 0, st,
+                       o.P, o.W, o.V2, o.QPs, o.kd, o.LL, d->rk_all, o.mu, o.var, kl_u, d->jitter, S, C, M, Mt, nblk, B, NRs, nbx, npd,
+                       nkx, rng_counter, a_term);
+  }
+  // fused softmax likelihood, C <= 16: adds the nll of B columns to scalars[2], the unscaled gradients to gmu / gvar
+  void softmax16(int B, const float* eps_f, const int64_t* y) const {
+    hipLaunchKernelGGL(t0_softmax_kernel<16>, dim3(cdiv((int64_t)S * F * B, 256)), dim3(256), 0, st, o.mu, o.var, eps_f, y,
+                       d->scalars + 2, o.gmu, o.gvar, S, F, C, B);
+  }
+
+  // ---- backward -----------------------------------------------------------------------------------------------------
+  // gscale (nullable): the seed of the stored unscaled softmax gradients.  accumulate (a tile of the sweep): the head role alone,
+  // adding; else the rest-of-gQPs role and the zero-fill of the r / c / gtheta accumulators ride along
+  void bwd_head(int B, const float* gscale, const float* seeds, bool accumulate, int a_term) const {
+    const int npd = SC * Mt;
+    const int nrest = accumulate ? 0 : cdiv((int64_t)npd * (NRs - 1), 256);
+    const int64_t zc = accumulate ? 0 : o.r_uu - o.r_uf;
+    const int nz = (int)std::min<int64_t>(64, cdiv(zc, 1024));
+    hipLaunchKernelGGL(tn_bwd_head_kernel, dim3(npd + nrest + nz), dim3(256), 0, st, o.P, o.W, o.V2, o.QPs, o.gmu, o.gvar, gscale, seeds,
+                       o.gP, o.gQPs, o.gkd, d->jitter, S, M, Mt, B, NRs, npd, nrest, accumulate ? (float*)nullptr : o.r_uf, zc,
+                       accumulate ? 1 : 0, a_term);
+  }
+  // The head kernel leaves gW in W and gV2 in V2 (in place).
+  // W_i = H_i^T P_i:  gH_i += P_i gW_i^T on top of the KL term / the earlier tiles -- splitk > 1: K-split with atomic
+  // accumulation; tril: the lower triangle only (only tril(gH_i) is used: by tril(gH_i Lu_i^T) in gT and by the packed-vector
+  // gradient; the head kernel left zeros above the diagonal)
+  TnGemm gh_gemm(int B, int splitk, bool tril) const {
+    const int64_t MtB = (int64_t)Mt * B, sP[3] = {C * MtB, MtB, (int64_t)M * B};
+    TnGemm g{blk_gemm(o.P, B, sP, o.W, B, sP, o.gQPs + 4, NRs, sQ, M, M, B, C, nblk), 0, 1, SC * nblk, "tn_gh_gemm"};
+    g.p.splitk = splitk;
+    if (splitk <= 1) g.onto_c();
+    if (tril) g.p.triC = 1;
+    return g;
+  }
+  // ... and gP_i += H_i gW_i
+  TnGemm gp_gemm(int B) const {
+    const int64_t MtB = (int64_t)Mt * B, sP[3] = {C * MtB, MtB, (int64_t)M * B};
+    TnGemm g{blk_gemm(o.QPs + 4, NRs, sQ, o.W, B, sP, o.gP, B, sP, M, B, M, C, nblk), 0, 0, SC * nblk, "tn_gp_gemm"};
+    g.p.triA = 1;
+    return g.onto_c();
+  }
+  // V2 = T^T P:  gP += T gV2
+  TnGemm gp_v2_gemm(int B) const {
+    TnGemm g = flat(o.TT, Mt, MtMt, o.V2, B, (int64_t)Mt * B, o.gP, B, (int64_t)Mt * B, Mt, B, Mt, 0, 0, "tn_gp_v2_gemm");
+    g.p.triA = 1;
+    return g.onto_c();
+  }
+  // gT = tril(gP K_uf^T + P gV2^T)  (P = T K_uf and V2 = T^T P): its two halves, each overwriting or adding
+  TnGemm gt_kuf_gemm(int B, bool accumulate) const {
+    TnGemm g = flat(o.gP, B, (int64_t)Mt * B, o.Kuf, B, (int64_t)Mt * B, o.gT, Mt, MtMt, Mt, Mt, B, 0, 1, "tn_gt_gemm");
+    g.p.triC = 1;
+    return accumulate ? g.onto_c() : g;
+  }
+  TnGemm gt_v2_gemm(int B, bool accumulate) const {
+    TnGemm g = flat(o.P, B, (int64_t)Mt * B, o.V2, B, (int64_t)Mt * B, o.gT, Mt, MtMt, Mt, Mt, B, 0, 1, "tn_gt_gemm");
+    g.p.triC = 1;
+    return accumulate ? g.onto_c() : g;
+  }
+  // gK_uf = T^T gP
+  TnGemm gkuf_gemm(int B) const {
+    TnGemm g = flat(o.TT, Mt, MtMt, o.gP, B, (int64_t)Mt * B, o.gKuf, B, (int64_t)Mt * B, Mt, B, Mt, 1, 0, "tn_gkuf_gemm");
+    g.p.triA = 2;
+    return g;
+  }
+  // the diagonal blocks' share of gT from the small products:  gT_ii += gQP_i RK_i^T
+  TnGemm gt_diag_gemm() const {
+    TnGemm g{blk_gemm(o.gQPs, NRs, sQ, d->rk_all, NRs, sRK, o.gT, Mt, sTd, M, M, NRs, C, nblk), 0, 1, SC * nblk, "tn_gt_diag_gemm"};
+    g.p.triC = 1;
+    return g.onto_c();
+  }
+  // the parameter gradients of the current task:  [g m_t | . | g Lu_t] = T_tt^T [ga_t | . | gH_t]
+  TnGemm grk_gemm() const {
+    const int64_t off = (int64_t)(Mt - M) * Mt + (Mt - M);
+    TnGemm g = flat(o.TT + off, Mt, MtMt, o.gQPs + (int64_t)(Mt - M) * NRs, NRs, MtN, o.gRKt, NRs, (int64_t)M * NRs, M, NRs, M, 1, 0,
+                    "tn_grk_gemm");
+    g.p.triA = 2;
+    return g;
+  }
+  // Cholesky backward, gT -> gK.  Only diag(L_tt) is used forward (log-determinant), so gL = diag(g / L_jj) on the current block:
+  //   P_low = tril(L^T gL - gT T^T) = g I_t - tril(gT T^T)   (the lower triangle of L^T diag(.) is its diagonal)
+  //   Smat  = (Phi(P_low) + Phi(P_low)^T) / 2 = -0.5 sym(tril(gT T^T)) + 0.5 g I_t,     gK = T^T Smat T
+  int chol_bwd(const float* seeds) const {
+    float* tmp = Smat() + SC * MtMt;
+    TnGemm p = flat(o.gT, Mt, MtMt, o.TT, Mt, MtMt, Smat(), Mt, MtMt, Mt, Mt, Mt, 0, 1, "tn_chol_bwd1");
+    p.p.alpha = -0.5f; p.p.triA = 1; p.p.triB = 2; p.p.triC = 2; p.p.symout = 1;
+    p.p.diag_ptr = seeds + 1; p.p.diag_scale = 0.5f / (float)S; p.p.diag_from = Mt - M;     // + g / 2 on the current task's diagonal
+    int rc = run(p);
+    if (rc) return rc;
+    // gK = T^T (Smat T) is symmetric: its lower triangle needs tril(Smat T) only, and as T^T [.] the tiles of the lower
+    // triangle are the ones with the SHORT K ranges (k >= row), 40 % of the work of the full product
+    TnGemm q = flat(Smat(), Mt, MtMt, o.TT, Mt, MtMt, tmp, Mt, MtMt, Mt, Mt, Mt, 0, 0, "tn_chol_bwd2");
+    q.p.triB = 1; q.p.triC = 1;
+    rc = run(q);
+    if (rc) return rc;
+    TnGemm r = flat(o.TT, Mt, MtMt, tmp, Mt, MtMt, o.gK, Mt, MtMt, Mt, Mt, Mt, 1, 0, "tn_chol_bwd3");
+    r.p.triA = 2; r.p.triB = 1; r.p.triC = 2; r.p.symout = 1;
+    return run(r);
+  }
+
+  // Kernel matrices -> theta, z: the fused passes of the first-task program (elbo_shared.h), each with its K_uf role on the B
+  // columns of x (uf), its K_all role (uu), or both.
+  // Matern: W = gK o (-2 g2 dk/dd2) needs the scaled squared distances, which K does not give back.  They are RECOMPUTED here --
+  // the forward's distance products once more with the epilogue EpiDist2 (operands, norms and tile choice are the forward's, still
+  // in the workspace: the x o w of this x in xs; 0 on the diagonal of K_all) -- into buffers that are dead by now.  No workspace
+  // beyond the RBF program's, and nothing of the forward is overwritten (a second backward on the same forward stays legal).
+  // DESIGN.md section 9 has the measurement against the alternatives.
+  int matern_d2(const float* x, int B, float* d2uf, float* d2uu) const {      // NULL: not needed
+    int rc;
+    if (D <= kRbfDirectD) {
+      if (d2uu) { rc = matern_direct_launch(d->z_all, nullptr, o.w, o.g2, d2uu, S, C, Mt, Mt, D, o.Dp, 0, kEpiDist2, st); if (rc) return rc; }
+      if (d2uf) { rc = matern_direct_launch(d->z_all, x, o.w, o.g2, d2uf, S, C, Mt, B, D, o.Dp, 1, kEpiDist2, st); if (rc) return rc; }
+      return VARGP_OK;
+    }
+    if (d2uu) { rc = gram(kall_gemm(d2uu), false, kEpiDist2); if (rc) return rc; }
+    if (d2uf) { rc = gram(kuf_gemm(d2uf, B), true, kEpiDist2); if (rc) return rc; }
+    return VARGP_OK;
+  }
+  // W = gK o K (Matern: see above) for both kernel matrices in one launch: K_uf in place on gK_uf, with its row sums (adding) and
+  // column sums; K_all: gK is symmetric, W + W^T = 2 W, and its row sums
+  int w_pass(const float* x, int B, bool uf, bool uu, const float* seeds) const {
+    float *d2uf = nullptr, *d2uu = nullptr;
+    if (nu2 && !tn_d2_invert(nu2)) {
+      if (uf) d2uf = o.gP;        // dead since the gK_uf product
+      if (uu) d2uu = Smat();      // dead since gK was written
+      const int rc = matern_d2(x, B, d2uf, d2uu);
+      if (rc) return rc;
+    }
+    const int gx = cdiv(B, 256), gy = cdiv(zrows, kWRows);
+    tn_w_launch(nu2, o, S, C, B, D, gx, gy, uf ? gx * gy * S : 0, uu ? SC * cdiv(Mt, kUuRows) : 0, seeds, d2uf, d2uu, st);
+    return VARGP_OK;
+  }
+  // the W.Y products: P_uu = W_uu z_all,  P_uf = W_uf x (accumulate: on top of the earlier tiles')
+  TnGemm wz_gemm() const {
+    GemmParams p{};
+    p.A = o.Wuu; p.B = d->z_all; p.C = o.Puu;
+    p.M = Mt; p.N = D; p.K = Mt; p.lda = Mt; p.ldb = D; p.ldc = D;
+    p.nb1 = C; p.nb2 = 1;
+    p.sA[0] = C * MtMt; p.sA[1] = MtMt;
+    p.sB[1] = (int64_t)Mt * D;
+    p.sC[0] = zrows * D; p.sC[1] = (int64_t)Mt * D;
+    p.alpha = 1.f;
+    return TnGemm{p, 0, 0, SC, "rbf_kuu_bwd_gemm"};
+  }
+  TnGemm wx_gemm(const float* x, int B, bool accumulate) const {
+    GemmParams p{};
+    p.A = o.gKuf; p.B = x; p.C = o.Puf;
+    p.M = C * Mt; p.N = D; p.K = B; p.lda = B; p.ldb = D; p.ldc = D;
+    p.nb1 = 1; p.nb2 = 1;
+    p.sA[0] = (int64_t)C * Mt * B;
+    p.sC[0] = zrows * D;
+    p.alpha = 1.f;
+    if (accumulate) { p.D = o.Puf; p.ldd = D; p.sD[0] = zrows * D; p.beta = 1.f; }
+    return TnGemm{p, 0, 0, S, "rbf_kuf_bwd_gemm"};
+  }
+  // one finalisation for the inducing-point side (z_side: gz_all, gtheta from r_uu, r_uf, P_uu, P_uf) and the minibatch side
+  // (x != NULL: gtheta += w sum_n c_uf x^2 over its B rows)
+  void final(const float* x, int B, bool z_side) const {
+    const int nzy = z_side ? cdiv(zrows, kFinRows) : 0, nxy = x ? cdiv(B, kFinRows) : 0;
+    hipLaunchKernelGGL(t0_final_kernel, dim3(cdiv(D, 64), nzy + nxy), dim3(256), 0, st, d->z_all, x, o.r_uu, o.r_uf, o.c_uf, o.Puu,
+                       o.Puf, o.w, o.gz_all, o.gtheta, zrows, (int64_t)(x ? B : 0), D, o.Dp, S, nzy);
+  }
+  // gRKt, gz_all -> the gradients of the current task's u_mean, u_tril_vec, z
+  void unpack(const float* seeds, float* g_u_mean, float* g_u_tril_vec, float* g_z) const {
+    const int nun = cdiv((int64_t)C * M * (M + 1), 256);
+    hipLaunchKernelGGL(tn_unpack_kernel, dim3(nun + cdiv((int64_t)C * M * D, 256)), dim3(256), 0, st, o.gRKt, d->u_tril_vec, rk_last(),
+                       seeds, o.gz_all, g_u_mean, g_u_tril_vec, g_z, S, C, M, Mt, D, NRs, nblk, nun);
+  }
+  void hyper_bwd(const float* eps_theta, const float* seeds, float* g_log_mean, float* g_log_logvar) const {
+    vargp_hyper_grad_desc h;
+    hyper_grad_desc_fill(d, o, eps_theta, seeds, &h);
+    hyper_bwd_launch(h, g_log_mean, g_log_logvar, st);
+  }
+};
+
 }  // namespace vargp
 
 using namespace vargp;
@@ -803,47 +1069,23 @@ extern "C" int vargp_elbo_tn_lik_buffers(const vargp_elbo_tn_desc* d, float** mu
 extern "C" int vargp_elbo_tn_fwd(const vargp_elbo_tn_desc* d, vargp_stream_t stream) {
   int rc = check_tn(d, "elbo_tn_fwd");
   if (rc) return rc;
-  hipStream_t st = as_stream(stream);
-  const int S = d->S, C = d->C, M = d->M, D = d->D, B = d->B, F = d->F, nblk = d->nblk, SC = S * C;
-  const TnWs o = carve_tn(d->ws, S, C, M, D, B, F, nblk, d->forward_only != 0);
-  const int Mt = o.Mt, NRs = o.NRs;
-  const int64_t MtMt = (int64_t)Mt * Mt, MtB = (int64_t)Mt * B, MtN = (int64_t)Mt * NRs;
+  const Tn t(d, d->forward_only != 0, stream);
+  const TnWs& o = t.o;
+  hipStream_t st = t.st;
+  const int S = t.S, C = t.C, M = t.M, D = t.D, B = d->B, F = t.F, nblk = t.nblk, SC = t.SC, Mt = t.Mt, NRs = t.NRs, nu2 = t.nu2;
+  const int64_t zrows = t.zrows;
   const bool lik = d->y != nullptr;                 // y == NULL: predictive moments only (no likelihood, no KL)
   const bool native = lik && d->eps_f == nullptr && !d->ext_lik;
-  const bool fused_softmax = C <= 16;
-  const float* eps_f = native ? o.eps_f : d->eps_f;
   {
     ProfScope prof("tn_prologue", st);
-    TnProArgs a{};
-    a.mean = d->log_mean; a.logvar = d->log_logvar; a.pmean = d->prior_log_mean; a.plogvar = d->prior_log_logvar;
-    a.eps_theta = d->eps_theta; a.vec = d->u_tril_vec; a.u_mean = d->u_mean; a.z = d->z;
-    a.theta = o.theta; a.g2 = o.g2; a.kd = o.kd; a.scalars = d->scalars; a.bump = d->bump;
-    a.rk_last = d->rk_all + (int64_t)(nblk - 1) * M * NRs; a.z_all = d->z_all;
-    a.info = d->info; a.ninfo = SC;
-    a.zero_begin = o.gmu; a.zero_count = o.Kall - o.gmu;
-    a.S = S; a.C = C; a.M = M; a.D = D; a.Mt = Mt; a.NRs = NRs; a.nblk = nblk; a.map_est = d->map_est;
-    a.nzero_blocks = (int)std::min<int64_t>(64, cdiv(a.zero_count, 1024));
-    if (native) {
-      const int64_t per_sample_f = (int64_t)F * C * B;
-      a.native = 1; a.seed = d->rng_seed; a.rng_counter = d->rng_counter;
-      a.g0_theta = (int64_t)d->rng_sample_offset * (D + 1); a.g0_f = (int64_t)d->rng_sample_offset * per_sample_f;
-      a.n_f = S * per_sample_f;
-      a.eps_theta_out = o.eps_theta; a.eps_f_out = o.eps_f;
-      a.nrng_blocks = (int)std::min<int64_t>(512, cdiv(a.n_f + 7, 1024));
-    }
-    a.npack_blocks = cdiv((int64_t)C * M * NRs, 256);
-    const int grid = 1 + S + a.nzero_blocks + a.nrng_blocks + a.npack_blocks + cdiv((int64_t)C * M * D, 256);
-    hipLaunchKernelGGL(tn_prologue_kernel, dim3(grid), dim3(256), 0, st, a);
+    t.prologue(o.Kall - o.gmu, native, native);
   }
   // kernel matrices over ALL inducing points (earlier tasks + current): K_all (S,C,Mt,Mt), K_uf (S,C,Mt,B)
-  const int64_t zrows = (int64_t)C * Mt;
-  const bool mfma = D > kRbfDirectD;
   bool kuf_done = false;
-  GemmParams pf{};       // K_uf = rbf(z_all, x): the classes' inducing points are just more rows of one [C*Mt, D] x [D, B] product
+  GemmParams pf{};
   rc = rbf_prep_norm_launch(o.theta, d->z_all, zrows, d->x, B, o.w, o.g2, o.na, o.nb, S, D, o.Dp, st, o.xs, o.zs);
   if (rc) return rc;
-  const int nu2 = d->kernel_nu2;
-  if (!mfma) {           // small input dimension: direct (cancellation-free) distances
+  if (D <= kRbfDirectD) {           // small input dimension: direct (cancellation-free) distances
     rc = nu2 ? matern_direct_launch(d->z_all, nullptr, o.w, o.g2, o.Kall, S, C, Mt, Mt, D, o.Dp, 0, tn_epi(nu2), st)
              : rbf_direct_launch(d->z_all, nullptr, o.w, o.g2, o.Kall, Mt, S, C, Mt, Mt, D, o.Dp, 0, st);
     if (rc) return rc;
@@ -852,30 +1094,9 @@ extern "C" int vargp_elbo_tn_fwd(const vargp_elbo_tn_desc* d, vargp_stream_t str
     if (rc) return rc;
     kuf_done = true;
   } else {
-    GemmParams p0{};     // K_all: tiles touching the lower triangle, mirrored (the matrix is symmetric)
-    p0.A = o.zs; p0.B = d->z_all; p0.C = o.Kall;        // A pre-scaled by the norm pass: no per-k scaling in the main loop
-    p0.M = Mt; p0.N = Mt; p0.K = D; p0.lda = D; p0.ldb = D; p0.ldc = Mt;
-    p0.nb1 = C; p0.nb2 = 1;
-    p0.sA[0] = zrows * D; p0.sA[1] = (int64_t)Mt * D; p0.sB[1] = (int64_t)Mt * D;
-    p0.sC[0] = C * MtMt; p0.sC[1] = MtMt;
-    p0.alpha = 1.f;
-    p0.kscale = nullptr; p0.ks_ld = o.Dp; p0.g2 = o.g2;
-    p0.na = o.na; p0.sNa[0] = zrows; p0.sNa[1] = Mt;
-    p0.nbv = o.na; p0.sNb[0] = zrows; p0.sNb[1] = Mt;
-    static const int ksym = [] { const char* e = getenv("VARGP_TN_KSYM"); return e ? atoi(e) : 1; }();   // tuning aid
-    p0.same_xy = 1;
-    if (ksym) { p0.triC = 2; p0.symout = 1; }
-    rc = tn_gram_gemm(p0, SC, nu2, st, "rbf_kuu_gemm", "matern_kuu_gemm");
+    rc = t.gram(t.kall_gemm(o.Kall), false, tn_epi(nu2));
     if (rc) return rc;
-    pf.A = d->z_all; pf.B = o.xs; pf.C = o.Kuf;
-    pf.M = C * Mt; pf.N = B; pf.K = D; pf.lda = D; pf.ldb = D; pf.ldc = B;
-    pf.nb1 = 1; pf.nb2 = 1;
-    pf.sB[0] = (int64_t)B * D;
-    pf.sC[0] = (int64_t)C * MtB;
-    pf.alpha = 1.f;
-    pf.kscale = nullptr; pf.ks_ld = o.Dp; pf.g2 = o.g2;      // pre-scaled B operand
-    pf.na = o.na; pf.sNa[0] = zrows;
-    pf.nbv = o.nb; pf.sNb[0] = B;
+    pf = t.kuf_gemm(o.Kuf, B);
   }
   // L = chol(K_all + eps I), T = L^-1: every factor of the reference's chain is a leading block of these.  The K_uf
   // GEMM, which nothing needs before T exists, shares the launch of the first diagonal block's pivot chain.
@@ -907,76 +1128,57 @@ extern "C" int vargp_elbo_tn_fwd(const vargp_elbo_tn_desc* d, vargp_stream_t str
                       hipEventRecord(reinterpret_cast<hipEvent_t>(d->info_event), st) == hipSuccess,
                   "elbo_tn_fwd: copy / event record of the early Cholesky status failed");
   }
-  if (!kuf_done) {
+  if (!kuf_done) {      // what the pivot chains did not take along
     if (consumed == 0) {
-      rc = tn_gram_gemm(pf, S, nu2, st, "rbf_kuf_gemm", "matern_kuf_gemm");
+      rc = t.gram(pf, true, tn_epi(nu2));
       if (rc) return rc;
     } else {
       for (int i = consumed; i < nsl; ++i) {
-        rc = launch_gemm(slices[i], 0, 1, S, true, st, "rbf_kuf_gemm");
+        rc = t.gram(slices[i], true, kEpiRbf);
         if (rc) return rc;
       }
     }
   }
-  {  // [a_i | . | H_i] = T_ii [m_i | 0 | Lu_i] for every (s, c, block i)
-    const int64_t sA[3] = {C * MtMt, MtMt, (int64_t)M * Mt + M}, sB[3] = {0, (int64_t)nblk * M * NRs, (int64_t)M * NRs},
-                  sC[3] = {C * MtN, MtN, (int64_t)M * NRs};
-    GemmParams p = blk_gemm(o.TT, Mt, sA, d->rk_all, NRs, sB, o.QPs, NRs, sC, M, NRs, M, C, nblk);
-    p.triA = 1;
-    // P = T K_uf: independent of the small products -- mid-size shapes share one launch
-    GemmParams q = flat_gemm(o.TT, Mt, MtMt, o.Kuf, B, MtB, o.P, B, MtB, Mt, B, Mt);
-    q.triA = 1;
+  {  // P = T K_uf is independent of the small products -- mid-size shapes share one launch
+    const TnGemm p = t.small_gemm(), q = t.p_gemm(B);
     const int64_t wgs = (int64_t)SC * (nblk * cdiv(M, 64) * cdiv(NRs, 64) + cdiv(Mt, 64) * cdiv(B, 64));
-    static const int pair_fwd = [] { const char* e = getenv("VARGP_TN_PAIRFWD"); return e ? atoi(e) : 1; }();   // tuning aid
-    if (pair_fwd && wgs <= 4096) {
-      rc = launch_gemm_pair2(p, 0, 0, SC * nblk, q, 0, 0, SC, st, "tn_p_gemm");
+    if (wgs <= 4096) {
+      rc = t.run_pair(p, q, "tn_p_gemm");
       if (rc) return rc;
     } else {
-      rc = launch_gemm(p, 0, 0, SC * nblk, false, st, "tn_small_gemm");
+      rc = t.run(p);
       if (rc) return rc;
-      rc = launch_gemm(q, 0, 0, SC, false, st, "tn_p_gemm");
+      rc = t.run(q);
       if (rc) return rc;
     }
   }
-  {  // V2 = T^T P  (= K'^-1 K_uf: the eps term of the variance)  and  W_i = H_i^T P_i: both only need P
-    GemmParams p = flat_gemm(o.TT, Mt, MtMt, o.P, B, MtB, o.V2, B, MtB, Mt, B, Mt);
-    p.triA = 2;
-    const int64_t sA[3] = {C * MtN, MtN, (int64_t)M * NRs}, sB[3] = {C * MtB, MtB, (int64_t)M * B};
-    GemmParams q = blk_gemm(o.QPs + 4, NRs, sA, o.P, B, sB, o.W, B, sB, M, B, M, C, nblk);
-    q.triA = 2;
+  {  // V2 and the W_i both only need P
+    const TnGemm p = t.v2_gemm(B), q = t.w_gemm(B);
     const int64_t wgs = (int64_t)SC * cdiv(B, 64) * (cdiv(Mt, 64) + nblk * cdiv(M, 64));
-    static const int pair_fwd = [] { const char* e = getenv("VARGP_TN_PAIRFWD"); return e ? atoi(e) : 1; }();   // tuning aid
-    if (pair_fwd && wgs <= 4096) {
-      rc = launch_gemm_pair2(p, 1, 0, SC, q, 1, 0, SC * nblk, st, "tn_v2_gemm");
+    if (wgs <= 4096) {
+      rc = t.run_pair(p, q, "tn_v2_gemm");
       if (rc) return rc;
     } else {
-      rc = launch_gemm(p, 1, 0, SC, false, st, "tn_v2_gemm");
+      rc = t.run(p);
       if (rc) return rc;
-      rc = launch_gemm(q, 1, 0, SC * nblk, false, st, "tn_w_gemm");
+      rc = t.run(q);
       if (rc) return rc;
     }
   }
-  {
-    const bool narrow = cdiv(B, 64) * SC < 512;
-    const int nbx = cdiv(B, narrow ? 32 : 64), npd = nbx * SC, nkx = cdiv(M, kTnKlRows);
-    const bool nomean = lik && d->no_var_mean && nblk > 1;
-    hipLaunchKernelGGL(narrow ? tn_pdiag_kl_kernel<32> : tn_pdiag_kl_kernel<64>, dim3(npd + (lik ? nkx * SC : 0)), dim3(256), 0, st, o.P, o.W, o.V2, o.QPs, o.kd,
-                       o.LL, d->rk_all, o.mu, o.var, lik ? d->scalars + 1 : nullptr, d->jitter, S, C, M, Mt, nblk, B, NRs,
-                       nbx, npd, nkx, native ? d->rng_counter : nullptr, nomean ? 0 : 1);
-    if (nomean) {   // the mean term of the KL at the n_v samples of u_<t (tn_nm_* above)
-      const int NV = d->n_v, Ml = Mt - M;
-      const int64_t nvl = (int64_t)SC * Ml * NV;
-      hipLaunchKernelGGL(tn_nm_v_kernel, dim3(cdiv(nvl, 256)), dim3(256), 0, st, o.QPs, d->eps_u, o.nm_v, S, C, M, Mt, NRs, NV);
-      hipLaunchKernelGGL(tn_nm_y1_kernel, dim3(cdiv(nvl, 256)), dim3(256), 0, st, o.TT, o.nm_v, o.nm_y1, (int64_t)SC, M, Mt, NV);
-      hipLaunchKernelGGL(tn_nm_y2_kernel, dim3(cdiv((int64_t)SC * M, 4)), dim3(256), 0, st, o.Kall, o.nm_y1, o.nm_y2, (int64_t)SC, M, Mt, NV);
-      hipLaunchKernelGGL(tn_nm_d_kernel, dim3(SC), dim3(256), 0, st, o.TT, o.QPs, o.nm_y2, o.nm_d, d->scalars + 1, S, M, Mt, NRs, NV);
-    }
+  const bool nomean = lik && d->no_var_mean && nblk > 1;
+  t.pdiag_kl(B, true, lik ? d->scalars + 1 : nullptr, native ? d->rng_counter : nullptr, nomean ? 0 : 1);
+  if (nomean) {   // the mean term of the KL at the n_v samples of u_<t (tn_nm_* above)
+    const int NV = d->n_v, Ml = Mt - M;
+    const int64_t nvl = (int64_t)SC * Ml * NV;
+    hipLaunchKernelGGL(tn_nm_v_kernel, dim3(cdiv(nvl, 256)), dim3(256), 0, st, o.QPs, d->eps_u, o.nm_v, S, C, M, Mt, NRs, NV);
+    hipLaunchKernelGGL(tn_nm_y1_kernel, dim3(cdiv(nvl, 256)), dim3(256), 0, st, o.TT, o.nm_v, o.nm_y1, (int64_t)SC, M, Mt, NV);
+    hipLaunchKernelGGL(tn_nm_y2_kernel, dim3(cdiv((int64_t)SC * M, 4)), dim3(256), 0, st, o.Kall, o.nm_y1, o.nm_y2, (int64_t)SC, M, Mt, NV);
+    hipLaunchKernelGGL(tn_nm_d_kernel, dim3(SC), dim3(256), 0, st, o.TT, o.QPs, o.nm_y2, o.nm_d, d->scalars + 1, S, M, Mt, NRs, NV);
   }
   if (lik && !d->ext_lik) {       // (ext_lik: the caller evaluates the likelihood on the moments of ALL classes, include/vargp_hip.h)
-    if (fused_softmax) {
-      const int64_t total = (int64_t)S * F * B;
-      hipLaunchKernelGGL(t0_softmax_kernel<16>, dim3(cdiv(total, 256)), dim3(256), 0, st, o.mu, o.var, eps_f, d->y,
-                         d->scalars + 2, o.gmu, o.gvar, S, F, C, B);
+    const float* eps_f = native ? o.eps_f : d->eps_f;
+    if (C <= 16) {
+      t.softmax16(B, eps_f, d->y);
     } else {
       rc = vargp_softmax_nll_fwd(o.mu, o.var, eps_f, d->y, d->scalars + 2, S, F, C, B, stream);
       if (rc) return rc;
@@ -992,30 +1194,18 @@ extern "C" int vargp_elbo_tn_bwd(const vargp_elbo_tn_desc* d, const float* seeds
   VARGP_REQUIRE(seeds && g_z && g_u_mean && g_u_tril_vec && d->y && (d->defer_hyper || (g_log_mean && g_log_logvar)),
                 "elbo_tn_bwd: null pointer");
   VARGP_REQUIRE(!d->forward_only, "elbo_tn_bwd: the program was carved forward_only");
-  hipStream_t st = as_stream(stream);
-  const int S = d->S, C = d->C, M = d->M, D = d->D, B = d->B, F = d->F, nblk = d->nblk, SC = S * C;
-  const TnWs o = carve_tn(d->ws, S, C, M, D, B, F, nblk);
-  const int Mt = o.Mt, NRs = o.NRs;
-  const int64_t MtMt = (int64_t)Mt * Mt, MtB = (int64_t)Mt * B, MtN = (int64_t)Mt * NRs;
+  const Tn t(d, false, stream);
+  const TnWs& o = t.o;
+  hipStream_t st = t.st;
+  const int S = t.S, C = t.C, M = t.M, D = t.D, B = d->B, F = t.F, nblk = t.nblk, SC = t.SC, Mt = t.Mt, NRs = t.NRs;
   const bool native = d->eps_f == nullptr && !d->ext_lik;
   const bool fused_softmax = C <= 16 && !d->ext_lik;      // ext_lik: gmu / gvar arrive seeded, as from the generic kernel
-  const float* eps_f = native ? o.eps_f : d->eps_f;
-  const float* eps_theta = native ? o.eps_theta : d->eps_theta;
-
   const bool nomean = d->no_var_mean && nblk > 1;
   if (!fused_softmax && !d->ext_lik) {
-    rc = vargp_softmax_nll_bwd(o.mu, o.var, eps_f, d->y, seeds + 2, o.gmu, o.gvar, S, F, C, B, stream);
+    rc = vargp_softmax_nll_bwd(o.mu, o.var, native ? o.eps_f : d->eps_f, d->y, seeds + 2, o.gmu, o.gvar, S, F, C, B, stream);
     if (rc) return rc;
   }
-  {
-    const int npd = SC * Mt;
-    const int nrest = cdiv((int64_t)npd * (NRs - 1), 256);
-    const int64_t zc = o.r_uu - o.r_uf;
-    const int nz = (int)std::min<int64_t>(64, cdiv(zc, 1024));
-    hipLaunchKernelGGL(tn_bwd_head_kernel, dim3(npd + nrest + nz), dim3(256), 0, st, o.P, o.W, o.V2, o.QPs, o.gmu, o.gvar,
-                       fused_softmax ? seeds + 2 : nullptr, seeds, o.gP, o.gQPs, o.gkd, d->jitter, S, M, Mt, B, NRs, npd,
-                       nrest, o.r_uf, zc, 0, nomean ? 0 : 1);
-  }
+  t.bwd_head(B, fused_softmax ? seeds + 2 : nullptr, seeds, false, nomean ? 0 : 1);
   if (nomean) {   // ep_var_mean = False: the KL's mean term back to ga / gH of every block (gQPs), keeping gy2 / gy1 for gT and gK
     const int NV = d->n_v, Ml = Mt - M;
     const int64_t nvl = (int64_t)SC * Ml * NV;
@@ -1024,75 +1214,44 @@ extern "C" int vargp_elbo_tn_bwd(const vargp_elbo_tn_desc* d, const float* seeds
     hipLaunchKernelGGL(tn_nm_bwd3_kernel, dim3(cdiv((int64_t)SC * Ml, 4)), dim3(256), 0, st, o.TT, o.nm_gy1, d->eps_u, o.gQPs, S, C, M, Mt,
                        NRs, NV);
   }
-  float* gW = o.W;      // in place (tn_bwd_head_kernel)
-  float* gV2 = o.V2;
-  {  // W_i = H_i^T P_i:  gH_i += P_i gW_i^T (K-split, atomic accumulation on top of the KL term),  gP_i += H_i gW_i
-    const int64_t sQ[3] = {C * MtN, MtN, (int64_t)M * NRs}, sP[3] = {C * MtB, MtB, (int64_t)M * B};
-    GemmParams p = blk_gemm(o.P, B, sP, gW, B, sP, o.gQPs + 4, NRs, sQ, M, M, B, C, nblk);
-    p.splitk = ksplit(B);
-    if (p.splitk <= 1) { p.D = o.gQPs + 4; p.ldd = NRs; p.beta = 1.f; for (int i = 0; i < 3; ++i) p.sD[i] = sQ[i]; }
-    GemmParams q = blk_gemm(o.QPs + 4, NRs, sQ, gW, B, sP, o.gP, B, sP, M, B, M, C, nblk);
-    q.triA = 1; q.D = o.gP; q.ldd = B; q.beta = 1.f;
-    const int64_t wgs = (int64_t)SC * nblk * (cdiv(M, 64) * cdiv(M, 64) * std::max(p.splitk, 1) + cdiv(M, 64) * cdiv(B, 64));
+  {  // gH (K-split on top of the KL term) and gP += H gW
+    const TnGemm p = t.gh_gemm(B, ksplit(B), false), q = t.gp_gemm(B);
+    const int64_t wgs = (int64_t)SC * nblk * (cdiv(M, 64) * cdiv(M, 64) * std::max(p.p.splitk, 1) + cdiv(M, 64) * cdiv(B, 64));
     if (wgs <= 4096) {     // mid-size: one launch for both
-      rc = launch_gemm_pair2(p, 0, 1, SC * nblk, q, 0, 0, SC * nblk, st, "tn_gh_gp_gemm");
+      rc = t.run_pair(p, q, "tn_gh_gp_gemm");
       if (rc) return rc;
     } else {               // each fills the chip by itself: own launches with the tile shape that suits them
-      // (only tril(gH_i) is used: by tril(gH_i Lu_i^T) in gT and by the packed-vector gradient; the head kernel left
-      //  zeros above the diagonal)
-      p.splitk = 1; p.D = o.gQPs + 4; p.ldd = NRs; p.beta = 1.f; p.triC = 1;
-      for (int i = 0; i < 3; ++i) p.sD[i] = sQ[i];
-      rc = launch_gemm(p, 0, 1, SC * nblk, false, st, "tn_gh_gemm");
+      rc = t.run(t.gh_gemm(B, 1, true));
       if (rc) return rc;
-      rc = launch_gemm(q, 0, 0, SC * nblk, false, st, "tn_gp_gemm");
+      rc = t.run(q);
       if (rc) return rc;
     }
   }
-  {  // V2 = T^T P:  gP += T gV2
-     // gT = tril(gP K_uf^T + P gV2^T)  (P = T K_uf and V2 = T^T P), then the diagonal blocks' share from the small products;
-     // gK_uf = T^T gP and the parameter gradients of the current task, [g m_t | . | g Lu_t] = T_tt^T [ga_t | . | gH_t], do not
-     // depend on gT.  Mid-size shapes (no product fills the chip alone) run the seven products as FOUR launches, ordered by what
-     // each needs:   [gT = P gV2^T  ||  gP += T gV2]  ->  [gT += gP K_uf^T  ||  gK_uf = T^T gP]  ->  [gT_ii += gQP_i RK_i^T  ||  gRK_t]
+  {  // gP += T gV2, then gT = tril(gP K_uf^T + P gV2^T) and the diagonal blocks' share from the small products; gK_uf = T^T gP and
+     // the parameter gradients of the current task (gRK_t) do not depend on gT.  Mid-size shapes (no product fills the chip alone)
+     // run the seven products as FOUR launches, ordered by what each needs:
+     //   [gT = P gV2^T  ||  gP += T gV2]  ->  [gT += gP K_uf^T  ||  gK_uf = T^T gP]  ->  [gT_ii += gQP_i RK_i^T  ||  gRK_t]
      // (P gV2^T needs nothing of this segment, so it leads and the gP product is added on top of it; round 4 ran five launches)
-    GemmParams v = flat_gemm(o.TT, Mt, MtMt, gV2, B, MtB, o.gP, B, MtB, Mt, B, Mt);
-    v.triA = 1; v.D = o.gP; v.beta = 1.f;
-    GemmParams p = flat_gemm(o.gP, B, MtB, o.Kuf, B, MtB, o.gT, Mt, MtMt, Mt, Mt, B);
-    p.triC = 1;
-    GemmParams q = flat_gemm(o.P, B, MtB, gV2, B, MtB, o.gT, Mt, MtMt, Mt, Mt, B);
-    q.triC = 1;
-    GemmParams ku = flat_gemm(o.TT, Mt, MtMt, o.gP, B, MtB, o.gKuf, B, MtB, Mt, B, Mt);
-    ku.triA = 2;
-    const int64_t off = (int64_t)(Mt - M) * Mt + (Mt - M);
-    GemmParams rk = flat_gemm(o.TT + off, Mt, MtMt, o.gQPs + (int64_t)(Mt - M) * NRs, NRs, MtN, o.gRKt, NRs, (int64_t)M * NRs, M,
-                              NRs, M);
-    rk.triA = 2;
-    const int64_t sQ[3] = {C * MtN, MtN, (int64_t)M * NRs}, sR[3] = {0, (int64_t)nblk * M * NRs, (int64_t)M * NRs},
-                  sT[3] = {C * MtMt, MtMt, (int64_t)M * Mt + M};
-    GemmParams r = blk_gemm(o.gQPs, NRs, sQ, d->rk_all, NRs, sR, o.gT, Mt, sT, M, M, NRs, C, nblk);
-    r.triC = 1; r.D = o.gT; r.ldd = Mt; r.beta = 1.f;
     const int64_t wgs = (int64_t)SC * cdiv(Mt, 64) * (cdiv(Mt, 64) + cdiv(B, 64));
-    static const int pair_bwd = [] { const char* e = getenv("VARGP_TN_PAIRBWD"); return e ? atoi(e) : 1; }();   // tuning aid
-    if (pair_bwd && wgs <= 4096) {
-      p.D = o.gT; p.beta = 1.f;           // on top of q, which leads
-      rc = launch_gemm_pair2(q, 0, 1, SC, v, 0, 0, SC, st, "tn_gt_gemm");
+    if (wgs <= 4096) {
+      rc = t.run_pair(t.gt_v2_gemm(B, false), t.gp_v2_gemm(B), "tn_gt_gemm");
       if (rc) return rc;
-      rc = launch_gemm_pair2(p, 0, 1, SC, ku, 1, 0, SC, st, "tn_gt_gemm");
+      rc = t.run_pair(t.gt_kuf_gemm(B, true), t.gkuf_gemm(B), "tn_gt_gemm");
       if (rc) return rc;
-      rc = launch_gemm_pair2(r, 0, 1, SC * nblk, rk, 1, 0, SC, st, "tn_gt_diag_gemm");
+      rc = t.run_pair(t.gt_diag_gemm(), t.grk_gemm(), "tn_gt_diag_gemm");
       if (rc) return rc;
     } else {
-      q.D = o.gT; q.beta = 1.f;           // on top of p
-      rc = launch_gemm(v, 0, 0, SC, false, st, "tn_gp_v2_gemm");
+      rc = t.run(t.gp_v2_gemm(B));
       if (rc) return rc;
-      rc = launch_gemm(p, 0, 1, SC, false, st, "tn_gt_gemm");
+      rc = t.run(t.gt_kuf_gemm(B, false));
       if (rc) return rc;
-      rc = launch_gemm(q, 0, 1, SC, false, st, "tn_gt_gemm");
+      rc = t.run(t.gt_v2_gemm(B, true));
       if (rc) return rc;
-      rc = launch_gemm(ku, 1, 0, SC, false, st, "tn_gkuf_gemm");
+      rc = t.run(t.gkuf_gemm(B));
       if (rc) return rc;
-      rc = launch_gemm(rk, 1, 0, SC, false, st, "tn_grk_gemm");
+      rc = t.run(t.grk_gemm());
       if (rc) return rc;
-      rc = launch_gemm(r, 0, 1, SC * nblk, false, st, "tn_gt_diag_gemm");
+      rc = t.run(t.gt_diag_gemm());
       if (rc) return rc;
     }
   }
@@ -1102,90 +1261,33 @@ extern "C" int vargp_elbo_tn_bwd(const vargp_elbo_tn_desc* d, const float* seeds
     hipLaunchKernelGGL(tn_nm_bwd4_kernel, dim3(cdiv(n_tt + n_ll, 256)), dim3(256), 0, st, o.nm_d, o.nm_y2, o.nm_v, o.nm_gy1, seeds, o.gT,
                        (int64_t)SC, S, M, Mt, NV, n_tt);
   }
-  // Cholesky backward.  Only diag(L_tt) is used forward (log-determinant), so gL = diag(g / L_jj) on the current block:
-  //   P_low = tril(L^T gL - gT T^T) = g I_t - tril(gT T^T)   (the lower triangle of L^T diag(.) is its diagonal)
-  //   Smat  = (Phi(P_low) + Phi(P_low)^T) / 2 = -0.5 sym(tril(gT T^T)) + 0.5 g I_t,     gK = T^T Smat T
-  float* Smat = reinterpret_cast<float*>(o.chol);
-  float* tmp = Smat + SC * MtMt;
-  {
-    GemmParams p = flat_gemm(o.gT, Mt, MtMt, o.TT, Mt, MtMt, Smat, Mt, MtMt, Mt, Mt, Mt);
-    p.alpha = -0.5f; p.triA = 1; p.triB = 2; p.triC = 2; p.symout = 1;
-    p.diag_ptr = seeds + 1; p.diag_scale = 0.5f / (float)S; p.diag_from = Mt - M;     // + g / 2 on the current task's diagonal
-    rc = launch_gemm(p, 0, 1, SC, false, st, "tn_chol_bwd1");
-    if (rc) return rc;
-    // gK = T^T (Smat T) is symmetric: its lower triangle needs tril(Smat T) only, and as T^T [.] the tiles of the lower
-    // triangle are the ones with the SHORT K ranges (k >= row), 40 % of the work of the full product
-    GemmParams q = flat_gemm(Smat, Mt, MtMt, o.TT, Mt, MtMt, tmp, Mt, MtMt, Mt, Mt, Mt);
-    q.triB = 1; q.triC = 1;
-    rc = launch_gemm(q, 0, 0, SC, false, st, "tn_chol_bwd2");
-    if (rc) return rc;
-    GemmParams r = flat_gemm(o.TT, Mt, MtMt, tmp, Mt, MtMt, o.gK, Mt, MtMt, Mt, Mt, Mt);
-    r.triA = 2; r.triB = 1; r.triC = 2; r.symout = 1;
-    rc = launch_gemm(r, 1, 0, SC, false, st, "tn_chol_bwd3");
-    if (rc) return rc;
-  }
+  rc = t.chol_bwd(seeds);
+  if (rc) return rc;
   if (nomean) {   // ... and the direct dependence of prior_mu on K_t<
     const int NV = d->n_v, Ml = Mt - M;
     hipLaunchKernelGGL(tn_nm_bwd5_kernel, dim3(cdiv((int64_t)SC * M * Ml, 256)), dim3(256), 0, st, o.nm_gy2, o.nm_y1, o.gK, (int64_t)SC, M,
                        Mt, NV);
   }
-  // kernel matrices -> theta, z  (the fused passes of the first-task program, elbo_shared.h):
-  //   W = gK o K for both kernel matrices in one launch (K_uf in place on gK_uf; K_all: gK is symmetric, W + W^T = 2 W),
-  //   both W.Y products, one finalisation for the inducing-point and the minibatch side
-  const int64_t zrows = (int64_t)C * Mt;
+  // kernel matrices -> theta, z: W for both kernel matrices in one launch, both W.Y products, one finalisation for the
+  // inducing-point and the minibatch side
+  rc = t.w_pass(d->x, B, true, true, seeds);
+  if (rc) return rc;
   {
-    const int gx = cdiv(B, 256), gy = cdiv(zrows, kWRows), nuf = gx * gy * S;
-    const int nuu = SC * cdiv(Mt, kUuRows);
-    const int nu2 = d->kernel_nu2;
-    float *d2uf = nullptr, *d2uu = nullptr;
-    if (nu2 && !tn_d2_invert(nu2)) {
-      d2uf = o.gP; d2uu = Smat;
-      rc = tn_matern_d2(d, o, d->x, B, true, true, d2uf, d2uu, st);
-      if (rc) return rc;
-    }
-    tn_w_launch(nu2, o, S, C, B, D, gx, gy, nuf, nuu, seeds, d2uf, d2uu, st);
-  }
-  {
-    GemmParams p0{}, p1{};
-    p0.A = o.Wuu; p0.B = d->z_all; p0.C = o.Puu;
-    p0.M = Mt; p0.N = D; p0.K = Mt; p0.lda = Mt; p0.ldb = D; p0.ldc = D;
-    p0.nb1 = C; p0.nb2 = 1;
-    p0.sA[0] = C * MtMt; p0.sA[1] = MtMt;
-    p0.sB[1] = (int64_t)Mt * D;
-    p0.sC[0] = zrows * D; p0.sC[1] = (int64_t)Mt * D;
-    p0.alpha = 1.f;
-    p1.A = o.gKuf; p1.B = d->x; p1.C = o.Puf;
-    p1.M = C * Mt; p1.N = D; p1.K = B; p1.lda = B; p1.ldb = D; p1.ldc = D;
-    p1.nb1 = 1; p1.nb2 = 1;
-    p1.sA[0] = C * MtB;
-    p1.sC[0] = zrows * D;
-    p1.alpha = 1.f;
+    const TnGemm p0 = t.wz_gemm(), p1 = t.wx_gemm(d->x, B, false);
     const int64_t wgs = (int64_t)cdiv(Mt, 64) * cdiv(D, 64) * SC + (int64_t)cdiv(C * Mt, 64) * cdiv(D, 64) * S;
     if (wgs <= 4096) {     // mid-size: neither fills the chip alone, one launch (64^3 tiles)
-      rc = launch_gemm_pair(p0, SC, p1, S, 0, 0, false, st, "rbf_kuu_bwd_gemm", "rbf_kuf_bwd_gemm");
+      rc = launch_gemm_pair(p0.p, p0.nbatch, p1.p, p1.nbatch, 0, 0, false, st, p0.tag, p1.tag);
       if (rc) return rc;
     } else {
-      rc = launch_gemm(p0, 0, 0, SC, false, st, "rbf_kuu_bwd_gemm");
+      rc = t.run(p0);
       if (rc) return rc;
-      rc = launch_gemm(p1, 0, 0, S, false, st, "rbf_kuf_bwd_gemm");
+      rc = t.run(p1);
       if (rc) return rc;
     }
   }
-  {
-    const int nzy = cdiv(zrows, kFinRows), nxy = cdiv(B, kFinRows);
-    hipLaunchKernelGGL(t0_final_kernel, dim3(cdiv(D, 64), nzy + nxy), dim3(256), 0, st, d->z_all, d->x, o.r_uu, o.r_uf, o.c_uf,
-                       o.Puu, o.Puf, o.w, o.gz_all, o.gtheta, zrows, (int64_t)B, D, o.Dp, S, nzy);
-  }
-  {
-    const int nun = cdiv((int64_t)C * M * (M + 1), 256);
-    hipLaunchKernelGGL(tn_unpack_kernel, dim3(nun + cdiv((int64_t)C * M * D, 256)), dim3(256), 0, st, o.gRKt, d->u_tril_vec,
-                       d->rk_all + (int64_t)(nblk - 1) * M * NRs, seeds, o.gz_all, g_u_mean, g_u_tril_vec, g_z, S, C, M, Mt, D,
-                       NRs, nblk, nun);
-  }
-  if (!d->defer_hyper)
-    hipLaunchKernelGGL(t0_hyper_bwd_kernel, dim3(cdiv(D + 1, 256)), dim3(256), 0, st, d->log_mean, d->log_logvar,
-                       d->prior_log_mean, d->prior_log_logvar, eps_theta, o.gtheta, o.g2, o.gkd, seeds, g_log_mean,
-                       g_log_logvar, S, C, D + 1, d->map_est);
+  t.final(d->x, B, true);
+  t.unpack(seeds, g_u_mean, g_u_tril_vec, g_z);
+  if (!d->defer_hyper) t.hyper_bwd(native ? o.eps_theta : d->eps_theta, seeds, g_log_mean, g_log_logvar);
   return check_launch("elbo_tn_bwd");
 }
 
@@ -1194,11 +1296,7 @@ extern "C" int vargp_elbo_tn_hyper_desc(const vargp_elbo_tn_desc* d, const float
   if (rc) return rc;
   VARGP_REQUIRE(seeds && out && !d->forward_only, "elbo_tn_hyper_desc: bad arguments");
   const TnWs o = carve_tn(d->ws, d->S, d->C, d->M, d->D, d->B, d->F, d->nblk);
-  out->log_mean = d->log_mean; out->log_logvar = d->log_logvar;
-  out->prior_log_mean = d->prior_log_mean; out->prior_log_logvar = d->prior_log_logvar;
-  out->eps_theta = (d->eps_f == nullptr && !d->ext_lik) ? o.eps_theta : d->eps_theta;
-  out->gtheta = o.gtheta; out->g2 = o.g2; out->gkd = o.gkd; out->seeds = seeds;
-  out->S = d->S; out->C = d->C; out->D1 = d->D + 1; out->map_est = d->map_est;
+  hyper_grad_desc_fill(d, o, (d->eps_f == nullptr && !d->ext_lik) ? o.eps_theta : d->eps_theta, seeds, out);
   return VARGP_OK;
 }
 
@@ -1207,7 +1305,7 @@ extern "C" int vargp_elbo_tn_hyper_desc(const vargp_elbo_tn_desc* d, const float
 // everything that does not depend on the data -- kernel matrix of the inducing points, its factorisation, the small
 // products, the KL -- computed ONCE (begin), a forward + partial backward per tile that only accumulates (tile), and the
 // Cholesky / kernel-matrix backward of the accumulated gradients at the end (end).  The nll seed multiplies every tile, so
-// the seeds are needed from the first tile on.  Same kernels as the one-minibatch program.
+// the seeds are needed from the first tile on.  Same launches as the one-minibatch program, nothing paired.
 // ------------------------------------------------------------------------------------------------------------------
 extern "C" int vargp_elbo_tn_begin(const vargp_elbo_tn_desc* d, vargp_stream_t stream) {
   int rc = check_tn(d, "elbo_tn_begin", true);
@@ -1215,73 +1313,32 @@ extern "C" int vargp_elbo_tn_begin(const vargp_elbo_tn_desc* d, vargp_stream_t s
   VARGP_REQUIRE(d->D > kRbfDirectD, "elbo_tn_begin: the tiled ELBO needs D > %d (MFMA distance path)", kRbfDirectD);
   // (refused here, before any launch, and not only by the first tile: see vargp_elbo_tn_tile)
   VARGP_REQUIRE(d->forward_only || d->C <= 16, "elbo_tn_begin: more than 16 classes is not supported by the tiled ELBO");
-  hipStream_t st = as_stream(stream);
-  const int S = d->S, C = d->C, M = d->M, D = d->D, B = d->B, F = d->F, nblk = d->nblk, SC = S * C;
   const bool fwd_only = d->forward_only != 0;      // predictive sweep (VARGP.predict(x, tile=)): no accumulators
-  const TnWs o = carve_tn(d->ws, S, C, M, D, B, F, nblk, fwd_only);
-  const int Mt = o.Mt, NRs = o.NRs;
-  const int64_t MtMt = (int64_t)Mt * Mt, MtN = (int64_t)Mt * NRs, zrows = (int64_t)C * Mt;
-  {
-    TnProArgs a{};
-    a.mean = d->log_mean; a.logvar = d->log_logvar; a.pmean = d->prior_log_mean; a.plogvar = d->prior_log_logvar;
-    a.eps_theta = d->eps_theta; a.vec = d->u_tril_vec; a.u_mean = d->u_mean; a.z = d->z;
-    a.theta = o.theta; a.g2 = o.g2; a.kd = o.kd; a.scalars = d->scalars; a.bump = d->bump;
-    a.rk_last = d->rk_all + (int64_t)(nblk - 1) * M * NRs; a.z_all = d->z_all;
-    a.info = d->info; a.ninfo = SC;
-    a.zero_begin = o.gmu; a.zero_count = 0;
-    a.S = S; a.C = C; a.M = M; a.D = D; a.Mt = Mt; a.NRs = NRs; a.nblk = nblk; a.map_est = d->map_est;
-    a.nzero_blocks = 0;
-    const bool native_theta = d->eps_theta == nullptr && !d->map_est;
-    if (native_theta) {   // theta noise from the generator (the per-tile likelihood noise is drawn by the tile calls)
-      VARGP_REQUIRE(d->rng_counter, "elbo_tn_begin: native noise needs rng_counter");
-      a.native = 1; a.seed = d->rng_seed; a.rng_counter = d->rng_counter;
-      a.g0_theta = (int64_t)d->rng_sample_offset * (D + 1);
-      a.eps_theta_out = o.eps_theta; a.nrng_blocks = 0; a.n_f = 0;
-    }
-    a.npack_blocks = cdiv((int64_t)C * M * NRs, 256);
-    const int grid = 1 + S + a.npack_blocks + cdiv((int64_t)C * M * D, 256);
-    hipLaunchKernelGGL(tn_prologue_kernel, dim3(grid), dim3(256), 0, st, a);
-  }
+  const Tn t(d, fwd_only, stream);
+  const TnWs& o = t.o;
+  hipStream_t st = t.st;
+  const int SC = t.SC, Mt = t.Mt;
+  const bool native_theta = d->eps_theta == nullptr && !d->map_est;
+  // theta noise from the generator (the per-tile likelihood noise is drawn by the tile calls)
+  VARGP_REQUIRE(!native_theta || d->rng_counter, "elbo_tn_begin: native noise needs rng_counter");
+  t.prologue(0, native_theta, false);
   // accumulators of the sweep
   if (!fwd_only) {
-    zero_async(o.gT, sizeof(float) * SC * MtMt, st);
-    zero_async(o.gQPs, sizeof(float) * SC * MtN, st);
+    zero_async(o.gT, sizeof(float) * SC * t.MtMt, st);
+    zero_async(o.gQPs, sizeof(float) * SC * t.MtN, st);
     zero_async(o.gkd, sizeof(float) * SC, st);
     zero_async(o.r_uf, sizeof(float) * (size_t)(o.r_uu - o.r_uf), st);
-    zero_async(o.Puf, sizeof(float) * SC * Mt * D, st);
+    zero_async(o.Puf, sizeof(float) * SC * Mt * t.D, st);
   }
-  rc = rbf_prep_norm_launch(o.theta, d->z_all, zrows, nullptr, 0, o.w, o.g2, o.na, o.nb, S, D, o.Dp, st, nullptr, o.zs);
+  rc = rbf_prep_norm_launch(o.theta, d->z_all, t.zrows, nullptr, 0, o.w, o.g2, o.na, o.nb, t.S, t.D, o.Dp, st, nullptr, o.zs);
   if (rc) return rc;
-  {
-    GemmParams p0{};
-    p0.A = o.zs; p0.B = d->z_all; p0.C = o.Kall;        // A pre-scaled by the norm pass: no per-k scaling in the main loop
-    p0.M = Mt; p0.N = Mt; p0.K = D; p0.lda = D; p0.ldb = D; p0.ldc = Mt;
-    p0.nb1 = C; p0.nb2 = 1;
-    p0.sA[0] = zrows * D; p0.sA[1] = (int64_t)Mt * D; p0.sB[1] = (int64_t)Mt * D;
-    p0.sC[0] = C * MtMt; p0.sC[1] = MtMt;
-    p0.alpha = 1.f;
-    p0.kscale = nullptr; p0.ks_ld = o.Dp; p0.g2 = o.g2;
-    p0.na = o.na; p0.sNa[0] = zrows; p0.sNa[1] = Mt;
-    p0.nbv = o.na; p0.sNb[0] = zrows; p0.sNb[1] = Mt;
-    p0.same_xy = 1; p0.triC = 2; p0.symout = 1;
-    rc = tn_gram_gemm(p0, SC, d->kernel_nu2, st, "rbf_kuu_gemm", "matern_kuu_gemm");
-    if (rc) return rc;
-  }
+  rc = t.gram(t.kall_gemm(o.Kall), false, tn_epi(t.nu2));
+  if (rc) return rc;
   rc = chol_inv_fwd_impl(o.Kall, d->jitter, o.LL, o.TT, nullptr, d->info, SC, Mt, o.chol, o.chol_bytes, false, st);
   if (rc) return rc;
-  {
-    const int64_t sA[3] = {C * MtMt, MtMt, (int64_t)M * Mt + M}, sB[3] = {0, (int64_t)nblk * M * NRs, (int64_t)M * NRs},
-                  sC[3] = {C * MtN, MtN, (int64_t)M * NRs};
-    GemmParams p = blk_gemm(o.TT, Mt, sA, d->rk_all, NRs, sB, o.QPs, NRs, sC, M, NRs, M, C, nblk);
-    p.triA = 1;
-    rc = launch_gemm(p, 0, 0, SC * nblk, false, st, "tn_small_gemm");
-    if (rc) return rc;
-  }
-  {   // the KL (data-independent): the KL role of the moments kernel alone
-    const int nkx = cdiv(M, kTnKlRows);
-    hipLaunchKernelGGL(tn_pdiag_kl_kernel<64>, dim3(nkx * SC), dim3(256), 0, st, o.P, o.W, o.V2, o.QPs, o.kd, o.LL, d->rk_all, o.mu,
-                       o.var, d->scalars + 1, d->jitter, S, C, M, Mt, nblk, B, NRs, 1, 0, nkx, (uint32_t*)nullptr, 1);
-  }
+  rc = t.run(t.small_gemm());
+  if (rc) return rc;
+  t.pdiag_kl(d->B, false, d->scalars + 1, nullptr, 1);      // the KL (data-independent): the KL role of the moments kernel alone
   return check_launch("elbo_tn_begin");
 }
 
@@ -1295,14 +1352,11 @@ extern "C" int vargp_elbo_tn_tile(const vargp_elbo_tn_desc* d, const float* seed
   VARGP_REQUIRE(moments_only || seeds, "elbo_tn_tile: seeds missing");
   VARGP_REQUIRE(moments_only || !d->forward_only, "elbo_tn_tile: a forward_only program takes y == NULL tiles only");
   VARGP_REQUIRE(moments_only || eps_f_in || d->rng_counter, "elbo_tn_tile: native noise needs rng_counter");
-  hipStream_t st = as_stream(stream);
-  const int S = d->S, C = d->C, M = d->M, D = d->D, F = d->F, nblk = d->nblk, SC = S * C, B = Bt;
-  const TnWs o = carve_tn(d->ws, S, C, M, D, d->B, F, nblk, d->forward_only != 0);
-  const int Mt = o.Mt, NRs = o.NRs;
-  const int64_t MtMt = (int64_t)Mt * Mt, MtB = (int64_t)Mt * B, MtN = (int64_t)Mt * NRs, zrows = (int64_t)C * Mt;
+  const Tn t(d, d->forward_only != 0, stream);
+  const TnWs& o = t.o;
+  hipStream_t st = t.st;
+  const int S = t.S, C = t.C, F = t.F, B = Bt;
   const bool native = eps_f_in == nullptr;
-  const bool fused_softmax = C <= 16;
-  const float* eps_f = native ? o.eps_f : eps_f_in;
   int rc;
   if (!moments_only) {
     const int64_t n0 = o.Kall - o.gmu, n1 = (int64_t)S * d->B;          // gmu | gvar, c_uf
@@ -1312,114 +1366,43 @@ extern "C" int vargp_elbo_tn_tile(const vargp_elbo_tn_desc* d, const float* seed
     hipLaunchKernelGGL(tn_tile_prep_kernel, dim3(nzero + nrng), dim3(256), 0, st, o.gmu, n0, o.c_uf, n1, nzero, native ? 1 : 0,
                        d->rng_seed, d->rng_counter, (int64_t)d->rng_sample_offset * F * C * B, n_f, o.eps_f);
   }
-  rc = rbf_prep_norm_launch(o.theta, nullptr, 0, x, B, o.w, o.g2, o.na, o.nb, S, D, o.Dp, st, o.xs);
+  rc = rbf_prep_norm_launch(o.theta, nullptr, 0, x, B, o.w, o.g2, o.na, o.nb, S, t.D, o.Dp, st, o.xs);
   if (rc) return rc;
-  {
-    GemmParams pf{};
-    pf.A = d->z_all; pf.B = o.xs; pf.C = o.Kuf;
-    pf.M = C * Mt; pf.N = B; pf.K = D; pf.lda = D; pf.ldb = D; pf.ldc = B;
-    pf.nb1 = 1; pf.nb2 = 1;
-    pf.sB[0] = (int64_t)B * D;
-    pf.sC[0] = (int64_t)C * MtB;
-    pf.alpha = 1.f;
-    pf.kscale = nullptr; pf.ks_ld = o.Dp; pf.g2 = o.g2;      // pre-scaled B operand
-    pf.na = o.na; pf.sNa[0] = zrows;
-    pf.nbv = o.nb; pf.sNb[0] = B;
-    rc = tn_gram_gemm(pf, S, d->kernel_nu2, st, "rbf_kuf_gemm", "matern_kuf_gemm");
-    if (rc) return rc;
-  }
-  {
-    GemmParams p = flat_gemm(o.TT, Mt, MtMt, o.Kuf, B, MtB, o.P, B, MtB, Mt, B, Mt);
-    p.triA = 1;
-    rc = launch_gemm(p, 0, 0, SC, false, st, "tn_p_gemm");
-    if (rc) return rc;
-    GemmParams q = flat_gemm(o.TT, Mt, MtMt, o.P, B, MtB, o.V2, B, MtB, Mt, B, Mt);
-    q.triA = 2;
-    rc = launch_gemm(q, 1, 0, SC, false, st, "tn_v2_gemm");
-    if (rc) return rc;
-    const int64_t sA[3] = {C * MtN, MtN, (int64_t)M * NRs}, sB[3] = {C * MtB, MtB, (int64_t)M * B};
-    GemmParams r = blk_gemm(o.QPs + 4, NRs, sA, o.P, B, sB, o.W, B, sB, M, B, M, C, nblk);
-    r.triA = 2;
-    rc = launch_gemm(r, 1, 0, SC * nblk, false, st, "tn_w_gemm");
-    if (rc) return rc;
-  }
-  {
-    const bool narrow = cdiv(B, 64) * SC < 512;
-    const int nbx = cdiv(B, narrow ? 32 : 64), npd = nbx * SC;
-    hipLaunchKernelGGL(narrow ? tn_pdiag_kl_kernel<32> : tn_pdiag_kl_kernel<64>, dim3(npd), dim3(256), 0, st, o.P, o.W, o.V2, o.QPs, o.kd, o.LL, d->rk_all, o.mu, o.var,
-                       (float*)nullptr, d->jitter, S, C, M, Mt, nblk, B, NRs, nbx, npd, 1,
-                       (native && !moments_only) ? d->rng_counter : nullptr, 1);
-  }
+  rc = t.gram(t.kuf_gemm(o.Kuf, B), true, tn_epi(t.nu2));
+  if (rc) return rc;
+  rc = t.run(t.p_gemm(B));
+  if (rc) return rc;
+  rc = t.run(t.v2_gemm(B));
+  if (rc) return rc;
+  rc = t.run(t.w_gemm(B));
+  if (rc) return rc;
+  t.pdiag_kl(B, true, nullptr, (native && !moments_only) ? d->rng_counter : nullptr, 1);
   if (moments_only) return check_launch("elbo_tn_tile");
-  if (fused_softmax) {
-    const int64_t total = (int64_t)S * F * B;
-    hipLaunchKernelGGL(t0_softmax_kernel<16>, dim3(cdiv(total, 256)), dim3(256), 0, st, o.mu, o.var, eps_f, y, d->scalars + 2,
-                       o.gmu, o.gvar, S, F, C, B);
+  if (C <= 16) {
+    t.softmax16(B, native ? o.eps_f : eps_f_in, y);
   } else {
     // the generic kernel overwrites nll: accumulate through a scratch scalar is not worth a kernel -- C <= 16 covers the configs
     VARGP_REQUIRE(false, "elbo_tn_tile: more than 16 classes is not supported by the tiled ELBO");
   }
-  // ---- the tile's share of the backward -------------------------------------------------------------------------------
-  {
-    const int npd = SC * Mt;
-    hipLaunchKernelGGL(tn_bwd_head_kernel, dim3(npd), dim3(256), 0, st, o.P, o.W, o.V2, o.QPs, o.gmu, o.gvar, seeds + 2, seeds, o.gP,
-                       o.gQPs, o.gkd, d->jitter, S, M, Mt, B, NRs, npd, 0, (float*)nullptr, (int64_t)0, 1, 1);
-  }
-  float* gW = o.W;
-  float* gV2 = o.V2;
-  {
-    const int64_t sQ[3] = {C * MtN, MtN, (int64_t)M * NRs}, sP[3] = {C * MtB, MtB, (int64_t)M * B};
-    GemmParams p = blk_gemm(o.P, B, sP, gW, B, sP, o.gQPs + 4, NRs, sQ, M, M, B, C, nblk);
-    p.D = o.gQPs + 4; p.ldd = NRs; p.beta = 1.f;
-    for (int i = 0; i < 3; ++i) p.sD[i] = sQ[i];
-    rc = launch_gemm(p, 0, 1, SC * nblk, false, st, "tn_gh_gemm");
-    if (rc) return rc;
-    GemmParams q = blk_gemm(o.QPs + 4, NRs, sQ, gW, B, sP, o.gP, B, sP, M, B, M, C, nblk);
-    q.triA = 1; q.D = o.gP; q.ldd = B; q.beta = 1.f;
-    rc = launch_gemm(q, 0, 0, SC * nblk, false, st, "tn_gp_gemm");
-    if (rc) return rc;
-  }
-  {
-    GemmParams p = flat_gemm(o.TT, Mt, MtMt, gV2, B, MtB, o.gP, B, MtB, Mt, B, Mt);
-    p.triA = 1; p.D = o.gP; p.beta = 1.f;
-    rc = launch_gemm(p, 0, 0, SC, false, st, "tn_gp_v2_gemm");
-    if (rc) return rc;
-    GemmParams q = flat_gemm(o.gP, B, MtB, o.Kuf, B, MtB, o.gT, Mt, MtMt, Mt, Mt, B);
-    q.triC = 1; q.D = o.gT; q.beta = 1.f;
-    rc = launch_gemm(q, 0, 1, SC, false, st, "tn_gt_gemm");
-    if (rc) return rc;
-    GemmParams r = flat_gemm(o.P, B, MtB, gV2, B, MtB, o.gT, Mt, MtMt, Mt, Mt, B);
-    r.triC = 1; r.D = o.gT; r.beta = 1.f;
-    rc = launch_gemm(r, 0, 1, SC, false, st, "tn_gt_gemm");
-    if (rc) return rc;
-    GemmParams u = flat_gemm(o.TT, Mt, MtMt, o.gP, B, MtB, o.gKuf, B, MtB, Mt, B, Mt);
-    u.triA = 2;
-    rc = launch_gemm(u, 1, 0, SC, false, st, "tn_gkuf_gemm");
-    if (rc) return rc;
-  }
-  {   // W_uf = gK_uf o K_uf in place, row sums (accumulating over the tiles), column sums (this tile's)
-    const int gx = cdiv(B, 256), gy = cdiv(zrows, kWRows), nuf = gx * gy * S;
-    const int nu2 = d->kernel_nu2;
-    float* d2uf = nullptr;      // (Matern) this tile's d2_uf into gP, dead since the gK_uf product; the tile's x o w is still in xs
-    if (nu2 && !tn_d2_invert(nu2)) {
-      d2uf = o.gP;
-      rc = tn_matern_d2(d, o, x, B, true, false, d2uf, nullptr, st);
-      if (rc) return rc;
-    }
-    tn_w_launch(nu2, o, S, C, B, D, gx, gy, nuf, 0, seeds, d2uf, nullptr, st);
-    GemmParams p1{};
-    p1.A = o.gKuf; p1.B = x; p1.C = o.Puf; p1.D = o.Puf;
-    p1.M = C * Mt; p1.N = D; p1.K = B; p1.lda = B; p1.ldb = D; p1.ldc = D; p1.ldd = D;
-    p1.nb1 = 1; p1.nb2 = 1;
-    p1.sA[0] = C * MtB;
-    p1.sC[0] = zrows * D; p1.sD[0] = zrows * D;
-    p1.alpha = 1.f; p1.beta = 1.f;
-    rc = launch_gemm(p1, 0, 0, S, false, st, "rbf_kuf_bwd_gemm");
-    if (rc) return rc;
-    const int nxy = cdiv(B, kFinRows);      // minibatch side only: gtheta += w sum_n c_uf x^2
-    hipLaunchKernelGGL(t0_final_kernel, dim3(cdiv(D, 64), nxy), dim3(256), 0, st, d->z_all, x, o.r_uu, o.r_uf, o.c_uf, o.Puu,
-                       o.Puf, o.w, o.gz_all, o.gtheta, zrows, (int64_t)B, D, o.Dp, S, 0);
-  }
+  // ---- the tile's share of the backward: every product adds to what the earlier tiles left ----------------------------------
+  t.bwd_head(B, seeds + 2, seeds, true, 1);
+  rc = t.run(t.gh_gemm(B, 0, false));
+  if (rc) return rc;
+  rc = t.run(t.gp_gemm(B));
+  if (rc) return rc;
+  rc = t.run(t.gp_v2_gemm(B));
+  if (rc) return rc;
+  rc = t.run(t.gt_kuf_gemm(B, true));
+  if (rc) return rc;
+  rc = t.run(t.gt_v2_gemm(B, true));
+  if (rc) return rc;
+  rc = t.run(t.gkuf_gemm(B));
+  if (rc) return rc;
+  rc = t.w_pass(x, B, true, false, seeds);      // row sums accumulate over the tiles, column sums are this tile's
+  if (rc) return rc;
+  rc = t.run(t.wx_gemm(x, B, true));
+  if (rc) return rc;
+  t.final(x, B, false);                         // minibatch side only
   return check_launch("elbo_tn_tile");
 }
 
@@ -1427,82 +1410,25 @@ extern "C" int vargp_elbo_tn_end(const vargp_elbo_tn_desc* d, const float* seeds
                                  float* g_z, float* g_u_mean, float* g_u_tril_vec, vargp_stream_t stream) {
   VARGP_REQUIRE(d && d->ws && seeds && g_log_mean && g_log_logvar && g_z && g_u_mean && g_u_tril_vec, "elbo_tn_end: null pointer");
   TN_REQUIRE_NU2(d, "elbo_tn_end");
-  hipStream_t st = as_stream(stream);
-  const int S = d->S, C = d->C, M = d->M, D = d->D, F = d->F, nblk = d->nblk, SC = S * C;
-  const TnWs o = carve_tn(d->ws, S, C, M, D, d->B, F, nblk);
-  const int Mt = o.Mt, NRs = o.NRs;
-  const int64_t MtMt = (int64_t)Mt * Mt, MtN = (int64_t)Mt * NRs, zrows = (int64_t)C * Mt;
-  const float* eps_theta = d->eps_theta ? d->eps_theta : o.eps_theta;
+  const Tn t(d, false, stream);
+  const TnWs& o = t.o;
   int rc;
   {
-    const int64_t total = (int64_t)SC * M * NRs;
-    hipLaunchKernelGGL(tn_kl_bwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, o.QPs, o.gQPs, seeds, S, M, Mt, NRs, total);
+    const int64_t total = (int64_t)t.SC * t.M * t.NRs;
+    hipLaunchKernelGGL(tn_kl_bwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, t.st, o.QPs, o.gQPs, seeds, t.S, t.M, t.Mt, t.NRs, total);
   }
-  {
-    const int64_t sQ[3] = {C * MtN, MtN, (int64_t)M * NRs}, sR[3] = {0, (int64_t)nblk * M * NRs, (int64_t)M * NRs},
-                  sT[3] = {C * MtMt, MtMt, (int64_t)M * Mt + M};
-    GemmParams r = blk_gemm(o.gQPs, NRs, sQ, d->rk_all, NRs, sR, o.gT, Mt, sT, M, M, NRs, C, nblk);
-    r.triC = 1; r.D = o.gT; r.ldd = Mt; r.beta = 1.f;
-    rc = launch_gemm(r, 0, 1, SC * nblk, false, st, "tn_gt_diag_gemm");
-    if (rc) return rc;
-    const int64_t off = (int64_t)(Mt - M) * Mt + (Mt - M);
-    GemmParams p = flat_gemm(o.TT + off, Mt, MtMt, o.gQPs + (int64_t)(Mt - M) * NRs, NRs, MtN, o.gRKt, NRs, (int64_t)M * NRs, M,
-                             NRs, M);
-    p.triA = 2;
-    rc = launch_gemm(p, 1, 0, SC, false, st, "tn_grk_gemm");
-    if (rc) return rc;
-  }
-  float* Smat = reinterpret_cast<float*>(o.chol);
-  float* tmp = Smat + SC * MtMt;
-  {
-    GemmParams p = flat_gemm(o.gT, Mt, MtMt, o.TT, Mt, MtMt, Smat, Mt, MtMt, Mt, Mt, Mt);
-    p.alpha = -0.5f; p.triA = 1; p.triB = 2; p.triC = 2; p.symout = 1;
-    p.diag_ptr = seeds + 1; p.diag_scale = 0.5f / (float)S; p.diag_from = Mt - M;     // + g / 2 on the current task's diagonal
-    rc = launch_gemm(p, 0, 1, SC, false, st, "tn_chol_bwd1");
-    if (rc) return rc;
-    // gK = T^T (Smat T) is symmetric: its lower triangle needs tril(Smat T) only, and as T^T [.] the tiles of the lower
-    // triangle are the ones with the SHORT K ranges (k >= row), 40 % of the work of the full product
-    GemmParams q = flat_gemm(Smat, Mt, MtMt, o.TT, Mt, MtMt, tmp, Mt, MtMt, Mt, Mt, Mt);
-    q.triB = 1; q.triC = 1;
-    rc = launch_gemm(q, 0, 0, SC, false, st, "tn_chol_bwd2");
-    if (rc) return rc;
-    GemmParams r = flat_gemm(o.TT, Mt, MtMt, tmp, Mt, MtMt, o.gK, Mt, MtMt, Mt, Mt, Mt);
-    r.triA = 2; r.triB = 1; r.triC = 2; r.symout = 1;
-    rc = launch_gemm(r, 1, 0, SC, false, st, "tn_chol_bwd3");
-    if (rc) return rc;
-  }
-  {   // K_all: W + W^T = 2 gK o K, its row sums; the W.z product; the inducing-point side of the finalisation
-    const int nuu = SC * cdiv(Mt, kUuRows);
-    const int nu2 = d->kernel_nu2;
-    float* d2uu = nullptr;      // (Matern) d2_all into the Cholesky backward's scratch, dead since gK was written
-    if (nu2 && !tn_d2_invert(nu2)) {
-      d2uu = Smat;
-      rc = tn_matern_d2(d, o, nullptr, d->B, false, true, nullptr, d2uu, st);
-      if (rc) return rc;
-    }
-    tn_w_launch(nu2, o, S, C, d->B, D, 1, 1, 0, nuu, seeds, nullptr, d2uu, st);
-    GemmParams p0{};
-    p0.A = o.Wuu; p0.B = d->z_all; p0.C = o.Puu;
-    p0.M = Mt; p0.N = D; p0.K = Mt; p0.lda = Mt; p0.ldb = D; p0.ldc = D;
-    p0.nb1 = C; p0.nb2 = 1;
-    p0.sA[0] = C * MtMt; p0.sA[1] = MtMt;
-    p0.sB[1] = (int64_t)Mt * D;
-    p0.sC[0] = zrows * D; p0.sC[1] = (int64_t)Mt * D;
-    p0.alpha = 1.f;
-    rc = launch_gemm(p0, 0, 0, SC, false, st, "rbf_kuu_bwd_gemm");
-    if (rc) return rc;
-    const int nzy = cdiv(zrows, kFinRows);
-    hipLaunchKernelGGL(t0_final_kernel, dim3(cdiv(D, 64), nzy), dim3(256), 0, st, d->z_all, (const float*)nullptr, o.r_uu, o.r_uf,
-                       o.c_uf, o.Puu, o.Puf, o.w, o.gz_all, o.gtheta, zrows, (int64_t)0, D, o.Dp, S, nzy);
-  }
-  {
-    const int nun = cdiv((int64_t)C * M * (M + 1), 256);
-    hipLaunchKernelGGL(tn_unpack_kernel, dim3(nun + cdiv((int64_t)C * M * D, 256)), dim3(256), 0, st, o.gRKt, d->u_tril_vec,
-                       d->rk_all + (int64_t)(nblk - 1) * M * NRs, seeds, o.gz_all, g_u_mean, g_u_tril_vec, g_z, S, C, M, Mt, D,
-                       NRs, nblk, nun);
-  }
-  hipLaunchKernelGGL(t0_hyper_bwd_kernel, dim3(cdiv(D + 1, 256)), dim3(256), 0, st, d->log_mean, d->log_logvar,
-                     d->prior_log_mean, d->prior_log_logvar, eps_theta, o.gtheta, o.g2, o.gkd, seeds, g_log_mean,
-                     g_log_logvar, S, C, D + 1, d->map_est);
+  rc = t.run(t.gt_diag_gemm());
+  if (rc) return rc;
+  rc = t.run(t.grk_gemm());
+  if (rc) return rc;
+  rc = t.chol_bwd(seeds);
+  if (rc) return rc;
+  rc = t.w_pass(nullptr, d->B, false, true, seeds);      // K_all side: W, the W.z product, the inducing-point side of the finalisation
+  if (rc) return rc;
+  rc = t.run(t.wz_gemm());
+  if (rc) return rc;
+  t.final(nullptr, 0, true);
+  t.unpack(seeds, g_u_mean, g_u_tril_vec, g_z);
+  t.hyper_bwd(d->eps_theta ? d->eps_theta : o.eps_theta, seeds, g_log_mean, g_log_logvar);
   return check_launch("elbo_tn_end");
 }
