@@ -154,6 +154,23 @@ static GemmParams flat_gemm(const float* A, int lda, int64_t sA, const float* B,
   return p;
 }
 
+// one plain product of an ELBO program: operands, transpositions, batch count, profiling tag
+struct ElboGemm {
+  GemmParams p;
+  int tA, tB, nbatch;
+  const char* tag;
+  ElboGemm& onto_c() {      // accumulate: D = C, beta = 1
+    p.D = p.C; p.ldd = p.ldc; p.beta = 1.f;
+    for (int i = 0; i < 3; ++i) p.sD[i] = p.sC[i];
+    return *this;
+  }
+  int run(hipStream_t st) const { return launch_gemm(p, tA, tB, nbatch, false, st, tag); }
+};
+// two of them in one launch
+static int run_gemm_pair(const ElboGemm& a, const ElboGemm& b, const char* tag, hipStream_t st) {
+  return launch_gemm_pair2(a.p, a.tA, a.tB, a.nbatch, b.p, b.tA, b.tB, b.nbatch, st, tag);
+}
+
 
 #ifndef VARGP_W_ROWS
 #define VARGP_W_ROWS 8

@@ -791,12 +791,13 @@ static int ensure_dynamic_lds(const void* fn, size_t bytes, std::atomic<unsigned
   return VARGP_OK;
 }
 
+static bool t0_native(const vargp_elbo_t0_desc* d) { return d->eps_f == nullptr && !d->ext_lik; }      // the program draws its own noise
 static int check_desc(const vargp_elbo_t0_desc* d, const char* who) {
   VARGP_REQUIRE(d, "%s: null descriptor", who);
   VARGP_REQUIRE(d->S > 0 && d->C > 0 && d->M > 0 && d->D > 0 && d->B > 0 && d->F > 0, "%s: bad dims", who);
   VARGP_REQUIRE(d->log_mean && d->z && d->u_mean && d->u_tril_vec && d->x && (d->y || d->ext_lik) && d->scalars && d->info && d->ws,
                 "%s: null pointer", who);
-  const bool native = d->eps_f == nullptr && !d->ext_lik;    // the program draws its own noise
+  const bool native = t0_native(d);
   VARGP_REQUIRE(!native || (d->rng_counter && d->eps_theta == nullptr && d->rng_sample_offset >= 0),
                 "%s: native noise needs rng_counter, eps_theta == eps_f == NULL and a sample offset >= 0", who);
   VARGP_REQUIRE(d->map_est ? d->S == 1
@@ -807,43 +808,32 @@ static int check_desc(const vargp_elbo_t0_desc* d, const char* who) {
   return VARGP_OK;
 }
 
+// Every tuning switch of this program (tuning aids: the defaults are what the measurements quoted in t0_plan chose): name,
+// default and the member the plan consults, read ONCE, when t0_tune() first runs (a function-local static: thread-safe).  What
+// each one does is said at the rule of t0_plan that consults it.
+struct T0Tune {
+  static long long env(const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }
+  int64_t units = env("VARGP_T0_UNITS", kT0TileUnitsMax);
+  int unmerge = env("VARGP_T0_UNMERGE", -1), side = env("VARGP_T0_SIDE", 1);
+  int multi = env("VARGP_T0_MULTI", 0), parts = env("VARGP_T0_PARTS", 0);
+  int fused = env("VARGP_T0_FUSED", 1), fused_bwd = env("VARGP_T0_FUSED_BWD", 1), mat_bwd = env("VARGP_T0_MAT_BWD", 1);
+  int front = env("VARGP_T0_FRONT", 1), gram_in_chain = env("VARGP_T0_GRAM_IN_CHAIN", -1), su = env("VARGP_T0_SU", 1);
+  int tail = env("VARGP_T0_TAIL", 1), tail_lds = env("VARGP_T0_TAIL_LDS", kTailLdsDefault);
+  int kuf_tile = env("VARGP_T0_KUF_TILE", 0), puf_tile = env("VARGP_T0_PUF_TILE", 0), puu_tile = env("VARGP_T0_PUU_TILE", 0);
+  // (VARGP_CHOL_F32: the arithmetic gemm.hip gives the chains of the merged launch)
+  int kuu_split = env("VARGP_KUU_SPLIT", kKuuSplit), chol_f32 = env("VARGP_CHOL_F32", kCholF32Default);
+};
+static const T0Tune& t0_tune() { static const T0Tune tune; return tune; }
+
 // Workgroups per (s, c) of the LDS-resident tile kernels (t0_fwd_fused_kernel, t0_bwd_mid_kernel): one workgroup per CU (their
 // LDS), so with SC * ntile tile units on `cus` CUs the launch takes  rounds x (set-up + tiles per workgroup x tile time).
 // nparts == ntile is the single-tile form (latency-bound shapes: every unit its own CU); fewer, longer workgroups stage T and
 // G once for several tiles and keep the M x M accumulators in registers across them (`setup` = that set-up in tile times).
-// VARGP_T0_MULTI (tuning aid): 1 = the multi-tile kernels also where every tile has a workgroup of its own (nparts == ntile)
-// most (sample, class, 64-column) tile units the LDS-resident middles take (beyond: the round-2 sequences / the block program;
-// vargp_amd/vargp.py: first_task_as_block mirrors it).  VARGP_T0_UNITS: tuning aid
-static int64_t t0_tile_units_max() {
-  static const int64_t env = [] { const char* e = getenv("VARGP_T0_UNITS"); return e ? atoll(e) : (int64_t)kT0TileUnitsMax; }();
-  return env;
-}
-// Role-merged launches (pivot / adjoint chains of the S C + C matrices beside the big product of the same phase) pay while the
-// chains are few: a latency chain on 40 CUs hides under a product on the other 216.  With many hyper-samples the chains are a
-// throughput problem of their own and the product does better as a launch of its own -- two workgroups per CU (the merged
-// kernels hold it to one: the chain role's registers / LDS), 128-row tiles -- with the chains on a side stream (SideFork) so that
-// the two launches share the chip.  Measured (MI355X, Split-MNIST first task, steps/s merged -> apart in line -> apart on two
-// streams): S = 8 (90 chains) 2472 -> 2226 -> 2400, S = 16 (170) 1372 -> 1366 -> 1418, S = 32 (330) 697 -> 745 -> 783,
-// S = 64 (650) 373 -> 413 -> 421; with the Gram matrices built by the chain workgroups (chol_gram.h, same rule) apart also wins at
-// S = 8: 2468 merged, 2495 merged + Gram, 2511 apart + Gram.  Default: apart from a third of the CU count on.
-// VARGP_T0_UNMERGE = chain count from which on (tuning aid).
-static int t0_unmerge_chains() {
-  static const int env = [] { const char* e = getenv("VARGP_T0_UNMERGE"); return e ? atoi(e) : -1; }();
-  return env >= 0 ? env : vargp_cu_count() / 3 + 1;
-}
-// ... and then the chains go to a side stream (SideFork, common.h).  VARGP_T0_SIDE=0: in line (tuning aid)
-static bool t0_side_stream() {
-  static const int env = [] { const char* e = getenv("VARGP_T0_SIDE"); return e ? atoi(e) : 1; }();
-  return env != 0;
-}
-static bool t0_force_multi() {
-  static const int env = [] { const char* e = getenv("VARGP_T0_MULTI"); return e ? atoi(e) : 0; }();
-  return env == 1;
-}
+// forced (VARGP_T0_PARTS, tuning aid): that many, if > 0
+constexpr float kFwdMidSetup = 0.5f;       // set-up of a multi-tile t0_fwd_fused_kernel workgroup in tile times
 constexpr float kBwdMidSetup = 0.35f;      // set-up of a t0_bwd_mid_multi_kernel workgroup (G / T staging + its round of atomics) in tile times
-static int t0_tile_parts(int64_t SC, int ntile, int cus, float setup) {
-  static const int env = [] { const char* e = getenv("VARGP_T0_PARTS"); return e ? atoi(e) : 0; }();   // tuning aid
-  if (env > 0) return env < ntile ? env : ntile;
+static int t0_tile_parts(int64_t SC, int ntile, int cus, float setup, int forced) {
+  if (forced > 0) return forced < ntile ? forced : ntile;
   if (SC * ntile <= cus) return ntile;
   int best = ntile;
   float best_t = 1e30f;
@@ -854,24 +844,104 @@ static int t0_tile_parts(int64_t SC, int ntile, int cus, float setup) {
   return best;
 }
 
-// which backward the shapes get (the forward needs to know: it clears the accumulators of the LDS-resident one)
-struct T0BwdPaths { bool fused_bwd, mat_bwd; };
-static T0BwdPaths t0_bwd_paths(const vargp_elbo_t0_desc* d, const T0Ws& o) {
-  const int S = d->S, C = d->C, M = d->M, D = d->D, B = d->B, LD = o.LD;
+// Which of its forms a step takes: every path decision of forward and backward and the counts they derive from them, each
+// explained at its rule.  t0_plan is the ONLY place that evaluates them -- pure host arithmetic on the dimensions, the descriptor's
+// flags, the alignment of d->z / d->x / eps_f, the CU count and the tuning switches -- so that the two sides cannot disagree.
+struct T0Plan {
+  bool native, generic_lik, unscaled_lik_grad, defer_softmax, fwd_softmax16;                                 // likelihood
+  bool direct_gram, merge_chol, split_kuu, front, gram_in_chain, su_in_chain, fused_mid, fwd_multi, w_vec4;   // forward
+  bool unmerge, side;                                                                                 // both
+  bool fused_bwd, mat_bwd, bwd_multi, fused_tail, tail_lds;                                           // backward
+  int kuf_tile, puf_tile, puu_tile;          // tile form of the products that run as launches of their own (0: launch_gemm's choice)
+  int ksp, ntile, fwd_parts, bwd_parts;      // K-splits of K_uu, 64-column tiles of the minibatch, workgroups per (s, c) of the middles
+};
+static T0Plan t0_plan(const vargp_elbo_t0_desc* d, const T0Ws& o, int cus) {
+  const T0Tune& tune = t0_tune();
+  const int S = d->S, C = d->C, M = d->M, D = d->D, B = d->B, F = d->F, LD = o.LD;
+  const int64_t SC = (int64_t)S * C;
+  const bool zx_aligned = ((reinterpret_cast<uintptr_t>(d->z) | reinterpret_cast<uintptr_t>(d->x)) & 15) == 0;
+  T0Plan p{};
+  p.native = t0_native(d);
+  // C <= 16: the fused softmax kernel, whose UNSCALED gradient in gmu / gvar the backward's kernels scale by seeds[2]; else the
+  // generic op, forward and backward (ext_lik: neither -- gmu / gvar arrive seeded, as from the generic kernel)
+  p.unscaled_lik_grad = C <= 16 && !d->ext_lik;
+  p.generic_lik = C > 16 && !d->ext_lik;
+  p.ntile = cdiv(B, 64);
+  p.kuf_tile = tune.kuf_tile; p.puf_tile = tune.puf_tile; p.puu_tile = tune.puu_tile;
+
+  p.direct_gram = D <= kRbfDirectD;
+  // the merged factorisation + K_uf launch also writes L_S into RK; then the prologue writes RK's other small columns
+  p.merge_chol = D > kRbfDirectD && M > 50 && M <= 100 && (D % 4) == 0 && (LD % 4) == 0 && zx_aligned;
+  p.ksp = tune.kuu_split;
+  // merged factorisation launch + K-split K_uu product: the norms ride along
+  p.split_kuu = p.merge_chol && D >= 256 && (int64_t)p.ksp * M <= LD && p.ksp > 1;
+  // ... and then the prologue shares the launch of the split product (every workgroup evaluates the 1/sigma^2 it needs itself),
+  // and the partial products are summed and exponentiated by the factorising workgroups as they load: two launches fewer
+  // (VARGP_T0_FRONT=0: off)
+  p.front = p.split_kuu && tune.front && p.ksp <= kCholPartMax && D <= kProKuuMaxD;
+
+  // Role-merged launches (pivot / adjoint chains of the S C + C matrices beside the big product of the same phase) pay while the
+  // chains are few: a latency chain on 40 CUs hides under a product on the other 216.  With many hyper-samples the chains are a
+  // throughput problem of their own and the product does better as a launch of its own -- two workgroups per CU (the merged
+  // kernels hold it to one: the chain role's registers / LDS), 128-row tiles -- with the chains on a side stream (SideFork) so that
+  // the two launches share the chip.  Measured (MI355X, Split-MNIST first task, steps/s merged -> apart in line -> apart on two
+  // streams): S = 8 (90 chains) 2472 -> 2226 -> 2400, S = 16 (170) 1372 -> 1366 -> 1418, S = 32 (330) 697 -> 745 -> 783,
+  // S = 64 (650) 373 -> 413 -> 421; with the Gram matrices built by the chain workgroups (chol_gram.h, same rule) apart also wins at
+  // S = 8: 2468 merged, 2495 merged + Gram, 2511 apart + Gram.  Default: apart from a third of the CU count on.
+  // VARGP_T0_UNMERGE = chain count from which on.
+  // (the chain count alone; in effect under merge_chol in the forward, under mat_bwd in the backward and its zero job in the forward)
+  p.unmerge = SC + C >= (tune.unmerge >= 0 ? tune.unmerge : cus / 3 + 1);
+  // ... and then the chains go to a side stream (SideFork, common.h).  VARGP_T0_SIDE=0: in line
+  p.side = p.unmerge && tune.side != 0;
+
+  // ... with several hyper-samples the Gram matrices are a throughput problem (64 x 64 tiles of a 100-row matrix: 1.64x the work,
+  // partial sums written and re-read) while a factorising workgroup has time to spare under the K_uf product of its launch: it
+  // builds its Gram matrix itself (chol_gram.h: 16-row MFMA blocks, lower triangle) and the front launch keeps prologue + norms.
+  // Not at S = 3: there the chain workgroups ARE the critical path of their launch.
+  // Measured (steps/s without -> with): S = 3 5113 -> 4577, S = 8 2476 -> 2500, S = 16 1405 -> 1441, S = 64 420 -> 434; on from the
+  // chain count at which the merged launches are taken apart (unmerge).  VARGP_T0_GRAM_IN_CHAIN = S from which on
+  p.gram_in_chain = p.front && (tune.gram_in_chain >= 0 ? S >= tune.gram_in_chain : p.unmerge) && M > 64 && (M % 4) == 0 &&
+                    D <= kCgMaxD && D >= 32;
+  // S_u = Lu Lu^T by the workgroup that factorises it (CholExtra::su_Lu, chol_small3.h: fp32 chains of 64 < M <= 100 on the matrix
+  // core) instead of 100-long dot products in the prologue's Lu role.
+  // VARGP_T0_SU=0: the Lu role's dot products.  Measured at Cfg2 (steps/s): 5323 with them; 5375 with the S_u chains
+  // building their matrix and the norm role in front of the (now short) prologue roles -- front launch 22.5 -> 19.0 us, the merged
+  // launch 35.2 -> 37.1 (the S_u chains become its longest); a workgroup per class inside the front launch instead: 5019 (its
+  // packed-vector loads are slow, and the heavier kernel costs the front launch a workgroup slot per SIMD)
+  p.su_in_chain = VARGP_CHOL_BLK16 && tune.su && tune.chol_f32 && p.merge_chol && M > 64 && (M % 4) == 0 && M <= 100;
+
+  // LDS-resident middles, at most tune.units (sample, class, 64-column) tile units (beyond: the round-2 sequences / the block
+  // program; vargp_amd/vargp.py: first_task_as_block mirrors it).  Multi-tile forms: t0_tile_parts; VARGP_T0_MULTI=1: the
+  // multi-tile kernels also where every tile has a workgroup of its own (nparts == ntile)
+  const bool units_ok = SC * p.ntile <= tune.units;
+  p.fused_mid = tune.fused && M <= kFusedK && (M % 4) == 0 && (LD % 4) == 0 && units_ok;
+  p.fwd_parts = t0_tile_parts(SC, p.ntile, cus, kFwdMidSetup, tune.parts);
+  p.fwd_multi = p.fwd_parts < p.ntile || tune.multi == 1;
+  p.w_vec4 = B % 4 == 0;      // float4 rows of W in t0_fwd_fused_kernel
   // LDS-resident backward middle (t0_bwd_mid.h): same shapes as the forward's fused middle, plus B % 4 == 0 (float4 rows of W)
-  static const int fused_bwd_env = [] { const char* e = getenv("VARGP_T0_FUSED_BWD"); return e ? atoi(e) : 1; }();   // tuning aid
-  const int ntile = cdiv(B, 64);
-  T0BwdPaths r;
-  r.fused_bwd = fused_bwd_env && M <= kBmKP && M >= 4 && (M % 4) == 0 && (LD % 4) == 0 && (B % 4) == 0 &&
-                (int64_t)S * C * ntile <= t0_tile_units_max();
+  p.fused_bwd = tune.fused_bwd && M <= kBmKP && M >= 4 && (M % 4) == 0 && (LD % 4) == 0 && (B % 4) == 0 && units_ok;
   // ... and everything per matrix after it (small columns of gT / gRK, Cholesky adjoint, W_uu) as one LDS-resident workgroup
   // per matrix inside the launch of the P_uf product (t0_bwd_mat.h)
-  static const int mat_bwd_env = [] { const char* e = getenv("VARGP_T0_MAT_BWD"); return e ? atoi(e) : 1; }();   // tuning aid
   // (the S_u matrices redo T_s^T gG_s for every hyper-sample: worth it for the few samples of the reference's configs and for
   // the 8 / 16 per GPU of BASELINE config 4 on 8 / 4 GPUs -- the product the chains hide under grows with S just as they do)
-  r.mat_bwd = r.fused_bwd && mat_bwd_env && (D % 4) == 0 && S <= kTailSMax &&
-              ((reinterpret_cast<uintptr_t>(d->z) | reinterpret_cast<uintptr_t>(d->x)) & 15) == 0;
-  return r;
+  // (then the forward clears the accumulators this backward adds into: ONE backward per forward, kT0Cleared)
+  p.mat_bwd = p.fused_bwd && tune.mat_bwd && (D % 4) == 0 && S <= kTailSMax && zx_aligned;
+  // throughput-bound shapes (more tile units than CUs): the multi-tile form (t0_bwd_mid_multi.h)
+  p.bwd_parts = t0_tile_parts(SC, p.ntile, cus, kBwdMidSetup, tune.parts);
+  p.bwd_multi = p.fused_bwd && (p.bwd_parts < p.ntile || tune.multi == 1);
+  // the likelihood inside the backward's tile kernel (one launch less): only where that kernel runs and its softmax fits
+  // (float4 reads of the noise there: a caller's eps_f must sit on a 16-byte boundary, the workspace's own does)
+  // (not on throughput-bound shapes -- the multi-tile form of that kernel, t0_bwd_mid_multi.h: the evaluation is C-fold redundant
+  //  there, 11k cycles of vector work per tile that such a launch cannot hide; those shapes keep the softmax launch)
+  p.defer_softmax = d->defer_softmax && p.unscaled_lik_grad && p.fused_bwd && !p.bwd_multi && F <= 4 * kBmSmF && C <= kBmSmC &&
+                    reinterpret_cast<uintptr_t>(p.native ? o.eps_f : d->eps_f) % 16 == 0;
+  p.fwd_softmax16 = p.unscaled_lik_grad && !p.defer_softmax;      // (kT0SoftmaxDeferred tells the backward; else the forward launches it)
+  // P_uu = W_uu z: with few samples inside the launch that consumes it (t0_bwd_tail.h).  VARGP_T0_TAIL=0: a launch of its own
+  p.fused_tail = p.mat_bwd && tune.tail && S <= kTailSMax;
+  // more than four samples: the per-sample operands of its z role staged through LDS (t0_puu_final_lds_kernel).
+  // VARGP_T0_TAIL_LDS = 0: never, 2: also with few samples
+  p.tail_lds = p.fused_tail && ((S > 4 && tune.tail_lds) || tune.tail_lds == 2);
+  return p;
 }
 
 // One backward per forward on the LDS-resident path (the forward clears what the backward adds into).  The C ABI enforces it
@@ -897,6 +967,413 @@ static int t0_state_get(const void* ws) {
   return it == g_t0_state.end() ? -1 : it->second;
 }
 
+// One step of the program: descriptor, carved workspace, plan, stream, derived sizes; the products several launches or both
+// branches of a decision share, described ONCE; and the forward and the backward as sequences of launches under the plan.
+struct T0 {
+  const vargp_elbo_t0_desc* d;
+  T0Ws o;
+  T0Plan plan;
+  vargp_stream_t stream;
+  hipStream_t st;
+  int S, C, M, D, B, F, SC, NR, LD;
+  int64_t MM, MLD, zrows;
+  const float *eps_f, *eps_theta;      // the noise of this step: the caller's, or what the forward drew into the workspace
+
+  T0(const vargp_elbo_t0_desc* d_, vargp_stream_t stream_)
+      : d(d_), o(carve_t0(d_->ws, d_->S, d_->C, d_->M, d_->D, d_->B, d_->F)), plan(t0_plan(d_, o, vargp_cu_count())),
+        stream(stream_), st(as_stream(stream_)), S(d_->S), C(d_->C), M(d_->M), D(d_->D), B(d_->B), F(d_->F), SC(d_->S * d_->C),
+        NR(o.NR), LD(o.LD), MM((int64_t)d_->M * d_->M), MLD((int64_t)d_->M * o.LD), zrows((int64_t)d_->C * d_->M),
+        eps_f(plan.native ? o.eps_f : d_->eps_f), eps_theta(plan.native ? o.eps_theta : d_->eps_theta) {}
+
+  // The two distance products (D > kRbfDirectD): K_uu -> KS[:SC] per (s, c) ...
+  GemmParams kuu_gemm() const {
+    GemmParams p = flat_gemm(d->z, D, 0, d->z, D, 0, o.KS, M, C * MM, M, M, D);
+    p.nb1 = C; p.sA[1] = (int64_t)M * D; p.sB[1] = (int64_t)M * D; p.sC[1] = MM;
+    p.kscale = o.w; p.ks_ld = o.Dp; p.g2 = o.g2;
+    p.na = o.na; p.sNa[0] = zrows; p.sNa[1] = M;
+    p.nbv = o.na; p.sNb[0] = zrows; p.sNb[1] = M;
+    p.same_xy = 1;
+    return p;
+  }
+  // ... and K_uf -> the trailing block of RK per s (the classes' inducing points are more rows of one product); prescaled: against
+  // the x o 1/sigma_s^2 the norm role of the front launch writes
+  GemmParams kuf_gemm(bool prescaled) const {
+    GemmParams p = flat_gemm(d->z, D, 0, d->x, D, 0, o.RK + NR, LD, (int64_t)C * MLD, C * M, B, D);
+    p.kscale = o.w; p.ks_ld = o.Dp; p.g2 = o.g2;
+    p.na = o.na; p.sNa[0] = zrows;
+    p.nbv = o.nb; p.sNb[0] = B;
+    if (prescaled) { p.B = o.xs; p.sB[0] = (int64_t)B * D; p.kscale = nullptr; }
+    return p;
+  }
+  // QP = T RK, its first ncols columns: NR = the small ones (a = T m, G = T L_S, G2 = T Lu), NR + B = all
+  ElboGemm qp_gemm(int ncols) const {
+    ElboGemm g{flat_gemm(o.TT, M, MM, o.RK, LD, MLD, o.QP, LD, MLD, M, ncols, M), 0, 0, SC, ncols == NR ? "t0_qps_gemm" : "t0_qp_gemm"};
+    g.p.triA = 1;
+    return g;
+  }
+  // ... its backward:  gT = tril(gQP RK^T) over all columns (K-split), or small: += over the small columns [a | . | G | G2 | .] alone,
+  // on top of the tile kernel's atomics
+  ElboGemm gt_gemm(bool small) const {
+    ElboGemm g{flat_gemm(o.gQP, LD, MLD, o.RK, LD, MLD, o.gTT, M, MM, M, M, small ? NR : NR + B), 0, 1, SC, "t0_gt_gemm"};
+    g.p.triC = 1;
+    if (small) return g.onto_c();
+    g.p.splitk = ksplit(NR + B);
+    return g;
+  }
+  // ... and gRK = T^T gQP, its first ncols columns
+  ElboGemm grk_gemm(int ncols) const {
+    ElboGemm g{flat_gemm(o.TT, M, MM, o.gQP, LD, MLD, o.gRK, LD, MLD, M, ncols, M), 1, 0, SC, "t0_grk_gemm"};
+    g.p.triA = 2;
+    return g;
+  }
+  // the W.Y products of the kernel-matrix backward: P_uu = W_uu z per (s, c) ...
+  GemmParams puu_gemm() const {
+    GemmParams p = flat_gemm(o.Wuu, M, C * MM, d->z, D, 0, o.Puu, D, zrows * D, M, D, M);
+    p.nb1 = C; p.sA[1] = MM; p.sB[1] = (int64_t)M * D; p.sC[1] = (int64_t)M * D;
+    return p;
+  }
+  // ... and P_uf = W_uf x per s
+  GemmParams puf_gemm() const { return flat_gemm(o.gRK + NR, LD, C * MLD, d->x, D, 0, o.Puf, D, zrows * D, C * M, D, B); }
+  int fwd() const;
+  int bwd(const float* seeds, float* g_log_mean, float* g_log_logvar, float* g_z, float* g_u_mean, float* g_u_tril_vec) const;
+};
+
+int T0::fwd() const {
+  int rc;
+  t0_state_set(d->ws, (plan.mat_bwd ? kT0Cleared : kT0NoClear) | (plan.defer_softmax ? kT0SoftmaxDeferred : 0));
+  ZeroJobs bwd_zero{};
+  if (plan.mat_bwd) {
+    // accumulators of the LDS-resident backward (atomics of t0_bwd_mid.h / t0_bwd_mat.h / t0_bwd_tail.h), cleared in the forward,
+    // where it costs nothing (spare workgroups under the pivot chains; shapes without that launch: the prologue's zero role):
+    // column 0 (ga) and the G block of gQP, gT, gkd, r_uf / c_uf / gtheta
+    bwd_zero.j[0] = ZeroJob{o.gQP, (int64_t)SC * M, 4 + M, LD};
+    bwd_zero.j[1] = ZeroJob{o.gTT, 1, (SC + C) * MM, 0};
+    bwd_zero.j[2] = ZeroJob{o.queue, 1, 8, 0};          // work queue of the P_uf tiles (launch_bwdmat_gemm)
+    bwd_zero.j[3] = ZeroJob{o.gkd, 1, SC, 0};
+    bwd_zero.j[4] = ZeroJob{o.r_uf, 1, o.r_uu - o.r_uf, 0};
+    if (plan.unmerge)                                   // per-class sums of the L_S gradient shares (BwdMatArgs::gL_acc; gLL's tail is free on this path)
+      bwd_zero.j[5] = ZeroJob{o.gLL + SC * MM, 1, C * MM, 0};
+  }
+  ProArgs a{};
+  if (plan.merge_chol) { a.RK = o.RK; a.u_mean = d->u_mean; a.NR = NR; a.LD = LD; }
+  a.mean = d->log_mean; a.logvar = d->log_logvar; a.pmean = d->prior_log_mean; a.plogvar = d->prior_log_logvar;
+  a.eps_theta = d->eps_theta; a.vec = d->u_tril_vec;
+  a.theta = o.theta; a.w = o.w; a.g2 = o.g2; a.kd = o.kd; a.Lu = o.Lu; a.Su = o.KS + SC * MM; a.scalars = d->scalars;
+  a.bump = d->bump;
+  a.su_in_chain = plan.su_in_chain ? 1 : 0;
+  a.zero_begin = o.gmu; a.zero_count = o.r_uf - o.gmu; a.info = d->info; a.Dp = o.Dp;
+  a.S = S; a.C = C; a.M = M; a.D = D; a.ninfo = SC + C; a.map_est = d->map_est;
+  a.nzero_blocks = (int)std::min<int64_t>(64, cdiv(a.zero_count, 1024));
+  if (plan.native) {
+    const int64_t per_sample_f = (int64_t)F * C * B;
+    a.native = 1; a.seed = d->rng_seed; a.rng_counter = d->rng_counter;
+    a.g0_theta = (int64_t)d->rng_sample_offset * (D + 1); a.g0_f = (int64_t)d->rng_sample_offset * per_sample_f;
+    a.n_f = S * per_sample_f;
+    a.eps_theta_out = o.eps_theta; a.eps_f_out = o.eps_f;
+    a.nrng_blocks = (int)std::min<int64_t>(512, cdiv(a.n_f + 7, 1024));
+  }
+  if (plan.mat_bwd && !plan.merge_chol) {      // no merged factorisation launch to take the zero jobs along
+    a.zero = bwd_zero;
+    const int64_t zt = (int64_t)SC * M * (4 + M) + (SC + 2 * C) * MM + (o.r_uu - o.r_uf);
+    a.nzero_blocks = (int)std::min<int64_t>(128, cdiv(a.zero_count + zt, 2048));
+  }
+  const int npro = 1 + S + a.nzero_blocks + a.nrng_blocks + cdiv((int64_t)C * MM, 256);
+  if (!plan.front) {
+    ProfScope prof("t0_prologue", st);
+    hipLaunchKernelGGL(t0_prologue_kernel, dim3(npro), dim3(256), 0, st, a);
+  }
+  // kernel matrices: K_uu -> KS[:SC], K_uf -> the trailing block of RK
+  if (plan.direct_gram) {
+    rc = rbf_direct_launch(d->z, nullptr, o.w, o.g2, o.KS, M, S, C, M, M, D, o.Dp, 0, st);
+    if (rc) return rc;
+    rc = rbf_direct_launch(d->z, d->x, o.w, o.g2, o.RK + NR, LD, S, C, M, B, D, o.Dp, 1, st);
+    if (rc) return rc;
+  } else {
+    if (!plan.split_kuu)
+      hipLaunchKernelGGL(t0_norm_kernel, dim3(cdiv(zrows + B, 4), S), dim3(256), 0, st, d->z, d->x, o.w, o.na, o.nb, zrows,
+                         (int64_t)B, D, o.Dp);
+    if (plan.merge_chol) {
+      // K_uu first, then ONE launch in which SC + C workgroups factorise (K_uu + eps I, S_u + eps I) while the rest of
+      // the chip builds K_uf, which nothing needs before the factors are done
+      VARGP_REQUIRE(chol_rbf_gemm_applicable(M, kuf_gemm(false)), "elbo_t0_fwd: merged launch expected but not applicable");
+      if (plan.split_kuu) {
+        // 4 SC workgroups with D/64 slabs each would leave half the chip idle for the length of that K loop: split K,
+        // partial inner products to scratch, distance/exp epilogue afterwards
+        GemmParams ps = kuu_gemm();
+        ps.splitk = plan.ksp; ps.sSplit = SC * MM; ps.C = o.kpart;
+        if (plan.front) {
+          // (the norm role also writes x o 1/sigma_s^2: the K_uf product then runs without scale loads / multiplies in its
+          // main loop -- step 209.5 -> 207.7 us at S = 3, 510 -> 494 us at S = 8)
+          NormArgs nr{d->z, d->x, o.na, o.nb, zrows, (int64_t)B, 16, (int)cdiv(zrows + B, 16), o.xs};
+          rc = launch_pro_kuu(a, npro, nr, ps, plan.gram_in_chain ? 0 : SC, st);
+          if (rc) return rc;
+        } else {
+          rc = launch_gemm(ps, 0, 1, SC, true, st, "rbf_kuu_gemm");
+          if (rc) return rc;
+          const int64_t total = SC * MM;
+          const int ncomb = cdiv(total, 256), nrow4 = cdiv(zrows + B, 4);
+          hipLaunchKernelGGL(t0_combine_norm_kernel, dim3(ncomb + nrow4 * S), dim3(256), 0, st, o.kpart, plan.ksp, SC * MM, o.g2,
+                             o.KS, C, M, total, ncomb, d->z, d->x, o.w, o.na, o.nb, zrows, (int64_t)B, D, o.Dp, nrow4);
+        }
+      } else {
+        rc = launch_gemm(kuu_gemm(), 0, 1, SC, true, st, "rbf_kuu_gemm");
+        if (rc) return rc;
+      }
+      // L_S[c] -> RK[s, c, :, 4:4+M] for every s; K_uu and S_u arrive with both triangles; of the K_uu factors only
+      // the diagonal of L is ever used (log-determinant, and L^T diag(.) in the backward), everything else goes through T
+      CholExtra lx{o.RK + 4, SC, LD, MLD, (int64_t)C * MLD, S, 1, 1};
+      if (plan.front) {   // the matrices b < SC arrive as K-split partial Gram matrices (and leave as K_uu in KS for the backward)
+        lx.part = o.kpart; lx.nsplit = plan.ksp; lx.sSplit = SC * MM; lx.g2 = o.g2; lx.part_C = C; lx.Kout = o.KS;
+        if (plan.gram_in_chain) { lx.part = nullptr; lx.gram_z = d->z; lx.gram_w = o.w; lx.gram_D = D; lx.gram_Dp = o.Dp; }
+      }
+      if (plan.su_in_chain) lx.su_Lu = o.Lu;
+      GemmParams kuf = kuf_gemm(plan.front);
+      // unmerge: the chains on a side stream, the product as a launch of its own on this one (T0Plan::unmerge)
+      SideFork fork(st, plan.side);
+      rc = launch_chol_rbf_gemm(o.KS, d->jitter, o.LL, o.TT, d->info, SC + C, M, kuf, plan.unmerge ? 0 : S, fork.side(), &lx,
+                                plan.mat_bwd ? &bwd_zero : nullptr);
+      if (rc) return rc;
+      if (plan.unmerge) {
+        kuf.tile = plan.kuf_tile;
+        rc = launch_gemm(kuf, 0, 1, S, true, st, "rbf_kuf_gemm");
+        if (rc) return rc;
+      }
+      rc = fork.join();
+      if (rc) return rc;
+    } else {
+      rc = launch_gemm_pair(kuu_gemm(), SC, kuf_gemm(false), S, 0, 1, true, st, "rbf_kuu_gemm", "rbf_kuf_gemm");
+      if (rc) return rc;
+    }
+  }
+  if (!plan.merge_chol) {
+    // both factorisations (K_uu + eps I for every (s, c); S_u + eps I for every c) in one batch, then RK's small columns
+    rc = chol_inv_fwd_impl(o.KS, d->jitter, o.LL, o.TT, nullptr, d->info, SC + C, M, o.chol, o.chol_bytes, false, st);
+    if (rc) return rc;
+    const int64_t total = (int64_t)SC * M * NR;
+    hipLaunchKernelGGL(t0_pack_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, d->u_mean, o.LL + SC * MM, o.Lu, o.RK, C,
+                       M, NR, LD, total);
+  }
+  // early hand-over of the Cholesky status (include/vargp_hip.h: info_host / info_event): every factorisation of the forward is
+  // behind us on the stream
+  if (d->info_host && d->info_event) {
+    VARGP_REQUIRE(hipMemcpyAsync(d->info_host, d->info, sizeof(int32_t) * (size_t)(SC + C), hipMemcpyDeviceToHost, st) == hipSuccess &&
+                      hipEventRecord(reinterpret_cast<hipEvent_t>(d->info_event), st) == hipSuccess,
+                  "elbo_t0_fwd: copy / event record of the early Cholesky status failed");
+  }
+  uint32_t* rngc = plan.native ? d->rng_counter : nullptr;
+  if (plan.fused_mid) {
+    // small columns first (one M x NR x M product per (s, c)), then the LDS-resident kernel
+    rc = qp_gemm(NR).run(st);
+    if (rc) return rc;
+    static std::atomic<unsigned> attr_set_mask[4][2] = {};      // 64 device ordinals per instantiation
+    const dim3 grid(8 * cdiv(SC, 8) * plan.fwd_parts);
+#define VARGP_FF(V4, MT, SLOT)                                                                                                  \
+  do {                                                                                                                          \
+    rc = ensure_dynamic_lds(reinterpret_cast<const void*>(t0_fwd_fused_kernel<V4, MT>), kFusedLdsBytes, attr_set_mask[SLOT],    \
+                            "elbo_t0_fwd");                                                                                     \
+    if (rc) return rc;                                                                                                          \
+    hipLaunchKernelGGL((t0_fwd_fused_kernel<V4, MT>), grid, dim3(256), kFusedLdsBytes, st, o.TT, o.QP, o.RK, o.W, o.kd, o.LL,   \
+                       o.Lu, o.mu, o.var, d->scalars + 1, S, C, M, B, NR, LD, plan.ntile, rngc, plan.fwd_parts);                  \
+  } while (0)
+    if (plan.w_vec4) { if (plan.fwd_multi) VARGP_FF(true, true, 0); else VARGP_FF(true, false, 1); }
+    else { if (plan.fwd_multi) VARGP_FF(false, true, 2); else VARGP_FF(false, false, 3); }
+#undef VARGP_FF
+  } else {
+    rc = qp_gemm(NR + B).run(st);
+    if (rc) return rc;
+    ElboGemm w{flat_gemm(o.QP + 4, LD, MLD, o.QP + NR, LD, MLD, o.W, B, (int64_t)M * B, M, B, M), 1, 0, SC, "t0_w_gemm"};      // W = G^T P
+    w.p.triA = 2;
+    rc = w.run(st);
+    if (rc) return rc;
+    const int ntile = plan.ntile, npd = ntile * SC, nkx = cdiv(M, kKlRows);      // moments of the minibatch + KL of q(u)
+    hipLaunchKernelGGL(t0_pdiag_kl_fwd_kernel, dim3(npd + nkx * SC), dim3(256), 0, st, o.QP, o.W, o.kd, o.LL, o.Lu, o.mu,
+                       o.var, d->scalars + 1, S, C, M, B, NR, LD, ntile, npd, nkx, rngc);
+  }
+  // (neither: t0_bwd_mid_kernel evaluates the likelihood of its tile -- value into scalars[2], gradient straight into its LDS;
+  // or ext_lik: the caller evaluates it on the moments of ALL classes and stores the seeded gradients into gmu / gvar)
+  if (plan.fwd_softmax16) {
+    const int64_t total = (int64_t)S * F * B;
+    hipLaunchKernelGGL(t0_softmax_kernel<16>, dim3(cdiv(total, 256)), dim3(256), 0, st, o.mu, o.var, eps_f, d->y,
+                       d->scalars + 2, o.gmu, o.gvar, S, F, C, B);
+  } else if (plan.generic_lik) {
+    rc = vargp_softmax_nll_fwd(o.mu, o.var, eps_f, d->y, d->scalars + 2, S, F, C, B, stream);
+    if (rc) return rc;
+  }
+  return check_launch("elbo_t0_fwd");
+}
+
+int T0::bwd(const float* seeds, float* g_log_mean, float* g_log_logvar, float* g_z, float* g_u_mean, float* g_u_tril_vec) const {
+  int rc;
+  const int64_t MB = (int64_t)M * B;
+  const float* lik_seed = plan.unscaled_lik_grad ? seeds + 2 : nullptr;      // (else gmu / gvar arrive scaled)
+  if (plan.generic_lik) {   // C > 16: gradient of the likelihood from the generic kernel (already scaled by its seed)
+    rc = vargp_softmax_nll_bwd(o.mu, o.var, eps_f, d->y, seeds + 2, o.gmu, o.gvar, S, F, C, B, stream);
+    if (rc) return rc;
+  }
+  const int state_all = t0_state_get(d->ws);
+  const bool softmax_deferred = state_all >= 0 && (state_all & kT0SoftmaxDeferred) != 0;
+  VARGP_REQUIRE(!softmax_deferred || plan.fused_bwd, "elbo_t0_bwd: the forward deferred the likelihood to a backward path this call does not take");
+  if (plan.mat_bwd) {
+    // the accumulators must have been cleared by a forward on THIS workspace that took the same decision (the decision
+    // depends on the alignment of d->z / d->x and on tuning variables) and must not have been consumed by a backward yet
+    const int state = state_all < 0 ? state_all : (state_all & ~kT0SoftmaxDeferred);
+    VARGP_REQUIRE(state == kT0Cleared,
+                  "elbo_t0_bwd: %s -- this path allows ONE vargp_elbo_t0_bwd per vargp_elbo_t0_fwd (the forward clears the "
+                  "accumulators the backward adds into); run the forward again",
+                  state == kT0Consumed ? "second backward on one forward"
+                                       : "no forward on this workspace with the same z / x alignment");
+    t0_state_set(d->ws, kT0Consumed);
+  } else if (softmax_deferred) {
+    t0_state_set(d->ws, kT0NoClear);           // (the likelihood is added into scalars[2] once)
+  }
+  // mat_bwd: no head launch -- the forward's zero role has cleared the accumulators, the seed-dependent KL columns (g a, g G2) are
+  // formed by the chain kernel from QP, g_u_mean is cleared by the tile kernel.  ONE backward per forward on this path.
+  if (!plan.mat_bwd) {
+    const int npd = plan.fused_bwd ? 0 : M * SC, nkx = cdiv(M, kKlRows), nkl = nkx * SC;
+    const int64_t zc = o.r_uu - o.r_uf;
+    const int nz = (int)std::min<int64_t>(64, cdiv(zc, 1024));
+    hipLaunchKernelGGL(t0_bwd_head_kernel, dim3(npd + nkl + nz), dim3(256), 0, st, o.QP, o.W, o.gmu, o.gvar, lik_seed, o.LL,
+                       seeds, o.gQP, o.gW, o.gkd, o.gLL, o.gTT, o.gTT + SC * MM, o.r_uf, zc, S, C, M, B, NR, LD, npd, nkx, nkl,
+                       plan.fused_bwd ? 1 : 0, (float*)nullptr, (float*)nullptr);
+  }
+  if (plan.fused_bwd) {
+    static std::atomic<unsigned> attr_set_mask[2] = {}, attr_set_mask_m[2] = {};
+    float* gum = plan.mat_bwd ? g_u_mean : nullptr;      // (cleared here on that path)
+    if (plan.bwd_multi) {
+      VARGP_REQUIRE(!softmax_deferred, "elbo_t0_bwd: the multi-tile backward does not evaluate a deferred likelihood");
+      rc = ensure_dynamic_lds(reinterpret_cast<const void*>(t0_bwd_mid_multi_kernel), kBwdMidMultiLdsBytes, attr_set_mask_m, "elbo_t0_bwd");
+      if (rc) return rc;
+      ProfScope prof("t0_bwd_mid", st);
+      hipLaunchKernelGGL(t0_bwd_mid_multi_kernel, dim3(8 * cdiv(SC, 8) * plan.bwd_parts), dim3(256), kBwdMidMultiLdsBytes, st, o.TT, o.QP,
+                         o.W, o.RK, o.gmu, o.gvar, lik_seed, o.gQP, o.gTT, o.gRK, o.gkd, o.r_uf, o.c_uf, o.gtheta, S, C, M,
+                         B, D, NR, LD, plan.ntile, plan.bwd_parts, gum, C * M);
+    } else {
+      const BmSoftmax smx = softmax_deferred ? BmSoftmax{o.mu, o.var, eps_f, d->y, d->scalars + 2, F} : BmSoftmax{};
+      rc = ensure_dynamic_lds(reinterpret_cast<const void*>(t0_bwd_mid_kernel), kBwdMidLdsBytes, attr_set_mask, "elbo_t0_bwd");
+      if (rc) return rc;
+      ProfScope prof("t0_bwd_mid", st);
+      hipLaunchKernelGGL(t0_bwd_mid_kernel, dim3(8 * cdiv(SC, 8) * plan.ntile), dim3(256), kBwdMidLdsBytes, st, o.TT, o.QP, o.W, o.RK, o.gmu, o.gvar,
+                         lik_seed, o.gQP, o.gTT, o.gRK, o.gkd, o.r_uf, o.c_uf, o.gtheta, S, C, M, B, D,
+                         NR, LD, plan.ntile, gum, C * M, smx);
+    }
+    if (!plan.mat_bwd) {
+      // what the tiles cannot see: the small columns [a | . | G | G2 | .] of QP = T RK (K = NR):
+      //   gT += tril(gQP[:, :NR] RK[:, :NR]^T)   on top of the tiles' atomics;   gRK[:, :NR] = T^T gQP[:, :NR]
+      rc = run_gemm_pair(gt_gemm(true), grk_gemm(NR), "t0_gt_grk_small", st);
+      if (rc) return rc;
+      rc = chol_inv_bwd_first(o.TT, o.gTT, SC + C, M, o.chol, o.chol_bytes, nullptr, 0, 0, 0, st);
+      if (rc) return rc;
+    }
+  } else {
+    // W = G^T P:  gG = P gW^T (G block of gQP),  gP += G gW   -- independent of each other: one launch
+    ElboGemm gg{flat_gemm(o.QP + NR, LD, MLD, o.gW, B, MB, o.gQP + 4, LD, MLD, M, M, B), 0, 1, SC, "t0_gg_gemm"};
+    gg.p.splitk = ksplit(B);     // 4 SC tiles with a B-long K loop: split K so that the chip is busy (atomic accumulation)
+    ElboGemm gp{flat_gemm(o.QP + 4, LD, MLD, o.gW, B, MB, o.gQP + NR, LD, MLD, M, B, M), 0, 0, SC, "t0_gp_gemm"};
+    gp.p.triA = 1;
+    rc = run_gemm_pair(gg, gp.onto_c(), "t0_gg_gp_gemm", st);
+    if (rc) return rc;
+    rc = gt_gemm(false).run(st);
+    if (rc) return rc;
+    // gRK = T^T gQP shares a launch with the first product of the Cholesky backward (w1 = gT T^T), which only needs gT
+    const ElboGemm grk = grk_gemm(NR + B);
+    rc = chol_inv_bwd_first(o.TT, o.gTT, SC + C, M, o.chol, o.chol_bytes, &grk.p, grk.tA, grk.tB, grk.nbatch, st);
+    if (rc) return rc;
+  }
+  if (plan.mat_bwd) {
+    BwdMatArgs ma{};
+    ma.QP = o.QP; ma.TT = o.TT; ma.LL = o.LL; ma.gQP = o.gQP; ma.RK = o.RK; ma.KS = o.KS; ma.seeds = seeds; ma.gTT = o.gTT;
+    ma.gKS = o.gKS; ma.Wuu = o.Wuu; ma.r_uu = o.r_uu; ma.gtheta = o.gtheta;
+    ma.g_u_mean = g_u_mean; ma.gLu_part = o.gLL;                 // (gLL is free on this path: no head launch, no Cholesky-adjoint op)
+    ma.S = S; ma.C = C; ma.M = M; ma.D = D; ma.NR = NR; ma.LD = LD;
+    // all S C + C matrices next to P_uf = W_uf x (which only needs the tile kernel's W_uf) ...
+    GemmParams puf = puf_gemm();
+    if (plan.unmerge) {
+      // ... or, as in the forward, the chains on a side stream and the product as a launch of its own; then the S_u roles -- which
+      // would walk all S samples, one workgroup per class, with nothing left to hide under -- read per-class sums the K_uu roles
+      // accumulate (cleared by the forward's zero role)
+      SideFork fork(st, plan.side);
+      ma.gL_acc = o.gLL + SC * MM;
+      rc = launch_bwdmat_gemm(ma, 0, SC, puf, 0, fork.side(), "t0_bwdmat_kuu", nullptr);
+      if (rc) return rc;
+      rc = launch_bwdmat_gemm(ma, SC, C, puf, 0, fork.side(), "t0_bwdmat_su", nullptr);
+      if (rc) return rc;
+      puf.tile = plan.puf_tile;
+      rc = launch_gemm(puf, 0, 0, S, false, st, "rbf_kuf_bwd_product");
+      if (rc) return rc;
+      rc = fork.join();
+    } else {
+      rc = launch_bwdmat_gemm(ma, 0, SC + C, puf, S, st, "rbf_kuf_bwd_gemm", reinterpret_cast<int*>(o.queue));
+    }
+    if (rc) return rc;
+    // ... then P_uu = W_uu z, unless the tail forms it itself
+    if (!plan.fused_tail) {
+      GemmParams puu = puu_gemm();
+      puu.tile = plan.puu_tile;
+      rc = launch_gemm(puu, 0, 0, SC, false, st, "rbf_kuu_bwd_gemm");
+      if (rc) return rc;
+    }
+  } else {
+    const int64_t total = (int64_t)C * M * (M + 1);
+    hipLaunchKernelGGL(t0_unpack_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, o.gRK, g_u_mean, o.gLL + SC * MM, S, C,
+                       M, LD, total);
+    // gLL is lower-triangular by construction (diagonal for the K_uu factors, the L_S block of gRK for the S_u ones)
+    rc = chol_inv_bwd_impl(o.LL, o.TT, o.gLL, o.gTT, o.gKS, SC + C, M, o.chol, o.chol_bytes, true, st, true);
+    if (rc) return rc;
+    // kernel matrices -> z, theta
+    const int gx = cdiv(B, 256), gy = cdiv(zrows, kWRows), nuf = plan.fused_bwd ? 0 : gx * gy * S;   // fused: W_uf is done
+    const int nuu = SC * cdiv(M, kUuRows);
+    const int ngv = cdiv((int64_t)C * MM, 256);      // + the gradient of the packed Cholesky vector of q(u)
+    hipLaunchKernelGGL(t0_w_kernel, dim3(nuf + nuu + ngv), dim3(256), 0, st, o.RK, o.gRK, o.KS, o.gKS, o.Wuu, o.r_uu, o.r_uf,
+                       o.c_uf, o.gtheta, S, C, M, B, D, NR, LD, gx, gy, nuf, nuu, d->u_tril_vec, o.Lu, seeds, g_u_tril_vec, 1);
+    rc = launch_gemm_pair(puu_gemm(), SC, puf_gemm(), S, 0, 0, false, st, "rbf_kuu_bwd_gemm", "rbf_kuf_bwd_gemm");
+    if (rc) return rc;
+  }
+  const int nzy = cdiv(zrows, kFinRows), nxy = cdiv(B, kFinRows), gx = cdiv(D, 64);
+  GvecArgs gv{};
+  int ngy = 0;
+  if (plan.mat_bwd) {               // the gradient of the packed Cholesky vector of q(u) from the per-class sums: extra grid rows
+    gv.vec = d->u_tril_vec; gv.Lu = o.Lu; gv.gSu = o.gKS + SC * MM; gv.gLu_part = o.gLL; gv.seeds = seeds;
+    gv.gvec = g_u_tril_vec; gv.S = S; gv.C = C; gv.M = M; gv.y0 = nzy + nxy;
+    ngy = cdiv(cdiv((int64_t)C * MM, 256), gx);
+  }
+  if (plan.fused_tail) {
+    ProfScope prof("t0_puu_final", st);
+    TailArgs ta{};
+    ta.z = d->z; ta.x = d->x; ta.Wuu = o.Wuu; ta.Puf = o.Puf; ta.r_uu = o.r_uu; ta.r_uf = o.r_uf; ta.c_uf = o.c_uf; ta.w = o.w;
+    ta.gz = g_z; ta.gtheta = o.gtheta; ta.S = S; ta.C = C; ta.M = M; ta.D = D; ta.B = B; ta.Dp = o.Dp;
+    const int rem = M % 32;
+    ta.nrb = (rem > 0 && rem <= 8) ? M / 32 : cdiv(M, 32);       // a short remainder goes to the vector units
+    const int ngr = cdiv(M, 32);
+    ta.ncb = cdiv(D, 32); ta.nz = cdiv(C * ta.nrb * ta.ncb + C * (ngr * (ngr + 1) / 2), 4);      // z + packed-vector wave-blocks
+    ta.nx = gx * cdiv(B, kTailXRows); ta.gx = gx;
+    ta.nrem = (rem > 0 && rem <= 8) ? C * gx * cdiv(rem, 4) : 0;
+    const dim3 grid(ta.nz + ta.nrem + ta.nx);
+    if (plan.tail_lds) {
+      static std::atomic<unsigned> attr_set_mask_t[2] = {};
+      rc = ensure_dynamic_lds(reinterpret_cast<const void*>(t0_puu_final_lds_kernel), kTailLdsBytes, attr_set_mask_t, "elbo_t0_bwd");
+      if (rc) return rc;
+      const int nzg = C * ta.nrb * cdiv(ta.ncb, 4), ngvw = cdiv(C * (ngr * (ngr + 1) / 2), 4);
+      hipLaunchKernelGGL(t0_puu_final_lds_kernel, dim3(nzg + ngvw + ta.nrem + ta.nx), dim3(512), kTailLdsBytes, st, ta, gv, nzg, ngvw);
+    } else
+    switch (S) {
+      case 1: hipLaunchKernelGGL(t0_puu_final_kernel<1>, grid, dim3(256), 0, st, ta, gv); break;
+      case 2: hipLaunchKernelGGL(t0_puu_final_kernel<2>, grid, dim3(256), 0, st, ta, gv); break;
+      case 3: hipLaunchKernelGGL(t0_puu_final_kernel<3>, grid, dim3(256), 0, st, ta, gv); break;
+      case 4: hipLaunchKernelGGL(t0_puu_final_kernel<4>, grid, dim3(256), 0, st, ta, gv); break;
+      default: hipLaunchKernelGGL(t0_puu_final_kernel<0>, grid, dim3(256), 0, st, ta, gv); break;      // 5 .. kTailSMax: a loop
+    }
+  } else {
+    hipLaunchKernelGGL(t0_final_kernel, dim3(gx, nzy + nxy + ngy), dim3(256), 0, st, d->z, d->x, o.r_uu, o.r_uf, o.c_uf,
+                       o.Puu, o.Puf, o.w, g_z, o.gtheta, zrows, (int64_t)B, D, o.Dp, S, nzy, gv);
+  }
+  if (!d->defer_hyper) {
+    vargp_hyper_grad_desc h;
+    hyper_grad_desc_fill(d, o, eps_theta, seeds, &h);
+    hyper_bwd_launch(h, g_log_mean, g_log_logvar, st);
+  }
+  return check_launch("elbo_t0_bwd");
+}
+
 }  // namespace vargp
 
 using namespace vargp;
@@ -916,494 +1393,17 @@ extern "C" int vargp_elbo_t0_lik_buffers(const vargp_elbo_t0_desc* d, float** mu
 }
 
 extern "C" int vargp_elbo_t0_fwd(const vargp_elbo_t0_desc* d, vargp_stream_t stream) {
-  int rc = check_desc(d, "elbo_t0_fwd");
-  if (rc) return rc;
-  hipStream_t st = as_stream(stream);
-  const int S = d->S, C = d->C, M = d->M, D = d->D, B = d->B, F = d->F, SC = S * C;
-  const T0Ws o = carve_t0(d->ws, S, C, M, D, B, F);
-  const int NR = o.NR, LD = o.LD;
-  const int64_t MM = (int64_t)M * M, MLD = (int64_t)M * LD;
-  const bool fused_softmax = C <= 16;
-  const bool native = d->eps_f == nullptr && !d->ext_lik;
-  const float* eps_f = native ? o.eps_f : d->eps_f;
-
-  // the merged factorisation + K_uf launch also writes L_S into RK; then the prologue writes RK's other small columns
-  const bool merge_chol = D > kRbfDirectD && M > 50 && M <= 100 && (D % 4) == 0 && (LD % 4) == 0 &&
-                          ((reinterpret_cast<uintptr_t>(d->z) | reinterpret_cast<uintptr_t>(d->x)) & 15) == 0;
-  static const int ksp = [] { const char* e = getenv("VARGP_KUU_SPLIT"); return e ? atoi(e) : kKuuSplit; }();   // tuning aid
-  static const int front_env = [] { const char* e = getenv("VARGP_T0_FRONT"); return e ? atoi(e) : 1; }();    // tuning aid
-  // merged factorisation launch + K-split K_uu product: the norms ride along
-  const bool split_kuu = merge_chol && D >= 256 && (int64_t)ksp * M <= LD && ksp > 1;
-  // ... and then the prologue shares the launch of the split product (every workgroup evaluates the 1/sigma^2 it needs itself),
-  // and the partial products are summed and exponentiated by the factorising workgroups as they load: two launches fewer
-  const bool front = split_kuu && front_env && ksp <= kCholPartMax && D <= kProKuuMaxD;
-  // ... with several hyper-samples the Gram matrices are a throughput problem (64 x 64 tiles of a 100-row matrix: 1.64x the work,
-  // partial sums written and re-read) while a factorising workgroup has time to spare under the K_uf product of its launch: it
-  // builds its Gram matrix itself (chol_gram.h: 16-row MFMA blocks, lower triangle) and the front launch keeps prologue + norms.
-  // Not at S = 3: there the chain workgroups ARE the critical path of their launch.
-  // Measured (steps/s without -> with): S = 3 5113 -> 4577, S = 8 2476 -> 2500, S = 16 1405 -> 1441, S = 64 420 -> 434; on from the
-  // chain count at which the merged launches are taken apart (t0_unmerge_chains).  VARGP_T0_GRAM_IN_CHAIN = S from which on (tuning aid)
-  static const int gic_env = [] { const char* e = getenv("VARGP_T0_GRAM_IN_CHAIN"); return e ? atoi(e) : -1; }();
-  const bool gram_in_chain = front && (gic_env >= 0 ? S >= gic_env : SC + C >= t0_unmerge_chains()) && M > 64 && (M % 4) == 0 &&
-                             D <= kCgMaxD && D >= 32;
-  ProArgs a{};
-  {
-    if (merge_chol) { a.RK = o.RK; a.u_mean = d->u_mean; a.NR = NR; a.LD = LD; }
-    a.mean = d->log_mean; a.logvar = d->log_logvar; a.pmean = d->prior_log_mean; a.plogvar = d->prior_log_logvar;
-    a.eps_theta = d->eps_theta; a.vec = d->u_tril_vec;
-    a.theta = o.theta; a.w = o.w; a.g2 = o.g2; a.kd = o.kd; a.Lu = o.Lu; a.Su = o.KS + SC * MM; a.scalars = d->scalars;
-    a.bump = d->bump;
-    // S_u = Lu Lu^T by the workgroup that factorises it (CholExtra::su_Lu, chol_small3.h: fp32 chains of 64 < M <= 100 on the matrix
-    // core) instead of 100-long dot products in the prologue's Lu role.  VARGP_T0_SU=0: off (tuning aid)
-    {
-      static const int f32_env = [] { const char* e = getenv("VARGP_CHOL_F32"); return e ? atoi(e) : kCholF32Default; }();
-      // VARGP_T0_SU=0: the Lu role's dot products (tuning aid).  Measured at Cfg2 (steps/s): 5323 with them; 5375 with the S_u chains
-      // building their matrix and the norm role in front of the (now short) prologue roles -- front launch 22.5 -> 19.0 us, the merged
-      // launch 35.2 -> 37.1 (the S_u chains become its longest); a workgroup per class inside the front launch instead: 5019 (its
-      // packed-vector loads are slow, and the heavier kernel costs the front launch a workgroup slot per SIMD)
-      static const int su_env = [] { const char* e = getenv("VARGP_T0_SU"); return e ? atoi(e) : 1; }();
-      a.su_in_chain = (VARGP_CHOL_BLK16 && su_env && f32_env && merge_chol && M > 64 && (M % 4) == 0 && M <= 100) ? 1 : 0;
-    }
-    a.zero_begin = o.gmu; a.zero_count = o.r_uf - o.gmu; a.info = d->info; a.Dp = o.Dp;
-    a.S = S; a.C = C; a.M = M; a.D = D; a.ninfo = SC + C; a.map_est = d->map_est;
-    a.nzero_blocks = (int)std::min<int64_t>(64, cdiv(a.zero_count, 1024));
-    if (native) {
-      const int64_t per_sample_f = (int64_t)F * C * B;
-      a.native = 1; a.seed = d->rng_seed; a.rng_counter = d->rng_counter;
-      a.g0_theta = (int64_t)d->rng_sample_offset * (D + 1); a.g0_f = (int64_t)d->rng_sample_offset * per_sample_f;
-      a.n_f = S * per_sample_f;
-      a.eps_theta_out = o.eps_theta; a.eps_f_out = o.eps_f;
-      a.nrng_blocks = (int)std::min<int64_t>(512, cdiv(a.n_f + 7, 1024));
-    }
-  }
-  ZeroJobs bwd_zero{};
-  const T0BwdPaths bwd_paths = t0_bwd_paths(d, o);
-  const bool clear_bwd = bwd_paths.mat_bwd;
-  // the likelihood inside the backward's tile kernel (one launch less): only where that kernel runs and its softmax fits
-  // (float4 reads of the noise there: a caller's eps_f must sit on a 16-byte boundary, the workspace's own does)
-  // (not on throughput-bound shapes -- the multi-tile form of that kernel, t0_bwd_mid_multi.h: the evaluation is C-fold redundant
-  //  there, 11k cycles of vector work per tile that such a launch cannot hide; those shapes keep the softmax launch)
-  const bool bwd_multi = bwd_paths.fused_bwd && (t0_tile_parts(SC, cdiv(B, 64), vargp_cu_count(), kBwdMidSetup) < cdiv(B, 64) || t0_force_multi());
-  const bool defer_softmax = d->defer_softmax && !d->ext_lik && fused_softmax && bwd_paths.fused_bwd && !bwd_multi &&
-                             F <= 4 * kBmSmF && C <= kBmSmC && reinterpret_cast<uintptr_t>(eps_f) % 16 == 0;
-  t0_state_set(d->ws, (clear_bwd ? kT0Cleared : kT0NoClear) | (defer_softmax ? kT0SoftmaxDeferred : 0));
-  if (clear_bwd) {
-    // accumulators of the LDS-resident backward (atomics of t0_bwd_mid.h / t0_bwd_mat.h / t0_bwd_tail.h), cleared in the forward,
-    // where it costs nothing (spare workgroups under the pivot chains; shapes without that launch: the prologue's zero role):
-    // column 0 (ga) and the G block of gQP, gT, gkd, r_uf / c_uf / gtheta
-    bwd_zero.j[0] = ZeroJob{o.gQP, (int64_t)SC * M, 4 + M, LD};
-    bwd_zero.j[1] = ZeroJob{o.gTT, 1, (SC + C) * MM, 0};
-    bwd_zero.j[2] = ZeroJob{o.queue, 1, 8, 0};          // work queue of the P_uf tiles (launch_bwdmat_gemm)
-    bwd_zero.j[3] = ZeroJob{o.gkd, 1, SC, 0};
-    bwd_zero.j[4] = ZeroJob{o.r_uf, 1, o.r_uu - o.r_uf, 0};
-    if (SC + C >= t0_unmerge_chains())                  // per-class sums of the L_S gradient shares (BwdMatArgs::gL_acc; gLL's tail is free on this path)
-      bwd_zero.j[5] = ZeroJob{o.gLL + SC * MM, 1, C * MM, 0};
-    if (!merge_chol) {
-      a.zero = bwd_zero;
-      const int64_t zt = (int64_t)SC * M * (4 + M) + (SC + 2 * C) * MM + (o.r_uu - o.r_uf);
-      a.nzero_blocks = (int)std::min<int64_t>(128, cdiv(a.zero_count + zt, 2048));
-    }
-  }
-  const int npro = 1 + S + a.nzero_blocks + a.nrng_blocks + cdiv((int64_t)C * MM, 256);
-  if (!front) {
-    ProfScope prof("t0_prologue", st);
-    hipLaunchKernelGGL(t0_prologue_kernel, dim3(npro), dim3(256), 0, st, a);
-  }
-  // kernel matrices: K_uu -> KS[:SC], K_uf -> the trailing block of RK
-  bool merged = false;
-  if (D <= kRbfDirectD) {
-    rc = rbf_direct_launch(d->z, nullptr, o.w, o.g2, o.KS, M, S, C, M, M, D, o.Dp, 0, st);
-    if (rc) return rc;
-    rc = rbf_direct_launch(d->z, d->x, o.w, o.g2, o.RK + NR, LD, S, C, M, B, D, o.Dp, 1, st);
-    if (rc) return rc;
-  } else {
-    const int64_t zrows = (int64_t)C * M;
-    if (!split_kuu)
-      hipLaunchKernelGGL(t0_norm_kernel, dim3(cdiv(zrows + B, 4), S), dim3(256), 0, st, d->z, d->x, o.w, o.na, o.nb, zrows,
-                         (int64_t)B, D, o.Dp);
-    GemmParams p0{}, p1{};
-    p0.A = d->z; p0.B = d->z; p0.C = o.KS;
-    p0.M = M; p0.N = M; p0.K = D; p0.lda = D; p0.ldb = D; p0.ldc = M;
-    p0.nb1 = C; p0.nb2 = 1;
-    p0.sA[1] = (int64_t)M * D; p0.sB[1] = (int64_t)M * D;
-    p0.sC[0] = C * MM; p0.sC[1] = MM;
-    p0.alpha = 1.f;
-    p0.kscale = o.w; p0.ks_ld = o.Dp; p0.g2 = o.g2;
-    p0.na = o.na; p0.sNa[0] = zrows; p0.sNa[1] = M;
-    p0.nbv = o.na; p0.sNb[0] = zrows; p0.sNb[1] = M;
-    p0.same_xy = 1;
-    p1.A = d->z; p1.B = d->x; p1.C = o.RK + NR;
-    p1.M = C * M; p1.N = B; p1.K = D; p1.lda = D; p1.ldb = D; p1.ldc = LD;
-    p1.nb1 = 1; p1.nb2 = 1;
-    p1.sC[0] = (int64_t)C * MLD;
-    p1.alpha = 1.f;
-    p1.kscale = o.w; p1.ks_ld = o.Dp; p1.g2 = o.g2;
-    p1.na = o.na; p1.sNa[0] = zrows;
-    p1.nbv = o.nb; p1.sNb[0] = B;
-    if (merge_chol && chol_rbf_gemm_applicable(M, p1)) {
-      // K_uu first, then ONE launch in which SC + C workgroups factorise (K_uu + eps I, S_u + eps I) while the rest of
-      // the chip builds K_uf, which nothing needs before the factors are done
-      if (split_kuu) {
-        // 4 SC workgroups with D/64 slabs each would leave half the chip idle for the length of that K loop: split K,
-        // partial inner products to scratch, distance/exp epilogue afterwards
-        GemmParams ps = p0;
-        ps.splitk = ksp; ps.sSplit = SC * MM; ps.C = o.kpart;
-        if (front) {
-          // (the norm role also writes x o 1/sigma_s^2: the K_uf product then runs without scale loads / multiplies in its
-          // main loop -- step 209.5 -> 207.7 us at S = 3, 510 -> 494 us at S = 8)
-          NormArgs nr{d->z, d->x, o.na, o.nb, zrows, (int64_t)B, 16, (int)cdiv(zrows + B, 16), o.xs};
-          rc = launch_pro_kuu(a, npro, nr, ps, gram_in_chain ? 0 : SC, st);
-          if (rc) return rc;
-          p1.B = o.xs; p1.sB[0] = (int64_t)B * D; p1.kscale = nullptr;
-        } else {
-          rc = launch_gemm(ps, 0, 1, SC, true, st, "rbf_kuu_gemm");
-          if (rc) return rc;
-          const int64_t total = SC * MM;
-          const int ncomb = cdiv(total, 256), nrow4 = cdiv(zrows + B, 4);
-          hipLaunchKernelGGL(t0_combine_norm_kernel, dim3(ncomb + nrow4 * S), dim3(256), 0, st, o.kpart, ksp, SC * MM, o.g2,
-                             o.KS, C, M, total, ncomb, d->z, d->x, o.w, o.na, o.nb, zrows, (int64_t)B, D, o.Dp, nrow4);
-        }
-      } else {
-        rc = launch_gemm(p0, 0, 1, SC, true, st, "rbf_kuu_gemm");
-        if (rc) return rc;
-      }
-      // L_S[c] -> RK[s, c, :, 4:4+M] for every s; K_uu and S_u arrive with both triangles; of the K_uu factors only
-      // the diagonal of L is ever used (log-determinant, and L^T diag(.) in the backward), everything else goes through T
-      CholExtra lx{o.RK + 4, SC, LD, MLD, (int64_t)C * MLD, S, 1, 1};
-      if (front) {   // the matrices b < SC arrive as K-split partial Gram matrices (and leave as K_uu in KS for the backward)
-        lx.part = o.kpart; lx.nsplit = ksp; lx.sSplit = SC * MM; lx.g2 = o.g2; lx.part_C = C; lx.Kout = o.KS;
-        if (gram_in_chain) { lx.part = nullptr; lx.gram_z = d->z; lx.gram_w = o.w; lx.gram_D = D; lx.gram_Dp = o.Dp; }
-      }
-      if (a.su_in_chain) lx.su_Lu = o.Lu;
-      // many hyper-samples: the chains fill the chip by themselves and hide nothing -- the product runs as a launch of its own, two
-      // workgroups per CU (the merged launch holds it to one by the chain role's registers): t0_unmerge_chains()
-      const bool unmerge = SC + C >= t0_unmerge_chains();
-      {
-        // (apart: the chains on a side stream, so that the product's workgroups fill the CUs the chains' rounds leave idle)
-        SideFork fork(st, unmerge && t0_side_stream());
-        rc = launch_chol_rbf_gemm(o.KS, d->jitter, o.LL, o.TT, d->info, SC + C, M, p1, unmerge ? 0 : S, fork.side(), &lx,
-                                  clear_bwd ? &bwd_zero : nullptr);
-        if (rc) return rc;
-        if (unmerge) {
-          static const int kuf_tile = [] { const char* e = getenv("VARGP_T0_KUF_TILE"); return e ? atoi(e) : 0; }();   // tuning aid
-          p1.tile = kuf_tile;
-          rc = launch_gemm(p1, 0, 1, S, true, st, "rbf_kuf_gemm");
-          if (rc) return rc;
-        }
-        rc = fork.join();
-        if (rc) return rc;
-      }
-      merged = true;
-    } else {
-      rc = launch_gemm_pair(p0, SC, p1, S, 0, 1, true, st, "rbf_kuu_gemm", "rbf_kuf_gemm");
-      if (rc) return rc;
-    }
-  }
-  // both factorisations (K_uu + eps I for every (s, c); S_u + eps I for every c) in one batch
-  if (!merged) {
-    rc = chol_inv_fwd_impl(o.KS, d->jitter, o.LL, o.TT, nullptr, d->info, SC + C, M, o.chol, o.chol_bytes, false, st);
-    if (rc) return rc;
-  }
-  if (!merged) {
-    VARGP_REQUIRE(!merge_chol, "elbo_t0_fwd: merged launch expected but not applicable");
-    const int64_t total = (int64_t)SC * M * NR;
-    hipLaunchKernelGGL(t0_pack_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, d->u_mean, o.LL + SC * MM, o.Lu, o.RK, C,
-                       M, NR, LD, total);
-  }
-  // early hand-over of the Cholesky status (include/vargp_hip.h: info_host / info_event): every factorisation of the forward is
-  // behind us on the stream
-  if (d->info_host && d->info_event) {
-    VARGP_REQUIRE(hipMemcpyAsync(d->info_host, d->info, sizeof(int32_t) * (size_t)(SC + C), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                      hipEventRecord(reinterpret_cast<hipEvent_t>(d->info_event), st) == hipSuccess,
-                  "elbo_t0_fwd: copy / event record of the early Cholesky status failed");
-  }
-  static const int fused_env = [] { const char* e = getenv("VARGP_T0_FUSED"); return e ? atoi(e) : 1; }();   // tuning aid
-  const int ntile = cdiv(B, 64);
-  const bool fused_mid = fused_env && M <= kFusedK && (M % 4) == 0 && (LD % 4) == 0 && (int64_t)SC * ntile <= t0_tile_units_max();
-  if (fused_mid) {
-    // small columns first (a = T m, G = T L_S, G2 = T Lu: one M x NR x M product per (s, c)), then the LDS-resident kernel
-    GemmParams p = flat_gemm(o.TT, M, MM, o.RK, LD, MLD, o.QP, LD, MLD, M, NR, M);
-    p.triA = 1;
-    rc = launch_gemm(p, 0, 0, SC, false, st, "t0_qps_gemm");
-    if (rc) return rc;
-    static std::atomic<unsigned> attr_set_mask[4][2] = {};      // 64 device ordinals per instantiation
-    const int nparts = t0_tile_parts(SC, ntile, vargp_cu_count(), 0.5f);
-    const bool multi = nparts < ntile || t0_force_multi();
-    const dim3 grid(8 * cdiv(SC, 8) * nparts);
-    uint32_t* rngc = native ? d->rng_counter : nullptr;
-#define VARGP_FF(V4, MT, SLOT)                                                                                                  \
-  do {                                                                                                                          \
-    rc = ensure_dynamic_lds(reinterpret_cast<const void*>(t0_fwd_fused_kernel<V4, MT>), kFusedLdsBytes, attr_set_mask[SLOT],    \
-                            "elbo_t0_fwd");                                                                                     \
-    if (rc) return rc;                                                                                                          \
-    hipLaunchKernelGGL((t0_fwd_fused_kernel<V4, MT>), grid, dim3(256), kFusedLdsBytes, st, o.TT, o.QP, o.RK, o.W, o.kd, o.LL,   \
-                       o.Lu, o.mu, o.var, d->scalars + 1, S, C, M, B, NR, LD, ntile, rngc, nparts);                             \
-  } while (0)
-    if (B % 4 == 0) { if (multi) VARGP_FF(true, true, 0); else VARGP_FF(true, false, 1); }
-    else { if (multi) VARGP_FF(false, true, 2); else VARGP_FF(false, false, 3); }
-#undef VARGP_FF
-  } else {
-    {  // QP = T RK
-      GemmParams p = flat_gemm(o.TT, M, MM, o.RK, LD, MLD, o.QP, LD, MLD, M, NR + B, M);
-      p.triA = 1;
-      rc = launch_gemm(p, 0, 0, SC, false, st, "t0_qp_gemm");
-      if (rc) return rc;
-    }
-    {  // W = G^T P
-      GemmParams p = flat_gemm(o.QP + 4, LD, MLD, o.QP + NR, LD, MLD, o.W, B, (int64_t)M * B, M, B, M);
-      p.triA = 2;
-      rc = launch_gemm(p, 1, 0, SC, false, st, "t0_w_gemm");
-      if (rc) return rc;
-    }
-    const int nbx = cdiv(B, 64), npd = nbx * SC, nkx = cdiv(M, kKlRows);
-    hipLaunchKernelGGL(t0_pdiag_kl_fwd_kernel, dim3(npd + nkx * SC), dim3(256), 0, st, o.QP, o.W, o.kd, o.LL, o.Lu, o.mu,
-                       o.var, d->scalars + 1, S, C, M, B, NR, LD, nbx, npd, nkx, native ? d->rng_counter : nullptr);
-  }
-  if (defer_softmax || d->ext_lik) {
-    // (nothing: t0_bwd_mid_kernel evaluates the likelihood of its tile -- value into scalars[2], gradient straight into its LDS;
-    // ext_lik: the caller evaluates it on the moments of ALL classes and stores the seeded gradients into gmu / gvar)
-  } else if (fused_softmax) {
-    const int64_t total = (int64_t)S * F * B;
-    hipLaunchKernelGGL(t0_softmax_kernel<16>, dim3(cdiv(total, 256)), dim3(256), 0, st, o.mu, o.var, eps_f, d->y,
-                       d->scalars + 2, o.gmu, o.gvar, S, F, C, B);
-  } else {
-    rc = vargp_softmax_nll_fwd(o.mu, o.var, eps_f, d->y, d->scalars + 2, S, F, C, B, stream);
-    if (rc) return rc;
-  }
-  return check_launch("elbo_t0_fwd");
+  const int rc = check_desc(d, "elbo_t0_fwd");
+  return rc ? rc : T0(d, stream).fwd();
 }
 
 extern "C" int vargp_elbo_t0_bwd(const vargp_elbo_t0_desc* d, const float* seeds, float* g_log_mean, float* g_log_logvar,
                                  float* g_z, float* g_u_mean, float* g_u_tril_vec, vargp_stream_t stream) {
-  int rc = check_desc(d, "elbo_t0_bwd");
+  const int rc = check_desc(d, "elbo_t0_bwd");
   if (rc) return rc;
   VARGP_REQUIRE(seeds && g_z && g_u_mean && g_u_tril_vec && (d->defer_hyper || (g_log_mean && g_log_logvar)),
                 "elbo_t0_bwd: null pointer");
-  hipStream_t st = as_stream(stream);
-  const int S = d->S, C = d->C, M = d->M, D = d->D, B = d->B, F = d->F, SC = S * C;
-  const T0Ws o = carve_t0(d->ws, S, C, M, D, B, F);
-  const int NR = o.NR, LD = o.LD;
-  const int64_t MM = (int64_t)M * M, MLD = (int64_t)M * LD, MB = (int64_t)M * B;
-  const bool fused_softmax = C <= 16 && !d->ext_lik;      // ext_lik: gmu / gvar arrive seeded, as from the generic kernel
-  const bool native = d->eps_f == nullptr && !d->ext_lik;
-  const float* eps_f = native ? o.eps_f : d->eps_f;
-  const float* eps_theta = native ? o.eps_theta : d->eps_theta;
-
-  if (!fused_softmax && !d->ext_lik) {   // C > 16: gradient of the likelihood from the generic kernel (already scaled by its seed)
-    rc = vargp_softmax_nll_bwd(o.mu, o.var, eps_f, d->y, seeds + 2, o.gmu, o.gvar, S, F, C, B, stream);
-    if (rc) return rc;
-  }
-  const int ntile = cdiv(B, 64);
-  const T0BwdPaths paths = t0_bwd_paths(d, o);
-  const bool fused_bwd = paths.fused_bwd, mat_bwd = paths.mat_bwd;
-  const int state_all = t0_state_get(d->ws);
-  const bool softmax_deferred = state_all >= 0 && (state_all & kT0SoftmaxDeferred) != 0;
-  VARGP_REQUIRE(!softmax_deferred || fused_bwd, "elbo_t0_bwd: the forward deferred the likelihood to a backward path this call does not take");
-  if (mat_bwd) {
-    // the accumulators must have been cleared by a forward on THIS workspace that took the same decision (the decision
-    // depends on the alignment of d->z / d->x and on tuning variables) and must not have been consumed by a backward yet
-    const int state = state_all < 0 ? state_all : (state_all & ~kT0SoftmaxDeferred);
-    VARGP_REQUIRE(state == kT0Cleared,
-                  "elbo_t0_bwd: %s -- this path allows ONE vargp_elbo_t0_bwd per vargp_elbo_t0_fwd (the forward clears the "
-                  "accumulators the backward adds into); run the forward again",
-                  state == kT0Consumed ? "second backward on one forward"
-                                       : "no forward on this workspace with the same z / x alignment");
-    t0_state_set(d->ws, kT0Consumed);
-  } else if (softmax_deferred) {
-    t0_state_set(d->ws, kT0NoClear);           // (the likelihood is added into scalars[2] once)
-  }
-  // mat_bwd: no head launch -- the forward's zero role has cleared the accumulators, the seed-dependent KL columns (g a, g G2) are
-  // formed by the chain kernel from QP, g_u_mean is cleared by the tile kernel.  ONE backward per forward on this path.
-  if (!mat_bwd)
-  {
-    const int npd = fused_bwd ? 0 : M * SC, nkx = cdiv(M, kKlRows), nkl = nkx * SC;
-    const int64_t zc = o.r_uu - o.r_uf;
-    const int nz = (int)std::min<int64_t>(64, cdiv(zc, 1024));
-    hipLaunchKernelGGL(t0_bwd_head_kernel, dim3(npd + nkl + nz), dim3(256), 0, st, o.QP, o.W, o.gmu, o.gvar,
-                       fused_softmax ? seeds + 2 : nullptr, o.LL, seeds, o.gQP, o.gW, o.gkd, o.gLL, o.gTT, o.gTT + SC * MM, o.r_uf,
-                       zc, S, C, M, B, NR, LD, npd, nkx, nkl, fused_bwd ? 1 : 0, mat_bwd ? g_u_mean : nullptr,
-                       mat_bwd ? o.gLL + SC * MM : nullptr);
-  }
-  if (fused_bwd) {
-    static std::atomic<unsigned> attr_set_mask[2] = {}, attr_set_mask_m[2] = {};
-    // throughput-bound shapes (more tile units than CUs): the multi-tile form (t0_bwd_mid_multi.h)
-    const int nparts = t0_tile_parts(SC, ntile, vargp_cu_count(), kBwdMidSetup);
-    const BmSoftmax smx = softmax_deferred ? BmSoftmax{o.mu, o.var, eps_f, d->y, d->scalars + 2, F} : BmSoftmax{};
-    if (nparts < ntile || t0_force_multi()) {
-      VARGP_REQUIRE(!softmax_deferred, "elbo_t0_bwd: the multi-tile backward does not evaluate a deferred likelihood");
-      rc = ensure_dynamic_lds(reinterpret_cast<const void*>(t0_bwd_mid_multi_kernel), kBwdMidMultiLdsBytes, attr_set_mask_m, "elbo_t0_bwd");
-      if (rc) return rc;
-      ProfScope prof("t0_bwd_mid", st);
-      hipLaunchKernelGGL(t0_bwd_mid_multi_kernel, dim3(8 * cdiv(SC, 8) * nparts), dim3(256), kBwdMidMultiLdsBytes, st, o.TT, o.QP, o.W, o.RK,
-                         o.gmu, o.gvar, fused_softmax ? seeds + 2 : nullptr, o.gQP, o.gTT, o.gRK, o.gkd, o.r_uf, o.c_uf, o.gtheta, S, C, M,
-                         B, D, NR, LD, ntile, nparts, mat_bwd ? g_u_mean : nullptr, C * M);
-    } else {
-      rc = ensure_dynamic_lds(reinterpret_cast<const void*>(t0_bwd_mid_kernel), kBwdMidLdsBytes, attr_set_mask, "elbo_t0_bwd");
-      if (rc) return rc;
-      ProfScope prof("t0_bwd_mid", st);
-      hipLaunchKernelGGL(t0_bwd_mid_kernel, dim3(8 * cdiv(SC, 8) * ntile), dim3(256), kBwdMidLdsBytes, st, o.TT, o.QP, o.W, o.RK, o.gmu, o.gvar,
-                         fused_softmax ? seeds + 2 : nullptr, o.gQP, o.gTT, o.gRK, o.gkd, o.r_uf, o.c_uf, o.gtheta, S, C, M, B, D,
-                         NR, LD, ntile, mat_bwd ? g_u_mean : nullptr, C * M, smx);
-    }
-    if (!mat_bwd) {
-      // what the tiles cannot see: the small columns [a | . | G | G2 | .] of QP = T RK (K = NR):
-      //   gT += tril(gQP[:, :NR] RK[:, :NR]^T)   on top of the tiles' atomics;   gRK[:, :NR] = T^T gQP[:, :NR]
-      GemmParams p = flat_gemm(o.gQP, LD, MLD, o.RK, LD, MLD, o.gTT, M, MM, M, M, NR);
-      p.triC = 1; p.D = o.gTT; p.ldd = M; p.beta = 1.f;
-      GemmParams q = flat_gemm(o.TT, M, MM, o.gQP, LD, MLD, o.gRK, LD, MLD, M, NR, M);
-      q.triA = 2;
-      rc = launch_gemm_pair2(p, 0, 1, SC, q, 1, 0, SC, st, "t0_gt_grk_small");
-      if (rc) return rc;
-      rc = chol_inv_bwd_first(o.TT, o.gTT, SC + C, M, o.chol, o.chol_bytes, nullptr, 0, 0, 0, st);
-      if (rc) return rc;
-    }
-  } else {
-  {  // W = G^T P:  gG = P gW^T (G block of gQP),  gP += G gW   -- independent of each other: one launch
-    GemmParams p = flat_gemm(o.QP + NR, LD, MLD, o.gW, B, MB, o.gQP + 4, LD, MLD, M, M, B);
-    p.splitk = ksplit(B);     // 4 SC tiles with a B-long K loop: split K so that the chip is busy (atomic accumulation)
-    GemmParams q = flat_gemm(o.QP + 4, LD, MLD, o.gW, B, MB, o.gQP + NR, LD, MLD, M, B, M);
-    q.triA = 1; q.D = o.gQP + NR; q.beta = 1.f;
-    rc = launch_gemm_pair2(p, 0, 1, SC, q, 0, 0, SC, st, "t0_gg_gp_gemm");
-    if (rc) return rc;
-  }
-  {  // QP = T RK:  gT = tril(gQP RK^T)
-    GemmParams p = flat_gemm(o.gQP, LD, MLD, o.RK, LD, MLD, o.gTT, M, MM, M, M, NR + B);
-    p.triC = 1;
-    p.splitk = ksplit(NR + B);
-    p.sSplit = 0;
-    rc = launch_gemm(p, 0, 1, SC, false, st, "t0_gt_gemm");
-    if (rc) return rc;
-  }
-  // gRK = T^T gQP shares a launch with the first product of the Cholesky backward (w1 = gT T^T), which only needs gT
-  GemmParams grk = flat_gemm(o.TT, M, MM, o.gQP, LD, MLD, o.gRK, LD, MLD, M, NR + B, M);
-  grk.triA = 2;
-  rc = chol_inv_bwd_first(o.TT, o.gTT, SC + C, M, o.chol, o.chol_bytes, &grk, 1, 0, SC, st);
-  if (rc) return rc;
-  }
-  const int64_t zrows = (int64_t)C * M;
-  bool fused_tail = false;
-  GemmParams p0{}, p1{};       // the W.Y products of the kernel-matrix backward: P_uu = W_uu z per (s, c), P_uf = W_uf x per s
-  p0.A = o.Wuu; p0.B = d->z; p0.C = o.Puu;
-  p0.M = M; p0.N = D; p0.K = M; p0.lda = M; p0.ldb = D; p0.ldc = D;
-  p0.nb1 = C; p0.nb2 = 1;
-  p0.sA[0] = C * MM; p0.sA[1] = MM;
-  p0.sB[1] = (int64_t)M * D;
-  p0.sC[0] = zrows * D; p0.sC[1] = (int64_t)M * D;
-  p0.alpha = 1.f;
-  p1.A = o.gRK + NR; p1.B = d->x; p1.C = o.Puf;
-  p1.M = C * M; p1.N = D; p1.K = B; p1.lda = LD; p1.ldb = D; p1.ldc = D;
-  p1.nb1 = 1; p1.nb2 = 1;
-  p1.sA[0] = C * MLD;
-  p1.sC[0] = zrows * D;
-  p1.alpha = 1.f;
-  if (mat_bwd) {
-    BwdMatArgs ma{};
-    ma.QP = o.QP; ma.TT = o.TT; ma.LL = o.LL; ma.gQP = o.gQP; ma.RK = o.RK; ma.KS = o.KS; ma.seeds = seeds; ma.gTT = o.gTT;
-    ma.gKS = o.gKS; ma.Wuu = o.Wuu; ma.r_uu = o.r_uu; ma.gtheta = o.gtheta;
-    ma.g_u_mean = g_u_mean; ma.gLu_part = o.gLL;                 // (gLL is free on this path: no head launch, no Cholesky-adjoint op)
-    ma.S = S; ma.C = C; ma.M = M; ma.D = D; ma.NR = NR; ma.LD = LD;
-    // all S C + C matrices next to P_uf = W_uf x (which only needs the tile kernel's W_uf) ...
-    // many hyper-samples (as in the forward: vargp_elbo_t0_fwd): the chains fill the chip by themselves, the product runs as a
-    // launch of its own (two workgroups per CU), and the S_u roles -- which would walk all S samples, one workgroup per class,
-    // with nothing left to hide under -- read per-class sums the K_uu roles accumulate (cleared by the forward's zero role)
-    const bool unmerge = SC + C >= t0_unmerge_chains();
-    if (unmerge) {
-      SideFork fork(st, t0_side_stream());               // (the chains on a side stream, as in the forward)
-      ma.gL_acc = o.gLL + SC * MM;
-      rc = launch_bwdmat_gemm(ma, 0, SC, p1, 0, fork.side(), "t0_bwdmat_kuu", nullptr);
-      if (rc) return rc;
-      rc = launch_bwdmat_gemm(ma, SC, C, p1, 0, fork.side(), "t0_bwdmat_su", nullptr);
-      if (rc) return rc;
-      static const int puf_tile = [] { const char* e = getenv("VARGP_T0_PUF_TILE"); return e ? atoi(e) : 0; }();   // tuning aid
-      p1.tile = puf_tile;
-      rc = launch_gemm(p1, 0, 0, S, false, st, "rbf_kuf_bwd_product");
-      if (rc) return rc;
-      rc = fork.join();
-    } else {
-      rc = launch_bwdmat_gemm(ma, 0, SC + C, p1, S, st, "rbf_kuf_bwd_gemm", reinterpret_cast<int*>(o.queue));
-    }
-    if (rc) return rc;
-    // ... then P_uu = W_uu z; with few samples inside the launch that consumes it (t0_bwd_tail.h)
-    static const int tail_env = [] { const char* e = getenv("VARGP_T0_TAIL"); return e ? atoi(e) : 1; }();   // tuning aid
-    fused_tail = tail_env && S <= kTailSMax;
-    if (!fused_tail) {
-      static const int puu_tile = [] { const char* e = getenv("VARGP_T0_PUU_TILE"); return e ? atoi(e) : 0; }();   // tuning aid
-      p0.tile = puu_tile;
-      rc = launch_gemm(p0, 0, 0, SC, false, st, "rbf_kuu_bwd_gemm");
-      if (rc) return rc;
-    }
-  } else {
-  {
-    const int64_t total = (int64_t)C * M * (M + 1);
-    hipLaunchKernelGGL(t0_unpack_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, o.gRK, g_u_mean, o.gLL + SC * MM, S, C,
-                       M, LD, total);
-  }
-  // gLL is lower-triangular by construction (diagonal for the K_uu factors, the L_S block of gRK for the S_u ones)
-  rc = chol_inv_bwd_impl(o.LL, o.TT, o.gLL, o.gTT, o.gKS, SC + C, M, o.chol, o.chol_bytes, true, st, true);
-  if (rc) return rc;
-  // kernel matrices -> z, theta
-  {
-    const int gx = cdiv(B, 256), gy = cdiv(zrows, kWRows), nuf = fused_bwd ? 0 : gx * gy * S;   // fused: W_uf is done
-    const int nuu = SC * cdiv(M, kUuRows);
-    const int ngv = cdiv((int64_t)C * MM, 256);      // + the gradient of the packed Cholesky vector of q(u)
-    hipLaunchKernelGGL(t0_w_kernel, dim3(nuf + nuu + ngv), dim3(256), 0, st, o.RK, o.gRK, o.KS, o.gKS, o.Wuu, o.r_uu, o.r_uf,
-                       o.c_uf, o.gtheta, S, C, M, B, D, NR, LD, gx, gy, nuf, nuu, d->u_tril_vec, o.Lu, seeds, g_u_tril_vec, 1);
-  }
-  rc = launch_gemm_pair(p0, SC, p1, S, 0, 0, false, st, "rbf_kuu_bwd_gemm", "rbf_kuf_bwd_gemm");
-  if (rc) return rc;
-  }
-  {
-    const int nzy = cdiv(zrows, kFinRows), nxy = cdiv(B, kFinRows), gx = cdiv(D, 64);
-    GvecArgs gv{};
-    int ngy = 0;
-    if (mat_bwd) {               // the gradient of the packed Cholesky vector of q(u) from the per-class sums: extra grid rows
-      gv.vec = d->u_tril_vec; gv.Lu = o.Lu; gv.gSu = o.gKS + SC * MM; gv.gLu_part = o.gLL; gv.seeds = seeds;
-      gv.gvec = g_u_tril_vec; gv.S = S; gv.C = C; gv.M = M; gv.y0 = nzy + nxy;
-      ngy = cdiv(cdiv((int64_t)C * MM, 256), gx);
-    }
-    if (fused_tail) {
-      ProfScope prof("t0_puu_final", st);
-      TailArgs ta{};
-      ta.z = d->z; ta.x = d->x; ta.Wuu = o.Wuu; ta.Puf = o.Puf; ta.r_uu = o.r_uu; ta.r_uf = o.r_uf; ta.c_uf = o.c_uf; ta.w = o.w;
-      ta.gz = g_z; ta.gtheta = o.gtheta; ta.S = S; ta.C = C; ta.M = M; ta.D = D; ta.B = B; ta.Dp = o.Dp;
-      const int rem = M % 32;
-      ta.nrb = (rem > 0 && rem <= 8) ? M / 32 : cdiv(M, 32);       // a short remainder goes to the vector units
-      const int ngr = cdiv(M, 32);
-      ta.ncb = cdiv(D, 32); ta.nz = cdiv(C * ta.nrb * ta.ncb + C * (ngr * (ngr + 1) / 2), 4);      // z + packed-vector wave-blocks
-      ta.nx = gx * cdiv(B, kTailXRows); ta.gx = gx;
-      ta.nrem = (rem > 0 && rem <= 8) ? C * gx * cdiv(rem, 4) : 0;
-      const dim3 grid(ta.nz + ta.nrem + ta.nx);
-      // more than four samples: the per-sample operands of the z role staged through LDS (t0_puu_final_lds_kernel)
-      static const int tail_lds_env = [] { const char* e = getenv("VARGP_T0_TAIL_LDS"); return e ? atoi(e) : kTailLdsDefault; }();   // tuning aid
-      if ((S > 4 && tail_lds_env) || tail_lds_env == 2) {      // (2: also with few samples -- tuning aid)
-        static std::atomic<unsigned> attr_set_mask_t[2] = {};
-        rc = ensure_dynamic_lds(reinterpret_cast<const void*>(t0_puu_final_lds_kernel), kTailLdsBytes, attr_set_mask_t, "elbo_t0_bwd");
-        if (rc) return rc;
-        int nzg = C * ta.nrb * cdiv(ta.ncb, 4), ngvw = cdiv(C * (ngr * (ngr + 1) / 2), 4);
-        // VARGP_EXP_TAIL (timing only, wrong results): 1 = the z groups alone, 2 = the other roles alone
-        static const int exp_tail = [] { const char* e = getenv("VARGP_EXP_TAIL"); return e ? atoi(e) : 0; }();
-        if (exp_tail == 1) { ngvw = 0; ta.nrem = 0; ta.nx = 0; }
-        if (exp_tail == 2) nzg = 0;
-        hipLaunchKernelGGL(t0_puu_final_lds_kernel, dim3(nzg + ngvw + ta.nrem + ta.nx), dim3(512), kTailLdsBytes, st, ta, gv, nzg, ngvw);
-      } else
-      switch (S) {
-        case 1: hipLaunchKernelGGL(t0_puu_final_kernel<1>, grid, dim3(256), 0, st, ta, gv); break;
-        case 2: hipLaunchKernelGGL(t0_puu_final_kernel<2>, grid, dim3(256), 0, st, ta, gv); break;
-        case 3: hipLaunchKernelGGL(t0_puu_final_kernel<3>, grid, dim3(256), 0, st, ta, gv); break;
-        case 4: hipLaunchKernelGGL(t0_puu_final_kernel<4>, grid, dim3(256), 0, st, ta, gv); break;
-        default: hipLaunchKernelGGL(t0_puu_final_kernel<0>, grid, dim3(256), 0, st, ta, gv); break;      // 5 .. kTailSMax: a loop
-      }
-    } else {
-      hipLaunchKernelGGL(t0_final_kernel, dim3(gx, nzy + nxy + ngy), dim3(256), 0, st, d->z, d->x, o.r_uu, o.r_uf, o.c_uf,
-                         o.Puu, o.Puf, o.w, g_z, o.gtheta, zrows, (int64_t)B, D, o.Dp, S, nzy, gv);
-    }
-  }
-  if (!d->defer_hyper) {
-    vargp_hyper_grad_desc h;
-    hyper_grad_desc_fill(d, o, eps_theta, seeds, &h);
-    hyper_bwd_launch(h, g_log_mean, g_log_logvar, st);
-  }
-  return check_launch("elbo_t0_bwd");
+  return T0(d, stream).bwd(seeds, g_log_mean, g_log_logvar, g_z, g_u_mean, g_u_tril_vec);
 }
 
 extern "C" int vargp_elbo_t0_hyper_desc(const vargp_elbo_t0_desc* d, const float* seeds, vargp_hyper_grad_desc* out) {
@@ -1411,6 +1411,6 @@ extern "C" int vargp_elbo_t0_hyper_desc(const vargp_elbo_t0_desc* d, const float
   if (rc) return rc;
   VARGP_REQUIRE(seeds && out, "elbo_t0_hyper_desc: null pointer");
   const T0Ws o = carve_t0(d->ws, d->S, d->C, d->M, d->D, d->B, d->F);
-  hyper_grad_desc_fill(d, o, (d->eps_f == nullptr && !d->ext_lik) ? o.eps_theta : d->eps_theta, seeds, out);
+  hyper_grad_desc_fill(d, o, t0_native(d) ? o.eps_theta : d->eps_theta, seeds, out);
   return VARGP_OK;
 }

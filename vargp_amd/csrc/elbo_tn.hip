@@ -713,18 +713,6 @@ static GemmParams blk_gemm(const float* A, int lda, const int64_t (&sA)[3], cons
   return p;
 }
 
-// one plain product of the program: operands, transpositions, batch count, profiling tag
-struct TnGemm {
-  GemmParams p;
-  int tA, tB, nbatch;
-  const char* tag;
-  TnGemm& onto_c() {      // accumulate: D = C, beta = 1
-    p.D = p.C; p.ldd = p.ldc; p.beta = 1.f;
-    for (int i = 0; i < 3; ++i) p.sD[i] = p.sC[i];
-    return *this;
-  }
-};
-
 // What every entry point of the program shares: descriptor, carved workspace, stream, derived sizes -- and, as members, the
 // description of each launch, ONCE: the GemmParams of a product, or a kernel launch with its grid and arguments, as a function of
 // what differs between callers (the width B and the x of the minibatch or tile, output and epilogue of a distance product,
@@ -748,13 +736,11 @@ struct Tn {
   float* rk_last() const { return d->rk_all + (int64_t)(nblk - 1) * M * NRs; }      // the current task's block of rk_all
   float* Smat() const { return reinterpret_cast<float*>(o.chol); }                  // scratch of the Cholesky backward
 
-  int run(const TnGemm& g) const { return launch_gemm(g.p, g.tA, g.tB, g.nbatch, false, st, g.tag); }
-  int run_pair(const TnGemm& a, const TnGemm& b, const char* tag) const {
-    return launch_gemm_pair2(a.p, a.tA, a.tB, a.nbatch, b.p, b.tA, b.tB, b.nbatch, st, tag);
-  }
-  TnGemm flat(const float* A, int lda, int64_t sA, const float* B, int ldb, int64_t sB, float* Cm, int ldc, int64_t sC, int m, int n,
+  int run(const ElboGemm& g) const { return g.run(st); }
+  int run_pair(const ElboGemm& a, const ElboGemm& b, const char* tag) const { return run_gemm_pair(a, b, tag, st); }
+  ElboGemm flat(const float* A, int lda, int64_t sA, const float* B, int ldb, int64_t sB, float* Cm, int ldc, int64_t sC, int m, int n,
               int k, int tA, int tB, const char* tag) const {
-    return TnGemm{flat_gemm(A, lda, sA, B, ldb, sB, Cm, ldc, sC, m, n, k), tA, tB, SC, tag};
+    return ElboGemm{flat_gemm(A, lda, sA, B, ldb, sB, Cm, ldc, sC, m, n, k), tA, tB, SC, tag};
   }
 
   // ---- forward ------------------------------------------------------------------------------------------------------
@@ -829,27 +815,27 @@ struct Tn {
   }
 
   // [a_i | . | H_i] = T_ii [m_i | 0 | Lu_i] for every (s, c, block i)
-  TnGemm small_gemm() const {
-    TnGemm g{blk_gemm(o.TT, Mt, sTd, d->rk_all, NRs, sRK, o.QPs, NRs, sQ, M, NRs, M, C, nblk), 0, 0, SC * nblk, "tn_small_gemm"};
+  ElboGemm small_gemm() const {
+    ElboGemm g{blk_gemm(o.TT, Mt, sTd, d->rk_all, NRs, sRK, o.QPs, NRs, sQ, M, NRs, M, C, nblk), 0, 0, SC * nblk, "tn_small_gemm"};
     g.p.triA = 1;
     return g;
   }
   // P = T K_uf
-  TnGemm p_gemm(int B) const {
-    TnGemm g = flat(o.TT, Mt, MtMt, o.Kuf, B, (int64_t)Mt * B, o.P, B, (int64_t)Mt * B, Mt, B, Mt, 0, 0, "tn_p_gemm");
+  ElboGemm p_gemm(int B) const {
+    ElboGemm g = flat(o.TT, Mt, MtMt, o.Kuf, B, (int64_t)Mt * B, o.P, B, (int64_t)Mt * B, Mt, B, Mt, 0, 0, "tn_p_gemm");
     g.p.triA = 1;
     return g;
   }
   // V2 = T^T P  (= K'^-1 K_uf: the eps term of the variance)
-  TnGemm v2_gemm(int B) const {
-    TnGemm g = flat(o.TT, Mt, MtMt, o.P, B, (int64_t)Mt * B, o.V2, B, (int64_t)Mt * B, Mt, B, Mt, 1, 0, "tn_v2_gemm");
+  ElboGemm v2_gemm(int B) const {
+    ElboGemm g = flat(o.TT, Mt, MtMt, o.P, B, (int64_t)Mt * B, o.V2, B, (int64_t)Mt * B, Mt, B, Mt, 1, 0, "tn_v2_gemm");
     g.p.triA = 2;
     return g;
   }
   // W_i = H_i^T P_i
-  TnGemm w_gemm(int B) const {
+  ElboGemm w_gemm(int B) const {
     const int64_t MtB = (int64_t)Mt * B, sP[3] = {C * MtB, MtB, (int64_t)M * B};
-    TnGemm g{blk_gemm(o.QPs + 4, NRs, sQ, o.P, B, sP, o.W, B, sP, M, B, M, C, nblk), 1, 0, SC * nblk, "tn_w_gemm"};
+    ElboGemm g{blk_gemm(o.QPs + 4, NRs, sQ, o.P, B, sP, o.W, B, sP, M, B, M, C, nblk), 1, 0, SC * nblk, "tn_w_gemm"};
     g.p.triA = 2;
     return g;
   }
@@ -884,54 +870,54 @@ struct Tn {
   // W_i = H_i^T P_i:  gH_i += P_i gW_i^T on top of the KL term / the earlier tiles -- splitk > 1: K-split with atomic
   // accumulation; tril: the lower triangle only (only tril(gH_i) is used: by tril(gH_i Lu_i^T) in gT and by the packed-vector
   // gradient; the head kernel left zeros above the diagonal)
-  TnGemm gh_gemm(int B, int splitk, bool tril) const {
+  ElboGemm gh_gemm(int B, int splitk, bool tril) const {
     const int64_t MtB = (int64_t)Mt * B, sP[3] = {C * MtB, MtB, (int64_t)M * B};
-    TnGemm g{blk_gemm(o.P, B, sP, o.W, B, sP, o.gQPs + 4, NRs, sQ, M, M, B, C, nblk), 0, 1, SC * nblk, "tn_gh_gemm"};
+    ElboGemm g{blk_gemm(o.P, B, sP, o.W, B, sP, o.gQPs + 4, NRs, sQ, M, M, B, C, nblk), 0, 1, SC * nblk, "tn_gh_gemm"};
     g.p.splitk = splitk;
     if (splitk <= 1) g.onto_c();
     if (tril) g.p.triC = 1;
     return g;
   }
   // ... and gP_i += H_i gW_i
-  TnGemm gp_gemm(int B) const {
+  ElboGemm gp_gemm(int B) const {
     const int64_t MtB = (int64_t)Mt * B, sP[3] = {C * MtB, MtB, (int64_t)M * B};
-    TnGemm g{blk_gemm(o.QPs + 4, NRs, sQ, o.W, B, sP, o.gP, B, sP, M, B, M, C, nblk), 0, 0, SC * nblk, "tn_gp_gemm"};
+    ElboGemm g{blk_gemm(o.QPs + 4, NRs, sQ, o.W, B, sP, o.gP, B, sP, M, B, M, C, nblk), 0, 0, SC * nblk, "tn_gp_gemm"};
     g.p.triA = 1;
     return g.onto_c();
   }
   // V2 = T^T P:  gP += T gV2
-  TnGemm gp_v2_gemm(int B) const {
-    TnGemm g = flat(o.TT, Mt, MtMt, o.V2, B, (int64_t)Mt * B, o.gP, B, (int64_t)Mt * B, Mt, B, Mt, 0, 0, "tn_gp_v2_gemm");
+  ElboGemm gp_v2_gemm(int B) const {
+    ElboGemm g = flat(o.TT, Mt, MtMt, o.V2, B, (int64_t)Mt * B, o.gP, B, (int64_t)Mt * B, Mt, B, Mt, 0, 0, "tn_gp_v2_gemm");
     g.p.triA = 1;
     return g.onto_c();
   }
   // gT = tril(gP K_uf^T + P gV2^T)  (P = T K_uf and V2 = T^T P): its two halves, each overwriting or adding
-  TnGemm gt_kuf_gemm(int B, bool accumulate) const {
-    TnGemm g = flat(o.gP, B, (int64_t)Mt * B, o.Kuf, B, (int64_t)Mt * B, o.gT, Mt, MtMt, Mt, Mt, B, 0, 1, "tn_gt_gemm");
+  ElboGemm gt_kuf_gemm(int B, bool accumulate) const {
+    ElboGemm g = flat(o.gP, B, (int64_t)Mt * B, o.Kuf, B, (int64_t)Mt * B, o.gT, Mt, MtMt, Mt, Mt, B, 0, 1, "tn_gt_gemm");
     g.p.triC = 1;
     return accumulate ? g.onto_c() : g;
   }
-  TnGemm gt_v2_gemm(int B, bool accumulate) const {
-    TnGemm g = flat(o.P, B, (int64_t)Mt * B, o.V2, B, (int64_t)Mt * B, o.gT, Mt, MtMt, Mt, Mt, B, 0, 1, "tn_gt_gemm");
+  ElboGemm gt_v2_gemm(int B, bool accumulate) const {
+    ElboGemm g = flat(o.P, B, (int64_t)Mt * B, o.V2, B, (int64_t)Mt * B, o.gT, Mt, MtMt, Mt, Mt, B, 0, 1, "tn_gt_gemm");
     g.p.triC = 1;
     return accumulate ? g.onto_c() : g;
   }
   // gK_uf = T^T gP
-  TnGemm gkuf_gemm(int B) const {
-    TnGemm g = flat(o.TT, Mt, MtMt, o.gP, B, (int64_t)Mt * B, o.gKuf, B, (int64_t)Mt * B, Mt, B, Mt, 1, 0, "tn_gkuf_gemm");
+  ElboGemm gkuf_gemm(int B) const {
+    ElboGemm g = flat(o.TT, Mt, MtMt, o.gP, B, (int64_t)Mt * B, o.gKuf, B, (int64_t)Mt * B, Mt, B, Mt, 1, 0, "tn_gkuf_gemm");
     g.p.triA = 2;
     return g;
   }
   // the diagonal blocks' share of gT from the small products:  gT_ii += gQP_i RK_i^T
-  TnGemm gt_diag_gemm() const {
-    TnGemm g{blk_gemm(o.gQPs, NRs, sQ, d->rk_all, NRs, sRK, o.gT, Mt, sTd, M, M, NRs, C, nblk), 0, 1, SC * nblk, "tn_gt_diag_gemm"};
+  ElboGemm gt_diag_gemm() const {
+    ElboGemm g{blk_gemm(o.gQPs, NRs, sQ, d->rk_all, NRs, sRK, o.gT, Mt, sTd, M, M, NRs, C, nblk), 0, 1, SC * nblk, "tn_gt_diag_gemm"};
     g.p.triC = 1;
     return g.onto_c();
   }
   // the parameter gradients of the current task:  [g m_t | . | g Lu_t] = T_tt^T [ga_t | . | gH_t]
-  TnGemm grk_gemm() const {
+  ElboGemm grk_gemm() const {
     const int64_t off = (int64_t)(Mt - M) * Mt + (Mt - M);
-    TnGemm g = flat(o.TT + off, Mt, MtMt, o.gQPs + (int64_t)(Mt - M) * NRs, NRs, MtN, o.gRKt, NRs, (int64_t)M * NRs, M, NRs, M, 1, 0,
+    ElboGemm g = flat(o.TT + off, Mt, MtMt, o.gQPs + (int64_t)(Mt - M) * NRs, NRs, MtN, o.gRKt, NRs, (int64_t)M * NRs, M, NRs, M, 1, 0,
                     "tn_grk_gemm");
     g.p.triA = 2;
     return g;
@@ -941,18 +927,18 @@ struct Tn {
   //   Smat  = (Phi(P_low) + Phi(P_low)^T) / 2 = -0.5 sym(tril(gT T^T)) + 0.5 g I_t,     gK = T^T Smat T
   int chol_bwd(const float* seeds) const {
     float* tmp = Smat() + SC * MtMt;
-    TnGemm p = flat(o.gT, Mt, MtMt, o.TT, Mt, MtMt, Smat(), Mt, MtMt, Mt, Mt, Mt, 0, 1, "tn_chol_bwd1");
+    ElboGemm p = flat(o.gT, Mt, MtMt, o.TT, Mt, MtMt, Smat(), Mt, MtMt, Mt, Mt, Mt, 0, 1, "tn_chol_bwd1");
     p.p.alpha = -0.5f; p.p.triA = 1; p.p.triB = 2; p.p.triC = 2; p.p.symout = 1;
     p.p.diag_ptr = seeds + 1; p.p.diag_scale = 0.5f / (float)S; p.p.diag_from = Mt - M;     // + g / 2 on the current task's diagonal
     int rc = run(p);
     if (rc) return rc;
     // gK = T^T (Smat T) is symmetric: its lower triangle needs tril(Smat T) only, and as T^T [.] the tiles of the lower
     // triangle are the ones with the SHORT K ranges (k >= row), 40 % of the work of the full product
-    TnGemm q = flat(Smat(), Mt, MtMt, o.TT, Mt, MtMt, tmp, Mt, MtMt, Mt, Mt, Mt, 0, 0, "tn_chol_bwd2");
+    ElboGemm q = flat(Smat(), Mt, MtMt, o.TT, Mt, MtMt, tmp, Mt, MtMt, Mt, Mt, Mt, 0, 0, "tn_chol_bwd2");
     q.p.triB = 1; q.p.triC = 1;
     rc = run(q);
     if (rc) return rc;
-    TnGemm r = flat(o.TT, Mt, MtMt, tmp, Mt, MtMt, o.gK, Mt, MtMt, Mt, Mt, Mt, 1, 0, "tn_chol_bwd3");
+    ElboGemm r = flat(o.TT, Mt, MtMt, tmp, Mt, MtMt, o.gK, Mt, MtMt, Mt, Mt, Mt, 1, 0, "tn_chol_bwd3");
     r.p.triA = 2; r.p.triB = 1; r.p.triC = 2; r.p.symout = 1;
     return run(r);
   }
@@ -990,7 +976,7 @@ struct Tn {
     return VARGP_OK;
   }
   // the W.Y products: P_uu = W_uu z_all,  P_uf = W_uf x (accumulate: on top of the earlier tiles')
-  TnGemm wz_gemm() const {
+  ElboGemm wz_gemm() const {
     GemmParams p{};
     p.A = o.Wuu; p.B = d->z_all; p.C = o.Puu;
     p.M = Mt; p.N = D; p.K = Mt; p.lda = Mt; p.ldb = D; p.ldc = D;
@@ -999,9 +985,9 @@ struct Tn {
     p.sB[1] = (int64_t)Mt * D;
     p.sC[0] = zrows * D; p.sC[1] = (int64_t)Mt * D;
     p.alpha = 1.f;
-    return TnGemm{p, 0, 0, SC, "rbf_kuu_bwd_gemm"};
+    return ElboGemm{p, 0, 0, SC, "rbf_kuu_bwd_gemm"};
   }
-  TnGemm wx_gemm(const float* x, int B, bool accumulate) const {
+  ElboGemm wx_gemm(const float* x, int B, bool accumulate) const {
     GemmParams p{};
     p.A = o.gKuf; p.B = x; p.C = o.Puf;
     p.M = C * Mt; p.N = D; p.K = B; p.lda = B; p.ldb = D; p.ldc = D;
@@ -1010,7 +996,7 @@ struct Tn {
     p.sC[0] = zrows * D;
     p.alpha = 1.f;
     if (accumulate) { p.D = o.Puf; p.ldd = D; p.sD[0] = zrows * D; p.beta = 1.f; }
-    return TnGemm{p, 0, 0, S, "rbf_kuf_bwd_gemm"};
+    return ElboGemm{p, 0, 0, S, "rbf_kuf_bwd_gemm"};
   }
   // one finalisation for the inducing-point side (z_side: gz_all, gtheta from r_uu, r_uf, P_uu, P_uf) and the minibatch side
   // (x != NULL: gtheta += w sum_n c_uf x^2 over its B rows)
@@ -1140,7 +1126,7 @@ extern "C" int vargp_elbo_tn_fwd(const vargp_elbo_tn_desc* d, vargp_stream_t str
     }
   }
   {  // P = T K_uf is independent of the small products -- mid-size shapes share one launch
-    const TnGemm p = t.small_gemm(), q = t.p_gemm(B);
+    const ElboGemm p = t.small_gemm(), q = t.p_gemm(B);
     const int64_t wgs = (int64_t)SC * (nblk * cdiv(M, 64) * cdiv(NRs, 64) + cdiv(Mt, 64) * cdiv(B, 64));
     if (wgs <= 4096) {
       rc = t.run_pair(p, q, "tn_p_gemm");
@@ -1153,7 +1139,7 @@ extern "C" int vargp_elbo_tn_fwd(const vargp_elbo_tn_desc* d, vargp_stream_t str
     }
   }
   {  // V2 and the W_i both only need P
-    const TnGemm p = t.v2_gemm(B), q = t.w_gemm(B);
+    const ElboGemm p = t.v2_gemm(B), q = t.w_gemm(B);
     const int64_t wgs = (int64_t)SC * cdiv(B, 64) * (cdiv(Mt, 64) + nblk * cdiv(M, 64));
     if (wgs <= 4096) {
       rc = t.run_pair(p, q, "tn_v2_gemm");
@@ -1215,7 +1201,7 @@ extern "C" int vargp_elbo_tn_bwd(const vargp_elbo_tn_desc* d, const float* seeds
                        NRs, NV);
   }
   {  // gH (K-split on top of the KL term) and gP += H gW
-    const TnGemm p = t.gh_gemm(B, ksplit(B), false), q = t.gp_gemm(B);
+    const ElboGemm p = t.gh_gemm(B, ksplit(B), false), q = t.gp_gemm(B);
     const int64_t wgs = (int64_t)SC * nblk * (cdiv(M, 64) * cdiv(M, 64) * std::max(p.p.splitk, 1) + cdiv(M, 64) * cdiv(B, 64));
     if (wgs <= 4096) {     // mid-size: one launch for both
       rc = t.run_pair(p, q, "tn_gh_gp_gemm");
@@ -1273,7 +1259,7 @@ extern "C" int vargp_elbo_tn_bwd(const vargp_elbo_tn_desc* d, const float* seeds
   rc = t.w_pass(d->x, B, true, true, seeds);
   if (rc) return rc;
   {
-    const TnGemm p0 = t.wz_gemm(), p1 = t.wx_gemm(d->x, B, false);
+    const ElboGemm p0 = t.wz_gemm(), p1 = t.wx_gemm(d->x, B, false);
     const int64_t wgs = (int64_t)cdiv(Mt, 64) * cdiv(D, 64) * SC + (int64_t)cdiv(C * Mt, 64) * cdiv(D, 64) * S;
     if (wgs <= 4096) {     // mid-size: neither fills the chip alone, one launch (64^3 tiles)
       rc = launch_gemm_pair(p0.p, p0.nbatch, p1.p, p1.nbatch, 0, 0, false, st, p0.tag, p1.tag);
