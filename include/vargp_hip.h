@@ -225,6 +225,52 @@ int vargp_bernoulli_predict(const float* mu, const float* var, int link, float* 
                             vargp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Poisson likelihood with a log link (counts), independent outputs, closed form.  Not in the reference.
+ *   mu, var [S, C, B]; y non-negative floats (not checked), [C, B] with row stride ldy, or one row [B] shared by every output
+ *   (ldy = 0).  With m = mu + var / 2:
+ *     ell[s,c,b] = y mu - exp(m) - lgamma(y + 1),     nll = - sum_b sum_c mean_s ell   (SUM over outputs, as the Bernoulli
+ *     likelihood: the ELBO of C independent outputs -- C times the Gaussian likelihood's mean-over-outputs convention)
+ * fwd WRITES *nll.  bwd, seed = d total / d nll (device, 1 float):
+ *     gmu = -seed (y - exp(m)) / S,   gvar = seed exp(m) / (2 S)     [S, C, B]
+ * and, with nll != NULL, also writes the (unseeded) value, bit-equal to fwd's, so a training step needs one call.
+ * exp(m) overflows fp32 above m ~ 88.7; value and gradients are then inf, as the formula says (nothing is clamped).
+ * predict: rate[S, C, B] = E exp(f) = exp(m).
+ * ws: vargp_poisson_workspace_bytes(S, C, B) bytes of 8-byte aligned device scratch, used inside the call only (per-workgroup
+ * partial values, kept as doubles; may be NULL in bwd when nll is NULL).  Deterministic: no float atomics, every sum in a fixed
+ * order.  Inputs and outputs are fp32; the element arithmetic and the sums run in fp64, so every output is rounded once.
+ */
+size_t vargp_poisson_workspace_bytes(int S, int C, int B);
+int vargp_poisson_nll_fwd(const float* mu, const float* var, const float* y, int64_t ldy, float* nll, int S, int C, int B,
+                          float* ws, size_t ws_bytes, vargp_stream_t stream);
+int vargp_poisson_nll_bwd(const float* mu, const float* var, const float* y, int64_t ldy, const float* seed, float* gmu,
+                          float* gvar, float* nll, int S, int C, int B, float* ws, size_t ws_bytes, vargp_stream_t stream);
+int vargp_poisson_predict(const float* mu, const float* var, float* rate, int S, int C, int B, vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Student-t likelihood (robust regression), independent outputs.  Not in the reference.
+ *   Fixed degrees of freedom df = nu > 0 (host float), learned log_scale [C], sigma_c = exp(log_scale[c]).  mu, var, y, ldy as
+ *   above.  lognorm = lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi) / 2, computed by the CALLER in double (the two lgamma cancel
+ *   in fp32 at large nu) and passed as one float.  With the 20-node Gauss-Hermite rule of the Bernoulli section (x_k, w^_k),
+ *   which is the definition of the expected log-likelihood and not an approximation left open, and
+ *   r_k = y - (mu + sqrt(2 var) x_k):
+ *     ell[s,c,b] = K_c - (nu + 1) / 2 sum_k w^_k log1p(r_k^2 / (nu sigma_c^2)),     K_c = lognorm - log_scale[c]
+ *     nll = - sum_b sum_c mean_s ell   (SUM over outputs: C times the Gaussian likelihood's convention)
+ * fwd WRITES *nll.  bwd, seed = d total / d nll (device, 1 float): gmu, gvar [S, C, B] and g_log_scale [C] = seed * the exact
+ * derivatives of that sum (g_log_scale[c] = -seed / S sum_{s,b} d ell / d log_scale[c], in a fixed order); at var = 0 the
+ * rule's variance gradient is exactly 0.  With nll != NULL bwd also writes the (unseeded) value, bit-equal to fwd's.
+ * The predictive location is mu itself: there is no predict entry.
+ * ws: vargp_studentt_workspace_bytes(S, C, B) bytes of 8-byte aligned device scratch, used inside the call only (per-workgroup
+ * partial values and log_scale gradients, kept as doubles; always needed).  Deterministic: no float atomics, every sum in a fixed
+ * order.  Inputs and outputs are fp32; the element arithmetic and the sums run in fp64, so every output is rounded once.
+ */
+size_t vargp_studentt_workspace_bytes(int S, int C, int B);
+int vargp_studentt_nll_fwd(const float* mu, const float* var, const float* y, int64_t ldy, const float* log_scale, float df,
+                           float lognorm, float* nll, int S, int C, int B, float* ws, size_t ws_bytes, vargp_stream_t stream);
+int vargp_studentt_nll_bwd(const float* mu, const float* var, const float* y, int64_t ldy, const float* log_scale, float df,
+                           float lognorm, const float* seed, float* gmu, float* gvar, float* g_log_scale, float* nll, int S,
+                           int C, int B, float* ws, size_t ws_bytes, vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Yogi optimiser step, fused over one flat parameter buffer (reference call site:
  * experiments/vargp.py:23,37 -> torch_optimizer.Yogi; algorithm from Zaheer et al. 2018).
  * bias1/bias2 = 1 - beta^t; if `step` (device pointer to the step count t as a float) is not NULL

@@ -108,6 +108,14 @@ _SIGNATURES = {
     'vargp_bernoulli_nll_fwd': (c_int, [_P, _P, _P, c_int64, _P, c_int, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
     'vargp_bernoulli_nll_bwd': (c_int, [_P, _P, _P, c_int64, _P, c_int] + [_P] * 4 + [c_int, c_int, c_int, _P, c_size_t, _P]),
     'vargp_bernoulli_predict': (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, _P]),
+    'vargp_poisson_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'vargp_poisson_nll_fwd': (c_int, [_P, _P, _P, c_int64, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    'vargp_poisson_nll_bwd': (c_int, [_P, _P, _P, c_int64] + [_P] * 4 + [c_int, c_int, c_int, _P, c_size_t, _P]),
+    'vargp_poisson_predict': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+    'vargp_studentt_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'vargp_studentt_nll_fwd': (c_int, [_P, _P, _P, c_int64, _P, c_float, c_float, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    'vargp_studentt_nll_bwd': (c_int, [_P, _P, _P, c_int64, _P, c_float, c_float] + [_P] * 5 + [c_int, c_int, c_int, _P, c_size_t,
+                                                                                                 _P]),
     'vargp_yogi_step_multi': (c_int, [c_int, _P, _P, _P, _P, _P] + [c_float] * 4 + [_P, c_int, _P]),
     'vargp_yogi_step_multi_hyper': (c_int, [c_int, _P, _P, _P, _P, _P] + [c_float] * 4 + [_P, c_int, POINTER(HyperGradDesc), c_int,
                                             c_int, _P]),

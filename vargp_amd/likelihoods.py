@@ -2,11 +2,16 @@
   * MulticlassSoftmax (var_gp/likelihoods.py:7-63): Monte-Carlo softmax on the fused `vargp_softmax_*` kernels;
   * GaussianLikelihood (var_gp/likelihoods.py:66-110): independent multi-output Gaussian, closed form on the
     `vargp_gauss_nll_*` kernels (csrc/gauss_lik.hip); draws no noise;
-and one that the reference does not have:
+and three that the reference does not have:
   * BernoulliLikelihood: independent outputs (binary, multi-label, one-vs-rest), a fixed 20-node Gauss-Hermite rule on the
-    `vargp_bernoulli_*` kernels (csrc/bernoulli_lik.hip); deterministic, no parameters.
-GaussianLikelihood and BernoulliLikelihood are "external": the native ELBO programs stop at the predictive moments and the KL
-(ext_lik) and these classes complete the step through one protocol -- ext_param / ext_target / ext_value / ext_backward."""
+    `vargp_bernoulli_*` kernels (csrc/bernoulli_lik.hip); deterministic, no parameters;
+  * PoissonLikelihood: counts with a log link, closed form on the `vargp_poisson_*` kernels (csrc/reg_lik.hip); no parameters;
+  * StudentTLikelihood: robust regression, fixed degrees of freedom and one learned log-scale per output, the same 20-node
+    rule on the `vargp_studentt_*` kernels (csrc/reg_lik.hip).
+All but the softmax are "external": the native ELBO programs stop at the predictive moments and the KL (ext_lik) and these
+classes complete the step through one protocol -- ext_param / ext_target / ext_value / ext_backward.
+Every class names the layout of what its `predict` returns in `predict_batch_dim`: the dim that runs over the data points
+(0 for probabilities (B, C), -1 for per-sample values (S, C, B)) -- what a tiled prediction concatenates along."""
 import torch
 import torch.nn as nn
 
@@ -14,6 +19,8 @@ from . import noise, ops
 
 
 class MulticlassSoftmax(nn.Module):
+    predict_batch_dim = 0
+
     def __init__(self, n_f=1):
         super().__init__()
         self.n_f = n_f
@@ -39,6 +46,7 @@ class MulticlassSoftmax(nn.Module):
 
 class GaussianLikelihood(nn.Module):
     """Independent multi-output Gaussian likelihood with one learned observation log-variance per output."""
+    predict_batch_dim = -1
 
     def __init__(self, out_size, init_log_var=-4.):
         super().__init__()
@@ -98,6 +106,7 @@ class BernoulliLikelihood(nn.Module):
     The loss SUMS over outputs: kl_u sums over outputs, so the ELBO of C independent outputs sums their log-likelihoods.
     (GaussianLikelihood keeps the reference's mean over outputs because it has the reference to match; this class has nothing
     to match.)"""
+    predict_batch_dim = 0
 
     def __init__(self, link='probit'):
         super().__init__()
@@ -138,17 +147,118 @@ class BernoulliLikelihood(nn.Module):
         return None
 
 
+class PoissonLikelihood(nn.Module):
+    """Independent-output Poisson likelihood with a log link, p(y | f) = Poisson(y; exp(f)): counts.  Not in the reference.  No
+    parameters, no noise, no quadrature -- under f ~ N(mu, var) the expected log-likelihood is closed form, with m = mu + var / 2:
+        ell = y mu - exp(m) - lgamma(y + 1)
+    Targets: non-negative floats (or integers, cast) of shape (C, B), or (B,) shared by every output; not checked on the device.
+    exp(m) overflows fp32 above m ~ 88.7: value and gradients are then inf, as the formula says -- nothing is clamped.
+    The loss SUMS over outputs and takes the mean over hyper-samples, as BernoulliLikelihood does: the ELBO of C independent
+    outputs, C times GaussianLikelihood's (the reference's) mean-over-outputs convention."""
+    predict_batch_dim = -1
+
+    def forward(self, mu, var):
+        """the rate E exp(f) per element, (S, C, B)."""
+        return ops.poisson_predict(mu, var)
+
+    def loss(self, pred_mu, pred_var, y):
+        """- sum_b sum_c mean_s ell[s, c, b]; y as ops.reg_target takes it."""
+        return ops.poisson_nll(pred_mu, pred_var, y)
+
+    def predict(self, mu, var):
+        """the predicted rate exp(mu + var / 2) per hyper-sample, (S, C, B) -- the layout of GaussianLikelihood.predict."""
+        return ops.poisson_predict(mu, var)
+
+    # -- the native programs' ext_lik route (see GaussianLikelihood) ------------------------------------------------------------
+    def ext_param(self):
+        return None
+
+    def ext_target(self, y, C, B):
+        return ops.reg_target(y, C, B)
+
+    def ext_value(self, prog, target):
+        from .fused import lik_views
+        mu, var, _, _ = lik_views(prog)
+        ops.poisson_nll_fwd(mu, var, *target, prog.scalars[2:])
+
+    def ext_backward(self, prog, target, seed, nll=None, grad=None):
+        from .fused import lik_views
+        mu, var, gmu, gvar = lik_views(prog)
+        ops.poisson_nll_bwd(mu, var, *target, seed, gmu, gvar, nll=nll)
+        return None
+
+
+class StudentTLikelihood(nn.Module):
+    """Independent-output Student-t likelihood, p(y | f) = t_df((y - f) / sigma_c) / sigma_c with sigma_c = exp(log_scale[c]):
+    regression that a few outliers do not pull along.  Not in the reference.  One learned log-scale per output; the degrees of
+    freedom `df` > 0 are a fixed constructor argument and NOT part of the state dict -- give them again when a checkpoint is
+    reloaded (as MaternKernel.nu).  No noise: the expected log-likelihood under f ~ N(mu, var) is DEFINED as the 20-node
+    Gauss-Hermite sum (BernoulliLikelihood's rule)
+        ell = K_c - (df + 1) / 2 sum_k w_k / sqrt(pi) log1p((y - mu - sqrt(2 var) x_k)^2 / (df sigma_c^2)),
+        K_c = lgamma((df + 1) / 2) - lgamma(df / 2) - log(df pi) / 2 - log_scale[c],
+    and the gradients are the exact derivatives of that sum.  (As an approximation of the integral the rule is as good as twenty
+    nodes resolve the density's width: with sqrt(var) ten times sigma_c single terms are up to 6 % away from a 200-node rule.)
+    Targets (C, B), or (B,) shared by every output.
+    The loss SUMS over outputs and takes the mean over hyper-samples, as BernoulliLikelihood does: the ELBO of C independent
+    outputs, C times GaussianLikelihood's (the reference's) mean-over-outputs convention."""
+    predict_batch_dim = -1
+
+    def __init__(self, out_size, df=4.0, init_log_scale=-2.):
+        super().__init__()
+        self.df = float(df)
+        ops.studentt_lognorm(self.df)           # (ValueError unless df > 0)
+        self.log_scale = nn.Parameter(init_log_scale * torch.ones(out_size))
+
+    def forward(self, mu, var):
+        """location and squared scale of the observation model around f's moments, (S, C, B, 1) each: mu, and
+        var + exp(2 log_scale).  Not on the hot path; kept for API symmetry with GaussianLikelihood."""
+        return mu.unsqueeze(-1), var.unsqueeze(-1) + (2 * self.log_scale).exp().view(1, -1, 1, 1)
+
+    def loss(self, pred_mu, pred_var, y):
+        """- sum_b sum_c mean_s ell[s, c, b]; y as ops.reg_target takes it."""
+        return ops.studentt_nll(pred_mu, pred_var, y, self.log_scale, self.df)
+
+    def predict(self, mu, var):
+        """the predictive location, the mean itself, (S, C, B) -- as GaussianLikelihood.predict."""
+        return mu
+
+    # -- the native programs' ext_lik route (see GaussianLikelihood) ------------------------------------------------------------
+    def ext_param(self):
+        return self.log_scale
+
+    def ext_target(self, y, C, B):
+        return ops.reg_target(y, C, B) + (self.log_scale.detach().contiguous(),)
+
+    def ext_value(self, prog, target):
+        from .fused import lik_views
+        mu, var, _, _ = lik_views(prog)
+        ops.studentt_nll_fwd(mu, var, *target, self.df, prog.scalars[2:])
+
+    def ext_backward(self, prog, target, seed, nll=None, grad=None):
+        from .fused import lik_views
+        mu, var, gmu, gvar = lik_views(prog)
+        grad = torch.empty_like(target[2]) if grad is None else grad
+        ops.studentt_nll_bwd(mu, var, *target, self.df, seed, gmu, gvar, grad, nll=nll)
+        return grad
+
+
 def n_f(likelihood):
-    """Monte-Carlo likelihood samples per hyper-sample: the F of the native programs' shapes.  The Gaussian likelihood is
-    evaluated in closed form and the Bernoulli likelihood by a fixed rule (the programs run them with ext_lik and F = 1)."""
+    """Monte-Carlo likelihood samples per hyper-sample: the F of the native programs' shapes.  The external likelihoods are
+    evaluated in closed form (Gaussian, Poisson) or by a fixed rule (Bernoulli, Student-t): the programs run them with ext_lik
+    and F = 1."""
     return 1 if is_external(likelihood) else likelihood.n_f
 
 
 def is_external(likelihood):
     """Is the likelihood the caller's -- do the native programs run it with ext_lik (moments + KL only) and leave value and
     gradients to the likelihood's ext_value / ext_backward?"""
-    return isinstance(likelihood, (GaussianLikelihood, BernoulliLikelihood))
+    return isinstance(likelihood, (GaussianLikelihood, BernoulliLikelihood, PoissonLikelihood, StudentTLikelihood))
 
 
 def is_gaussian(likelihood):
     return isinstance(likelihood, GaussianLikelihood)
+
+
+def predict_batch_dim(likelihood):
+    """The dim of likelihood.predict(...) that runs over the data points: what a tiled prediction concatenates along."""
+    return likelihood.predict_batch_dim

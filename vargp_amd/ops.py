@@ -1,6 +1,8 @@
 """torch.autograd.Function wrappers over the C ABI: every forward AND backward below is a call into
 libvargp_hip.so (hand-written HIP), torch only owns the memory and the stream.
 """
+import math
+
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -760,6 +762,140 @@ def bernoulli_nll(mu, var, y, link='probit'):
     """- sum_b sum_c mean_s E_{f ~ N(mu, var)} log Lambda((2 t - 1) f) by the 20-node Gauss-Hermite rule
     (BernoulliLikelihood.loss); y as bernoulli_target takes it.  Differentiable in mu and var."""
     return _BernoulliNll.apply(mu, var, y, bernoulli_link(link))
+
+
+# ------------------------------------------------------------------------------------------------
+# Poisson (log link) and Student-t likelihoods (independent outputs; csrc/reg_lik.hip -- not in the reference)
+# ------------------------------------------------------------------------------------------------
+def reg_target(y, C, B):
+    """A regression / count target as the Poisson and Student-t kernels read it: (fp32 contiguous tensor, row stride ldy) --
+    (C, B) -> ldy = B, (B,) -> ldy = 0 (one row shared by every output).  Values are not checked."""
+    if not torch.is_tensor(y):
+        raise TypeError(f'reg_target: a tensor is needed, got {type(y).__name__}')
+    y = y.detach().to(torch.float32).contiguous()
+    if tuple(y.shape) == (B,):
+        return y, 0
+    if tuple(y.shape) == (C, B):
+        return y, B
+    raise ValueError(f'reg_target: targets must have shape ({C}, {B}) or ({B},), got {tuple(y.shape)}')
+
+
+def _reg_ws(name, S, C, B, device):
+    return scratch(getattr(lib(), f'vargp_{name}_workspace_bytes')(S, C, B), device)
+
+
+def poisson_nll_fwd(mu, var, y, ldy, out):
+    """Writes the Poisson nll of mu, var (S, C, B) contiguous into the one-float device tensor `out`; (y, ldy) from
+    reg_target."""
+    S, C, B = mu.shape
+    ws = _reg_ws('poisson', S, C, B, mu.device)
+    check(lib().vargp_poisson_nll_fwd(ptr(mu), ptr(var), ptr(y), ldy, ptr(out), S, C, B, ptr(ws), ws.numel() * 4,
+                                      stream_ptr()), 'vargp_poisson_nll_fwd')
+
+
+def poisson_nll_bwd(mu, var, y, ldy, seed, gmu, gvar, nll=None):
+    """Seeded gradients of the Poisson nll into gmu, gvar (S, C, B); with `nll`, the value too (bit-equal to the forward's)."""
+    S, C, B = mu.shape
+    ws = _reg_ws('poisson', S, C, B, mu.device) if nll is not None else None
+    check(lib().vargp_poisson_nll_bwd(ptr(mu), ptr(var), ptr(y), ldy, ptr(seed), ptr(gmu), ptr(gvar), ptr(nll), S, C, B,
+                                      ptr(ws), ws.numel() * 4 if ws is not None else 0, stream_ptr()),
+          'vargp_poisson_nll_bwd')
+
+
+def poisson_predict(mu, var):
+    """rate (S, C, B) = E exp(f) = exp(mu + var / 2)."""
+    require_device(mu, var)
+    mu, var = mu.contiguous(), var.contiguous()
+    S, C, B = mu.shape
+    rate = torch.empty_like(mu)
+    check(lib().vargp_poisson_predict(ptr(mu), ptr(var), ptr(rate), S, C, B, stream_ptr()), 'vargp_poisson_predict')
+    return rate
+
+
+class _PoissonNll(Function):
+    @staticmethod
+    def forward(ctx, mu, var, y):
+        require_device(mu, var, y)
+        mu, var = mu.contiguous(), var.contiguous()
+        S, C, B = mu.shape
+        assert var.shape == mu.shape and mu.dtype == torch.float32 and var.dtype == torch.float32, (mu.shape, var.shape, mu.dtype, var.dtype)
+        yt, ldy = reg_target(y, C, B)
+        nll = torch.empty((), dtype=torch.float32, device=mu.device)
+        poisson_nll_fwd(mu, var, yt, ldy, nll)
+        ctx.save_for_backward(mu, var, yt)
+        ctx.ldy = ldy
+        return nll
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        mu, var, yt = ctx.saved_tensors
+        gmu, gvar = torch.empty_like(mu), torch.empty_like(var)
+        poisson_nll_bwd(mu, var, yt, ctx.ldy, g.float().contiguous(), gmu, gvar)
+        return gmu, gvar, None
+
+
+def poisson_nll(mu, var, y):
+    """- sum_b sum_c mean_s [y mu - exp(mu + var / 2) - lgamma(y + 1)]  (PoissonLikelihood.loss); y (C, B) or (B,), non-negative.
+    Differentiable in mu and var."""
+    return _PoissonNll.apply(mu, var, y)
+
+
+def studentt_lognorm(df):
+    """lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi) / 2 in double on the host: the two lgamma cancel in fp32 at large nu."""
+    df = float(df)
+    if not df > 0.0:
+        raise ValueError(f'Student-t degrees of freedom must be > 0, got {df!r}')
+    return math.lgamma(0.5 * (df + 1.0)) - math.lgamma(0.5 * df) - 0.5 * math.log(df * math.pi)
+
+
+def studentt_nll_fwd(mu, var, y, ldy, log_scale, df, out):
+    """Writes the Student-t nll of mu, var (S, C, B) contiguous into the one-float device tensor `out`; (y, ldy) from
+    reg_target, log_scale (C,), df a host float."""
+    S, C, B = mu.shape
+    ws = _reg_ws('studentt', S, C, B, mu.device)
+    check(lib().vargp_studentt_nll_fwd(ptr(mu), ptr(var), ptr(y), ldy, ptr(log_scale), df, studentt_lognorm(df), ptr(out), S, C,
+                                       B, ptr(ws), ws.numel() * 4, stream_ptr()), 'vargp_studentt_nll_fwd')
+
+
+def studentt_nll_bwd(mu, var, y, ldy, log_scale, df, seed, gmu, gvar, g_log_scale, nll=None):
+    """Seeded gradients of the Student-t nll into gmu, gvar (S, C, B) and g_log_scale (C,); with `nll`, the value too
+    (bit-equal to the forward's)."""
+    S, C, B = mu.shape
+    ws = _reg_ws('studentt', S, C, B, mu.device)
+    check(lib().vargp_studentt_nll_bwd(ptr(mu), ptr(var), ptr(y), ldy, ptr(log_scale), df, studentt_lognorm(df), ptr(seed),
+                                       ptr(gmu), ptr(gvar), ptr(g_log_scale), ptr(nll), S, C, B, ptr(ws), ws.numel() * 4,
+                                       stream_ptr()), 'vargp_studentt_nll_bwd')
+
+
+class _StudentTNll(Function):
+    @staticmethod
+    def forward(ctx, mu, var, y, log_scale, df):
+        require_device(mu, var, y, log_scale)
+        mu, var, log_scale = mu.contiguous(), var.contiguous(), log_scale.contiguous()
+        S, C, B = mu.shape
+        assert var.shape == mu.shape and log_scale.shape == (C,), (mu.shape, var.shape, log_scale.shape)
+        assert mu.dtype == torch.float32 and var.dtype == torch.float32 and log_scale.dtype == torch.float32
+        yt, ldy = reg_target(y, C, B)
+        nll = torch.empty((), dtype=torch.float32, device=mu.device)
+        studentt_nll_fwd(mu, var, yt, ldy, log_scale, df, nll)
+        ctx.save_for_backward(mu, var, yt, log_scale)
+        ctx.ldy, ctx.df = ldy, df
+        return nll
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        mu, var, yt, log_scale = ctx.saved_tensors
+        gmu, gvar, gls = torch.empty_like(mu), torch.empty_like(var), torch.empty_like(log_scale)
+        studentt_nll_bwd(mu, var, yt, ctx.ldy, log_scale, ctx.df, g.float().contiguous(), gmu, gvar, gls)
+        return gmu, gvar, None, gls, None
+
+
+def studentt_nll(mu, var, y, log_scale, df=4.0):
+    """- sum_b sum_c mean_s E_{f ~ N(mu, var)} log t_df((y - f) / exp(log_scale[c])) / exp(log_scale[c]) by the 20-node
+    Gauss-Hermite rule (StudentTLikelihood.loss); y (C, B) or (B,).  Differentiable in mu, var and log_scale."""
+    return _StudentTNll.apply(mu, var, y, log_scale, float(df))
 
 # ------------------------------------------------------------------------------------------------
 # variational hyper-parameters

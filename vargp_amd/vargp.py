@@ -22,7 +22,8 @@ import torch.nn as nn
 from . import fused, gp_utils, noise, ops
 from .gp_utils import vec2tril, mat2trilvec, cholesky, rev_cholesky, gp_cond, block_joint, linear_marginal_diag
 from .kernels import RBFKernel, DeepRBFKernel, MaternKernel, native_code
-from .likelihoods import BernoulliLikelihood, MulticlassSoftmax, is_external, is_gaussian, n_f
+from .likelihoods import (BernoulliLikelihood, GaussianLikelihood, MulticlassSoftmax, PoissonLikelihood, StudentTLikelihood,
+                          is_external, n_f, predict_batch_dim)
 from .ops import LOWER
 
 
@@ -36,6 +37,29 @@ def make_clf_likelihood(likelihood, n_f, link='probit'):
     if likelihood == 'bernoulli':
         return BernoulliLikelihood(link=link)
     raise ValueError(f"create_clf: likelihood must be 'softmax' or 'bernoulli', got {likelihood!r}")
+
+
+def make_reg_likelihood(likelihood, out_size, df=4.0):
+    """create_reg(likelihood=, df=) -> the likelihood module; ValueError for an unknown name."""
+    if likelihood == 'gaussian':
+        return GaussianLikelihood(out_size)
+    if likelihood == 'studentt':
+        return StudentTLikelihood(out_size, df=df)
+    if likelihood == 'poisson':
+        return PoissonLikelihood()
+    raise ValueError(f"create_reg: likelihood must be 'gaussian', 'studentt' or 'poisson', got {likelihood!r}")
+
+
+def _hand_over_hyper_prior(prev_params):
+    """The hyper-prior of the next task = the last task's hyper-posterior: popped from prev_params, which is mutated like the
+    reference does (vargp.py:213-222).  -> (prior_log_mean, prior_log_logvar)"""
+    if not prev_params:
+        return None, None
+    prior = prev_params[-1].get('kernel.log_mean'), prev_params[-1].get('kernel.log_logvar')
+    for p in prev_params:
+        for k in [k for k in p if k.startswith('kernel')]:
+            p.pop(k)
+    return prior
 
 
 class VARGP(nn.Module):
@@ -396,11 +420,12 @@ class VARGP(nn.Module):
 
     def predict(self, x, tile=None):
         """Class probabilities (B, C)  (vargp.py:196-198; BernoulliLikelihood: per-output P(t = 1), not normalised over the
-        outputs); for a GaussianLikelihood model the predictive means (S, C, B).
+        outputs); for a GaussianLikelihood or StudentTLikelihood model the predictive means (S, C, B), for a PoissonLikelihood
+        model the predicted rates (S, C, B).
         With `tile`, a large x is swept in blocks of `tile` points that share ONE hyper-sample and ONE set of x-independent
         factors (K_uu, its Cholesky / inverse, Lz^-1 m, Lz^-1 L_S): the same result as a single call on all of x, in bounded
         memory."""
-        cat_dim = -1 if is_gaussian(self.likelihood) else 0          # blocks along B: last dim of (S, C, B), first of (B, C)
+        cat_dim = predict_batch_dim(self.likelihood)                 # blocks along B: last dim of (S, C, B), first of (B, C)
         if tile is None or x.size(0) <= tile:
             pred_mu, pred_var = self(x)
             return self.likelihood.predict(pred_mu, pred_var)
@@ -479,3 +504,34 @@ class VARGP(nn.Module):
                              map_est=map_est_hypers)
         return VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean,
                      prev_params=prev_params)
+
+    @staticmethod
+    def create_reg(dataset, M=20, n_var_samples=3, likelihood='gaussian', df=4.0, prev_params=None, ep_var_mean=True,
+                   map_est_hypers=False, kernel='rbf', native_kernel=False):
+        """Regression / count factory, the counterpart of create_clf (not in the reference): dataset[i] -> (x, y), dataset.targets
+        (N,) (one output) or (N, C); inducing points at M random data points per output; hyper-prior = the previous task's
+        hyper-posterior (popped from prev_params[-1], which is mutated as in create_clf).  likelihood: 'gaussian'
+        (GaussianLikelihood), 'studentt' (StudentTLikelihood(df=df): robust to outliers) or 'poisson' (PoissonLikelihood:
+        non-negative counts, log link; df is unused by the other two).  kernel / native_kernel: as create_clf, without dkl.
+        None of likelihood, df, kernel and native_kernel is part of a checkpoint: give them again on reload.  A minibatch's
+        targets go to loss() as (C, B) -- y.t() of a (B, C) batch -- or (B,)."""
+        if kernel not in _KERNEL_NU:
+            raise ValueError(f'create_reg: kernel must be one of {sorted(_KERNEL_NU)}, got {kernel!r}')
+        if native_kernel and kernel == 'rbf':
+            raise ValueError('create_reg: native_kernel=True selects the native route of a Matern kernel (kernel="matern12" / '
+                             '"matern32" / "matern52"); the RBF kernel is always native')
+        targets = torch.as_tensor(dataset.targets)
+        if targets.dim() not in (1, 2):
+            raise ValueError(f'create_reg: dataset.targets must have shape (N,) or (N, C), got {tuple(targets.shape)}')
+        out_size = 1 if targets.dim() == 1 else targets.size(1)
+        lik = make_reg_likelihood(likelihood, out_size, df)
+        N = len(dataset)
+        z = torch.stack([dataset[torch.randperm(N)[:M]][0] for _ in range(out_size)])
+        prior_log_mean, prior_log_logvar = _hand_over_hyper_prior(prev_params)
+        if kernel != 'rbf':
+            kern = MaternKernel(z.size(-1), nu=_KERNEL_NU[kernel], prior_log_mean=prior_log_mean,
+                                prior_log_logvar=prior_log_logvar, map_est=map_est_hypers, native=bool(native_kernel))
+        else:
+            kern = RBFKernel(z.size(-1), prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
+                             map_est=map_est_hypers)
+        return VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean, prev_params=prev_params)

@@ -16,6 +16,7 @@ import torch.nn as nn
 from . import gp_utils, noise, ops
 from .gp_utils import vec2tril, rev_cholesky, linear_marginal_diag
 from .kernels import RBFKernel
+from .likelihoods import predict_batch_dim
 from .ops import LOWER
 
 _HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
@@ -166,7 +167,9 @@ class VARGPRetrain(nn.Module):
         """Class probabilities (B, C)  (vargp_retrain.py:235-237).  `tile`: a large x in chunks of `tile` points (same
         signature as VARGP.predict; every chunk draws its own hyper-parameter sample, as one call per batch would)."""
         if tile is not None and x.size(0) > tile:
-            return torch.cat([self.predict(x[i:i + tile]) for i in range(0, x.size(0), tile)], dim=0)
+            # (blocks along B: first dim of probabilities (B, C), last of the regression likelihoods' (S, C, B))
+            return torch.cat([self.predict(x[i:i + tile]) for i in range(0, x.size(0), tile)],
+                             dim=predict_batch_dim(self.likelihood))
         pred_mu, pred_var = self(x)
         return self.likelihood.predict(pred_mu, pred_var)
 
