@@ -271,6 +271,42 @@ int vargp_studentt_nll_bwd(const float* mu, const float* var, const float* y, in
                            int C, int B, float* ws, size_t ws_bytes, vargp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Held-out log predictive density (LPD) of every likelihood above: log E_q[p(y | f)], the mixture over the hyper-samples of the
+ * marginal likelihood of the targets (vargp_amd/csrc/lpd.hip).  Not in the reference.  (The nll entries give E_q[log p].)
+ *   mu, var [S, C, B]: the predictive moments of f under hyper-sample s.  Targets and ldy / ldt / labels: exactly the conventions
+ *   of the matching *_nll_fwd entry.  With the 20-node Gauss-Hermite rule of the Bernoulli section (x_k, w^_k), which here too is
+ *   the definition and not an approximation left open, and f_k = mu + sqrt(2 var) x_k, the log marginal likelihood per (s, c, b):
+ *     gauss             lp = log N(y; mu, var + exp(obs_log_var[c]))                                          (closed form)
+ *     poisson           lp = logsumexp_k( log w^_k + y f_k - exp(f_k) - lgamma(y + 1) )
+ *     studentt          lp = logsumexp_k( log w^_k + K_c - (nu + 1) / 2 log1p((y - f_k)^2 / (nu sigma_c^2)) ),  K_c, lognorm, df
+ *                       as in the Student-t section
+ *     bernoulli probit  lp = log Phi(s_cb mu / sqrt(1 + var)), s = 2 t - 1, evaluated as log(erfc(-z / sqrt2) / 2) in fp64: finite
+ *                       for z >= -37; below, erfc underflows and lp = -inf (log 0), which drops out of the mixture without a NaN
+ *     bernoulli logit   lp = logsumexp_k( log w^_k + log sigma(s_cb f_k) )
+ *   The hyper-sample is shared by all outputs of a point, so the density of its whole target vector is the mixture of products:
+ *     lpd[b]       = logsumexp_s( sum_c lp[s,c,b] ) - log S         [B]      (required)
+ *     lpd_out[c,b] = logsumexp_s( lp[s,c,b] )       - log S         [C, B]   (per-output marginals; may be NULL)
+ *   softmax, eps [S, F, C, B], y int64 [B] (labels unchecked, as vargp_softmax_nll_fwd; a label outside [0, C) gives a
+ *   meaningless value for that point and reads nothing out of bounds):
+ *     lpd[b] = logsumexp_{s,f}( log_softmax_c(mu + sqrt(var) eps)[y_b] ) - log(S F);  no per-output marginals.
+ * Every logsumexp subtracts its running maximum; a term of -inf produces no NaN, and a point whose every term is -inf gets -inf.
+ * No workspace.  Deterministic: no float atomics, every sum in a fixed order (same inputs -> bitwise identical outputs).  Inputs
+ * and outputs are fp32; the element arithmetic and every sum run in fp64, so each output is rounded once.  No gradients.
+ * Argument errors (NULL required pointer, non-positive size, bad link, both or neither of t and labels, ldy / ldt neither 0 nor
+ * >= B, df <= 0) return VARGP_EINVAL before any launch.
+ */
+int vargp_softmax_lpd(const float* mu, const float* var, const float* eps, const int64_t* y, float* lpd, int S, int F, int C,
+                      int B, vargp_stream_t stream);
+int vargp_gauss_lpd(const float* mu, const float* var, const float* y, int64_t ldy, const float* obs_log_var, float* lpd,
+                    float* lpd_out, int S, int C, int B, vargp_stream_t stream);
+int vargp_bernoulli_lpd(const float* mu, const float* var, const float* t, int64_t ldt, const int64_t* labels, int link,
+                        float* lpd, float* lpd_out, int S, int C, int B, vargp_stream_t stream);
+int vargp_poisson_lpd(const float* mu, const float* var, const float* y, int64_t ldy, float* lpd, float* lpd_out, int S, int C,
+                      int B, vargp_stream_t stream);
+int vargp_studentt_lpd(const float* mu, const float* var, const float* y, int64_t ldy, const float* log_scale, float df,
+                       float lognorm, float* lpd, float* lpd_out, int S, int C, int B, vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Yogi optimiser step, fused over one flat parameter buffer (reference call site:
  * experiments/vargp.py:23,37 -> torch_optimizer.Yogi; algorithm from Zaheer et al. 2018).
  * bias1/bias2 = 1 - beta^t; if `step` (device pointer to the step count t as a float) is not NULL

@@ -116,6 +116,11 @@ _SIGNATURES = {
     'vargp_studentt_nll_fwd': (c_int, [_P, _P, _P, c_int64, _P, c_float, c_float, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
     'vargp_studentt_nll_bwd': (c_int, [_P, _P, _P, c_int64, _P, c_float, c_float] + [_P] * 5 + [c_int, c_int, c_int, _P, c_size_t,
                                                                                                  _P]),
+    'vargp_softmax_lpd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    'vargp_gauss_lpd': (c_int, [_P, _P, _P, c_int64, _P, _P, _P, c_int, c_int, c_int, _P]),
+    'vargp_bernoulli_lpd': (c_int, [_P, _P, _P, c_int64, _P, c_int, _P, _P, c_int, c_int, c_int, _P]),
+    'vargp_poisson_lpd': (c_int, [_P, _P, _P, c_int64, _P, _P, c_int, c_int, c_int, _P]),
+    'vargp_studentt_lpd': (c_int, [_P, _P, _P, c_int64, _P, c_float, c_float, _P, _P, c_int, c_int, c_int, _P]),
     'vargp_yogi_step_multi': (c_int, [c_int, _P, _P, _P, _P, _P] + [c_float] * 4 + [_P, c_int, _P]),
     'vargp_yogi_step_multi_hyper': (c_int, [c_int, _P, _P, _P, _P, _P] + [c_float] * 4 + [_P, c_int, POINTER(HyperGradDesc), c_int,
                                             c_int, _P]),

@@ -11,7 +11,9 @@ and three that the reference does not have:
 All but the softmax are "external": the native ELBO programs stop at the predictive moments and the KL (ext_lik) and these
 classes complete the step through one protocol -- ext_param / ext_target / ext_value / ext_backward.
 Every class names the layout of what its `predict` returns in `predict_batch_dim`: the dim that runs over the data points
-(0 for probabilities (B, C), -1 for per-sample values (S, C, B)) -- what a tiled prediction concatenates along."""
+(0 for probabilities (B, C), -1 for per-sample values (S, C, B)) -- what a tiled prediction concatenates along.
+Every class has `log_prob(mu, var, y, per_output=False)`: the held-out log predictive density per point (B,), log E_q[p(y)] -- the
+mixture over the hyper-samples of the marginal likelihood of the point's targets (csrc/lpd.hip; not in the reference, no gradients)."""
 import torch
 import torch.nn as nn
 
@@ -43,6 +45,14 @@ class MulticlassSoftmax(nn.Module):
         """class probabilities (B, C) averaged over the S*F samples  (likelihoods.py:49-63)."""
         return ops.softmax_predict(mu, var, self._eps(mu))
 
+    def log_prob(self, mu, var, y, per_output=False):
+        """Held-out log predictive density (B,): log of the label's mean probability over the S F samples,
+        logsumexp_{s,f} log_softmax(mu + sqrt(var) eps)[y] - log(S F).  The classes share one normaliser: there are no
+        per-output marginals (per_output=True: ValueError)."""
+        if per_output:
+            raise ValueError('MulticlassSoftmax.log_prob: the softmax has no per-output marginals (per_output=True)')
+        return ops.softmax_lpd(mu, var, self._eps(mu), y)
+
 
 class GaussianLikelihood(nn.Module):
     """Independent multi-output Gaussian likelihood with one learned observation log-variance per output."""
@@ -64,6 +74,12 @@ class GaussianLikelihood(nn.Module):
     def predict(self, mu, var):
         """the predictive mean itself, (S, C, B)  (likelihoods.py:109-110)."""
         return mu
+
+    def log_prob(self, mu, var, y, per_output=False):
+        """Held-out log predictive density: lpd (B,) = logsumexp_s sum_c log N(y | mu, var + exp(obs_log_var)) - log S, the joint
+        density of a point's targets under the mixture over hyper-samples (they share the hyper-sample); per_output: (lpd,
+        lpd_out (C, B)) with the per-output marginals.  Not in the reference.  No gradients."""
+        return ops.gauss_lpd(mu, var, y, self.obs_log_var, per_output=per_output)
 
     # -- the native programs' ext_lik route ------------------------------------------------------------------------------------
     def ext_param(self):
@@ -128,6 +144,11 @@ class BernoulliLikelihood(nn.Module):
         the 20-node rule on the logistic function."""
         return ops.bernoulli_predict(mu, var, self.link)
 
+    def log_prob(self, mu, var, y, per_output=False):
+        """Held-out log predictive density (B,), or (lpd, lpd_out (C, B)) -- see GaussianLikelihood.log_prob; per element
+        log Phi(s mu / sqrt(1 + var)) (probit) or the 20-node rule on the logistic function (logit)."""
+        return ops.bernoulli_lpd(mu, var, y, self.link, per_output=per_output)
+
     # -- the native programs' ext_lik route (see GaussianLikelihood) ------------------------------------------------------------
     def ext_param(self):
         return None
@@ -168,6 +189,11 @@ class PoissonLikelihood(nn.Module):
     def predict(self, mu, var):
         """the predicted rate exp(mu + var / 2) per hyper-sample, (S, C, B) -- the layout of GaussianLikelihood.predict."""
         return ops.poisson_predict(mu, var)
+
+    def log_prob(self, mu, var, y, per_output=False):
+        """Held-out log predictive density (B,), or (lpd, lpd_out (C, B)) -- see GaussianLikelihood.log_prob; the marginal
+        likelihood of a count is the 20-node Gauss-Hermite sum of Poisson(y; exp(f_k))."""
+        return ops.poisson_lpd(mu, var, y, per_output=per_output)
 
     # -- the native programs' ext_lik route (see GaussianLikelihood) ------------------------------------------------------------
     def ext_param(self):
@@ -221,6 +247,11 @@ class StudentTLikelihood(nn.Module):
     def predict(self, mu, var):
         """the predictive location, the mean itself, (S, C, B) -- as GaussianLikelihood.predict."""
         return mu
+
+    def log_prob(self, mu, var, y, per_output=False):
+        """Held-out log predictive density (B,), or (lpd, lpd_out (C, B)) -- see GaussianLikelihood.log_prob; the marginal
+        likelihood of a target is the 20-node Gauss-Hermite sum of the Student-t density."""
+        return ops.studentt_lpd(mu, var, y, self.log_scale, self.df, per_output=per_output)
 
     # -- the native programs' ext_lik route (see GaussianLikelihood) ------------------------------------------------------------
     def ext_param(self):

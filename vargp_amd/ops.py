@@ -897,6 +897,93 @@ def studentt_nll(mu, var, y, log_scale, df=4.0):
     Gauss-Hermite rule (StudentTLikelihood.loss); y (C, B) or (B,).  Differentiable in mu, var and log_scale."""
     return _StudentTNll.apply(mu, var, y, log_scale, float(df))
 
+
+# ------------------------------------------------------------------------------------------------
+# held-out log predictive density, every likelihood (csrc/lpd.hip -- not in the reference).  No autograd.
+# ------------------------------------------------------------------------------------------------
+def _lpd_moments(mu, var, *others):
+    """The moments as the LPD kernels read them: fp32, contiguous, (S, C, B) each, on the device like every other operand."""
+    require_device(mu, var, *others)
+    mu, var = mu.detach().contiguous(), var.detach().contiguous()
+    assert mu.dim() == 3 and var.shape == mu.shape and mu.dtype == torch.float32 and var.dtype == torch.float32, \
+        (mu.shape, var.shape, mu.dtype, var.dtype)
+    return mu, var
+
+
+def _lpd_outputs(mu, per_output):
+    S, C, B = mu.shape
+    lpd = torch.empty(B, dtype=torch.float32, device=mu.device)
+    return lpd, (torch.empty(C, B, dtype=torch.float32, device=mu.device) if per_output else None)
+
+
+def softmax_lpd(mu, var, eps, y):
+    """lpd (B,) = logsumexp_{s,f} log_softmax_c(mu + sqrt(var) eps)[y_b] - log(S F): the log of the mean probability of the
+    label over the S F samples.  mu, var (S, C, B), eps (S, F, C, B), y int64 (B,) (not checked)."""
+    mu, var = _lpd_moments(mu, var, eps, y)
+    eps, y = eps.detach().contiguous(), y.detach().contiguous()
+    assert y.dtype == torch.int64 and eps.dtype == torch.float32
+    S, F, C, B = eps.shape
+    assert mu.shape == (S, C, B) and y.shape == (B,), (mu.shape, eps.shape, y.shape)
+    lpd, _ = _lpd_outputs(mu, False)
+    check(lib().vargp_softmax_lpd(ptr(mu), ptr(var), ptr(eps), ptr(y), ptr(lpd), S, F, C, B, stream_ptr()), 'vargp_softmax_lpd')
+    return lpd
+
+
+def _lpd_result(lpd, lpd_out, per_output):
+    return (lpd, lpd_out) if per_output else lpd
+
+
+def gauss_lpd(mu, var, y, obs_log_var, per_output=False):
+    """lpd (B,) = logsumexp_s sum_c log N(y | mu, var + exp(obs_log_var[c])) - log S, the joint density of a point's targets under
+    the mixture over hyper-samples; per_output: also lpd_out (C, B) = logsumexp_s log N(...) - log S.  y as gauss_target takes it."""
+    mu, var = _lpd_moments(mu, var, y, obs_log_var)
+    S, C, B = mu.shape
+    olv = obs_log_var.detach().to(torch.float32).contiguous()
+    assert olv.shape == (C,), (mu.shape, olv.shape)
+    yt, ldy = gauss_target(y, C, B)
+    lpd, out = _lpd_outputs(mu, per_output)
+    check(lib().vargp_gauss_lpd(ptr(mu), ptr(var), ptr(yt), ldy, ptr(olv), ptr(lpd), ptr(out), S, C, B, stream_ptr()),
+          'vargp_gauss_lpd')
+    return _lpd_result(lpd, out, per_output)
+
+
+def bernoulli_lpd(mu, var, y, link='probit', per_output=False):
+    """lpd (B,) = logsumexp_s sum_c lp[s, c, b] - log S with lp = log Phi(s mu / sqrt(1 + var)) (probit, closed form; -inf below
+    z ~ -37, where fp64 erfc underflows) or the 20-node rule on the logistic function (logit); y as bernoulli_target takes it."""
+    mu, var = _lpd_moments(mu, var, y)
+    S, C, B = mu.shape
+    t, ldt, labels = bernoulli_target(y, C, B)
+    lpd, out = _lpd_outputs(mu, per_output)
+    check(lib().vargp_bernoulli_lpd(ptr(mu), ptr(var), ptr(t), ldt, ptr(labels), bernoulli_link(link), ptr(lpd), ptr(out), S, C, B,
+                                    stream_ptr()), 'vargp_bernoulli_lpd')
+    return _lpd_result(lpd, out, per_output)
+
+
+def poisson_lpd(mu, var, y, per_output=False):
+    """lpd (B,) = logsumexp_s sum_c lp[s, c, b] - log S, lp = logsumexp_k(log w_k + y f_k - exp(f_k) - lgamma(y + 1)) on the 20-node
+    rule; y as reg_target takes it."""
+    mu, var = _lpd_moments(mu, var, y)
+    S, C, B = mu.shape
+    yt, ldy = reg_target(y, C, B)
+    lpd, out = _lpd_outputs(mu, per_output)
+    check(lib().vargp_poisson_lpd(ptr(mu), ptr(var), ptr(yt), ldy, ptr(lpd), ptr(out), S, C, B, stream_ptr()), 'vargp_poisson_lpd')
+    return _lpd_result(lpd, out, per_output)
+
+
+def studentt_lpd(mu, var, y, log_scale, df=4.0, per_output=False):
+    """lpd (B,) = logsumexp_s sum_c lp[s, c, b] - log S, lp = logsumexp_k(log w_k + K_c - (df + 1) / 2 log1p((y - f_k)^2 /
+    (df sigma_c^2))) on the 20-node rule; y as reg_target takes it, log_scale (C,)."""
+    mu, var = _lpd_moments(mu, var, y, log_scale)
+    S, C, B = mu.shape
+    ls = log_scale.detach().to(torch.float32).contiguous()
+    assert ls.shape == (C,), (mu.shape, ls.shape)
+    yt, ldy = reg_target(y, C, B)
+    lpd, out = _lpd_outputs(mu, per_output)
+    df = float(df)
+    check(lib().vargp_studentt_lpd(ptr(mu), ptr(var), ptr(yt), ldy, ptr(ls), df, studentt_lognorm(df), ptr(lpd), ptr(out), S, C, B,
+                                   stream_ptr()), 'vargp_studentt_lpd')
+    return _lpd_result(lpd, out, per_output)
+
 # ------------------------------------------------------------------------------------------------
 # variational hyper-parameters
 # ------------------------------------------------------------------------------------------------

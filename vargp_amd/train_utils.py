@@ -93,6 +93,29 @@ def compute_acc_ent(dataset, gp, batch_size=512, device=None, shared_hypers=Fals
     return int(hits) / len(dataset), float(ent) / len(dataset)
 
 
+def compute_lpd(dataset, gp, batch_size=512, device=None, shared_hypers=False):
+    """Mean held-out log predictive density per point, gp.log_prob(x, y).mean() over `dataset` (not in the reference): the
+    likelihood-aware counterpart of compute_accuracy for every likelihood.  dataset[i] -> (x, y) with y a label / one target or a
+    (C,) target vector (passed on as (C, B), the layout of loss()).  Accumulated on the device: ONE host sync per data set;
+    asserts on NaN.  shared_hypers: ONE log_prob(x, y, tile=batch_size) call -- one hyper-parameter draw and one factorisation
+    for the sweep instead of one per batch."""
+    as_targets = lambda y: y.to(device).t().contiguous() if y.dim() == 2 else y.to(device)
+    loader = DataLoader(dataset, batch_size=batch_size)
+    with torch.no_grad():
+        if shared_hypers:
+            xs, ys = zip(*[(x, y) for x, y in loader])
+            parts = [gp.log_prob(torch.cat(xs).to(device), as_targets(torch.cat(ys)), tile=batch_size)]
+        else:
+            parts = (gp.log_prob(x.to(device), as_targets(y)) for x, y in loader)
+        total, bad = None, None
+        for lpd in parts:
+            t, b = lpd.double().sum(), torch.isnan(lpd).any()
+            total, bad = (t, b) if total is None else (total + t, bad | b)
+        total, bad = torch.stack([total, bad.double()]).tolist()                      # the one host sync
+    assert not bad, 'Found NaNs'
+    return total / len(dataset)
+
+
 def compute_bwt(acc_mat):
     assert acc_mat.ndim == 2 and acc_mat.shape[0] == acc_mat.shape[1]
     return (acc_mat[-1][:-1] - acc_mat.diagonal()[:-1]).mean()

@@ -429,6 +429,16 @@ class VARGP(nn.Module):
         if tile is None or x.size(0) <= tile:
             pred_mu, pred_var = self(x)
             return self.likelihood.predict(pred_mu, pred_var)
+        out = []
+        for _, mu, var in self._moment_sweep(x, tile):
+            p = self.likelihood.predict(mu, var)
+            out.append(p.clone() if p is mu else p)          # (the Gaussian mean may be a view the next tile overwrites)
+        return torch.cat(out, dim=cat_dim)
+
+    def _moment_sweep(self, x, tile):
+        """The tiled sweep of predict / log_prob: yields (i, mu, var), the predictive moments (S, C, <= tile) of x[i:i + tile], for
+        i = 0, tile, ...; every tile shares ONE hyper-sample and ONE set of x-independent factors.  The moments of a tile may be
+        views that the next tile overwrites: consume (or clone) them before asking for the next."""
         if self.prev_params and not torch.is_grad_enabled() and self._tn_applicable() and self.z.size(-1) > 32:
             # the block program, forward only: K(z_<=t), its factorisation and the small products ONCE (vargp_elbo_tn_begin),
             # then K_uf, P, V2, W and the moments per tile.  (First-task models keep the per-op sweep below: with the factor of
@@ -438,12 +448,10 @@ class VARGP(nn.Module):
             eps_theta = None if kern.map_est else noise.draw('eps_theta', (self.n_v, kern.log_mean.shape[0]), x.device)
             prog = self._tn_eval_program(int(tile))
             prog.sweep_begin(*self._operands(), *self._tn_operands(), None if eps_theta is None else eps_theta.contiguous())
-            out = []
             for i in range(0, x.size(0), tile):
                 mu, var = prog.sweep_moments(x[i:i + tile].contiguous())
-                p = self.likelihood.predict(mu, var)
-                out.append(p.clone() if p is mu else p)      # (the Gaussian mean is a view the next tile overwrites)
-            return torch.cat(out, dim=cat_dim)
+                yield i, mu, var
+            return
         theta = self.kernel.sample_hypers(self.n_v)
         if self.prev_params:
             _, _, mu_leq_t, S_leq_t, z_leq_t = self.compute_q(theta)
@@ -452,12 +460,25 @@ class VARGP(nn.Module):
             S_leq_t = rev_cholesky(vec2tril(self.u_tril_vec, self.M))
         prep = gp_utils.marginal_prepare(mu_leq_t, S_leq_t, self.kernel.compute(theta, z_leq_t))
         Kxx_diag = self.kernel.compute_diag(theta)
-        out = []
         for i in range(0, x.size(0), tile):
-            xt = x[i:i + tile]
-            mu, var, _ = gp_utils.marginal_apply(prep, self.kernel.compute(theta, z_leq_t, xt), Kxx_diag)
-            out.append(self.likelihood.predict(mu, var))
-        return torch.cat(out, dim=cat_dim)
+            mu, var, _ = gp_utils.marginal_apply(prep, self.kernel.compute(theta, z_leq_t, x[i:i + tile]), Kxx_diag)
+            yield i, mu, var
+
+    def log_prob(self, x, y, tile=None, per_output=False):
+        """Held-out log predictive density of the targets y at x (N, D), per point: lpd (N,) = log of the mean over hyper-samples
+        of the marginal likelihood of the point's whole target vector (likelihoods.py: log_prob; csrc/lpd.hip) -- log E_q[p(y)],
+        not the ELBO's E_q[log p].  per_output=True: (lpd (N,), lpd_out (C, N)) with each output's own marginal (ValueError for
+        the softmax, which has none).  y as loss() takes it: (N,) labels / shared targets, or (C, N) per-output targets.
+        Evaluated under torch.no_grad() from the moment routes of predict: one self(x) call, or with `tile` and N > tile the
+        same sweep as predict(tile=) (one hyper-sample draw and one factorisation for all tiles), targets sliced per tile."""
+        with torch.no_grad():
+            if tile is None or x.size(0) <= tile:
+                return self.likelihood.log_prob(*self(x), y, per_output=per_output)
+            out = [self.likelihood.log_prob(mu, var, y[..., i:i + tile], per_output=per_output)
+                   for i, mu, var in self._moment_sweep(x, tile)]
+            if per_output:
+                return torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out], dim=-1)
+            return torch.cat(out)
 
     @staticmethod
     def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None,

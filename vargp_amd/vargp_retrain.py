@@ -173,6 +173,17 @@ class VARGPRetrain(nn.Module):
         pred_mu, pred_var = self(x)
         return self.likelihood.predict(pred_mu, pred_var)
 
+    def log_prob(self, x, y, tile=None, per_output=False):
+        """Held-out log predictive density per point, (N,), or ((N,), (C, N)) with per_output=True: the signature and meaning
+        of VARGP.log_prob.  `tile`: chunks of `tile` points, every chunk with its own hyper-parameter sample, as predict."""
+        with torch.no_grad():
+            if tile is not None and x.size(0) > tile:
+                out = [self.log_prob(x[i:i + tile], y[..., i:i + tile], per_output=per_output) for i in range(0, x.size(0), tile)]
+                if per_output:
+                    return torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out], dim=-1)
+                return torch.cat(out)
+            return self.likelihood.log_prob(*self(x), y, per_output=per_output)
+
     @staticmethod
     def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None, likelihood='softmax', link='probit'):
         """Factory (vargp_retrain.py:239-267): inducing points at random data points per class, hyper-prior = the last
