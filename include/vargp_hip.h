@@ -152,6 +152,22 @@ int vargp_predictive_diag_bwd(const float* P, const float* W, const float* a, in
                               int nbatch, int M, int B, vargp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Full predictive covariance of one block of B test points (the reference has the formula only in gp_cond; nothing there
+ * forms the marginal's off-diagonal).  With P and W [S*C, Mt, B] exactly as for vargp_predictive_diag_fwd, theta [S, D+1] and
+ * X [B, D] the block itself, shared by all classes:
+ *   Sigma[s, c] = K_theta_s(X, X) - P[s,c]^T P[s,c] + W[s,c]^T W[s,c]        Sigma [S*C, B, B], dense, fp32
+ * in ONE pass over the output (a tile stays in the MFMA accumulators from the distance product through the kernel epilogue
+ * and the product over the stacked 2 Mt rows to its only store).  nu2: 0 = RBF, 1 | 3 | 5 = Matern, nu = nu2 / 2 (the coding
+ * of vargp_elbo_tn_desc.kernel_nu2; anything else is an error).  K follows the gram entries with Y = NULL: exactly gamma^2 on
+ * the diagonal, the direct distance form for D <= 32, the inner-product form above (d2 clamped at 0 for the Matern kernels
+ * only).  Only the lower triangle is computed and every entry is written to both halves: Sigma is bitwise symmetric, and
+ * its diagonal is vargp_predictive_diag_fwd's var up to the order of summation.  Any Mt, B, D >= 1; S*C <= 65535.
+ */
+size_t vargp_predictive_cov_workspace_bytes(int S, int B, int D);
+int vargp_predictive_cov(const float* theta, const float* X, const float* P, const float* W, float* Sigma, int S, int C,
+                         int Mt, int B, int D, int nu2, void* ws, size_t ws_bytes, vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * KL(N(mu_q, Lq Lq^T) || N(mu_p, Lp Lp^T)) from its triangular ingredients (reference:
  * torch.distributions kl_divergence(MVN, MVN) as called from var_gp/vargp.py:182-190):
  *   kl = logdet_p - logdet_q + 0.5 * (|G|_F^2 + |d|^2 - M),  G = Lp^-1 Lq [nb, M, M],

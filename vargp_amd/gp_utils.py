@@ -127,6 +127,17 @@ def marginal_apply(prep, Kzx, Kxx_diag):
     return mu, var, P
 
 
+def marginal_apply_full(prep, Kzx):
+    """The operands of the full predictive covariance for one block of columns Kzx (.., M, B), given marginal_prepare()'s
+    factors: mu (.., B) = P^T Lz^-1 m, P = Lz^-1 Kzx and W = G^T P (both (.., M, B)) -- what marginal_apply reduces to the
+    diagonal, kept whole for ops.predictive_cov (Sigma = Kxx - P^T P + W^T W)."""
+    Tz, a, G = prep['Tz'], prep['Lz_m'], prep['G']
+    P = ops.matmul(Tz, Kzx, triA=LOWER)
+    W = ops.matmul(G.mT, P, triA=UPPER)
+    mu = ops.matmul(P.mT, a).squeeze(-1)
+    return mu, P, W
+
+
 def linear_marginal_diag(m, S, Kzz, Kzx, Kxx_diag, cache=None):
     """Diagonal of the marginal of N(z; m, S) N(y; A z, V): mu = A m,
     var = Kxx_diag - diag(Kxz Kzz^-1 Kzx) + diag(A (S + eps I) A^T)   (gp_utils.py:150-191).

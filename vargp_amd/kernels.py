@@ -47,6 +47,11 @@ class RBFKernel(nn.Module):
         K = gram(kern_samples, X, Y, shared)
         return K.reshape(kern_samples.shape[0], *batch, M, K.shape[-1])
 
+    def compute_cov(self, kern_samples, x, P, W):
+        """Full predictive covariance of the block x (B, D): K(x, x) - P^T P + W^T W, (S, C, B, B), in one fused pass
+        (ops.predictive_cov; P, W (S, C, Mt, B) from gp_utils.marginal_apply_full).  No autograd."""
+        return ops.predictive_cov(kern_samples, x, P, W, nu2=0)
+
     def compute_diag(self, kern_samples):
         """gamma^2 as (S, 1, 1)  (kernels.py:58-60)."""
         return (2.0 * kern_samples[..., -1:]).exp().unsqueeze(-2)
@@ -83,6 +88,10 @@ class MaternKernel(RBFKernel):
     def compute(self, kern_samples, x, y=None):
         nu = self.nu
         return self._compute(lambda th, X, Y, shared: ops.matern_gram(th, X, Y, shared, nu), kern_samples, x, y)
+
+    def compute_cov(self, kern_samples, x, P, W):
+        # (one op for native=False and native=True alike)
+        return ops.predictive_cov(kern_samples, x, P, W, nu2=int(round(2 * self.nu)))
 
 
 def native_code(kernel):
@@ -124,3 +133,6 @@ class DeepRBFKernel(RBFKernel):
                 y = y[(0,) * (y.dim() - 2)]           # an expand() of one (N, D) block: map it once
             y = self.features(y)
         return super().compute(kern_samples, x, y=y)
+
+    def compute_cov(self, kern_samples, x, P, W):
+        return super().compute_cov(kern_samples, self.features(x), P, W)

@@ -512,6 +512,24 @@ def predictive_diag(P, W, a, kdiag):
     return _PredictiveDiag.apply(P, W, a, kdiag)
 
 
+def predictive_cov(theta, X, P, W, nu2=0):
+    """Full predictive covariance of one block of points (csrc/pred_cov.hip), no autograd:
+    theta (S, D+1); X (B, D), shared by the classes; P, W (S, C, Mt, B) as for predictive_diag; nu2 0 (RBF) | 1 | 3 | 5
+    (Matern, nu = nu2 / 2)  ->  Sigma (S, C, B, B) = K_theta(X, X) - P^T P + W^T W, bitwise symmetric, 4 S C B^2 bytes."""
+    require_device(theta, X, P, W)
+    theta, X, P, W = theta.detach().contiguous(), X.detach().contiguous(), P.detach().contiguous(), W.detach().contiguous()
+    S, D = theta.shape[0], theta.shape[1] - 1
+    B = X.shape[0]
+    assert X.dim() == 2 and X.shape[1] == D, (X.shape, theta.shape)
+    assert P.dim() == 4 and P.shape == W.shape and P.shape[0] == S and P.shape[-1] == B, (P.shape, W.shape, S, B)
+    C, Mt = P.shape[1], P.shape[2]
+    out = torch.empty(S, C, B, B, dtype=torch.float32, device=X.device)
+    ws = scratch(lib().vargp_predictive_cov_workspace_bytes(S, B, D), X.device)
+    check(lib().vargp_predictive_cov(ptr(theta), ptr(X), ptr(P), ptr(W), ptr(out), S, C, Mt, B, D, int(nu2), ptr(ws),
+                                     ws.numel() * 4, stream_ptr()), 'vargp_predictive_cov')
+    return out
+
+
 class _LogdetTril(Function):
     @staticmethod
     def forward(ctx, L):

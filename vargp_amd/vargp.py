@@ -480,6 +480,43 @@ class VARGP(nn.Module):
                 return torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out], dim=-1)
             return torch.cat(out)
 
+    def predict_f(self, x, full_cov=False):
+        """The posterior over the latent functions at x (B, D), under torch.no_grad().  full_cov=False: what self(x) returns,
+        (mu, var), both (S, C, B).  full_cov=True: (mu (S, C, B), cov (S, C, B, B)), the joint covariance of the B function
+        values per hyper-sample and output: cov = K(x, x) - P^T P + W^T W with P = Lz^-1 Kzx, W = (Lz^-1 chol(S + eps I))^T P
+        (csrc/pred_cov.hip), the convention of the variance route -- its diagonal is the pred_var of forward() for the same
+        hyper-sample.  Every model (previous tasks or none, ep_var_mean on or off, any kernel, any likelihood) runs the
+        composed route here: sample_hypers, compute_q, marginal_prepare, K(z, x), P, W, then the fused covariance op.
+        Memory: cov takes 4 S C B^2 bytes (S C = 30, B = 4096: 2 GB).  A large x has to be handled in blocks by the caller;
+        nothing here forms the cross-covariance between two blocks."""
+        with torch.no_grad():
+            if not full_cov:
+                return self(x)
+            theta = self.kernel.sample_hypers(self.n_v)
+            if self.prev_params:
+                _, _, mu_leq_t, S_leq_t, z_leq_t = self.compute_q(theta)
+            else:
+                mu_leq_t, z_leq_t = self.u_mean, self.z
+                S_leq_t = rev_cholesky(vec2tril(self.u_tril_vec, self.M))
+            prep = gp_utils.marginal_prepare(mu_leq_t, S_leq_t, self.kernel.compute(theta, z_leq_t))
+            mu, P, W = gp_utils.marginal_apply_full(prep, self.kernel.compute(theta, z_leq_t, x))
+            return mu, self.kernel.compute_cov(theta, x, P, W)
+
+    def sample_f(self, x, n_samples=1):
+        """Joint draws of the latent functions at x (B, D): (n_samples, S, C, B), f = mu + chol(cov + JITTER I) eps with
+        (mu, cov) = predict_f(x, full_cov=True) and eps = noise.draw('eps_fs', (n_samples, S, C, B)) (noise.inject can supply
+        it); n_samples draws per hyper-sample.  The factorisation is ops.chol: a cov that is not positive definite after the
+        jitter is reported by the Cholesky error mode in force (ops.set_cholesky_error_mode).  Memory: cov and its factor,
+        2 x 4 S C B^2 bytes.  A large x must be sampled in blocks by the caller, each under the same injected eps_theta; the
+        blocks are then independent given the hyper-sample (no cross-covariance between blocks is formed)."""
+        with torch.no_grad():
+            mu, cov = self.predict_f(x, full_cov=True)
+            S, C, B = mu.shape
+            L = ops.chol(cov)
+            eps = noise.draw('eps_fs', (int(n_samples), S, C, B), x.device)
+            f = ops.bgemm(L, eps.permute(1, 2, 3, 0), D=mu.unsqueeze(-1), beta=1.0, triA=LOWER)       # (S, C, B, n)
+            return f.permute(3, 0, 1, 2).contiguous()
+
     @staticmethod
     def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None,
                    ep_var_mean=True, map_est_hypers=False, dkl=False, kernel='rbf', native_kernel=False,
