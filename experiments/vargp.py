@@ -52,17 +52,19 @@ def train(task_id, train_set, val_set, test_set, ep_var_mean=True, map_est_hyper
           epochs=1, M=20, n_f=10, n_var_samples=3, batch_size=512, lr=1e-2, beta=1.0,
           eval_interval=10, patience=20, prev_params=None, logger=None, device=None, graph=False, seed=None,
           retrain=False, eval_shared_hypers=False, dataloader=False, kernel='rbf', native_kernel=False,
-          likelihood='softmax', link='probit', lpd=False):
+          likelihood='softmax', link='probit', lpd=False, z_init='random', kmeans_iters=20, lengthscale_init='default'):
     if retrain:      # the variant of experiments/vargp_retrain.py:14-19 (earlier tasks' inducing parameters re-optimised)
         from vargp_amd.vargp_retrain import VARGPRetrain
         assert kernel == 'rbf', '--retrain builds its model with the RBF kernel'
+        assert z_init == 'random' and lengthscale_init == 'default', "--retrain builds its model with the reference's initialisation"
         gp = VARGPRetrain.create_clf(train_set, M=M, n_f=n_f, n_var_samples=n_var_samples, prev_params=prev_params,
                                      likelihood=likelihood, link=link).to(device)
         graph = False
     else:
         gp = VARGP.create_clf(train_set, M=M, n_f=n_f, n_var_samples=n_var_samples, prev_params=prev_params,
                               ep_var_mean=ep_var_mean, map_est_hypers=map_est_hypers, dkl=dkl, kernel=kernel,
-                              native_kernel=native_kernel, likelihood=likelihood, link=link).to(device)
+                              native_kernel=native_kernel, likelihood=likelihood, link=link, z_init=z_init,
+                              kmeans_iters=kmeans_iters, lengthscale_init=lengthscale_init).to(device)
     stopper = EarlyStopper(patience=patience)
     N = len(train_set)
     # the program's counter-based noise generator is keyed by the run's seed (the reference draws from the torch global
@@ -195,7 +197,7 @@ def toy(args):
                    link=args.link, prev_params=prev_params, logger=logger, device=device, patience=-1,
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed, retrain=args.retrain,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
-                   lpd=args.lpd)
+                   lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init)
         prev_params.append(sd)
     logger.close()
 
@@ -222,7 +224,7 @@ def split_mnist(args):
                    link=args.link, prev_params=prev_params, logger=logger, device=device,
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
-                   lpd=args.lpd)
+                   lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init)
         prev_params.append(sd)
     logger.close()
 
@@ -252,7 +254,7 @@ def permuted_mnist(args):
                    link=args.link, prev_params=prev_params, logger=logger,
                    device=device, eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
-                   lpd=args.lpd)
+                   lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init)
         prev_params.append(sd)
     logger.close()
 
@@ -286,6 +288,13 @@ def parse_args(argv=None):
                              'Bernoulli outputs (deterministic 20-node Gauss-Hermite rule; not stored in checkpoints)')
         sp.add_argument('--link', choices=('probit', 'logit'), default='probit',
                         help='link function of --likelihood bernoulli')
+        sp.add_argument('--z_init', choices=('random', 'kmeans'), default='random',
+                        help="inducing points of a new task: M random data points per output (the reference's), or the "
+                             'k-means centres of the task found from them on the device')
+        sp.add_argument('--kmeans_iters', type=int, default=20, help='Lloyd iterations of --z_init kmeans (at most)')
+        sp.add_argument('--lengthscale_init', choices=('default', 'median'), default='default',
+                        help="lengthscales of the first task: 0.5 (the reference's), or the median distance between pairs of "
+                             'its points (not with --dkl)')
         sp.add_argument('--seed', type=int, default=None)
         sp.add_argument('--eval_interval', type=int, default=10)
         sp.add_argument('--log_dir', default=os.path.join('runs', f'{name}-{int(time.time())}'))

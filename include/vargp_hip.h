@@ -168,6 +168,26 @@ int vargp_predictive_cov(const float* theta, const float* X, const float* P, con
                          int Mt, int B, int D, int nu2, void* ws, size_t ws_bytes, vargp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Lloyd's two steps for G independent sets of K centres Z [G, K, D] over one data matrix X [N, D] (the model's z [C, M, D]: one
+ * set per output).  Data-dependent initialisation of the inducing points; nothing of this is in the reference, whose inducing
+ * points start at random data points (var_gp/vargp.py:207).
+ *   assign: label[g, n] = argmin_k |x_n - z_gk|^2 in plain squared Euclidean distance, the smallest index on a tie, and
+ *           dist2[g, n] = that distance, clamped at 0.  The N x K distances stay in registers (f32 MFMA inner products for
+ *           D > 32, compared as |z|^2 - 2 x.z; the direct sum of squared differences for D <= 32, exactly 0 for coincident
+ *           points); only the two [G, N] vectors are stored.
+ *   update: Z[g, k] = mean of the points with label[g, n] == k (fp64 sums in ascending point order), count[g, k] = their number;
+ *           a centre without points keeps its value bit for bit.  Labels outside [0, K) are ignored.
+ * Both are deterministic (no atomics): two calls on the same input are bitwise equal.  The workspace holds the squared norms
+ * of the rows of X and Z only (4 (N + G K) bytes and padding for D > 32): it never grows with N K.  Any G, K, N, D >= 1;
+ * G <= 65535 (update: K <= 65535 too).
+ */
+size_t vargp_kmeans_workspace_bytes(int G, int K, int N, int D);
+int vargp_kmeans_assign(const float* X, const float* Z, int32_t* label, float* dist2, int G, int K, int N, int D, void* ws,
+                        size_t ws_bytes, vargp_stream_t stream);
+int vargp_kmeans_update(const float* X, const int32_t* label, float* Z, int32_t* count, int G, int K, int N, int D, void* ws,
+                        size_t ws_bytes, vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * KL(N(mu_q, Lq Lq^T) || N(mu_p, Lp Lp^T)) from its triangular ingredients (reference:
  * torch.distributions kl_divergence(MVN, MVN) as called from var_gp/vargp.py:182-190):
  *   kl = logdet_p - logdet_q + 0.5 * (|G|_F^2 + |d|^2 - M),  G = Lp^-1 Lq [nb, M, M],

@@ -24,6 +24,16 @@ class RBFKernel(nn.Module):
         self.register_buffer('prior_log_logvar', torch.zeros(in_size + 1) if prior_log_logvar is None
                              else prior_log_logvar.detach().clone())
 
+    def set_lengthscale_(self, ell):
+        """Start every lengthscale at ell > 0 (not in the reference: init.median_lengthscale supplies a data-dependent one):
+        log_mean[:D] = log(ell) in place; the log gamma entry and log_logvar stay as they are.  For DeepRBFKernel these are
+        the lengthscales of the feature space."""
+        if not ell > 0:
+            raise ValueError(f'set_lengthscale_: the lengthscale must be positive, got {ell!r}')
+        with torch.no_grad():
+            self.log_mean[:-1] = math.log(ell)
+        return self
+
     def compute(self, kern_samples, x, y=None):
         """kern_samples (S, D+1); x (...batch, M, D); y (...batch, N, D) or None (= x).
         Returns (S, ...batch, M, N)  (kernels.py:24-56).  A `y` that is an expand() of one (N, D)

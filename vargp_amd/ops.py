@@ -530,6 +530,42 @@ def predictive_cov(theta, X, P, W, nu2=0):
     return out
 
 
+# Lloyd's two steps for G sets of K centres over one data matrix (csrc/kmeans.hip -- not in the reference).  No autograd.
+
+def _kmeans_args(X, Z):
+    assert X.dim() == 2 and Z.dim() == 3 and Z.shape[-1] == X.shape[1], (X.shape, Z.shape)
+    assert X.dtype == torch.float32 and Z.dtype == torch.float32, (X.dtype, Z.dtype)
+    (N, D), (G, K) = X.shape, Z.shape[:2]
+    return G, K, N, D, scratch(lib().vargp_kmeans_workspace_bytes(G, K, N, D), X.device)
+
+
+def kmeans_assign(X, Z):
+    """X (N, D), Z (G, K, D) -> label int32 (G, N): the nearest centre of set g in squared Euclidean distance (the smallest index
+    on a tie), and dist2 (G, N): that distance, >= 0.  The N x K distances are never stored."""
+    require_device(X, Z)
+    X, Z = X.detach().contiguous(), Z.detach().contiguous()
+    G, K, N, D, ws = _kmeans_args(X, Z)
+    label = torch.empty(G, N, dtype=torch.int32, device=X.device)
+    dist2 = torch.empty(G, N, dtype=torch.float32, device=X.device)
+    check(lib().vargp_kmeans_assign(ptr(X), ptr(Z), ptr(label), ptr(dist2), G, K, N, D, ptr(ws), ws.numel() * 4, stream_ptr()),
+          'vargp_kmeans_assign')
+    return label, dist2
+
+
+def kmeans_update(X, label, Z):
+    """X (N, D), label int32 (G, N), Z (G, K, D) -> Z_new (G, K, D): the mean of the points of each label (a centre without points
+    keeps its row of Z bit for bit), and count int32 (G, K).  Z itself is not modified.  Bitwise reproducible."""
+    require_device(X, label, Z)
+    X, label = X.detach().contiguous(), label.detach().contiguous()
+    Z_new = Z.detach().clone(memory_format=torch.contiguous_format)
+    G, K, N, D, ws = _kmeans_args(X, Z_new)
+    assert label.dtype == torch.int32 and label.shape == (G, N), (label.dtype, label.shape, G, N)
+    count = torch.empty(G, K, dtype=torch.int32, device=X.device)
+    check(lib().vargp_kmeans_update(ptr(X), ptr(label), ptr(Z_new), ptr(count), G, K, N, D, ptr(ws), ws.numel() * 4, stream_ptr()),
+          'vargp_kmeans_update')
+    return Z_new, count
+
+
 class _LogdetTril(Function):
     @staticmethod
     def forward(ctx, L):

@@ -19,7 +19,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import fused, gp_utils, noise, ops
+from . import fused, gp_utils, init, noise, ops
 from .gp_utils import vec2tril, mat2trilvec, cholesky, rev_cholesky, gp_cond, block_joint, linear_marginal_diag
 from .kernels import RBFKernel, DeepRBFKernel, MaternKernel, native_code
 from .likelihoods import (BernoulliLikelihood, GaussianLikelihood, MulticlassSoftmax, PoissonLikelihood, StudentTLikelihood,
@@ -60,6 +60,37 @@ def _hand_over_hyper_prior(prev_params):
         for k in [k for k in p if k.startswith('kernel')]:
             p.pop(k)
     return prior
+
+
+_Z_INITS = ('kmeans', 'random')                    # create_clf / create_reg (z_init=)
+_LENGTHSCALE_INITS = ('default', 'median')        # (lengthscale_init=)
+
+
+def _check_init_names(who, z_init, lengthscale_init):
+    if z_init not in _Z_INITS:
+        raise ValueError(f'{who}: z_init must be one of {sorted(_Z_INITS)}, got {z_init!r}')
+    if lengthscale_init not in _LENGTHSCALE_INITS:
+        raise ValueError(f'{who}: lengthscale_init must be one of {sorted(_LENGTHSCALE_INITS)}, got {lengthscale_init!r}')
+
+
+def _init_inducing(dataset, out_size, M, z_init, kmeans_iters):
+    """z (out_size, M, D) of a new model.  'random': M random data points per output (vargp.py:207).  'kmeans' (not in the
+    reference): Lloyd's algorithm from those very points over the task's data, on the current CUDA device (init.kmeans_inducing);
+    the result comes back to the device and dtype the random route would have produced."""
+    N = len(dataset)
+    if z_init == 'random':
+        return torch.stack([dataset[torch.randperm(N)[:M]][0] for _ in range(out_size)])
+    x = dataset[torch.arange(N)][0]
+    xd = x.to(device=torch.device('cuda', torch.cuda.current_device()), dtype=torch.float32)
+    return init.kmeans_inducing(xd, out_size, M, n_iter=kmeans_iters).to(device=x.device, dtype=x.dtype)
+
+
+def _init_lengthscale(kern, dataset, lengthscale_init, first_task):
+    """'median' (not in the reference): the first task's lengthscales start at the median pair distance of its data
+    (init.median_lengthscale); a later task starts from the handed-over hyper-posterior whatever is asked."""
+    if lengthscale_init == 'median' and first_task:
+        kern.set_lengthscale_(init.median_lengthscale(dataset[torch.arange(len(dataset))][0]))
+    return kern
 
 
 class VARGP(nn.Module):
@@ -520,15 +551,22 @@ class VARGP(nn.Module):
     @staticmethod
     def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None,
                    ep_var_mean=True, map_est_hypers=False, dkl=False, kernel='rbf', native_kernel=False,
-                   likelihood='softmax', link='probit'):
+                   likelihood='softmax', link='probit', z_init='random', kmeans_iters=20, lengthscale_init='default'):
         """Factory used by the experiment driver (vargp.py:200-243): inducing points at random data
         points per class, hyper-prior = previous task's hyper-posterior (popped from prev_params[-1],
         which is mutated like the reference does).  kernel: 'rbf' (the reference's), or 'matern12' / 'matern32' /
         'matern52' (MaternKernel; not with dkl).  native_kernel=True: the Matern model runs the native block program
         (MaternKernel(native=True)); an error with 'rbf' or dkl, which have no such choice.  likelihood: 'softmax' (the
         reference's MulticlassSoftmax(n_f)) or 'bernoulli' (BernoulliLikelihood(link), the integer labels read as one-vs-rest
-        targets; n_f is then unused), with any kernel choice.  None of these is part of a checkpoint: give them again on reload."""
+        targets; n_f is then unused), with any kernel choice.  None of these is part of a checkpoint: give them again on reload.
+        z_init: 'random' (the reference's) or 'kmeans' (k-means centres of the task's data from those random points, at most
+        kmeans_iters Lloyd iterations on the current CUDA device).  lengthscale_init: 'default' (0.5, the reference's) or 'median'
+        (the median pair distance of the task's data, first task only; not with dkl, whose features are untrained)."""
         lik = make_clf_likelihood(likelihood, n_f, link)
+        _check_init_names('create_clf', z_init, lengthscale_init)
+        if dkl and lengthscale_init == 'median':
+            raise ValueError("create_clf: lengthscale_init='median' measures distances between inputs; with dkl=True the kernel "
+                             'acts on the features of an untrained network')
         if kernel not in _KERNEL_NU:
             raise ValueError(f'create_clf: kernel must be one of {sorted(_KERNEL_NU)}, got {kernel!r}')
         if dkl and kernel != 'rbf':
@@ -536,10 +574,10 @@ class VARGP(nn.Module):
         if native_kernel and (dkl or kernel == 'rbf'):
             raise ValueError('create_clf: native_kernel=True selects the native route of a Matern kernel (kernel="matern12" / '
                              '"matern32" / "matern52", dkl=False); the RBF kernel is always native, DeepRBFKernel never')
-        N = len(dataset)
         out_size = torch.unique(dataset.targets).size(0)
-        z = torch.stack([dataset[torch.randperm(N)[:M]][0] for _ in range(out_size)])
+        z = _init_inducing(dataset, out_size, M, z_init, kmeans_iters)
 
+        first_task = not prev_params
         prior_log_mean, prior_log_logvar, phi_params = None, None, None
         if prev_params:
             prior_log_mean = prev_params[-1].get('kernel.log_mean')
@@ -560,17 +598,20 @@ class VARGP(nn.Module):
         else:
             kern = RBFKernel(z.size(-1), prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
                              map_est=map_est_hypers)
+        _init_lengthscale(kern, dataset, lengthscale_init, first_task)
         return VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean,
                      prev_params=prev_params)
 
     @staticmethod
     def create_reg(dataset, M=20, n_var_samples=3, likelihood='gaussian', df=4.0, prev_params=None, ep_var_mean=True,
-                   map_est_hypers=False, kernel='rbf', native_kernel=False):
+                   map_est_hypers=False, kernel='rbf', native_kernel=False, z_init='random', kmeans_iters=20,
+                   lengthscale_init='default'):
         """Regression / count factory, the counterpart of create_clf (not in the reference): dataset[i] -> (x, y), dataset.targets
         (N,) (one output) or (N, C); inducing points at M random data points per output; hyper-prior = the previous task's
         hyper-posterior (popped from prev_params[-1], which is mutated as in create_clf).  likelihood: 'gaussian'
         (GaussianLikelihood), 'studentt' (StudentTLikelihood(df=df): robust to outliers) or 'poisson' (PoissonLikelihood:
-        non-negative counts, log link; df is unused by the other two).  kernel / native_kernel: as create_clf, without dkl.
+        non-negative counts, log link; df is unused by the other two).  kernel / native_kernel / z_init / kmeans_iters /
+        lengthscale_init: as create_clf, without dkl.
         None of likelihood, df, kernel and native_kernel is part of a checkpoint: give them again on reload.  A minibatch's
         targets go to loss() as (C, B) -- y.t() of a (B, C) batch -- or (B,)."""
         if kernel not in _KERNEL_NU:
@@ -578,13 +619,14 @@ class VARGP(nn.Module):
         if native_kernel and kernel == 'rbf':
             raise ValueError('create_reg: native_kernel=True selects the native route of a Matern kernel (kernel="matern12" / '
                              '"matern32" / "matern52"); the RBF kernel is always native')
+        _check_init_names('create_reg', z_init, lengthscale_init)
         targets = torch.as_tensor(dataset.targets)
         if targets.dim() not in (1, 2):
             raise ValueError(f'create_reg: dataset.targets must have shape (N,) or (N, C), got {tuple(targets.shape)}')
         out_size = 1 if targets.dim() == 1 else targets.size(1)
         lik = make_reg_likelihood(likelihood, out_size, df)
-        N = len(dataset)
-        z = torch.stack([dataset[torch.randperm(N)[:M]][0] for _ in range(out_size)])
+        z = _init_inducing(dataset, out_size, M, z_init, kmeans_iters)
+        first_task = not prev_params
         prior_log_mean, prior_log_logvar = _hand_over_hyper_prior(prev_params)
         if kernel != 'rbf':
             kern = MaternKernel(z.size(-1), nu=_KERNEL_NU[kernel], prior_log_mean=prior_log_mean,
@@ -592,4 +634,5 @@ class VARGP(nn.Module):
         else:
             kern = RBFKernel(z.size(-1), prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
                              map_est=map_est_hypers)
+        _init_lengthscale(kern, dataset, lengthscale_init, first_task)
         return VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean, prev_params=prev_params)
