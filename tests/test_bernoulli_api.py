@@ -1,5 +1,5 @@
 """CPU: BernoulliLikelihood (independent outputs: binary, multi-label, one-vs-rest; not in the reference) -- the class and its
-helpers, the C-ABI symbols of csrc/bernoulli_lik.hip, target conversion, create_clf(likelihood=) and the driver's flags."""
+helpers, the C-ABI symbols of csrc/indep_lik.hip, target conversion, create_clf(likelihood=) and the driver's flags."""
 import ctypes
 import os
 import re

@@ -1,4 +1,4 @@
-"""GPU: BernoulliLikelihood (csrc/bernoulli_lik.hip; not in the reference, so no reference goldens).  Yardstick: the fp64
+"""GPU: BernoulliLikelihood (csrc/indep_lik.hip; not in the reference, so no reference goldens).  Yardstick: the fp64
 restatement `rule()` below -- the 20-node Gauss-Hermite sum that DEFINES the likelihood, with torch.special.log_ndtr /
 -softplus(-z) and torch.autograd -- at op level on a grid of shapes, links, target forms and input ranges, and at model level
 on top of the fp64 oracle's predictive moments and KL ingredients, per route (composed, first-task program, block program,
@@ -126,9 +126,9 @@ def test_bwd_writes_the_forward_value(shape, link):
     for y in (labels, multi):
         tgt = ops.bernoulli_target(y, C, B)
         a, b = torch.empty(1, device=DEV), torch.empty(1, device=DEV)
-        ops.bernoulli_nll_fwd(mu, var, *tgt, ops.BERNOULLI_LINKS[link], a)
+        ops.lik_nll_fwd('bernoulli', mu, var, tgt, (ops.BERNOULLI_LINKS[link],), a)
         gmu, gvar = torch.empty_like(mu), torch.empty_like(var)
-        ops.bernoulli_nll_bwd(mu, var, *tgt, ops.BERNOULLI_LINKS[link], torch.tensor([3.0], device=DEV), gmu, gvar, nll=b)
+        ops.lik_nll_bwd('bernoulli', mu, var, tgt, (ops.BERNOULLI_LINKS[link],), torch.tensor([3.0], device=DEV), gmu, gvar, nll=b)
         assert torch.equal(a, b)
 
 
@@ -145,7 +145,7 @@ def test_c_abi_argument_checks():
     assert call(t, None, 2) != 0 and call(t, None, -1) != 0            # link in {0, 1}
     assert call(t, None, 0, ldt=3) != 0 and call(t, None, 0, wsb=0) != 0
     with pytest.raises(VargpHipError):
-        ops.bernoulli_nll_fwd(mu, var, t, 4, lab, 0, out)
+        ops.lik_nll_fwd('bernoulli', mu, var, (t, 4, lab), (0,), out)
     torch.cuda.synchronize()
 
 

@@ -120,12 +120,12 @@ def test_gauss_bwd_writes_the_forward_value():
     """The trainer's single launch (bwd with nll != NULL) leaves exactly the forward's value."""
     from vargp_amd import ops
     mu, var, y, olv = (t.to(DEV) for t in _op_inputs(3, 10, 512, False, seed=7))
-    yt, ldy = ops.gauss_target(y, 10, 512)
+    tgt = ops.gauss_target(y, 10, 512)
     a, b = torch.empty(1, device=DEV), torch.empty(1, device=DEV)
-    ops.gauss_nll_fwd(mu, var, yt, ldy, olv, a)
+    ops.lik_nll_fwd('gauss', mu, var, tgt, (olv,), a)
     seed = torch.tensor([3.0], device=DEV)
     gmu, gvar, go = torch.empty_like(mu), torch.empty_like(var), torch.empty_like(olv)
-    ops.gauss_nll_bwd(mu, var, yt, ldy, olv, seed, gmu, gvar, go, nll=b)
+    ops.lik_nll_bwd('gauss', mu, var, tgt, (olv,), seed, gmu, gvar, go, nll=b)
     assert torch.equal(a, b)
 
 

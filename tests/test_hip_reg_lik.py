@@ -1,4 +1,4 @@
-"""PoissonLikelihood and StudentTLikelihood (csrc/reg_lik.hip; not in the reference, so no reference goldens).  Yardstick at op
+"""PoissonLikelihood and StudentTLikelihood (csrc/indep_lik.hip; not in the reference, so no reference goldens).  Yardstick at op
 level: the fp64 restatements `poisson_ell` / `studentt_ell` below (the closed form, and the 20-node Gauss-Hermite sum that DEFINES
 the Student-t expectation) with torch.autograd.  At model level: the composed per-op route of the same model.
 
@@ -13,7 +13,7 @@ against fp64 as everywhere else.
 Each edge kind runs with one target form ((C, B) and the shared row alternate over the kinds); typical inputs run with both.
 
 The bound has no floor, and an fp32 result can land within 1e-10 of the exact value by chance, so it can only be met by
-rounding once: the kernels take and return fp32 but evaluate an element and every sum in fp64 (csrc/reg_lik.hip), which makes
+rounding once: the kernels take and return fp32 but evaluate an element and every sum in fp64 (csrc/indep_lik.hip), which makes
 each output the nearest fp32 to the formula's value -- never further from it than another fp32 result.  (With fp32 element
 arithmetic, measured: 58 of 2556 edge checks missed the bound, 55 of them with a kernel error of at most four fp32 epsilons.)"""
 import functools
@@ -320,8 +320,8 @@ def test_bwd_writes_the_forward_value(shape):
         for _ in range(2):
             a, b = torch.empty(1, device=DEV), torch.empty(1, device=DEV)
             gmu, gvar = torch.empty_like(mu), torch.empty_like(var)
-            ops.poisson_nll_fwd(mu, var, *tgt, a)
-            ops.poisson_nll_bwd(mu, var, *tgt, seed, gmu, gvar, nll=b)
+            ops.lik_nll_fwd('poisson', mu, var, tgt, (), a)
+            ops.lik_nll_bwd('poisson', mu, var, tgt, (), seed, gmu, gvar, nll=b)
             assert torch.equal(a, b) and torch.isfinite(a).all()
             out.append((a, gmu, gvar, ops.poisson_predict(mu, var)))
         assert all(torch.equal(p, q) for p, q in zip(*out))
@@ -332,8 +332,9 @@ def test_bwd_writes_the_forward_value(shape):
         for _ in range(2):
             a, b = torch.empty(1, device=DEV), torch.empty(1, device=DEV)
             gmu, gvar, gls = torch.empty_like(mu), torch.empty_like(var), torch.empty_like(ls)
-            ops.studentt_nll_fwd(mu, var, *tgt, ls, df, a)
-            ops.studentt_nll_bwd(mu, var, *tgt, ls, df, seed, gmu, gvar, gls, nll=b)
+            extra = (ls, df, ops.studentt_lognorm(df))
+            ops.lik_nll_fwd('studentt', mu, var, tgt, extra, a)
+            ops.lik_nll_bwd('studentt', mu, var, tgt, extra, seed, gmu, gvar, gls, nll=b)
             assert torch.equal(a, b) and torch.isfinite(a).all()
             out.append((a, gmu, gvar, gls))
         assert all(torch.equal(p, q) for p, q in zip(*out))

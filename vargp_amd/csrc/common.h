@@ -104,7 +104,8 @@ static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // ---- wave / block reductions (64-lane wavefronts) -------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
+template <class T>       // float or double
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
@@ -115,14 +116,14 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 // sum over a block of NT threads (NT multiple of 64, <= 1024); result valid in every thread
-template <int NT>
-__device__ __forceinline__ float block_sum(float v, float* red /* >= NT/64 floats of LDS */) {
+template <int NT, class T>
+__device__ __forceinline__ T block_sum(T v, T* red /* >= NT/64 values of LDS */) {
   v = wave_sum(v);
   const int w = threadIdx.x >> 6;
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[w] = v;
   __syncthreads();
-  float t = 0.f;
+  T t = 0;
 #pragma unroll
   for (int i = 0; i < NT / 64; ++i) t += red[i];
   return t;

@@ -6,7 +6,7 @@
 //   Bernoulli logit   lp = logsumexp_k( log w^_k + log sigma(s_cb f_k) )
 //   Poisson           lp = logsumexp_k( log w^_k + y f_k - exp(f_k) ) - lgamma(y + 1)
 //   Student-t         lp = logsumexp_k( log w^_k - (nu + 1) / 2 log1p((y - f_k)^2 / (nu sigma_c^2)) ) + K_c
-// with f_k = mu + sqrt(2 var) x_k and (x_k, w^_k) the 20-node Gauss-Hermite rule of bernoulli_lik.hip / reg_lik.hip; as there, the
+// with f_k = mu + sqrt(2 var) x_k and (x_k, w^_k) the 20-node Gauss-Hermite rule of lik.h (which also has each likelihood's lp and tail); as in indep_lik.hip, the
 // quadrature sums are the DEFINITION.  The hyper-sample is shared by all outputs of a point, so the density of a point's whole
 // target vector is the mixture of products, and the per-output marginals mix each output alone:
 //   lpd[b]       = logsumexp_s( sum_c lp[s,c,b] ) - log S
@@ -21,27 +21,14 @@
 // depend on s (lgamma(y + 1), K_c: `tail`) are added once, after the mixture.  Per-output kernel (a second loop order, c outer and
 // s inner, recomputing lp; optional and cheap): workgroup (j, q), wave w owns output c = 4 q + w of the same 64 points and walks
 // s in order; no LDS.  No workspace, no float atomics: every sum has a fixed order and two runs are bitwise equal.
-// Precision: inputs and outputs are fp32; element arithmetic and every sum run in fp64 (as reg_lik.hip), so each output is the
+// Precision: inputs and outputs are fp32; element arithmetic and every sum run in fp64 (as the Poisson and Student-t ELBO terms), so each output is the
 // definition's value rounded ONCE.  All logsumexp's subtract the running maximum.
-#include "common.h"
+#include "lik.h"
 
 namespace vargp {
 
 constexpr int kLpdMaxWaves = 8;
 constexpr int kLpdOutWaves = 4;
-constexpr int kLpdPairs = 10;
-constexpr double kLpdInf = __builtin_huge_val();
-// x, w = numpy.polynomial.hermite.hermgauss(20); the positive half x[10:] and log(w[10:] / sqrt(pi))
-__device__ constexpr double kLpdX[kLpdPairs] = {0.24534070830090124, 0.73747372854539439, 1.2340762153953231,
-                                                1.7385377121165861,  2.2549740020892757,  2.7888060584281305,
-                                                3.3478545673832163,  3.9447640401156252,  4.6036824495507442,
-                                                5.3874808900112328};
-__device__ constexpr double kLpdLogW[kLpdPairs] = {-1.344028046485978,  -1.8217692891416608, -2.7886144987405204,
-                                                   -4.268852429362512,  -6.303382957935046,  -8.957045728135233,
-                                                   -12.333424067234969, -16.60789549709157,  -22.11676111764163,
-                                                   -29.704241511181127};
-constexpr double kLpdHalfLog2Pi = 0.9189385332046727;
-constexpr double kLpdInvSqrt2 = 0.70710678118654752440;
 
 // running logsumexp: (m, s) stands for m + log(s); the empty sum is (-inf, 0).  A term of -inf changes nothing; a NaN term makes
 // s NaN (it is not dropped).
@@ -49,126 +36,20 @@ __device__ __forceinline__ void lse_push(double& m, double& s, double a) {
   if (a > m) {
     s = s * exp(m - a) + 1.0;
     m = a;
-  } else if (!(a == -kLpdInf)) {
+  } else if (!(a == -kInf)) {
     s += exp(a - m);
   }
 }
 __device__ __forceinline__ void lse_merge(double& m, double& s, double m2, double s2) {
   const double mx = fmax(m, m2);
-  if (mx == -kLpdInf) {                             // both empty, or all terms -inf: the sums are 0 (or NaN, which is kept)
+  if (mx == -kInf) {                             // both empty, or all terms -inf: the sums are 0 (or NaN, which is kept)
     s += s2;
     return;
   }
   s = s * exp(m - mx) + s2 * exp(m2 - mx);
   m = mx;
 }
-__device__ __forceinline__ double lse_value(double m, double s) { return s == 0.0 ? -kLpdInf : m + log(s); }
-
-// logsumexp_k( log w^_k + term(f_k) ), f_k = mu + sqrt(2 var) x_k: the twenty terms, their maximum, then the sum in node order
-template <class TERM>
-__device__ __forceinline__ double gh_lse(double mu, double var, TERM term) {
-  const double sd = sqrt(2.0 * var);
-  double t[2 * kLpdPairs], mx = -kLpdInf;
-#pragma unroll
-  for (int k = 0; k < kLpdPairs; ++k) {
-    const double d = sd * kLpdX[k];
-    t[2 * k] = kLpdLogW[k] + term(mu + d);
-    t[2 * k + 1] = kLpdLogW[k] + term(mu - d);
-    mx = fmax(mx, fmax(t[2 * k], t[2 * k + 1]));
-  }
-  const double sh = mx == -kLpdInf ? 0.0 : mx;      // every term -inf: the sum is 0 and the value log(0) = -inf, not NaN
-  double s = 0.0;
-#pragma unroll
-  for (int k = 0; k < 2 * kLpdPairs; ++k) s += exp(t[k] - sh);
-  return sh + log(s);
-}
-
-// A likelihood: Args (by value into the kernel), Cls = what is constant over one output,
-//   target(args, c, b) = the target of (c, b) as a double,  lp(cls, mu, var, y) = the part of lp that depends on s,
-//   tail(cls, y) = the rest (constant over the hyper-samples: added after the mixture)
-struct LpdTarget {            // y [C, B] with row stride ldy, or one row shared by every output (ldy = 0)
-  const float* y;
-  int64_t ldy;
-  __device__ __forceinline__ double at(int c, size_t b) const { return (double)y[(size_t)c * (size_t)ldy + b]; }
-};
-
-struct LpdGauss {
-  struct Args {
-    LpdTarget y;
-    const float* obs_log_var;
-  };
-  struct Cls {
-    double obs;
-  };
-  static __device__ __forceinline__ Cls cls(const Args& a, int c) { return Cls{exp((double)a.obs_log_var[c])}; }
-  static __device__ __forceinline__ double target(const Args& a, int c, size_t b) { return a.y.at(c, b); }
-  static __device__ __forceinline__ double lp(const Cls& p, double mu, double var, double y) {
-    const double v = var + p.obs, r = y - mu;
-    return -kLpdHalfLog2Pi - 0.5 * (log(v) + r * r / v);
-  }
-  static __device__ __forceinline__ double tail(const Cls&, double) { return 0.0; }
-};
-
-template <int LINK>           // 0: probit (closed form), 1: logit (the rule); the "target" is the sign 2 t - 1
-struct LpdBernoulli {
-  struct Args {
-    const float* t;
-    int64_t ldt;
-    const int64_t* labels;
-  };
-  struct Cls {};
-  static __device__ __forceinline__ Cls cls(const Args&, int) { return Cls{}; }
-  static __device__ __forceinline__ double target(const Args& a, int c, size_t b) {
-    // one-vs-rest labels: a label outside [0, C) matches no output (every output of that point is a negative)
-    if (a.labels) return a.labels[b] == (int64_t)c ? 1.0 : -1.0;
-    return 2.0 * (double)a.t[(size_t)c * (size_t)a.ldt + b] - 1.0;
-  }
-  static __device__ __forceinline__ double lp(const Cls&, double mu, double var, double sgn) {
-    if (LINK == 0) return log(0.5 * erfc(-(sgn * mu / sqrt(1.0 + var)) * kLpdInvSqrt2));
-    // log sigma(z) = min(z, 0) - log1p(exp(-|z|))
-    return gh_lse(mu, var, [sgn](double f) {
-      const double z = sgn * f;
-      return fmin(z, 0.0) - log1p(exp(-fabs(z)));
-    });
-  }
-  static __device__ __forceinline__ double tail(const Cls&, double) { return 0.0; }
-};
-
-struct LpdPoisson {
-  struct Args {
-    LpdTarget y;
-  };
-  struct Cls {};
-  static __device__ __forceinline__ Cls cls(const Args&, int) { return Cls{}; }
-  static __device__ __forceinline__ double target(const Args& a, int c, size_t b) { return a.y.at(c, b); }
-  static __device__ __forceinline__ double lp(const Cls&, double mu, double var, double y) {
-    return gh_lse(mu, var, [y](double f) { return y * f - exp(f); });
-  }
-  static __device__ __forceinline__ double tail(const Cls&, double y) { return -lgamma(y + 1.0); }
-};
-
-struct LpdStudentT {
-  struct Args {
-    LpdTarget y;
-    const float* log_scale;
-    float df, lognorm;
-  };
-  struct Cls {
-    double inv, hnp1, k;     // 1 / (nu sigma^2), (nu + 1) / 2, K_c
-  };
-  static __device__ __forceinline__ Cls cls(const Args& a, int c) {
-    const double ls = a.log_scale[c];
-    return Cls{exp(-2.0 * ls) / (double)a.df, 0.5 * ((double)a.df + 1.0), (double)a.lognorm - ls};
-  }
-  static __device__ __forceinline__ double target(const Args& a, int c, size_t b) { return a.y.at(c, b); }
-  static __device__ __forceinline__ double lp(const Cls& p, double mu, double var, double y) {
-    return gh_lse(mu, var, [p, y](double f) {
-      const double r = y - f;
-      return -p.hnp1 * log1p(r * r * p.inv);
-    });
-  }
-  static __device__ __forceinline__ double tail(const Cls& p, double) { return p.k; }
-};
+__device__ __forceinline__ double lse_value(double m, double s) { return s == 0.0 ? -kInf : m + log(s); }
 
 // Wave 0 of a joint workgroup: the other waves' (max, sum) pairs of each lane's point, merged in wave order
 __device__ __forceinline__ void lpd_merge_waves(double& m, double& s, double (*red)[2][kWave], int nw, int lane) {
@@ -184,13 +65,13 @@ __global__ __launch_bounds__(kLpdMaxWaves* kWave) void lpd_joint_kernel(const fl
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6, nw = blockDim.x >> 6;
   const size_t b = (size_t)blockIdx.x * kWave + lane;
   const bool live = b < (size_t)B;
-  double m = -kLpdInf, sum = 0.0;
+  double m = -kInf, sum = 0.0;
   if (live) {
     for (int s = w; s < S; s += nw) {
       double a = 0.0;
       for (int c = 0; c < C; ++c) {
         const size_t i = ((size_t)s * C + c) * (size_t)B + b;
-        a += LIK::lp(LIK::cls(args, c), (double)mu[i], (double)var[i], LIK::target(args, c, b));
+        a += LIK::lp(LIK::cls(args, c), (double)mu[i], (double)var[i], LIK::template target<double>(args, c, b));
       }
       lse_push(m, sum, a);
     }
@@ -201,7 +82,7 @@ __global__ __launch_bounds__(kLpdMaxWaves* kWave) void lpd_joint_kernel(const fl
   if (w != 0 || !live) return;
   lpd_merge_waves(m, sum, red, nw, lane);
   double tail = 0.0;
-  for (int c = 0; c < C; ++c) tail += LIK::tail(LIK::cls(args, c), LIK::target(args, c, b));
+  for (int c = 0; c < C; ++c) tail += LIK::tail(LIK::cls(args, c), LIK::template target<double>(args, c, b));
   lpd[b] = (float)(lse_value(m, sum) - log((double)S) + tail);
 }
 
@@ -214,8 +95,8 @@ __global__ __launch_bounds__(kLpdOutWaves* kWave) void lpd_out_kernel(const floa
   const size_t b = (size_t)blockIdx.x * kWave + lane;
   if (c >= C || b >= (size_t)B) return;
   const typename LIK::Cls cls = LIK::cls(args, c);
-  const double y = LIK::target(args, c, b);
-  double m = -kLpdInf, sum = 0.0;
+  const double y = LIK::template target<double>(args, c, b);
+  double m = -kInf, sum = 0.0;
   for (int s = 0; s < S; ++s) {
     const size_t i = ((size_t)s * C + c) * (size_t)B + b;
     lse_push(m, sum, LIK::lp(cls, (double)mu[i], (double)var[i], y));
@@ -236,12 +117,12 @@ __global__ __launch_bounds__(kLpdMaxWaves* kWave) void lpd_softmax_kernel(const 
   const size_t b = (size_t)blockIdx.x * kWave + lane;
   const bool live = b < (size_t)B;
   const int SF = S * F;
-  double m = -kLpdInf, sum = 0.0;
+  double m = -kInf, sum = 0.0;
   if (live) {
     const int64_t yb = y[b];
     for (int p = w; p < SF; p += nw) {
       const int s = p / F;
-      double cm = -kLpdInf, cs = 0.0, fy = 0.0;
+      double cm = -kInf, cs = 0.0, fy = 0.0;
       for (int c = 0; c < C; ++c) {
         const size_t i = ((size_t)s * C + c) * (size_t)B + b, j = ((size_t)p * C + c) * (size_t)B + b;
         const double f = (double)mu[i] + sqrt((double)var[i]) * (double)eps[j];
@@ -295,7 +176,7 @@ extern "C" int vargp_gauss_lpd(const float* mu, const float* var, const float* y
   LPD_CHECK_COMMON("gauss_lpd");
   LPD_CHECK_TARGET("gauss_lpd");
   VARGP_REQUIRE(obs_log_var, "gauss_lpd: obs_log_var must be given");
-  return lpd_launch<LpdGauss>("gauss_lpd", mu, var, LpdGauss::Args{{y, ldy}, obs_log_var}, lpd, lpd_out, S, C, B,
+  return lpd_launch<Gauss>("gauss_lpd", mu, var, {{y, ldy}, obs_log_var}, lpd, lpd_out, S, C, B,
                               as_stream(stream));
 }
 
@@ -306,17 +187,15 @@ extern "C" int vargp_bernoulli_lpd(const float* mu, const float* var, const floa
   VARGP_REQUIRE((t != nullptr) != (labels != nullptr), "bernoulli_lpd: exactly one of t and labels");
   VARGP_REQUIRE(labels || ldt == 0 || ldt >= B, "bernoulli_lpd: ldt must be 0 or >= B");
   if (link == 0)
-    return lpd_launch<LpdBernoulli<0>>("bernoulli_lpd", mu, var, LpdBernoulli<0>::Args{t, ldt, labels}, lpd, lpd_out, S, C, B,
-                                       as_stream(stream));
-  return lpd_launch<LpdBernoulli<1>>("bernoulli_lpd", mu, var, LpdBernoulli<1>::Args{t, ldt, labels}, lpd, lpd_out, S, C, B,
-                                     as_stream(stream));
+    return lpd_launch<Bernoulli<LinkProbit>>("bernoulli_lpd", mu, var, {t, ldt, labels}, lpd, lpd_out, S, C, B, as_stream(stream));
+  return lpd_launch<Bernoulli<LinkLogit>>("bernoulli_lpd", mu, var, {t, ldt, labels}, lpd, lpd_out, S, C, B, as_stream(stream));
 }
 
 extern "C" int vargp_poisson_lpd(const float* mu, const float* var, const float* y, int64_t ldy, float* lpd, float* lpd_out,
                                  int S, int C, int B, vargp_stream_t stream) {
   LPD_CHECK_COMMON("poisson_lpd");
   LPD_CHECK_TARGET("poisson_lpd");
-  return lpd_launch<LpdPoisson>("poisson_lpd", mu, var, LpdPoisson::Args{{y, ldy}}, lpd, lpd_out, S, C, B, as_stream(stream));
+  return lpd_launch<Poisson>("poisson_lpd", mu, var, {{y, ldy}}, lpd, lpd_out, S, C, B, as_stream(stream));
 }
 
 extern "C" int vargp_studentt_lpd(const float* mu, const float* var, const float* y, int64_t ldy, const float* log_scale,
@@ -325,6 +204,6 @@ extern "C" int vargp_studentt_lpd(const float* mu, const float* var, const float
   LPD_CHECK_COMMON("studentt_lpd");
   LPD_CHECK_TARGET("studentt_lpd");
   VARGP_REQUIRE(log_scale && df > 0.f, "studentt_lpd: log_scale must be given, df > 0");
-  return lpd_launch<LpdStudentT>("studentt_lpd", mu, var, LpdStudentT::Args{{y, ldy}, log_scale, df, lognorm}, lpd, lpd_out, S,
-                                 C, B, as_stream(stream));
+  return lpd_launch<StudentT>("studentt_lpd", mu, var, {{y, ldy}, log_scale, df, lognorm}, lpd, lpd_out, S, C, B,
+                              as_stream(stream));
 }

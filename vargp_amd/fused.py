@@ -401,7 +401,7 @@ class TnProgram(_Program):
 # External likelihoods (likelihoods.is_external: GaussianLikelihood -- regression, var_gp/likelihoods.py:66-110 --,
 # BernoulliLikelihood, PoissonLikelihood, StudentTLikelihood) on either program: the program's forward with ext_lik stops
 # at the predictive moments and the KL, the likelihood's value and its seeded gradients are one call each
-# (likelihood.ext_value / ext_backward over lik_views(prog): csrc/gauss_lik.hip, csrc/bernoulli_lik.hip, csrc/reg_lik.hip),
+# (likelihood.ext_value / ext_backward over lik_views(prog): csrc/gauss_lik.hip, csrc/indep_lik.hip),
 # and the program's backward takes those gradients from its likelihood buffers
 # ----------------------------------------------------------------------------------------------------------------
 _Y_DUMMY = {}

@@ -4,12 +4,12 @@
     `vargp_gauss_nll_*` kernels (csrc/gauss_lik.hip); draws no noise;
 and three that the reference does not have:
   * BernoulliLikelihood: independent outputs (binary, multi-label, one-vs-rest), a fixed 20-node Gauss-Hermite rule on the
-    `vargp_bernoulli_*` kernels (csrc/bernoulli_lik.hip); deterministic, no parameters;
-  * PoissonLikelihood: counts with a log link, closed form on the `vargp_poisson_*` kernels (csrc/reg_lik.hip); no parameters;
+    `vargp_bernoulli_*` kernels (csrc/indep_lik.hip); deterministic, no parameters;
+  * PoissonLikelihood: counts with a log link, closed form on the `vargp_poisson_*` kernels (csrc/indep_lik.hip); no parameters;
   * StudentTLikelihood: robust regression, fixed degrees of freedom and one learned log-scale per output, the same 20-node
-    rule on the `vargp_studentt_*` kernels (csrc/reg_lik.hip).
-All but the softmax are "external": the native ELBO programs stop at the predictive moments and the KL (ext_lik) and these
-classes complete the step through one protocol -- ext_param / ext_target / ext_value / ext_backward.
+    rule on the `vargp_studentt_*` kernels (csrc/indep_lik.hip).
+All but the softmax are "external" (_ExternalLikelihood): the native ELBO programs stop at the predictive moments and the KL
+(ext_lik) and these classes complete the step through one protocol -- ext_param / ext_target / ext_value / ext_backward.
 Every class names the layout of what its `predict` returns in `predict_batch_dim`: the dim that runs over the data points
 (0 for probabilities (B, C), -1 for per-sample values (S, C, B)) -- what a tiled prediction concatenates along.
 Every class has `log_prob(mu, var, y, per_output=False)`: the held-out log predictive density per point (B,), log E_q[p(y)] -- the
@@ -54,9 +54,65 @@ class MulticlassSoftmax(nn.Module):
         return ops.softmax_lpd(mu, var, self._eps(mu), y)
 
 
-class GaussianLikelihood(nn.Module):
-    """Independent multi-output Gaussian likelihood with one learned observation log-variance per output."""
+class _ExternalLikelihood(nn.Module):
+    """A likelihood with independent outputs on the uniform `vargp_<kind>_*` entries (ops.lik_nll_fwd / lik_nll_bwd / lik_lpd).
+    A subclass names its `kind`, its own differentiable tensor (ext_param(): at most one (C,), or None) and its host constants
+    (_consts()); `_extra()` is what the entries take between target and outputs: the DETACHED parameter -- a view of the
+    parameter's storage, so one taken when a graph is captured stays current -- and the constants."""
+    kind = None
+
+    def ext_param(self):
+        """The likelihood's own differentiable tensor (at most one), or None."""
+        return None
+
+    def _consts(self):
+        return ()
+
+    def _extra(self):
+        own = self.ext_param()
+        return (() if own is None else (own.detach().contiguous(),)) + self._consts()
+
+    def loss(self, pred_mu, pred_var, y):
+        """The nll of the moments (S, C, B): minus the expected log-likelihood under f ~ N(mu, var), summed over the points and
+        averaged over the hyper-samples; y as the kind's ops.*_target takes it.  Differentiable in mu, var and ext_param()."""
+        return ops.lik_nll(self.kind, pred_mu, pred_var, y, self.ext_param(), *self._consts())
+
+    def log_prob(self, mu, var, y, per_output=False):
+        """Held-out log predictive density: lpd (B,) = logsumexp_s sum_c lp[s, c, b] - log S, the joint density of a point's
+        targets under the mixture over hyper-samples (they share the hyper-sample), with lp the log marginal likelihood of one
+        target under f ~ N(mu, var); per_output: (lpd, lpd_out (C, B)) with the per-output marginals.  Not in the reference.
+        No gradients."""
+        return ops.lik_lpd(self.kind, mu, var, y, self._extra(), per_output)
+
+    # -- the native programs' ext_lik route ------------------------------------------------------------------------------------
+    def ext_target(self, y, C, B):
+        """(y as the kernels read it, _extra()): what ext_value / ext_backward take."""
+        return ops.lik_target(self.kind, y, C, B), self._extra()
+
+    def ext_value(self, prog, target):
+        """After a program forward with ext_lik: the nll of its moments into prog.scalars[2], completing the
+        (kl_hypers, kl_u, nll) triple."""
+        from .fused import lik_views
+        mu, var, _, _ = lik_views(prog)
+        ops.lik_nll_fwd(self.kind, mu, var, *target, prog.scalars[2:])
+
+    def ext_backward(self, prog, target, seed, nll=None, grad=None):
+        """Before the program's backward: ONE launch -- the seeded d nll / d (mu, var) into the program's likelihood buffers,
+        d nll / d ext_param() into `grad` (None: a new tensor), with `nll` the value too.  -> the parameter's gradient."""
+        from .fused import lik_views
+        mu, var, gmu, gvar = lik_views(prog)
+        if grad is None and self.ext_param() is not None:
+            grad = torch.empty_like(target[1][0])
+        ops.lik_nll_bwd(self.kind, mu, var, *target, seed, gmu, gvar, grad, nll=nll)
+        return grad
+
+
+class GaussianLikelihood(_ExternalLikelihood):
+    """Independent multi-output Gaussian likelihood with one learned observation log-variance per output.
+    loss: sum_b mean_{s,c} -log N(y | mu, var + exp(obs_log_var))  (likelihoods.py:91-107), the reference's MEAN over outputs;
+    y (C, B) or (B,).  log_prob: lp = log N(y | mu, var + exp(obs_log_var)), closed form."""
     predict_batch_dim = -1
+    kind = 'gauss'
 
     def __init__(self, out_size, init_log_var=-4.):
         super().__init__()
@@ -67,49 +123,15 @@ class GaussianLikelihood(nn.Module):
         compatibility."""
         return mu.unsqueeze(-1), var.unsqueeze(-1) + self.obs_log_var.exp().view(1, -1, 1, 1)
 
-    def loss(self, pred_mu, pred_var, y):
-        """sum_b mean_{s,c} -log N(y | mu, var + exp(obs_log_var))  (likelihoods.py:91-107); y (C, B) or (B,)."""
-        return ops.gauss_nll(pred_mu, pred_var, y, self.obs_log_var)
-
     def predict(self, mu, var):
         """the predictive mean itself, (S, C, B)  (likelihoods.py:109-110)."""
         return mu
 
-    def log_prob(self, mu, var, y, per_output=False):
-        """Held-out log predictive density: lpd (B,) = logsumexp_s sum_c log N(y | mu, var + exp(obs_log_var)) - log S, the joint
-        density of a point's targets under the mixture over hyper-samples (they share the hyper-sample); per_output: (lpd,
-        lpd_out (C, B)) with the per-output marginals.  Not in the reference.  No gradients."""
-        return ops.gauss_lpd(mu, var, y, self.obs_log_var, per_output=per_output)
-
-    # -- the native programs' ext_lik route ------------------------------------------------------------------------------------
     def ext_param(self):
-        """The likelihood's own differentiable tensor (at most one), or None."""
         return self.obs_log_var
 
-    def ext_target(self, y, C, B):
-        """y as the kernels read it, plus the detached parameter: what ext_value / ext_backward take."""
-        return ops.gauss_target(y, C, B) + (self.obs_log_var.detach().contiguous(),)
 
-    def ext_value(self, prog, target):
-        """After a program forward with ext_lik: the nll of its moments into prog.scalars[2], completing the
-        (kl_hypers, kl_u, nll) triple."""
-        from .fused import lik_views
-        mu, var, _, _ = lik_views(prog)
-        yt, ldy, olv = target
-        ops.gauss_nll_fwd(mu, var, yt, ldy, olv, prog.scalars[2:])
-
-    def ext_backward(self, prog, target, seed, nll=None, grad=None):
-        """Before the program's backward: ONE launch -- the seeded d nll / d (mu, var) into the program's likelihood buffers,
-        d nll / d ext_param() into `grad` (None: a new tensor), with `nll` the value too.  -> the parameter's gradient."""
-        from .fused import lik_views
-        mu, var, gmu, gvar = lik_views(prog)
-        yt, ldy, olv = target
-        grad = torch.empty_like(olv) if grad is None else grad
-        ops.gauss_nll_bwd(mu, var, yt, ldy, olv, seed, gmu, gvar, grad, nll=nll)
-        return grad
-
-
-class BernoulliLikelihood(nn.Module):
+class BernoulliLikelihood(_ExternalLikelihood):
     """Independent-output Bernoulli likelihood, p(t | f) = Lambda((2 t - 1) f) per output with Lambda the standard normal cdf
     (link='probit', the default) or the logistic function (link='logit').  Not in the reference.  No parameters, no
     Monte-Carlo noise (no n_f): the expected log-likelihood under f ~ N(mu, var) is DEFINED as the 20-node Gauss-Hermite sum
@@ -119,10 +141,12 @@ class BernoulliLikelihood(nn.Module):
     at var <= 25 it is 5e-3.
     Targets: int64 (B,) class indices read as one-vs-rest (t[c, b] = (y[b] == c); a label outside [0, C) gives no positive
     output), or float / bool 0 / 1 targets (C, B) (multi-label) or (B,) (shared by every output).
-    The loss SUMS over outputs: kl_u sums over outputs, so the ELBO of C independent outputs sums their log-likelihoods.
-    (GaussianLikelihood keeps the reference's mean over outputs because it has the reference to match; this class has nothing
-    to match.)"""
+    The loss SUMS over outputs, - sum_b sum_c mean_s ell[s, c, b]: kl_u sums over outputs, so the ELBO of C independent outputs
+    sums their log-likelihoods.  (GaussianLikelihood keeps the reference's mean over outputs because it has the reference to
+    match; this class has nothing to match.)
+    log_prob: per element log Phi(s mu / sqrt(1 + var)) (probit) or the 20-node rule on the logistic function (logit)."""
     predict_batch_dim = 0
+    kind = 'bernoulli'
 
     def __init__(self, link='probit'):
         super().__init__()
@@ -134,87 +158,38 @@ class BernoulliLikelihood(nn.Module):
         S, C, B = mu.shape
         return ops.bernoulli_predict(mu.reshape(1, S * C, B), var.reshape(1, S * C, B), self.link).t().reshape(S, C, B)
 
-    def loss(self, pred_mu, pred_var, y):
-        """- sum_b sum_c mean_s ell[s, c, b]; y as ops.bernoulli_target takes it."""
-        return ops.bernoulli_nll(pred_mu, pred_var, y, self.link)
-
     def predict(self, mu, var):
         """probs (B, C) = mean_s P(t = 1), laid out like the softmax's so that an argmax over the last dim picks the class.
         The outputs are independent: a row is NOT normalised over c.  Probit: Phi(mu / sqrt(1 + var)) in closed form; logit:
         the 20-node rule on the logistic function."""
         return ops.bernoulli_predict(mu, var, self.link)
 
-    def log_prob(self, mu, var, y, per_output=False):
-        """Held-out log predictive density (B,), or (lpd, lpd_out (C, B)) -- see GaussianLikelihood.log_prob; per element
-        log Phi(s mu / sqrt(1 + var)) (probit) or the 20-node rule on the logistic function (logit)."""
-        return ops.bernoulli_lpd(mu, var, y, self.link, per_output=per_output)
-
-    # -- the native programs' ext_lik route (see GaussianLikelihood) ------------------------------------------------------------
-    def ext_param(self):
-        return None
-
-    def ext_target(self, y, C, B):
-        return ops.bernoulli_target(y, C, B)
-
-    def ext_value(self, prog, target):
-        from .fused import lik_views
-        mu, var, _, _ = lik_views(prog)
-        ops.bernoulli_nll_fwd(mu, var, *target, self._link, prog.scalars[2:])
-
-    def ext_backward(self, prog, target, seed, nll=None, grad=None):
-        from .fused import lik_views
-        mu, var, gmu, gvar = lik_views(prog)
-        ops.bernoulli_nll_bwd(mu, var, *target, self._link, seed, gmu, gvar, nll=nll)
-        return None
+    def _consts(self):
+        return (self._link,)
 
 
-class PoissonLikelihood(nn.Module):
+class PoissonLikelihood(_ExternalLikelihood):
     """Independent-output Poisson likelihood with a log link, p(y | f) = Poisson(y; exp(f)): counts.  Not in the reference.  No
     parameters, no noise, no quadrature -- under f ~ N(mu, var) the expected log-likelihood is closed form, with m = mu + var / 2:
         ell = y mu - exp(m) - lgamma(y + 1)
     Targets: non-negative floats (or integers, cast) of shape (C, B), or (B,) shared by every output; not checked on the device.
     exp(m) overflows fp32 above m ~ 88.7: value and gradients are then inf, as the formula says -- nothing is clamped.
-    The loss SUMS over outputs and takes the mean over hyper-samples, as BernoulliLikelihood does: the ELBO of C independent
-    outputs, C times GaussianLikelihood's (the reference's) mean-over-outputs convention."""
+    The loss SUMS over outputs and takes the mean over hyper-samples, - sum_b sum_c mean_s ell[s, c, b], as BernoulliLikelihood
+    does: the ELBO of C independent outputs, C times GaussianLikelihood's (the reference's) mean-over-outputs convention.
+    log_prob: the marginal likelihood of a count is the 20-node Gauss-Hermite sum of Poisson(y; exp(f_k))."""
     predict_batch_dim = -1
+    kind = 'poisson'
 
     def forward(self, mu, var):
         """the rate E exp(f) per element, (S, C, B)."""
         return ops.poisson_predict(mu, var)
 
-    def loss(self, pred_mu, pred_var, y):
-        """- sum_b sum_c mean_s ell[s, c, b]; y as ops.reg_target takes it."""
-        return ops.poisson_nll(pred_mu, pred_var, y)
-
     def predict(self, mu, var):
         """the predicted rate exp(mu + var / 2) per hyper-sample, (S, C, B) -- the layout of GaussianLikelihood.predict."""
         return ops.poisson_predict(mu, var)
 
-    def log_prob(self, mu, var, y, per_output=False):
-        """Held-out log predictive density (B,), or (lpd, lpd_out (C, B)) -- see GaussianLikelihood.log_prob; the marginal
-        likelihood of a count is the 20-node Gauss-Hermite sum of Poisson(y; exp(f_k))."""
-        return ops.poisson_lpd(mu, var, y, per_output=per_output)
 
-    # -- the native programs' ext_lik route (see GaussianLikelihood) ------------------------------------------------------------
-    def ext_param(self):
-        return None
-
-    def ext_target(self, y, C, B):
-        return ops.reg_target(y, C, B)
-
-    def ext_value(self, prog, target):
-        from .fused import lik_views
-        mu, var, _, _ = lik_views(prog)
-        ops.poisson_nll_fwd(mu, var, *target, prog.scalars[2:])
-
-    def ext_backward(self, prog, target, seed, nll=None, grad=None):
-        from .fused import lik_views
-        mu, var, gmu, gvar = lik_views(prog)
-        ops.poisson_nll_bwd(mu, var, *target, seed, gmu, gvar, nll=nll)
-        return None
-
-
-class StudentTLikelihood(nn.Module):
+class StudentTLikelihood(_ExternalLikelihood):
     """Independent-output Student-t likelihood, p(y | f) = t_df((y - f) / sigma_c) / sigma_c with sigma_c = exp(log_scale[c]):
     regression that a few outliers do not pull along.  Not in the reference.  One learned log-scale per output; the degrees of
     freedom `df` > 0 are a fixed constructor argument and NOT part of the state dict -- give them again when a checkpoint is
@@ -225,9 +200,11 @@ class StudentTLikelihood(nn.Module):
     and the gradients are the exact derivatives of that sum.  (As an approximation of the integral the rule is as good as twenty
     nodes resolve the density's width: with sqrt(var) ten times sigma_c single terms are up to 6 % away from a 200-node rule.)
     Targets (C, B), or (B,) shared by every output.
-    The loss SUMS over outputs and takes the mean over hyper-samples, as BernoulliLikelihood does: the ELBO of C independent
-    outputs, C times GaussianLikelihood's (the reference's) mean-over-outputs convention."""
+    The loss SUMS over outputs and takes the mean over hyper-samples, - sum_b sum_c mean_s ell[s, c, b], as BernoulliLikelihood
+    does: the ELBO of C independent outputs, C times GaussianLikelihood's (the reference's) mean-over-outputs convention.
+    log_prob: the marginal likelihood of a target is the 20-node Gauss-Hermite sum of the Student-t density."""
     predict_batch_dim = -1
+    kind = 'studentt'
 
     def __init__(self, out_size, df=4.0, init_log_scale=-2.):
         super().__init__()
@@ -240,37 +217,15 @@ class StudentTLikelihood(nn.Module):
         var + exp(2 log_scale).  Not on the hot path; kept for API symmetry with GaussianLikelihood."""
         return mu.unsqueeze(-1), var.unsqueeze(-1) + (2 * self.log_scale).exp().view(1, -1, 1, 1)
 
-    def loss(self, pred_mu, pred_var, y):
-        """- sum_b sum_c mean_s ell[s, c, b]; y as ops.reg_target takes it."""
-        return ops.studentt_nll(pred_mu, pred_var, y, self.log_scale, self.df)
-
     def predict(self, mu, var):
         """the predictive location, the mean itself, (S, C, B) -- as GaussianLikelihood.predict."""
         return mu
 
-    def log_prob(self, mu, var, y, per_output=False):
-        """Held-out log predictive density (B,), or (lpd, lpd_out (C, B)) -- see GaussianLikelihood.log_prob; the marginal
-        likelihood of a target is the 20-node Gauss-Hermite sum of the Student-t density."""
-        return ops.studentt_lpd(mu, var, y, self.log_scale, self.df, per_output=per_output)
-
-    # -- the native programs' ext_lik route (see GaussianLikelihood) ------------------------------------------------------------
     def ext_param(self):
         return self.log_scale
 
-    def ext_target(self, y, C, B):
-        return ops.reg_target(y, C, B) + (self.log_scale.detach().contiguous(),)
-
-    def ext_value(self, prog, target):
-        from .fused import lik_views
-        mu, var, _, _ = lik_views(prog)
-        ops.studentt_nll_fwd(mu, var, *target, self.df, prog.scalars[2:])
-
-    def ext_backward(self, prog, target, seed, nll=None, grad=None):
-        from .fused import lik_views
-        mu, var, gmu, gvar = lik_views(prog)
-        grad = torch.empty_like(target[2]) if grad is None else grad
-        ops.studentt_nll_bwd(mu, var, *target, self.df, seed, gmu, gvar, grad, nll=nll)
-        return grad
+    def _consts(self):
+        return self.df, ops.studentt_lognorm(self.df)
 
 
 def n_f(likelihood):
@@ -283,7 +238,7 @@ def n_f(likelihood):
 def is_external(likelihood):
     """Is the likelihood the caller's -- do the native programs run it with ext_lik (moments + KL only) and leave value and
     gradients to the likelihood's ext_value / ext_backward?"""
-    return isinstance(likelihood, (GaussianLikelihood, BernoulliLikelihood, PoissonLikelihood, StudentTLikelihood))
+    return isinstance(likelihood, _ExternalLikelihood)
 
 
 def is_gaussian(likelihood):

@@ -666,63 +666,32 @@ def softmax_predict(mu, var, eps):
 
 
 
-def gauss_target(y, C, B):
-    """A regression target as the Gaussian kernels read it: (fp32 contiguous tensor, class stride ldy) -- (C, B) -> ldy = B,
-    (B,) -> ldy = 0 (one row shared by every output: the reference's y.unsqueeze(0).unsqueeze(-1) broadcast)."""
+# ------------------------------------------------------------------------------------------------
+# Likelihoods with independent outputs -- Gaussian (csrc/gauss_lik.hip), Bernoulli / Poisson / Student-t (csrc/indep_lik.hip;
+# not in the reference) -- and every likelihood's held-out log predictive density (csrc/lpd.hip; not in the reference, no
+# autograd).  Their C ABI is uniform, so ONE table-driven call serves them all:
+#   vargp_<kind>_nll_fwd(mu, var, <target...>, <extra...>, nll, S, C, B, [ws, ws_bytes], stream)
+#   vargp_<kind>_nll_bwd(mu, var, <target...>, <extra...>, seed, gmu, gvar, [g_param], nll, S, C, B, [ws, ws_bytes], stream)
+#   vargp_<kind>_lpd    (mu, var, <target...>, <extra...>, lpd, lpd_out, S, C, B, stream)
+# target: the tuple from the kind's *_target;  extra: the output's own parameter (C,) and / or host constants --
+#   gauss (obs_log_var,)   bernoulli (link 0 / 1,)   poisson ()   studentt (log_scale, df, studentt_lognorm(df))
+# ------------------------------------------------------------------------------------------------
+def reg_target(y, C, B):
+    """A regression / count target as the Gaussian, Poisson and Student-t kernels read it: (fp32 contiguous tensor, row stride
+    ldy) -- (C, B) -> ldy = B, (B,) -> ldy = 0 (one row shared by every output: the reference's y.unsqueeze(0).unsqueeze(-1)
+    broadcast).  Values are not checked."""
+    if not torch.is_tensor(y):
+        raise TypeError(f'reg_target: a tensor is needed, got {type(y).__name__}')
     y = y.detach().to(torch.float32).contiguous()
-    if y.dim() == 1:
-        assert y.shape[0] == B, (tuple(y.shape), C, B)
+    if tuple(y.shape) == (B,):
         return y, 0
-    assert tuple(y.shape) == (C, B), (tuple(y.shape), C, B)
-    return y, B
+    if tuple(y.shape) == (C, B):
+        return y, B
+    raise ValueError(f'reg_target: targets must have shape ({C}, {B}) or ({B},), got {tuple(y.shape)}')
 
 
-def gauss_nll_fwd(mu, var, y, ldy, obs_log_var, out):
-    """Writes the Gaussian nll of mu, var (S, C, B) contiguous into the one-float device tensor `out`."""
-    S, C, B = mu.shape
-    check(lib().vargp_gauss_nll_fwd(ptr(mu), ptr(var), ptr(y), ldy, ptr(obs_log_var), ptr(out), S, C, B, stream_ptr()),
-          'vargp_gauss_nll_fwd')
+gauss_target = reg_target
 
-
-def gauss_nll_bwd(mu, var, y, ldy, obs_log_var, seed, gmu, gvar, g_obs_log_var, nll=None):
-    """Seeded gradients of the Gaussian nll into gmu, gvar (S, C, B) and g_obs_log_var (C,); with `nll`, the value too."""
-    S, C, B = mu.shape
-    check(lib().vargp_gauss_nll_bwd(ptr(mu), ptr(var), ptr(y), ldy, ptr(obs_log_var), ptr(seed), ptr(gmu), ptr(gvar),
-                                    ptr(g_obs_log_var), ptr(nll), S, C, B, stream_ptr()), 'vargp_gauss_nll_bwd')
-
-
-class _GaussNll(Function):
-    @staticmethod
-    def forward(ctx, mu, var, y, obs_log_var):
-        require_device(mu, var, y, obs_log_var)
-        mu, var, obs_log_var = mu.contiguous(), var.contiguous(), obs_log_var.contiguous()
-        S, C, B = mu.shape
-        assert var.shape == mu.shape and obs_log_var.shape == (C,), (mu.shape, var.shape, obs_log_var.shape)
-        yt, ldy = gauss_target(y, C, B)
-        nll = torch.empty((), dtype=torch.float32, device=mu.device)
-        gauss_nll_fwd(mu, var, yt, ldy, obs_log_var, nll)
-        ctx.save_for_backward(mu, var, yt, obs_log_var)
-        ctx.ldy = ldy
-        return nll
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        mu, var, yt, obs_log_var = ctx.saved_tensors
-        gmu, gvar, golv = torch.empty_like(mu), torch.empty_like(var), torch.empty_like(obs_log_var)
-        gauss_nll_bwd(mu, var, yt, ctx.ldy, obs_log_var, g.float().contiguous(), gmu, gvar, golv)
-        return gmu, gvar, None, golv
-
-
-def gauss_nll(mu, var, y, obs_log_var):
-    """sum_b mean_{s,c} -log N(y | mu, var + exp(obs_log_var[c]))  (GaussianLikelihood.loss, likelihoods.py:92-107);
-    y (C, B) or (B,).  Differentiable in mu, var and obs_log_var."""
-    return _GaussNll.apply(mu, var, y, obs_log_var)
-
-
-# ------------------------------------------------------------------------------------------------
-# Bernoulli likelihood (independent outputs; csrc/bernoulli_lik.hip -- not in the reference)
-# ------------------------------------------------------------------------------------------------
 BERNOULLI_LINKS = {'probit': 0, 'logit': 1}
 
 
@@ -756,26 +725,107 @@ def bernoulli_target(y, C, B):
     raise ValueError(f'bernoulli_target: targets must have shape ({C}, {B}) or ({B},), got {tuple(y.shape)}')
 
 
-def _bernoulli_ws(S, C, B, device):
-    return scratch(lib().vargp_bernoulli_workspace_bytes(S, C, B), device)
+def studentt_lognorm(df):
+    """lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi) / 2 in double on the host: the two lgamma cancel in fp32 at large nu."""
+    df = float(df)
+    if not df > 0.0:
+        raise ValueError(f'Student-t degrees of freedom must be > 0, got {df!r}')
+    return math.lgamma(0.5 * (df + 1.0)) - math.lgamma(0.5 * df) - 0.5 * math.log(df * math.pi)
 
 
-def bernoulli_nll_fwd(mu, var, t, ldt, labels, link, out):
-    """Writes the Bernoulli nll of mu, var (S, C, B) contiguous into the one-float device tensor `out`; (t, ldt, labels) from
-    bernoulli_target, link 0 (probit) / 1 (logit)."""
+# kind -> (target function, do the nll entries take a workspace, does nll_bwd write a parameter gradient)
+_LIK = {'gauss': (reg_target, False, True), 'bernoulli': (bernoulli_target, True, False),
+        'poisson': (reg_target, True, False), 'studentt': (reg_target, True, True)}
+
+
+def lik_target(kind, y, C, B):
+    return _LIK[kind][0](y, C, B)
+
+
+def _lik_call(kind, entry, mu, var, target, extra, outs, ws=None):
+    """vargp_<kind>_<entry>(mu, var, *target, *extra, *outs, S, C, B, [ws, ws_bytes], stream).  Tensors and None go as pointers,
+    host scalars as they are.  ws: None -- the entry takes no workspace; False -- it gets a null one; True -- pooled scratch."""
     S, C, B = mu.shape
-    ws = _bernoulli_ws(S, C, B, mu.device)
-    check(lib().vargp_bernoulli_nll_fwd(ptr(mu), ptr(var), ptr(t), ldt, ptr(labels), link, ptr(out), S, C, B, ptr(ws),
-                                        ws.numel() * 4, stream_ptr()), 'vargp_bernoulli_nll_fwd')
+    tail = ()
+    if ws is not None:
+        buf = scratch(getattr(lib(), f'vargp_{kind}_workspace_bytes')(S, C, B), mu.device) if ws else None
+        tail = (ptr(buf), buf.numel() * 4 if ws else 0)
+    name = f'vargp_{kind}_{entry}'
+    args = [ptr(a) if a is None or torch.is_tensor(a) else a for a in (mu, var, *target, *extra, *outs)]
+    check(getattr(lib(), name)(*args, S, C, B, *tail, stream_ptr()), name)
 
 
-def bernoulli_nll_bwd(mu, var, t, ldt, labels, link, seed, gmu, gvar, nll=None):
-    """Seeded gradients of the Bernoulli nll into gmu, gvar (S, C, B); with `nll`, the value too (bit-equal to the forward's)."""
-    S, C, B = mu.shape
-    ws = _bernoulli_ws(S, C, B, mu.device) if nll is not None else None
-    check(lib().vargp_bernoulli_nll_bwd(ptr(mu), ptr(var), ptr(t), ldt, ptr(labels), link, ptr(seed), ptr(gmu), ptr(gvar),
-                                        ptr(nll), S, C, B, ptr(ws), ws.numel() * 4 if ws is not None else 0, stream_ptr()),
-          'vargp_bernoulli_nll_bwd')
+def lik_nll_fwd(kind, mu, var, target, extra, out):
+    """Writes the nll of mu, var (S, C, B) fp32 contiguous into the one-float device tensor `out`."""
+    _lik_call(kind, 'nll_fwd', mu, var, target, extra, (out,), ws=True if _LIK[kind][1] else None)
+
+
+def lik_nll_bwd(kind, mu, var, target, extra, seed, gmu, gvar, gparam=None, nll=None):
+    """ONE launch: the seeded gradients of the nll into gmu, gvar (S, C, B) and, for the kinds with a parameter, gparam (C,);
+    with `nll`, the value too (bit-equal to the forward's).  Scratch is fetched only where the launch needs it (the value, or
+    a parameter gradient): a captured training step without either sees no allocation."""
+    _, has_ws, has_param = _LIK[kind]
+    outs = (seed, gmu, gvar) + ((gparam,) if has_param else ()) + (nll,)
+    _lik_call(kind, 'nll_bwd', mu, var, target, extra, outs, ws=(nll is not None or has_param) if has_ws else None)
+
+
+class _LikNll(Function):
+    @staticmethod
+    def forward(ctx, kind, mu, var, y, param, *consts):
+        require_device(mu, var, y, param)
+        mu, var = mu.contiguous(), var.contiguous()
+        S, C, B = mu.shape
+        assert var.shape == mu.shape and mu.dtype == torch.float32 and var.dtype == torch.float32, (mu.shape, var.shape, mu.dtype, var.dtype)
+        if param is not None:
+            param = param.contiguous()
+            assert param.shape == (C,) and param.dtype == torch.float32, (mu.shape, param.shape, param.dtype)
+        target = lik_target(kind, y, C, B)
+        extra = (() if param is None else (param,)) + consts
+        nll = torch.empty((), dtype=torch.float32, device=mu.device)
+        lik_nll_fwd(kind, mu, var, target, extra, nll)
+        ctx.save_for_backward(mu, var, param)
+        ctx.kind, ctx.target, ctx.consts = kind, target, consts
+        return nll
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        mu, var, param = ctx.saved_tensors
+        gmu, gvar = torch.empty_like(mu), torch.empty_like(var)
+        gparam = torch.empty_like(param) if _LIK[ctx.kind][2] else None
+        extra = (() if param is None else (param,)) + ctx.consts
+        lik_nll_bwd(ctx.kind, mu, var, ctx.target, extra, g.float().contiguous(), gmu, gvar, gparam)
+        return (None, gmu, gvar, None, gparam) + (None,) * len(ctx.consts)
+
+
+def lik_nll(kind, mu, var, y, param, *consts):
+    """The nll of mu, var (S, C, B) under the likelihood `kind`; y as its *_target takes it; param: the output's own parameter
+    (C,) or None; consts: the host constants behind it in `extra`.  Differentiable in mu, var and param."""
+    return _LikNll.apply(kind, mu, var, y, param, *consts)
+
+
+def gauss_nll(mu, var, y, obs_log_var):
+    """sum_b mean_{s,c} -log N(y | mu, var + exp(obs_log_var[c]))  (GaussianLikelihood.loss, likelihoods.py:92-107);
+    y (C, B) or (B,).  Differentiable in mu, var and obs_log_var."""
+    return lik_nll('gauss', mu, var, y, obs_log_var)
+
+
+def bernoulli_nll(mu, var, y, link='probit'):
+    """- sum_b sum_c mean_s E_{f ~ N(mu, var)} log Lambda((2 t - 1) f) by the 20-node Gauss-Hermite rule
+    (BernoulliLikelihood.loss); y as bernoulli_target takes it.  Differentiable in mu and var."""
+    return lik_nll('bernoulli', mu, var, y, None, bernoulli_link(link))
+
+
+def poisson_nll(mu, var, y):
+    """- sum_b sum_c mean_s [y mu - exp(mu + var / 2) - lgamma(y + 1)]  (PoissonLikelihood.loss); y (C, B) or (B,), non-negative.
+    Differentiable in mu and var."""
+    return lik_nll('poisson', mu, var, y, None)
+
+
+def studentt_nll(mu, var, y, log_scale, df=4.0):
+    """- sum_b sum_c mean_s E_{f ~ N(mu, var)} log t_df((y - f) / exp(log_scale[c])) / exp(log_scale[c]) by the 20-node
+    Gauss-Hermite rule (StudentTLikelihood.loss); y (C, B) or (B,).  Differentiable in mu, var and log_scale."""
+    return lik_nll('studentt', mu, var, y, log_scale, float(df), studentt_lognorm(df))
 
 
 def bernoulli_predict(mu, var, link='probit'):
@@ -789,73 +839,6 @@ def bernoulli_predict(mu, var, link='probit'):
     return probs
 
 
-class _BernoulliNll(Function):
-    @staticmethod
-    def forward(ctx, mu, var, y, link):
-        require_device(mu, var, y)
-        mu, var = mu.contiguous(), var.contiguous()
-        S, C, B = mu.shape
-        assert var.shape == mu.shape and mu.dtype == torch.float32 and var.dtype == torch.float32, (mu.shape, var.shape, mu.dtype, var.dtype)
-        t, ldt, labels = bernoulli_target(y, C, B)
-        nll = torch.empty((), dtype=torch.float32, device=mu.device)
-        bernoulli_nll_fwd(mu, var, t, ldt, labels, link, nll)
-        ctx.save_for_backward(mu, var, t, labels)
-        ctx.ldt, ctx.link = ldt, link
-        return nll
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        mu, var, t, labels = ctx.saved_tensors
-        gmu, gvar = torch.empty_like(mu), torch.empty_like(var)
-        bernoulli_nll_bwd(mu, var, t, ctx.ldt, labels, ctx.link, g.float().contiguous(), gmu, gvar)
-        return gmu, gvar, None, None
-
-
-def bernoulli_nll(mu, var, y, link='probit'):
-    """- sum_b sum_c mean_s E_{f ~ N(mu, var)} log Lambda((2 t - 1) f) by the 20-node Gauss-Hermite rule
-    (BernoulliLikelihood.loss); y as bernoulli_target takes it.  Differentiable in mu and var."""
-    return _BernoulliNll.apply(mu, var, y, bernoulli_link(link))
-
-
-# ------------------------------------------------------------------------------------------------
-# Poisson (log link) and Student-t likelihoods (independent outputs; csrc/reg_lik.hip -- not in the reference)
-# ------------------------------------------------------------------------------------------------
-def reg_target(y, C, B):
-    """A regression / count target as the Poisson and Student-t kernels read it: (fp32 contiguous tensor, row stride ldy) --
-    (C, B) -> ldy = B, (B,) -> ldy = 0 (one row shared by every output).  Values are not checked."""
-    if not torch.is_tensor(y):
-        raise TypeError(f'reg_target: a tensor is needed, got {type(y).__name__}')
-    y = y.detach().to(torch.float32).contiguous()
-    if tuple(y.shape) == (B,):
-        return y, 0
-    if tuple(y.shape) == (C, B):
-        return y, B
-    raise ValueError(f'reg_target: targets must have shape ({C}, {B}) or ({B},), got {tuple(y.shape)}')
-
-
-def _reg_ws(name, S, C, B, device):
-    return scratch(getattr(lib(), f'vargp_{name}_workspace_bytes')(S, C, B), device)
-
-
-def poisson_nll_fwd(mu, var, y, ldy, out):
-    """Writes the Poisson nll of mu, var (S, C, B) contiguous into the one-float device tensor `out`; (y, ldy) from
-    reg_target."""
-    S, C, B = mu.shape
-    ws = _reg_ws('poisson', S, C, B, mu.device)
-    check(lib().vargp_poisson_nll_fwd(ptr(mu), ptr(var), ptr(y), ldy, ptr(out), S, C, B, ptr(ws), ws.numel() * 4,
-                                      stream_ptr()), 'vargp_poisson_nll_fwd')
-
-
-def poisson_nll_bwd(mu, var, y, ldy, seed, gmu, gvar, nll=None):
-    """Seeded gradients of the Poisson nll into gmu, gvar (S, C, B); with `nll`, the value too (bit-equal to the forward's)."""
-    S, C, B = mu.shape
-    ws = _reg_ws('poisson', S, C, B, mu.device) if nll is not None else None
-    check(lib().vargp_poisson_nll_bwd(ptr(mu), ptr(var), ptr(y), ldy, ptr(seed), ptr(gmu), ptr(gvar), ptr(nll), S, C, B,
-                                      ptr(ws), ws.numel() * 4 if ws is not None else 0, stream_ptr()),
-          'vargp_poisson_nll_bwd')
-
-
 def poisson_predict(mu, var):
     """rate (S, C, B) = E exp(f) = exp(mu + var / 2)."""
     require_device(mu, var)
@@ -866,95 +849,6 @@ def poisson_predict(mu, var):
     return rate
 
 
-class _PoissonNll(Function):
-    @staticmethod
-    def forward(ctx, mu, var, y):
-        require_device(mu, var, y)
-        mu, var = mu.contiguous(), var.contiguous()
-        S, C, B = mu.shape
-        assert var.shape == mu.shape and mu.dtype == torch.float32 and var.dtype == torch.float32, (mu.shape, var.shape, mu.dtype, var.dtype)
-        yt, ldy = reg_target(y, C, B)
-        nll = torch.empty((), dtype=torch.float32, device=mu.device)
-        poisson_nll_fwd(mu, var, yt, ldy, nll)
-        ctx.save_for_backward(mu, var, yt)
-        ctx.ldy = ldy
-        return nll
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        mu, var, yt = ctx.saved_tensors
-        gmu, gvar = torch.empty_like(mu), torch.empty_like(var)
-        poisson_nll_bwd(mu, var, yt, ctx.ldy, g.float().contiguous(), gmu, gvar)
-        return gmu, gvar, None
-
-
-def poisson_nll(mu, var, y):
-    """- sum_b sum_c mean_s [y mu - exp(mu + var / 2) - lgamma(y + 1)]  (PoissonLikelihood.loss); y (C, B) or (B,), non-negative.
-    Differentiable in mu and var."""
-    return _PoissonNll.apply(mu, var, y)
-
-
-def studentt_lognorm(df):
-    """lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi) / 2 in double on the host: the two lgamma cancel in fp32 at large nu."""
-    df = float(df)
-    if not df > 0.0:
-        raise ValueError(f'Student-t degrees of freedom must be > 0, got {df!r}')
-    return math.lgamma(0.5 * (df + 1.0)) - math.lgamma(0.5 * df) - 0.5 * math.log(df * math.pi)
-
-
-def studentt_nll_fwd(mu, var, y, ldy, log_scale, df, out):
-    """Writes the Student-t nll of mu, var (S, C, B) contiguous into the one-float device tensor `out`; (y, ldy) from
-    reg_target, log_scale (C,), df a host float."""
-    S, C, B = mu.shape
-    ws = _reg_ws('studentt', S, C, B, mu.device)
-    check(lib().vargp_studentt_nll_fwd(ptr(mu), ptr(var), ptr(y), ldy, ptr(log_scale), df, studentt_lognorm(df), ptr(out), S, C,
-                                       B, ptr(ws), ws.numel() * 4, stream_ptr()), 'vargp_studentt_nll_fwd')
-
-
-def studentt_nll_bwd(mu, var, y, ldy, log_scale, df, seed, gmu, gvar, g_log_scale, nll=None):
-    """Seeded gradients of the Student-t nll into gmu, gvar (S, C, B) and g_log_scale (C,); with `nll`, the value too
-    (bit-equal to the forward's)."""
-    S, C, B = mu.shape
-    ws = _reg_ws('studentt', S, C, B, mu.device)
-    check(lib().vargp_studentt_nll_bwd(ptr(mu), ptr(var), ptr(y), ldy, ptr(log_scale), df, studentt_lognorm(df), ptr(seed),
-                                       ptr(gmu), ptr(gvar), ptr(g_log_scale), ptr(nll), S, C, B, ptr(ws), ws.numel() * 4,
-                                       stream_ptr()), 'vargp_studentt_nll_bwd')
-
-
-class _StudentTNll(Function):
-    @staticmethod
-    def forward(ctx, mu, var, y, log_scale, df):
-        require_device(mu, var, y, log_scale)
-        mu, var, log_scale = mu.contiguous(), var.contiguous(), log_scale.contiguous()
-        S, C, B = mu.shape
-        assert var.shape == mu.shape and log_scale.shape == (C,), (mu.shape, var.shape, log_scale.shape)
-        assert mu.dtype == torch.float32 and var.dtype == torch.float32 and log_scale.dtype == torch.float32
-        yt, ldy = reg_target(y, C, B)
-        nll = torch.empty((), dtype=torch.float32, device=mu.device)
-        studentt_nll_fwd(mu, var, yt, ldy, log_scale, df, nll)
-        ctx.save_for_backward(mu, var, yt, log_scale)
-        ctx.ldy, ctx.df = ldy, df
-        return nll
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        mu, var, yt, log_scale = ctx.saved_tensors
-        gmu, gvar, gls = torch.empty_like(mu), torch.empty_like(var), torch.empty_like(log_scale)
-        studentt_nll_bwd(mu, var, yt, ctx.ldy, log_scale, ctx.df, g.float().contiguous(), gmu, gvar, gls)
-        return gmu, gvar, None, gls, None
-
-
-def studentt_nll(mu, var, y, log_scale, df=4.0):
-    """- sum_b sum_c mean_s E_{f ~ N(mu, var)} log t_df((y - f) / exp(log_scale[c])) / exp(log_scale[c]) by the 20-node
-    Gauss-Hermite rule (StudentTLikelihood.loss); y (C, B) or (B,).  Differentiable in mu, var and log_scale."""
-    return _StudentTNll.apply(mu, var, y, log_scale, float(df))
-
-
-# ------------------------------------------------------------------------------------------------
-# held-out log predictive density, every likelihood (csrc/lpd.hip -- not in the reference).  No autograd.
-# ------------------------------------------------------------------------------------------------
 def _lpd_moments(mu, var, *others):
     """The moments as the LPD kernels read them: fp32, contiguous, (S, C, B) each, on the device like every other operand."""
     require_device(mu, var, *others)
@@ -962,12 +856,6 @@ def _lpd_moments(mu, var, *others):
     assert mu.dim() == 3 and var.shape == mu.shape and mu.dtype == torch.float32 and var.dtype == torch.float32, \
         (mu.shape, var.shape, mu.dtype, var.dtype)
     return mu, var
-
-
-def _lpd_outputs(mu, per_output):
-    S, C, B = mu.shape
-    lpd = torch.empty(B, dtype=torch.float32, device=mu.device)
-    return lpd, (torch.empty(C, B, dtype=torch.float32, device=mu.device) if per_output else None)
 
 
 def softmax_lpd(mu, var, eps, y):
@@ -978,65 +866,46 @@ def softmax_lpd(mu, var, eps, y):
     assert y.dtype == torch.int64 and eps.dtype == torch.float32
     S, F, C, B = eps.shape
     assert mu.shape == (S, C, B) and y.shape == (B,), (mu.shape, eps.shape, y.shape)
-    lpd, _ = _lpd_outputs(mu, False)
+    lpd = torch.empty(B, dtype=torch.float32, device=mu.device)
     check(lib().vargp_softmax_lpd(ptr(mu), ptr(var), ptr(eps), ptr(y), ptr(lpd), S, F, C, B, stream_ptr()), 'vargp_softmax_lpd')
     return lpd
 
 
-def _lpd_result(lpd, lpd_out, per_output):
-    return (lpd, lpd_out) if per_output else lpd
+def lik_lpd(kind, mu, var, y, extra, per_output=False):
+    """lpd (B,) = logsumexp_s sum_c lp[s, c, b] - log S, the joint density of a point's targets under the mixture over
+    hyper-samples (lp: the log marginal likelihood of one target under f ~ N(mu, var)); per_output: (lpd, lpd_out (C, B)) with
+    lpd_out = logsumexp_s lp[s, c, b] - log S.  y as the kind's *_target takes it; a tensor in `extra` is the parameter (C,)."""
+    mu, var = _lpd_moments(mu, var, y, *(a for a in extra if torch.is_tensor(a)))
+    S, C, B = mu.shape
+    extra = tuple(a.detach().to(torch.float32).contiguous() if torch.is_tensor(a) else a for a in extra)
+    assert all(a.shape == (C,) for a in extra if torch.is_tensor(a)), (mu.shape, extra)
+    lpd = torch.empty(B, dtype=torch.float32, device=mu.device)
+    out = torch.empty(C, B, dtype=torch.float32, device=mu.device) if per_output else None
+    _lik_call(kind, 'lpd', mu, var, lik_target(kind, y, C, B), extra, (lpd, out))
+    return (lpd, out) if per_output else lpd
 
 
 def gauss_lpd(mu, var, y, obs_log_var, per_output=False):
-    """lpd (B,) = logsumexp_s sum_c log N(y | mu, var + exp(obs_log_var[c])) - log S, the joint density of a point's targets under
-    the mixture over hyper-samples; per_output: also lpd_out (C, B) = logsumexp_s log N(...) - log S.  y as gauss_target takes it."""
-    mu, var = _lpd_moments(mu, var, y, obs_log_var)
-    S, C, B = mu.shape
-    olv = obs_log_var.detach().to(torch.float32).contiguous()
-    assert olv.shape == (C,), (mu.shape, olv.shape)
-    yt, ldy = gauss_target(y, C, B)
-    lpd, out = _lpd_outputs(mu, per_output)
-    check(lib().vargp_gauss_lpd(ptr(mu), ptr(var), ptr(yt), ldy, ptr(olv), ptr(lpd), ptr(out), S, C, B, stream_ptr()),
-          'vargp_gauss_lpd')
-    return _lpd_result(lpd, out, per_output)
+    """lik_lpd with lp = log N(y | mu, var + exp(obs_log_var[c])); y as gauss_target takes it."""
+    return lik_lpd('gauss', mu, var, y, (obs_log_var,), per_output)
 
 
 def bernoulli_lpd(mu, var, y, link='probit', per_output=False):
-    """lpd (B,) = logsumexp_s sum_c lp[s, c, b] - log S with lp = log Phi(s mu / sqrt(1 + var)) (probit, closed form; -inf below
-    z ~ -37, where fp64 erfc underflows) or the 20-node rule on the logistic function (logit); y as bernoulli_target takes it."""
-    mu, var = _lpd_moments(mu, var, y)
-    S, C, B = mu.shape
-    t, ldt, labels = bernoulli_target(y, C, B)
-    lpd, out = _lpd_outputs(mu, per_output)
-    check(lib().vargp_bernoulli_lpd(ptr(mu), ptr(var), ptr(t), ldt, ptr(labels), bernoulli_link(link), ptr(lpd), ptr(out), S, C, B,
-                                    stream_ptr()), 'vargp_bernoulli_lpd')
-    return _lpd_result(lpd, out, per_output)
+    """lik_lpd with lp = log Phi(s mu / sqrt(1 + var)) (probit, closed form; -inf below z ~ -37, where fp64 erfc underflows) or
+    the 20-node rule on the logistic function (logit); y as bernoulli_target takes it."""
+    return lik_lpd('bernoulli', mu, var, y, (bernoulli_link(link),), per_output)
 
 
 def poisson_lpd(mu, var, y, per_output=False):
-    """lpd (B,) = logsumexp_s sum_c lp[s, c, b] - log S, lp = logsumexp_k(log w_k + y f_k - exp(f_k) - lgamma(y + 1)) on the 20-node
-    rule; y as reg_target takes it."""
-    mu, var = _lpd_moments(mu, var, y)
-    S, C, B = mu.shape
-    yt, ldy = reg_target(y, C, B)
-    lpd, out = _lpd_outputs(mu, per_output)
-    check(lib().vargp_poisson_lpd(ptr(mu), ptr(var), ptr(yt), ldy, ptr(lpd), ptr(out), S, C, B, stream_ptr()), 'vargp_poisson_lpd')
-    return _lpd_result(lpd, out, per_output)
+    """lik_lpd with lp = logsumexp_k(log w_k + y f_k - exp(f_k) - lgamma(y + 1)) on the 20-node rule; y as reg_target takes it."""
+    return lik_lpd('poisson', mu, var, y, (), per_output)
 
 
 def studentt_lpd(mu, var, y, log_scale, df=4.0, per_output=False):
-    """lpd (B,) = logsumexp_s sum_c lp[s, c, b] - log S, lp = logsumexp_k(log w_k + K_c - (df + 1) / 2 log1p((y - f_k)^2 /
-    (df sigma_c^2))) on the 20-node rule; y as reg_target takes it, log_scale (C,)."""
-    mu, var = _lpd_moments(mu, var, y, log_scale)
-    S, C, B = mu.shape
-    ls = log_scale.detach().to(torch.float32).contiguous()
-    assert ls.shape == (C,), (mu.shape, ls.shape)
-    yt, ldy = reg_target(y, C, B)
-    lpd, out = _lpd_outputs(mu, per_output)
-    df = float(df)
-    check(lib().vargp_studentt_lpd(ptr(mu), ptr(var), ptr(yt), ldy, ptr(ls), df, studentt_lognorm(df), ptr(lpd), ptr(out), S, C, B,
-                                   stream_ptr()), 'vargp_studentt_lpd')
-    return _lpd_result(lpd, out, per_output)
+    """lik_lpd with lp = logsumexp_k(log w_k + K_c - (df + 1) / 2 log1p((y - f_k)^2 / (df sigma_c^2))) on the 20-node rule; y as
+    reg_target takes it, log_scale (C,)."""
+    return lik_lpd('studentt', mu, var, y, (log_scale, float(df), studentt_lognorm(df)), per_output)
+
 
 # ------------------------------------------------------------------------------------------------
 # variational hyper-parameters
