@@ -168,6 +168,23 @@ int vargp_predictive_cov(const float* theta, const float* X, const float* P, con
                          int Mt, int B, int D, int nu2, void* ws, size_t ws_bytes, vargp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Random-Fourier-feature paths (csrc/rff.hip; nothing of this is in the reference): the feature matrix of a point set times a
+ * block of weight columns, for every hyper-sample s and output c, without the features ever being written to memory.  With
+ * theta [S, D+1] (log lengthscales, log gamma), omega [R, D] the frequencies and coef [S*C, 2R, N]:
+ *   p[s, i, r]      = sum_d X[i, d] omega[r, d] / exp(theta[s, d])
+ *   Phi_s(X)[i, :]  = exp(theta[s, D]) / sqrt(R) [cos p[s, i, :] | sin p[s, i, :]]
+ *   out[s, c, i, k] = sum_j Phi_s(X)[i, j] coef[s, c, j, k]                  out [S*C, n, N], dense, fp32
+ * x_shared = 1: X [n, D], one point set for all outputs (the C N columns of a hyper-sample share one set of features);
+ * x_shared = 0: X [C, n, D], a point set per output.  One pre-scaling launch (omega / lengthscales into the workspace) and ONE
+ * launch for everything else: f32 MFMA phase tiles, sin / cos on the phase reduced to revolutions (accurate at any |p|), the
+ * second MFMA product accumulated over all of R by the workgroup that owns the output tile -- no atomics, two calls are bitwise
+ * equal.  Any n, D, R, N >= 1; S*C <= 65535; C*N <= 2^22.
+ */
+size_t vargp_rff_paths_workspace_bytes(int S, int D, int R);
+int vargp_rff_paths(const float* theta, const float* X, const float* omega, const float* coef, float* out, int S, int C, int n,
+                    int D, int R, int N, int x_shared, void* ws, size_t ws_bytes, vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Lloyd's two steps for G independent sets of K centres Z [G, K, D] over one data matrix X [N, D] (the model's z [C, M, D]: one
  * set per output).  Data-dependent initialisation of the inducing points; nothing of this is in the reference, whose inducing
  * points start at random data points (var_gp/vargp.py:207).

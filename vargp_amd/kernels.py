@@ -66,6 +66,12 @@ class RBFKernel(nn.Module):
         """gamma^2 as (S, 1, 1)  (kernels.py:58-60)."""
         return (2.0 * kern_samples[..., -1:]).exp().unsqueeze(-2)
 
+    def spectral_frequencies(self, n_features, device):
+        """omega (R, D), R = n_features draws from the spectral law of the kernel at unit lengthscales -- N(0, I) for
+        exp(-d2 / 2) -- so that gamma^2 / R sum_r cos((x - y) / lengthscale . omega_r) -> k(x, y) (paths.py; not in the
+        reference).  Pure torch, any device; the noise is noise.draw('rff_omega', (R, D))."""
+        return noise.draw('rff_omega', (int(n_features), self.log_mean.shape[0] - 1), device)
+
     def sample_hypers(self, n_hypers):
         """reparameterised theta ~ N(log_mean, exp(log_logvar))  (kernels.py:62-68)."""
         if self.map_est:
@@ -102,6 +108,15 @@ class MaternKernel(RBFKernel):
     def compute_cov(self, kern_samples, x, P, W):
         # (one op for native=False and native=True alike)
         return ops.predictive_cov(kern_samples, x, P, W, nu2=int(round(2 * self.nu)))
+
+    def spectral_frequencies(self, n_features, device):
+        """The Matern kernel is a scale mixture of RBF kernels, so its spectral law is multivariate t with nu2 = 2 nu degrees
+        of freedom: omega_r = g_r sqrt(nu2 / chi2_r), g as for the RBF kernel and chi2_r the sum of the squares of the nu2
+        standard normals noise.draw('rff_mix', (R, nu2))[r]."""
+        nu2 = int(round(2 * self.nu))
+        g = super().spectral_frequencies(n_features, device)
+        chi2 = noise.draw('rff_mix', (int(n_features), nu2), device).square().sum(-1, keepdim=True)
+        return g * (nu2 / chi2).sqrt()
 
 
 def native_code(kernel):

@@ -530,6 +530,31 @@ def predictive_cov(theta, X, P, W, nu2=0):
     return out
 
 
+def rff_paths(theta, X, omega, coef, x_shared):
+    """Random-Fourier-feature paths (csrc/rff.hip), no autograd: theta (S, D+1); omega (R, D); coef (S, C, 2R, N);
+    X (n, D) with x_shared (one point set for all outputs) or (C, n, D) without  ->  out (S, C, n, N) = Phi_s(X) coef[s, c] with
+    Phi_s(X) = gamma_s / sqrt(R) [cos p | sin p], p = (X / lengthscale_s) omega^T.  The S n 2R features are never stored; two
+    calls are bitwise equal."""
+    require_device(theta, X, omega, coef)
+    theta, X, omega, coef = (t.detach().contiguous() for t in (theta, X, omega, coef))
+    assert all(t.dtype == torch.float32 for t in (theta, X, omega, coef)), (theta.dtype, X.dtype, omega.dtype, coef.dtype)
+    S, D = theta.shape[0], theta.shape[1] - 1
+    assert omega.dim() == 2 and omega.shape[1] == D, (omega.shape, theta.shape)
+    R = omega.shape[0]
+    assert coef.dim() == 4 and coef.shape[0] == S and coef.shape[2] == 2 * R, (coef.shape, S, R)
+    C, N = coef.shape[1], coef.shape[3]
+    if x_shared:
+        assert X.dim() == 2 and X.shape[1] == D, (X.shape, theta.shape)
+    else:
+        assert X.dim() == 3 and X.shape[0] == C and X.shape[2] == D, (X.shape, C, D)
+    n = X.shape[-2]
+    out = torch.empty(S, C, n, N, dtype=torch.float32, device=X.device)
+    ws = scratch(lib().vargp_rff_paths_workspace_bytes(S, D, R), X.device)
+    check(lib().vargp_rff_paths(ptr(theta), ptr(X), ptr(omega), ptr(coef), ptr(out), S, C, n, D, R, N, int(bool(x_shared)),
+                                ptr(ws), ws.numel() * 4, stream_ptr()), 'vargp_rff_paths')
+    return out
+
+
 # Lloyd's two steps for G sets of K centres over one data matrix (csrc/kmeans.hip -- not in the reference).  No autograd.
 
 def _kmeans_args(X, Z):

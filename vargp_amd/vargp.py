@@ -25,6 +25,7 @@ from .kernels import RBFKernel, DeepRBFKernel, MaternKernel, native_code
 from .likelihoods import (BernoulliLikelihood, GaussianLikelihood, MulticlassSoftmax, PoissonLikelihood, StudentTLikelihood,
                           is_external, n_f, predict_batch_dim)
 from .ops import LOWER
+from .paths import PosteriorPaths
 
 
 _KERNEL_NU = {'rbf': None, 'matern12': 0.5, 'matern32': 1.5, 'matern52': 2.5}   # create_clf(kernel=)
@@ -539,7 +540,8 @@ class VARGP(nn.Module):
         it); n_samples draws per hyper-sample.  The factorisation is ops.chol: a cov that is not positive definite after the
         jitter is reported by the Cholesky error mode in force (ops.set_cholesky_error_mode).  Memory: cov and its factor,
         2 x 4 S C B^2 bytes.  A large x must be sampled in blocks by the caller, each under the same injected eps_theta; the
-        blocks are then independent given the hyper-sample (no cross-covariance between blocks is formed)."""
+        blocks are then independent given the hyper-sample (no cross-covariance between blocks is formed); sample_paths draws
+        functions that can be evaluated at any number of points instead."""
         with torch.no_grad():
             mu, cov = self.predict_f(x, full_cov=True)
             S, C, B = mu.shape
@@ -547,6 +549,15 @@ class VARGP(nn.Module):
             eps = noise.draw('eps_fs', (int(n_samples), S, C, B), x.device)
             f = ops.bgemm(L, eps.permute(1, 2, 3, 0), D=mu.unsqueeze(-1), beta=1.0, triA=LOWER)       # (S, C, B, n)
             return f.permute(3, 0, 1, 2).contiguous()
+
+    def sample_paths(self, n_paths=1, n_features=1024):
+        """Pathwise draws of the latent functions (paths.PosteriorPaths): paths = gp.sample_paths(n); paths(x) -> (n, S, C, B),
+        the layout of sample_f, for any x and as often as asked -- every call evaluates the SAME n functions per hyper-sample
+        and output, at a cost linear in B (K(z, x) and n_features random Fourier features per point, csrc/rff.hip).  The
+        draw is frozen: training the model afterwards does not change it.  Every model (previous tasks or none, ep_var_mean on
+        or off, any kernel, any likelihood); the mean over draws is predict_f's, the covariance tends to predict_f's as
+        n_features grows."""
+        return PosteriorPaths(self, n_paths=n_paths, n_features=n_features)
 
     @staticmethod
     def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None,
