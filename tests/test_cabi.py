@@ -49,3 +49,23 @@ def test_product_does_not_import_oracle():
             if f.endswith('.py'):
                 src = open(os.path.join(dirpath, f)).read()
                 assert not re.search(r'^\s*(from|import)\s+oracle', src, flags=re.M), f
+
+
+# (S, C, M, N, D) -> (rbf fwd, rbf bwd, matern fwd, matern bwd) bytes, recorded from the build before the two gram ops were put
+# on one workspace carve (csrc/gram.hip); D = 2, 32 | 33, 784: both sides of kRbfDirectD
+WORKSPACE_BYTES = {
+    (1, 1, 1, 1, 1): (1792, 2048, 1280, 2560),
+    (2, 3, 40, 72, 2): (143104, 78336, 3584, 81152),
+    (2, 3, 40, 72, 32): (160256, 158720, 3584, 161536),
+    (2, 3, 40, 72, 33): (161280, 161792, 161280, 322048),
+    (3, 10, 100, 512, 784): (17188352, 63804416, 17188352, 80982784),
+}
+
+
+@pytest.mark.parametrize('shape', sorted(WORKSPACE_BYTES))
+def test_gram_workspace_bytes_are_unchanged(shape):
+    """Callers size their scratch with these host-only functions: the byte counts are part of the C ABI."""
+    from vargp_amd._lib import lib
+    got = tuple(f(*shape, backward) for f in (lib().vargp_rbf_workspace_bytes, lib().vargp_matern_workspace_bytes)
+                for backward in (0, 1))
+    assert got == WORKSPACE_BYTES[shape]

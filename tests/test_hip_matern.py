@@ -1,4 +1,6 @@
-"""GPU: the Matern kernel (nu = 1/2, 3/2, 5/2) -- vargp_matern_gram_{fwd,bwd}, ops.matern_gram, kernels.MaternKernel.
+"""GPU: the Matern kernel (nu = 1/2, 3/2, 5/2) -- vargp_matern_gram_{fwd,bwd}, ops.matern_gram, kernels.MaternKernel -- and, at
+op level (section a and b), the RBF op built on the same frame (csrc/gram.hip): vargp_rbf_gram_{fwd,bwd}, ops.rbf_gram, as the
+kernel 'rbf' of the same matrix, K / gamma^2 = exp(-d2 / 2).
 
 The reference has no Matern kernel, so the yardstick is `matern_ref` below: an fp64 torch restatement of
 
@@ -30,6 +32,8 @@ pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 DIRECT_D = 32                      # csrc/common.h kRbfDirectD: D <= this takes the direct distance form, above it the GEMM
 NUS = (0.5, 1.5, 2.5)
+RBF = 'rbf'
+KERNELS = (RBF,) + NUS             # the op-level matrix: `nu` is RBF or a Matern nu
 EPS32 = float(np.finfo(np.float32).eps)
 
 
@@ -48,6 +52,8 @@ class _Sqrt0(torch.autograd.Function):
 
 
 def _k_of_d2(d2, nu):
+    if nu == RBF:
+        return (-0.5 * d2).exp()
     d2 = d2.clamp_min(0)
     if nu == 0.5:
         return (-_Sqrt0.apply(d2)).exp()
@@ -128,7 +134,7 @@ def _hip_op(theta, X, Y, gK, nu, shared):
     from vargp_amd import ops
     th, x = theta.to(DEV).requires_grad_(True), X.to(DEV).requires_grad_(True)
     y = None if Y is None else Y.to(DEV).requires_grad_(True)
-    K = ops.matern_gram(th, x, y, shared, nu)
+    K = ops.rbf_gram(th, x, y, shared) if nu == RBF else ops.matern_gram(th, x, y, shared, nu)
     gs = torch.autograd.grad(K, [th, x] + ([] if y is None else [y]), gK.to(DEV))
     torch.cuda.synchronize()
     out = dict(K=K.detach().cpu(), gtheta=gs[0].cpu(), gX=gs[1].cpu())
@@ -154,9 +160,12 @@ def _run_op_case(S, C, M, N, D, mode, nu, seed):
     r32 = _one_thread(lambda: _ref_op(theta, X, Y, gK, nu, torch.float32))
     got = _hip_op(theta, X, Y, gK, nu, mode == 'shared')
     _check_rule(got, r32, r64, f'nu={nu} {mode} S{S} C{C} M{M} N{N} D{D}')
+    if mode == 'self':             # exact gamma^2 diagonal (tests/test_hip_ops.py: test_rbf_gram_fwd_bwd)
+        g2 = torch.exp(2 * theta.to(DEV)[:, -1]).cpu()
+        assert torch.equal(got['K'].diagonal(dim1=-2, dim2=-1), g2.view(-1, 1, 1).expand(S, C, M))
 
 
-@pytest.mark.parametrize('nu', NUS)
+@pytest.mark.parametrize('nu', KERNELS)
 @pytest.mark.parametrize('mode', ['self', 'batched', 'shared'])
 @pytest.mark.parametrize('D', [1, 2, DIRECT_D, DIRECT_D + 1, 36, 784])
 def test_op_vs_fp64_over_D(nu, mode, D):
@@ -164,7 +173,7 @@ def test_op_vs_fp64_over_D(nu, mode, D):
     _run_op_case(2, 3, 40, 72, D, mode, nu, seed=100 + D)
 
 
-@pytest.mark.parametrize('nu', NUS)
+@pytest.mark.parametrize('nu', KERNELS)
 @pytest.mark.parametrize('mode', ['self', 'batched', 'shared'])
 @pytest.mark.parametrize('M,N', [(1, 1), (63, 65), (64, 64), (65, 63), (100, 257), (257, 100)])
 def test_op_vs_fp64_edge_sizes(nu, mode, M, N):
@@ -172,7 +181,7 @@ def test_op_vs_fp64_edge_sizes(nu, mode, M, N):
     _run_op_case(2, 2, M, N, 40, mode, nu, seed=7 * M + N)
 
 
-@pytest.mark.parametrize('nu', NUS)
+@pytest.mark.parametrize('nu', KERNELS)
 @pytest.mark.parametrize('mode', ['self', 'batched', 'shared'])
 @pytest.mark.parametrize('tile', [1, 2, 3])
 def test_op_vs_fp64_every_gemm_tile(nu, mode, tile):
@@ -187,7 +196,7 @@ def test_op_vs_fp64_every_gemm_tile(nu, mode, tile):
         lib().vargp_tune_gemm_tile(0)
 
 
-@pytest.mark.parametrize('nu', NUS)
+@pytest.mark.parametrize('nu', KERNELS)
 @pytest.mark.parametrize('D', [2, 40])
 def test_op_edge_sizes_direct_and_accumulate(nu, D):
     """accumulate = 1 of the C entry: a second backward adds into gX / gY / gtheta."""
@@ -197,16 +206,18 @@ def test_op_edge_sizes_direct_and_accumulate(nu, D):
     r64 = _ref_op(theta, X, Y, gK, nu, torch.float64)
     r32 = _one_thread(lambda: _ref_op(theta, X, Y, gK, nu, torch.float32))
     th, x, y, g = (t.to(DEV).contiguous() for t in (theta, X, Y, gK))
-    nu2 = int(round(2 * nu))
+    if nu == RBF:                  # (its forward and backward workspaces are laid out differently: the larger of the two)
+        ws_bytes, fwd, bwd, kind = lib().vargp_rbf_workspace_bytes, lib().vargp_rbf_gram_fwd, lib().vargp_rbf_gram_bwd, (0,)
+    else:
+        ws_bytes, fwd, bwd = lib().vargp_matern_workspace_bytes, lib().vargp_matern_gram_fwd, lib().vargp_matern_gram_bwd
+        kind = (0, int(round(2 * nu)))                                    # y_shared, nu2
     K = torch.empty(S, C, M, N, device=DEV)
-    ws = scratch(lib().vargp_matern_workspace_bytes(S, C, M, N, D, 1), torch.device(DEV))
-    check(lib().vargp_matern_gram_fwd(ptr(th), ptr(x), ptr(y), ptr(K), S, C, M, N, D, 0, nu2, ptr(ws), ws.numel() * 4,
-                                      stream_ptr()), 'fwd')
+    ws = scratch(max(ws_bytes(S, C, M, N, D, 0), ws_bytes(S, C, M, N, D, 1)), torch.device(DEV))
+    check(fwd(ptr(th), ptr(x), ptr(y), ptr(K), S, C, M, N, D, *kind, ptr(ws), ws.numel() * 4, stream_ptr()), 'fwd')
     base = dict(gX=torch.randn(C, M, D), gY=torch.randn(C, N, D), gtheta=torch.randn(S, D + 1))
     out = {k: v.to(DEV).clone() for k, v in base.items()}
-    check(lib().vargp_matern_gram_bwd(ptr(th), ptr(x), ptr(y), ptr(K), ptr(g), ptr(out['gX']), ptr(out['gY']),
-                                      ptr(out['gtheta']), S, C, M, N, D, 0, nu2, 1, ptr(ws), ws.numel() * 4, stream_ptr()),
-          'bwd')
+    check(bwd(ptr(th), ptr(x), ptr(y), ptr(K), ptr(g), ptr(out['gX']), ptr(out['gY']), ptr(out['gtheta']), S, C, M, N, D,
+              *kind, 1, ptr(ws), ws.numel() * 4, stream_ptr()), 'bwd')
     torch.cuda.synchronize()
     got = {k: out[k].cpu() - base[k] for k in base}
     got['K'] = K.cpu()
@@ -231,7 +242,7 @@ _SPLITK_SCRIPT = '''
 import sys
 sys.path.insert(0, %r); sys.path.insert(0, %r)
 import test_hip_matern as t
-for nu in t.NUS:
+for nu in t.KERNELS:
     for mode in ('self', 'batched', 'shared'):
         t._run_op_case(2, 3, 70, 130, 784, mode, nu, seed=11)
 print('splitk ok')
@@ -249,14 +260,15 @@ def test_op_vs_fp64_split_k():
 
 
 # -- b. r = 0 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('nu', NUS)
+@pytest.mark.parametrize('nu', KERNELS)
 @pytest.mark.parametrize('D', [2, 40])
 @pytest.mark.parametrize('copy', [False, True])
 def test_coincident_points(nu, D, copy):
     """Y = NULL (the diagonal is gamma^2 by construction) and Y a copy of X (the diagonal distance comes out of the arithmetic:
     exactly 0 in the direct form, D <= 32; rounding noise of the inner-product form above, clamped at 0).
     Bound for the copy's diagonal, D > 32: d2 = na + nb - 2 ab with three fp32 dot products of D terms, each within
-    D eps |a|^2 of its value (worst-case summation), so |d2| <= 4 D eps na, and 1 - k(r) <= sqrt(2 nu) r for every nu here."""
+    D eps |a|^2 of its value (worst-case summation), so |d2| <= 4 D eps na, and 1 - k(r) <= sqrt(2 nu) r for every nu here.
+    The RBF does not clamp d2: |1 - exp(-d2 / 2)| <= t exp(t) with t = |d2| / 2 <= 2 D eps na."""
     S, C, M = 2, 2, 50
     theta, X, _, gK = _op_inputs(S, C, M, M, D, 'self', 31 + D)
     Y = X.clone() if copy else None
@@ -269,7 +281,8 @@ def test_coincident_points(nu, D, copy):
         np.testing.assert_allclose(hip_g2.numpy(), g2.numpy(), rtol=4 * EPS32)
     else:
         na = ((X.double().unsqueeze(0) / theta[:, :-1].double().exp().view(S, 1, 1, D)) ** 2).sum(-1)      # (S, C, M)
-        bound = (2 * nu * 4 * D * EPS32 * na).sqrt() + 4 * EPS32
+        t = 2 * D * EPS32 * na
+        bound = (t * t.exp() if nu == RBF else (2 * nu * 4 * D * EPS32 * na).sqrt()) + 4 * EPS32
         dev = (1.0 - diag.double() / g2.double().view(S, 1, 1)).abs()
         print('copy diagonal: worst deviation %.2e, bound there %.2e' % (dev.max().item(), bound.flatten()[dev.argmax()].item()))
         assert (dev <= bound).all()

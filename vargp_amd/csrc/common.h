@@ -311,16 +311,9 @@ int launch_chol_rbf_gemm(const float* A, float eps, float* L, float* T, int32_t*
 int rbf_splitk(int M, int N, int K, int nbatch);
 
 constexpr int kRbfDirectD = 32;   // D <= this: kernel matrices from the direct (no-cancellation) distance form
-int rbf_direct_launch(const float* X, const float* Y, const float* w, const float* g2, float* K, int64_t ldk, int S,
-                      int C, int M, int N, int D, int64_t Dp, int y_shared, hipStream_t st);
-// the same with a Matern / distance epilogue (matern.hip; epi: kEpiMatern12 / 32 / 52 / kEpiDist2), K dense [S, C, M, N]
-int matern_direct_launch(const float* X, const float* Y, const float* w, const float* g2, float* K, int S, int C, int M, int N,
-                         int D, int64_t Dp, int y_shared, int epi, hipStream_t st);
-int rbf_gram_fwd_impl(const float* theta, const float* X, const float* Y, float* K, int S, int C, int M, int N, int D,
-                      int y_shared, void* ws, size_t ws_bytes, int sym_out, hipStream_t st);
-int rbf_gram_bwd_impl(const float* theta, const float* X, const float* Y, const float* K, const float* gK, float* gX,
-                      float* gY, float* gtheta, int S, int C, int M, int N, int D, int y_shared, int accumulate, void* ws,
-                      size_t ws_bytes, int sym_gk, hipStream_t st);
+// the direct form after the caller's own pre-pass (gram.hip): K [S, C, M, ldk] = epi(d2), epi a DistEpi other than kEpiPlain
+int dist_direct_launch(const float* X, const float* Y, const float* w, const float* g2, float* K, int64_t ldk, int S, int C,
+                       int M, int N, int D, int64_t Dp, int y_shared, int epi, hipStream_t st);
 int chol_inv_fwd_impl(const float* A, float eps, float* L, float* T, float* logdet, int32_t* info, int nbatch, int n,
                       void* ws, size_t ws_bytes, bool zero_info, hipStream_t st, const GemmParams* co = nullptr,
                       int co_nbatch = 0, int* co_done = nullptr, int nco = 1, bool chain_f32 = false);
@@ -341,7 +334,7 @@ int rbf_prep_norm_launch(const float* theta, const float* x, int64_t xrows, cons
                          float* g2, float* na, float* nb, int S, int D, int64_t Dp, hipStream_t st, float* ys = nullptr,
                          float* xs = nullptr);
 
-// the backward's finalisation of one side (rbf.hip: rbf_final_kernel), shared by every kernel built on d2
+// the backward's finalisation of one side (gram.hip: rbf_final_kernel), shared by every kernel built on d2
 int rbf_final_launch(const float* x, const float* R, const float* P, const float* theta, float* g, float* gtheta, int64_t rows,
                      int D, int64_t Dp, int S, float kappa, int accumulate, hipStream_t st);
 

@@ -237,7 +237,7 @@ struct GvecArgs {
   int S, C, M, y0;
 };
 
-// W = gK o K for both kernel matrices (see rbf.hip for the algebra).
+// W = gK o K for both kernel matrices (see gram.hip for the algebra).
 //   blocks < nuf : K_uf, in place on the K_uf block of gRK (row stride LD); row sums r_uf, column sums c_uf (atomics),
 //                  2 sum W into gtheta[s, D]
 //   next nuu     : K_uu, one wave per row: Wuu = W + W^T, r_uu = its row sums, sum Wuu (= 2 sum W) into gtheta[s, D]
@@ -399,7 +399,7 @@ __device__ __forceinline__ void t0_w_body(const float* __restrict__ RK, float* _
         if (i < i1 && j < M) {
           // sym_guu: gK_uu is symmetric (it comes out of the Cholesky backward), so W + W^T = 2 W: no transposed reads
           float v = sym_guu ? 2.f * kv[r][h] * gv[r][h] : kv[r][h] * gv[r][h] + kt[r][h] * gt[r][h];
-          // the diagonal counts for gamma only (K_ii = gamma^2: see rbf_w_self_kernel, rbf.hip)
+          // the diagonal counts for gamma only (K_ii = gamma^2: see gram_w_self_kernel, gram.hip)
           const bool dg = i == j;
           if constexpr (NU2 != 0) {      // dsum = sum gK o K over every entry; d2 is symmetric: one weight for both mirrored entries
             dsum += v;
@@ -490,7 +490,7 @@ __device__ __forceinline__ void t0_final_x_body(const float* __restrict__ x, con
   }
 }
 
-// RBF finalisation (rbf.hip), both kernel matrices at once.  grid (ceil(D/64), nzy + nxy), 64 d-columns x 4 row lanes.
+// RBF finalisation (gram.hip), both kernel matrices at once.  grid (ceil(D/64), nzy + nxy), 64 d-columns x 4 row lanes.
 //   y-blocks < nzy  (inducing points):  gz[row,d] = -sum_s w_sd ((r_uu + r_uf) z - (P_uu + P_uf))
 //                                       gtheta[s,d] += w_sd sum_row z ((r_uu z - P_uu) + (r_uf z - 2 P_uf))
 //   y-blocks >= nzy (minibatch side):   gtheta[s,d] += w_sd sum_n c_uf x^2

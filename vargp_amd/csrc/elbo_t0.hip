@@ -1084,9 +1084,9 @@ int T0::fwd() const {
   }
   // kernel matrices: K_uu -> KS[:SC], K_uf -> the trailing block of RK
   if (plan.direct_gram) {
-    rc = rbf_direct_launch(d->z, nullptr, o.w, o.g2, o.KS, M, S, C, M, M, D, o.Dp, 0, st);
+    rc = dist_direct_launch(d->z, nullptr, o.w, o.g2, o.KS, M, S, C, M, M, D, o.Dp, 0, kEpiRbf, st);
     if (rc) return rc;
-    rc = rbf_direct_launch(d->z, d->x, o.w, o.g2, o.RK + NR, LD, S, C, M, B, D, o.Dp, 1, st);
+    rc = dist_direct_launch(d->z, d->x, o.w, o.g2, o.RK + NR, LD, S, C, M, B, D, o.Dp, 1, kEpiRbf, st);
     if (rc) return rc;
   } else {
     if (!plan.split_kuu)

@@ -953,8 +953,8 @@ struct Tn {
   int matern_d2(const float* x, int B, float* d2uf, float* d2uu) const {      // NULL: not needed
     int rc;
     if (D <= kRbfDirectD) {
-      if (d2uu) { rc = matern_direct_launch(d->z_all, nullptr, o.w, o.g2, d2uu, S, C, Mt, Mt, D, o.Dp, 0, kEpiDist2, st); if (rc) return rc; }
-      if (d2uf) { rc = matern_direct_launch(d->z_all, x, o.w, o.g2, d2uf, S, C, Mt, B, D, o.Dp, 1, kEpiDist2, st); if (rc) return rc; }
+      if (d2uu) { rc = dist_direct_launch(d->z_all, nullptr, o.w, o.g2, d2uu, Mt, S, C, Mt, Mt, D, o.Dp, 0, kEpiDist2, st); if (rc) return rc; }
+      if (d2uf) { rc = dist_direct_launch(d->z_all, x, o.w, o.g2, d2uf, B, S, C, Mt, B, D, o.Dp, 1, kEpiDist2, st); if (rc) return rc; }
       return VARGP_OK;
     }
     if (d2uu) { rc = gram(kall_gemm(d2uu), false, kEpiDist2); if (rc) return rc; }
@@ -1072,11 +1072,9 @@ extern "C" int vargp_elbo_tn_fwd(const vargp_elbo_tn_desc* d, vargp_stream_t str
   rc = rbf_prep_norm_launch(o.theta, d->z_all, zrows, d->x, B, o.w, o.g2, o.na, o.nb, S, D, o.Dp, st, o.xs, o.zs);
   if (rc) return rc;
   if (D <= kRbfDirectD) {           // small input dimension: direct (cancellation-free) distances
-    rc = nu2 ? matern_direct_launch(d->z_all, nullptr, o.w, o.g2, o.Kall, S, C, Mt, Mt, D, o.Dp, 0, tn_epi(nu2), st)
-             : rbf_direct_launch(d->z_all, nullptr, o.w, o.g2, o.Kall, Mt, S, C, Mt, Mt, D, o.Dp, 0, st);
+    rc = dist_direct_launch(d->z_all, nullptr, o.w, o.g2, o.Kall, Mt, S, C, Mt, Mt, D, o.Dp, 0, tn_epi(nu2), st);
     if (rc) return rc;
-    rc = nu2 ? matern_direct_launch(d->z_all, d->x, o.w, o.g2, o.Kuf, S, C, Mt, B, D, o.Dp, 1, tn_epi(nu2), st)
-             : rbf_direct_launch(d->z_all, d->x, o.w, o.g2, o.Kuf, B, S, C, Mt, B, D, o.Dp, 1, st);
+    rc = dist_direct_launch(d->z_all, d->x, o.w, o.g2, o.Kuf, B, S, C, Mt, B, D, o.Dp, 1, tn_epi(nu2), st);
     if (rc) return rc;
     kuf_done = true;
   } else {

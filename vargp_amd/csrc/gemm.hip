@@ -716,7 +716,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, const int tile_id
           float v;
           if constexpr (RBF) {
             if (p.splitk > 1) {
-              v = acc[a][c][r];               // partial inner product; rbf_combine_kernel finishes the job
+              v = acc[a][c][r];               // partial inner product; dist_combine_kernel finishes the job
             } else {
               const float d2 = na[row] + nbc - 2.f * acc[a][c][r];
               v = (p.same_xy && row == col) ? EPI::diag(g2) : EPI::off(g2, d2);
@@ -1105,7 +1105,7 @@ static void dispatch_tile(const GemmParams& p, int transA, int transB, int nbatc
 //   128x64 xBK32 : 32 MFMA / slab / wave  - mid-size problems (K_uf at Split-MNIST: 192 workgroups)
 //   64 x64 xBK64 :  32 MFMA / slab / wave - small problems; the K extent of the (M x M) products of the
 //                  ELBO (K <= 128) is covered by one or two slabs, i.e. one or two global-load latencies.
-// Split-K for mid-size RBF products is implemented (partials + rbf_combine_kernel) but OFF by default: at the
+// Split-K for mid-size RBF products is implemented (partials + dist_combine_kernel) but OFF by default: at the
 // Split-MNIST K_uf shape (384 tiles of 64x64 on 256 CUs) two splits measured 69.8 us against 61.6 us unsplit.
 // The per-slab cost of a wave is its 32 MFMAs plus ~1000 cycles of VALU/LDS issue that do not overlap them, and
 // waves sharing a SIMD serialise, so more, shorter workgroups only add prologue/epilogue and the combine pass.

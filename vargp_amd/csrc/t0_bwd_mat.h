@@ -228,7 +228,7 @@ __device__ __forceinline__ void mat_tail(float* __restrict__ sT, float* __restri
     const bool ok = e < kBmKP * kBmNQ && i < M && j < M;
     if (kmul) {
       v.x *= 2.f * kr[u].x; v.y *= 2.f * kr[u].y; v.z *= 2.f * kr[u].z; v.w *= 2.f * kr[u].w;
-      // the diagonal of W_uu counts for gamma only (K_ii = gamma^2: see rbf_w_self_kernel, rbf.hip): out of W_uu and r_uu
+      // the diagonal of W_uu counts for gamma only (K_ii = gamma^2: see gram_w_self_kernel, gram.hip): out of W_uu and r_uu
       const int q = i - j;
       const float dv = q == 0 ? v.x : q == 1 ? v.y : q == 2 ? v.z : v.w;
       dsum += (ok && q >= 0 && q < 4) ? dv : 0.f;

@@ -6,7 +6,7 @@
 //     gT += tril(gP K_uf^T)                            gK_uf = T^T gP
 //     W_uf = gK_uf o K_uf  -> the K_uf block of gRK,   r_uf += row sums,  c_uf += column sums,  gtheta[s, D] += 2 sum W_uf
 // i.e. the predictive-moment backward, the products gG || gP, the K_uf share of gT = tril(gQP RK^T) and of gRK = T^T gQP,
-// and the K_uf role of the W = gK o K pass (rbf.hip) -- four launches and the HBM round trips of gP, gW, gK_uf -- with
+// and the K_uf role of the W = gK o K pass (gram.hip) -- four launches and the HBM round trips of gP, gW, gK_uf -- with
 // G, T, and the P / W / K_uf tiles resident in LDS.  What is left for GEMM launches afterwards is the small-column part
 // (K = NR): gT += tril(gQP[:, :NR] RK[:, :NR]^T) and gRK[:, :NR] = T^T gQP[:, :NR].
 // 256 threads = 4 waves.  f32 MFMA 32x32x2 with the k-pairing of gemm.hip (half-wave h supplies k = 8 g + 4 h + j, j < 4).

@@ -1,7 +1,7 @@
 // The last launch of the first-task backward (M <= 104, M % 4 == 0, D % 4 == 0, S <= kTailSMax = 64): the product P_uu = W_uu z of the
 // kernel-matrix backward and the finalisation that consumes it, in one kernel -- P_uu never goes to memory.
 // Reference: autograd of kernels.py:24-44 (the RBF kernel matrix of scaled inputs) w.r.t. z and the lengthscales; with
-// W = gK o K, r = row sums of W, P = W y (see rbf.hip for the algebra):
+// W = gK o K, r = row sums of W, P = W y (see gram.hip for the algebra):
 //   gz[c,i,d]       = -sum_s w_sd ((r_uu z - P_uu) + (r_uf z - P_uf))                (W_uu = W + W^T already)
 //   gtheta[s,d]    +=  w_sd sum_{c,i} z ((r_uu z - P_uu) + (r_uf z - 2 P_uf))      (+ the minibatch side: x^2 c_uf)
 // Roles by block index:

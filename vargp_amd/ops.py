@@ -228,54 +228,15 @@ def matmul(A, B, D=None, alpha=1.0, beta=1.0, triA=NONE, triB=NONE, triC=NONE):
 
 
 # ------------------------------------------------------------------------------------------------
-# RBF gram
-# ------------------------------------------------------------------------------------------------
-class _RbfGram(Function):
-    @staticmethod
-    def forward(ctx, theta, X, Y, y_shared):
-        require_device(theta, X, Y)
-        theta, X = theta.contiguous(), X.contiguous()
-        Y = Y.contiguous() if Y is not None else None
-        S, C, M, D = theta.shape[0], X.shape[0], X.shape[1], X.shape[2]
-        N = M if Y is None else Y.shape[-2]
-        K = torch.empty(S, C, M, N, dtype=torch.float32, device=X.device)
-        ws = scratch(lib().vargp_rbf_workspace_bytes(S, C, M, N, D, 0), X.device)
-        check(lib().vargp_rbf_gram_fwd(ptr(theta), ptr(X), ptr(Y), ptr(K), S, C, M, N, D, int(y_shared), ptr(ws),
-                                       ws.numel() * 4, stream_ptr()), 'vargp_rbf_gram_fwd')
-        ctx.save_for_backward(theta, X, Y, K)
-        ctx.y_shared = int(y_shared)
-        return K
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gK):
-        theta, X, Y, K = ctx.saved_tensors
-        S, C, M, D = theta.shape[0], X.shape[0], X.shape[1], X.shape[2]
-        N = M if Y is None else Y.shape[-2]
-        gK = gK.contiguous()
-        gX = torch.empty_like(X)
-        want_gY = Y is not None and ctx.needs_input_grad[2]
-        gY = torch.empty_like(Y) if want_gY else None
-        gtheta = torch.empty_like(theta)
-        ws = scratch(lib().vargp_rbf_workspace_bytes(S, C, M, N, D, 1), X.device)
-        check(lib().vargp_rbf_gram_bwd(ptr(theta), ptr(X), ptr(Y), ptr(K), ptr(gK), ptr(gX), ptr(gY), ptr(gtheta),
-                                       S, C, M, N, D, ctx.y_shared, 0, ptr(ws), ws.numel() * 4, stream_ptr()),
-              'vargp_rbf_gram_bwd')
-        return gtheta, gX, gY, None
-
-
-def rbf_gram(theta, X, Y=None, y_shared=False):
-    """theta (S,D+1); X (C,M,D); Y None | (C,N,D) | (N,D) with y_shared -> K (S,C,M,N)."""
-    return _RbfGram.apply(theta, X, Y, y_shared)
-
-
-# ------------------------------------------------------------------------------------------------
-# Matern gram (nu = 1/2, 3/2, 5/2)
+# RBF and Matern (nu = 1/2, 3/2, 5/2) gram
 # ------------------------------------------------------------------------------------------------
 _MATERN_NU2 = {0.5: 1, 1.5: 3, 2.5: 5}
+_GRAM_ENTRIES = {False: ('vargp_rbf_workspace_bytes', 'vargp_rbf_gram_fwd', 'vargp_rbf_gram_bwd'),
+                 True: ('vargp_matern_workspace_bytes', 'vargp_matern_gram_fwd', 'vargp_matern_gram_bwd')}
 
 
-class _MaternGram(Function):
+class _Gram(Function):
+    """nu2 = 0: RBF; 1, 3, 5: Matern (its entries take nu2 behind y_shared)."""
     @staticmethod
     def forward(ctx, theta, X, Y, y_shared, nu2):
         require_device(theta, X, Y)
@@ -283,12 +244,14 @@ class _MaternGram(Function):
         Y = Y.contiguous() if Y is not None else None
         S, C, M, D = theta.shape[0], X.shape[0], X.shape[1], X.shape[2]
         N = M if Y is None else Y.shape[-2]
+        ws_bytes, fwd, _ = _GRAM_ENTRIES[nu2 != 0]
         K = torch.empty(S, C, M, N, dtype=torch.float32, device=X.device)
-        ws = scratch(lib().vargp_matern_workspace_bytes(S, C, M, N, D, 0), X.device)
-        check(lib().vargp_matern_gram_fwd(ptr(theta), ptr(X), ptr(Y), ptr(K), S, C, M, N, D, int(y_shared), nu2, ptr(ws),
-                                          ws.numel() * 4, stream_ptr()), 'vargp_matern_gram_fwd')
+        ws = scratch(getattr(lib(), ws_bytes)(S, C, M, N, D, 0), X.device)
+        kind = (int(y_shared), nu2) if nu2 else (int(y_shared),)
+        check(getattr(lib(), fwd)(ptr(theta), ptr(X), ptr(Y), ptr(K), S, C, M, N, D, *kind, ptr(ws), ws.numel() * 4,
+                                  stream_ptr()), fwd)
         ctx.save_for_backward(theta, X, Y, K)
-        ctx.y_shared, ctx.nu2 = int(y_shared), nu2
+        ctx.kind, ctx.nu2 = kind, nu2
         return K
 
     @staticmethod
@@ -297,23 +260,28 @@ class _MaternGram(Function):
         theta, X, Y, K = ctx.saved_tensors
         S, C, M, D = theta.shape[0], X.shape[0], X.shape[1], X.shape[2]
         N = M if Y is None else Y.shape[-2]
+        ws_bytes, _, bwd = _GRAM_ENTRIES[ctx.nu2 != 0]
         gK = gK.contiguous()
         gX = torch.empty_like(X)
         want_gY = Y is not None and ctx.needs_input_grad[2]
         gY = torch.empty_like(Y) if want_gY else None
         gtheta = torch.empty_like(theta)
-        ws = scratch(lib().vargp_matern_workspace_bytes(S, C, M, N, D, 1), X.device)
-        check(lib().vargp_matern_gram_bwd(ptr(theta), ptr(X), ptr(Y), ptr(K), ptr(gK), ptr(gX), ptr(gY), ptr(gtheta),
-                                          S, C, M, N, D, ctx.y_shared, ctx.nu2, 0, ptr(ws), ws.numel() * 4, stream_ptr()),
-              'vargp_matern_gram_bwd')
+        ws = scratch(getattr(lib(), ws_bytes)(S, C, M, N, D, 1), X.device)
+        check(getattr(lib(), bwd)(ptr(theta), ptr(X), ptr(Y), ptr(K), ptr(gK), ptr(gX), ptr(gY), ptr(gtheta), S, C, M, N, D,
+                                  *ctx.kind, 0, ptr(ws), ws.numel() * 4, stream_ptr()), bwd)
         return gtheta, gX, gY, None, None
+
+
+def rbf_gram(theta, X, Y=None, y_shared=False):
+    """theta (S,D+1); X (C,M,D); Y None | (C,N,D) | (N,D) with y_shared -> K (S,C,M,N)."""
+    return _Gram.apply(theta, X, Y, y_shared, 0)
 
 
 def matern_gram(theta, X, Y=None, y_shared=False, nu=2.5):
     """Matern kernel matrix, nu in {0.5, 1.5, 2.5}; arguments and result as rbf_gram."""
     if nu not in _MATERN_NU2:
         raise ValueError(f'matern_gram: nu must be 0.5, 1.5 or 2.5, got {nu!r}')
-    return _MaternGram.apply(theta, X, Y, y_shared, _MATERN_NU2[nu])
+    return _Gram.apply(theta, X, Y, y_shared, _MATERN_NU2[nu])
 
 
 # ------------------------------------------------------------------------------------------------
