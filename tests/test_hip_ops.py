@@ -184,10 +184,12 @@ def test_chol_blocked_logdet_through_the_c_abi(ops, n, want_t):
         assert rel_l2(T.cpu(), T64) < 1e-4 and torch.equal(T.triu(1), torch.zeros_like(T))
 
 
-@pytest.mark.parametrize('D,B,n', [(784, 512, 6000), (37, 30, 100), (40, 64, 70)])
+@pytest.mark.parametrize('D,B,n', [(784, 512, 6000), (37, 30, 100), (40, 64, 70), (40, 1, 70), (40, 5, 70)])
 def test_gather_minibatch_follows_the_device_step_count(ops, D, B, n):
     """vargp_gather_minibatch: minibatch i = (*step_now - *step_base) of a permutation, read on the DEVICE -- float4 rows and the
-    scalar form (D % 4 != 0), positions past the end of the permutation clamp to its last entry."""
+    scalar form (D % 4 != 0), positions past the end of the permutation clamp to its last entry, a count behind its base clamps
+    to position 0; one row, and a last block of rows that is partly filled (B = 5).  With D % 4 == 0, `data` or `x` one element
+    into a larger buffer (4-byte aligned) takes the scalar form: the same rows, and nothing written around x or y."""
     from vargp_amd._lib import check, lib, ptr, stream_ptr
     gen = torch.Generator().manual_seed(D + B)
     data = torch.randn(n, D, generator=gen).to(DEV)
@@ -202,6 +204,34 @@ def test_gather_minibatch_follows_the_device_step_count(ops, D, B, n):
         idx = perm[(torch.arange(B, device=DEV) + i * B).clamp(max=n - 1)]
         assert torch.equal(x, data[idx]) and torch.equal(y, targets[idx]), i
         now += 1.0               # (what the first kernel of the ELBO programs does through `bump`)
+
+    def gather(data_at, x_off, step_now, step_base):
+        """-> (x, y) gathered into the middle of guarded buffers, x starting x_off floats into its own."""
+        xb = torch.full((4 + x_off + B * D + 8,), -7777.0, device=DEV)
+        yb = torch.full((B + 2,), -7777, dtype=torch.int64, device=DEV)
+        xv, yv = xb[4 + x_off:4 + x_off + B * D], yb[1:B + 1]
+        assert xv.data_ptr() % 16 == 4 * x_off and data_at.data_ptr() % 4 == 0
+        check(lib().vargp_gather_minibatch(ptr(data_at), ptr(targets), ptr(perm), ptr(step_now), ptr(step_base), n, B, D, ptr(xv),
+                                           ptr(yv), stream_ptr()), 'vargp_gather_minibatch')
+        assert (xb[:4 + x_off] == -7777.0).all() and (xb[4 + x_off + B * D:] == -7777.0).all()
+        assert yb[0] == -7777 and yb[B + 1] == -7777
+        return xv.view(B, D).clone(), yv.clone()
+
+    one, three = torch.tensor([1.0], device=DEV), torch.tensor([3.0], device=DEV)
+    first = perm[torch.arange(B, device=DEV).clamp(max=n - 1)]
+    for behind in (one, torch.tensor([-40.0], device=DEV)):               # step_now < step_base: every row clamps to position 0
+        gx, gy = gather(data, 0, behind, three)
+        assert torch.equal(gx, data[perm[:1]].expand(B, D)) and torch.equal(gy, targets[perm[:1]].expand(B))
+    assert one.item() == 1.0 and three.item() == 3.0
+    want = gather(data, 0, three, three)
+    assert torch.equal(want[0], data[first]) and torch.equal(want[1], targets[first])
+    if D % 4 == 0:
+        shifted = torch.full((n * D + 5,), -7777.0, device=DEV)
+        shifted[1:n * D + 1] = data.reshape(-1)
+        assert shifted[1:].data_ptr() % 16 == 4
+        for data_at, x_off in ((shifted[1:n * D + 1], 0), (data, 1), (shifted[1:n * D + 1], 1)):
+            got = gather(data_at, x_off, three, three)
+            assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), (data_at is data, x_off)
 
 
 @pytest.mark.parametrize('n', [20, 64, 100])

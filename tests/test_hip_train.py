@@ -264,18 +264,12 @@ def test_epoch_graphs_equal_the_per_step_loop(n_prev):
         ops.set_cholesky_error_mode('raise')
 
 
-@pytest.mark.parametrize('shape,map_est', [((3, 3, 4, 56, 784, 64), False), ((2, 3, 3, 24, 40, 32), False),
-                                          ((1, 3, 3, 56, 300, 64), True)])
-def test_deferred_hyper_backward_equals_its_own_launch(shape, map_est, monkeypatch):
-    """The trainer finishes the hyper-parameter backward inside the optimiser's launch (vargp_yogi_step_multi_hyper); with
-    VARGP_DEFER_HYPER=0 the program's own last kernel (t0_hyper_bwd_kernel) does it before a plain Yogi step.  Same
-    gradients of log_mean / log_logvar and the same parameters after three steps -- D + 1 = 785 > 256 (several blocks of
-    the hyper role), a small D, and a MAP estimate of the hyper-parameters (log_logvar receives no gradient)."""
+def _deferred_against_own_launch(shape, map_est, monkeypatch, n_prev=0):
     from vargp_amd import noise
     from vargp_amd.train import ElboTrainer
     from gpu_common import build_gp
     S, F_, C, M, D, B = shape
-    params, prev, x, y, nz = orc.make_problem(S, F_, C, M, D, B, seed=21, kind='gauss')
+    params, prev, x, y, nz = orc.make_problem(S, F_, C, M, D, B, n_prev=n_prev, seed=21, kind='gauss')
     xd, yd = x.to(DEV), y.to(DEV)
     res = []
     for defer in ('1', '0'):
@@ -283,13 +277,15 @@ def test_deferred_hyper_backward_equals_its_own_launch(shape, map_est, monkeypat
         gp = build_gp(params, prev, S, F_)
         gp.kernel.map_est = map_est
         tr = ElboTrainer(gp, lr=3e-3, beta=2.0, n_total=10 * B)
-        assert tr._t0 and tr._defer_hyper() == (defer == '1')
+        assert tr._t0 and tr._tn == bool(n_prev) and tr._defer_hyper() == (defer == '1')
         for it in range(3):
             inj = dict(eps_f=(nz['eps_f'] + 0.1 * it).to(DEV))
             if not map_est:
                 inj['eps_theta'] = (nz['eps_theta'] - 0.05 * it).to(DEV)
             with noise.inject(**inj):
                 tr.step(xd, yd)
+        assert tr._tn == bool(n_prev)
+        assert tr._prog._C['hyper_desc'] == ('vargp_elbo_tn_hyper_desc' if n_prev else 'vargp_elbo_t0_hyper_desc')
         k = gp.kernel
         res.append(dict(g_mean=k.log_mean.grad.clone().cpu(), g_logvar=None if map_est else k.log_logvar.grad.clone().cpu(),
                         params={n: p.detach().clone().cpu() for n, p in gp.named_parameters()}))
@@ -299,6 +295,24 @@ def test_deferred_hyper_backward_equals_its_own_launch(shape, map_est, monkeypat
         assert rel_l2(a['g_logvar'], b['g_logvar']) < 1e-5
     for n in a['params']:
         assert rel_l2(a['params'][n], b['params'][n]) < 1e-5, n
+
+
+@pytest.mark.parametrize('shape,map_est', [((3, 3, 4, 56, 784, 64), False), ((2, 3, 3, 24, 40, 32), False),
+                                          ((1, 3, 3, 56, 300, 64), True), ((9, 2, 3, 24, 40, 32), False),
+                                          ((9, 1, 33, 12, 40, 32), False)])
+def test_deferred_hyper_backward_equals_its_own_launch(shape, map_est, monkeypatch):
+    """The trainer finishes the hyper-parameter backward inside the optimiser's launch (vargp_yogi_step_multi_hyper); with
+    VARGP_DEFER_HYPER=0 the program's own last kernel (t0_hyper_bwd_kernel) does it before a plain Yogi step.  Same
+    gradients of log_mean / log_logvar and the same parameters after three steps -- D + 1 = 785 > 256 (several blocks of
+    the hyper role), a small D, a MAP estimate of the hyper-parameters (log_logvar receives no gradient), S = 9 (a second,
+    partly filled batch of eight samples) and S C = 297 > 256 (a second pass of the block over the gamma^2 terms)."""
+    _deferred_against_own_launch(shape, map_est, monkeypatch)
+
+
+def test_deferred_hyper_backward_equals_its_own_launch_on_the_block_program(monkeypatch):
+    """The same comparison for a model with one previous task: the block program (elbo_tn.hip) hands over its
+    vargp_elbo_tn_hyper_desc, and its own last kernel is the other side."""
+    _deferred_against_own_launch((9, 2, 3, 24, 40, 32), False, monkeypatch, n_prev=1)
 
 
 def test_defer_hyper_needs_both_hyper_tensors_in_the_optimiser():

@@ -140,6 +140,19 @@ struct YogiPack {
 };
 constexpr int kYogiPerBlock = 1024;   // 256 threads x 4 elements
 struct YogiHyper { vargp_hyper_grad_desc h; int idx_mean, idx_logvar; };     // idx_mean < 0: off
+// One element of the step.  The three places that run it (float4 lanes, the scalar tail / unaligned form, the hyper-parameter
+// role) must give the same bits for the same values, so the contraction of a * b + c is written out here and switched off
+// for the rest: left to the compiler, it fused the same line differently from one call site to the next (1 ulp apart in m).
+// step_size = lr / (1 - b1^t), sb2 = sqrt(1 - b2^t)
+__device__ __forceinline__ void yogi_upd(float& pi, float gi, float& mi, float& vi, float b1, float b2, float eps, float step_size,
+                                         float sb2) {
+#pragma clang fp contract(off)
+  const float g2 = gi * gi;
+  mi = fmaf(b1, mi, (1.f - b1) * gi);
+  const float df = vi - g2;
+  vi = fmaf(-((1.f - b2) * (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f))), g2, vi);
+  pi -= step_size * mi / (sqrtf(vi) / sb2 + eps);
+}
 // gradients of log_mean[d] and log_logvar[d]: the arithmetic of t0_hyper_bwd_kernel (elbo_shared.h).  tm / tv: the block's
 // sums over (s, c) of the gamma^2 terms (only added at d = D)
 __device__ __forceinline__ void yogi_hyper_grad(const vargp_hyper_grad_desc& h, int d, float tm, float tv, float& gm, float& gv) {
@@ -213,11 +226,7 @@ __global__ __launch_bounds__(256) void yogi_multi_kernel(YogiPack pk, int ntenso
         const float gi = lv ? gv : gm;
         const_cast<float*>(g)[i] = gi;
         float pi = p[i], mi = m[i], vi = v[i];
-        const float g2 = gi * gi;
-        mi = b1 * mi + (1.f - b1) * gi;
-        const float df = vi - g2;
-        vi -= (1.f - b2) * (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f)) * g2;
-        pi -= (lr / bias1) * mi / (sqrtf(vi) / sb2 + eps);
+        yogi_upd(pi, gi, mi, vi, b1, b2, eps, lr / bias1, sb2);
         p[i] = pi; m[i] = mi; v[i] = vi;
       }
     }
@@ -225,13 +234,7 @@ __global__ __launch_bounds__(256) void yogi_multi_kernel(YogiPack pk, int ntenso
   }
   const float tt = step[0] + (step_mode ? 1.f : 0.f);
   const float bias1 = 1.f - powf(b1, tt), sb2 = sqrtf(1.f - powf(b2, tt));
-  auto upd = [&](float& pi, float gi, float& mi, float& vi) {
-    const float g2 = gi * gi;
-    mi = b1 * mi + (1.f - b1) * gi;
-    const float df = vi - g2;
-    vi -= (1.f - b2) * (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f)) * g2;
-    pi -= (lr / bias1) * mi / (sqrtf(vi) / sb2 + eps);
-  };
+  auto upd = [&](float& pi, float gi, float& mi, float& vi) { yogi_upd(pi, gi, mi, vi, b1, b2, eps, lr / bias1, sb2); };
   const int64_t i0 = (int64_t)blk * kYogiPerBlock + 4 * threadIdx.x;
   const bool aligned = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
                          reinterpret_cast<uintptr_t>(v)) & 15) == 0;

@@ -13,6 +13,20 @@ import torch
 from ._lib import check, lib, ptr, require_device, stream_ptr
 
 
+def _dense(t):
+    """Do the numel() elements of t fill one block of storage without gaps or overlap, in some order of the axes?"""
+    expect = 1
+    for stride, size in sorted((st, n) for n, st in zip(t.shape, t.stride()) if n != 1):
+        if stride != expect:
+            return False
+        expect *= size
+    return True
+
+
+def _same_layout(a, b):
+    return a.stride() == b.stride() or (a.is_contiguous() and b.is_contiguous())
+
+
 class Yogi(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-2, betas=(0.9, 0.999), eps=1e-3, initial_accumulator=1e-6):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, initial_accumulator=initial_accumulator))
@@ -69,9 +83,6 @@ class Yogi(torch.optim.Optimizer):
             for i in range(0, len(ps), 8):
                 chunk = ps[i:i + 8]
                 k = len(chunk)
-                grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in chunk]
-                if not all(g.is_cuda for g in grads):
-                    require_device(*grads)
                 arr = lambda ts: (ctypes.c_void_p * k)(*[t.data_ptr() for t in ts])
                 # parameters and moment buffers keep their addresses from step to step: their pointer arrays are built once
                 # per chunk (the eager drop-in loop is host-bound; this call used to cost ~60 us of Python)
@@ -81,11 +92,27 @@ class Yogi(torch.optim.Optimizer):
                 # tensor replaced through optim.state, state.clear(), a move to another device: rebuilt)
                 where = tuple(t.data_ptr() for p in chunk for t in (p, self.state[p]['exp_avg'], self.state[p]['exp_avg_sq']))
                 if cached is None or cached[0] != where:
+                    for p in chunk:
+                        if not _dense(p):
+                            raise ValueError(
+                                f'Yogi: a parameter of shape {tuple(p.shape)} with strides {p.stride()} is not dense (a strided '
+                                'slice of a larger tensor?): the fused step would update memory between its elements. Optimise '
+                                'the whole tensor, or a contiguous copy of the slice.')
+                        for name in ('exp_avg', 'exp_avg_sq'):
+                            if not _same_layout(self.state[p][name], p):
+                                raise ValueError(f'Yogi: {name} has strides {self.state[p][name].stride()}, its parameter '
+                                                 f'{p.stride()}: the moment buffers must share the layout of their parameter')
                     cached = (where, arr(chunk), arr([self.state[p]['exp_avg'] for p in chunk]),
                               arr([self.state[p]['exp_avg_sq'] for p in chunk]),
                               (ctypes.c_int64 * k)(*[p.numel() for p in chunk]))
                     self._chunk_cache[key] = cached
                 _, a_p, a_m, a_v, sizes = cached
+                # the kernel walks p, g, m, v in STORAGE order: the gradient goes in the parameter's own layout (row-major for
+                # the usual contiguous parameter; the strides of a dense transposed one -- checked where the cache is built)
+                grads = [(p.grad if p.grad.is_contiguous() else p.grad.contiguous()) if p.is_contiguous() else
+                         (p.grad if p.grad.stride() == p.stride() else torch.empty_like(p).copy_(p.grad)) for p in chunk]
+                if not all(g.is_cuda for g in grads):
+                    require_device(*grads)
                 ids = list(key)
                 if hyper is not None and id(hyper[1]) in ids:
                     h, p_mean, p_logvar = hyper
