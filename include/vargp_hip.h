@@ -184,6 +184,20 @@ size_t vargp_rff_paths_workspace_bytes(int S, int D, int R);
 int vargp_rff_paths(const float* theta, const float* X, const float* omega, const float* coef, float* out, int S, int C, int n,
                     int D, int R, int N, int x_shared, void* ws, size_t ws_bytes, vargp_stream_t stream);
 
+/* The backward of vargp_rff_paths in the points, same operand layouts; gout [S*C, n, N] is the gradient of out.  With
+ * om[s, r, d] = omega[r, d] / exp(theta[s, d]) and gs[s] = exp(theta[s, D]) / sqrt(R):
+ *   h[s, i, r] = sum_(c, k) gout[s, c, i, k] (-sin p[s, i, r] coef[s, c, r, k] + cos p[s, i, r] coef[s, c, R + r, k])
+ *   gX[i, d]   = sum_s gs[s] sum_r h[s, i, r] om[s, r, d]                      gX [n, D] (x_shared = 1) | [C, n, D] (0)
+ * (x_shared = 0: the sum in h runs over k only, on output c's own points, and gX keeps its c index.)  One pre-scaling launch,
+ * ONE fused launch (phase tile, gout coef^T, h and h om per 64 frequencies; neither p, the features nor h reach memory) whose
+ * workgroups each own one hyper-sample and one piece of R, and -- when that makes more than one partial sum -- one launch that
+ * adds the partial sums from the workspace in ascending order.  No atomics: two calls are bitwise equal.  Any n, D, R, N >= 1;
+ * S*C <= 65535; C*N <= 2^22; gX below 2^31 elements.
+ */
+size_t vargp_rff_paths_bwd_workspace_bytes(int S, int C, int n, int D, int R, int x_shared);
+int vargp_rff_paths_bwd(const float* theta, const float* X, const float* omega, const float* coef, const float* gout, float* gX,
+                        int S, int C, int n, int D, int R, int N, int x_shared, void* ws, size_t ws_bytes, vargp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Lloyd's two steps for G independent sets of K centres Z [G, K, D] over one data matrix X [N, D] (the model's z [C, M, D]: one
  * set per output).  Data-dependent initialisation of the inducing points; nothing of this is in the reference, whose inducing

@@ -99,6 +99,8 @@ _SIGNATURES = {
     'vargp_predictive_cov': (c_int, [_P] * 5 + [c_int] * 6 + [_P, c_size_t, _P]),
     'vargp_rff_paths_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'vargp_rff_paths': (c_int, [_P] * 5 + [c_int] * 7 + [_P, c_size_t, _P]),
+    'vargp_rff_paths_bwd_workspace_bytes': (c_size_t, [c_int] * 6),
+    'vargp_rff_paths_bwd': (c_int, [_P] * 6 + [c_int] * 7 + [_P, c_size_t, _P]),
     'vargp_kmeans_workspace_bytes': (c_size_t, [c_int] * 4),
     'vargp_kmeans_assign': (c_int, [_P] * 4 + [c_int] * 4 + [_P, c_size_t, _P]),
     'vargp_kmeans_update': (c_int, [_P] * 4 + [c_int] * 4 + [_P, c_size_t, _P]),

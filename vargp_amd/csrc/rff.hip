@@ -25,6 +25,29 @@
 // Tiles as pred_cov.hip: four waves as 2 x 2, slabs staged in LDS as [k][64 + 1], fragment maps as in gemm.hip.  The phase
 // product's next slab is fetched into registers while the current one is multiplied.  Any n, D, R, N: every staging load is
 // guarded and out-of-range elements enter as zeros.
+//
+// The backward in the points (vargp_rff_paths_bwd, rff_paths_bwd_kernel), gout [S][C][n][N] -> gX [n][D] | [C][n][D]:
+//
+//   h[s, i, r] = sum_(c, k) gout[s, c, i, k] (-sin p[s, i, r] coef[s, c, r, k] + cos p[s, i, r] coef[s, c, R + r, k])
+//   gX[i, d]   = sum_s gamma_s / sqrt(R) sum_r h[s, i, r] omega[r, d] / ell[s, d]
+//
+// (x_shared = 0: the sum in h runs over k only and gX keeps its c index.)  The same frame: a workgroup owns 64 points x BN = 64 WN
+// input dimensions of gX (WN = 1 | 2 | 4, 256-wide tiles of D side by side), one batch entry and one piece of R, and per 64
+// frequencies forms
+//   1. the phase tile, exactly as the forward kernel (same operands from rff_prep_kernel, same slabs, same prefetch);
+//   2. tc = gout coef[:R]^T and ts = gout coef[R:]^T over the C N (or N) columns, slabs of 16 columns of both staged through
+//      the area of the phase slabs -- 64 x 64 tiles with the SAME fragment map as the phases (point on the registers,
+//      frequency on the lanes);
+//   3. h = gamma / sqrt(R) (cos p ts - sin p tc) register by register with rff_sincos, stored to LDS as [frequency][point];
+//   4. gacc += h om: h is the A operand, the 64 rows of om (slabs of 64 | 32 | 16 rows through the same staging area) the B
+//      operand; gacc (64 x BN) lives across the loop over R.
+// Neither p, the features nor h reach memory.  The sum over the hyper-samples and over the pieces of R (as many pieces as bring
+// the launch to about 512 workgroups -- a function of the sizes alone) is not done with atomics: every workgroup stores its
+// tile of ONE partial sum [s][piece] in the workspace and rff_bwd_reduce_kernel adds them in ascending order (a single
+// partial sum is stored to gX directly).  One summation order: two calls are bitwise equal.  A D tile recomputes the phases
+// over all of D, which is the price of keeping h on the chip: D = 784 is four tiles.
+#include <algorithm>
+
 #include "common.h"
 
 namespace vargp {
@@ -185,6 +208,182 @@ __global__ __launch_bounds__(256, 2) void rff_paths_kernel(const RffArgs a) {
   }
 }
 
+// ---- backward in the points -------------------------------------------------------------------------------------------------
+struct RffBwdArgs {
+  const float *X, *om, *gs, *coef, *gout;
+  float* dst;                          // gX itself when there is one partial sum, else the partial sums [S KS][Cx][n][D]
+  int C, n, D, R, N;
+  int shared, Cc, cols;                // as RffArgs
+  int KS, steps;                       // the loop over R is cut into KS pieces of `steps` 64-frequency steps
+};
+
+// One workgroup: 64 points x BN = 64 WN input dimensions of gX for one batch entry and one piece of R.  Per step of 64
+// frequencies: acc = the phase tile (as the forward kernel); tc, ts = gout coef^T for the cos and the sin rows of coef, in the
+// SAME fragment positions as acc (point on the registers, frequency on the lanes), so h is formed register by register; h goes
+// to LDS as [frequency][point], the A operand of h om, whose accumulators gacc live across the loop.
+template <int WN>
+__global__ __launch_bounds__(256, 2) void rff_paths_bwd_kernel(const RffBwdArgs a) {
+  constexpr int BM = kRfBM, BR = kRfBR, BK = kRfBK, LD = BM + 1, BN = 64 * WN, LDN = BN + 1;
+  constexpr int JK = ((2 * BK * LD) / LDN) & ~1;        // rows of om that fit the staging area: 64 | 32 | 16
+  constexpr int QK = 16, LDC = 2 * BR + 1;              // columns (c, k) per slab of gout coef^T
+  static_assert(BM == BR && BM * BK == 8 * 256 && JK * BN == 16 * 256 && BR % JK == 0, "rff bwd: tile shape");
+  static_assert(QK * (LD + LDC) <= 2 * BK * LD && QK * BM == 4 * 256 && QK * 2 * BR == 8 * 256, "rff bwd: slabs of gout, coef");
+  __shared__ float stage[2 * BK * LD];                  // the slabs of the phase product; of gout and coef; of om
+  __shared__ float hs[BR * LD];                         // h [frequency][point]
+  float* Xs = stage;
+  float* Os = stage + BK * LD;
+  float* Gs = stage;
+  float* Cs = stage + QK * LD;
+
+  const int dt = blockIdx.y / a.KS, ks = blockIdx.y - dt * a.KS;
+  const int row0 = blockIdx.x * BM, col0 = dt * BN;
+  const int64_t b = blockIdx.z;
+  const int n = a.n, D = a.D, R = a.R, N = a.N;
+  const int s = a.shared ? (int)b : (int)(b / a.C);
+  const int cc = a.shared ? 0 : (int)(b % a.C);
+  const float* __restrict__ Xb = a.X + (int64_t)cc * n * D;
+  const float* __restrict__ om = a.om + (int64_t)s * R * D;
+  const float g = a.gs[s];
+  const int rbeg = ks * a.steps * BR, rend = min(R, rbeg + a.steps * BR);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = (wave >> 1) * 32, wf = (wave & 1) * 32, wc = (wave & 1) * 32 * WN;
+  const int l31 = lane & 31, h = lane >> 5;
+
+  // this thread's column of the om slabs
+  const int dq = col0 + tid % BN;
+  const bool dq_ok = dq < D;
+  const float* __restrict__ omd = om + (dq_ok ? dq : 0);
+
+  rf_f32x16 gacc[WN];
+#pragma unroll
+  for (int w = 0; w < WN; ++w)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) gacc[w][r] = 0.f;
+
+  float xr[8], orr[8];
+  auto gload = [&](int r0, int k0) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int e = tid + 256 * i, r = e / BK, k = e % BK;
+      const bool kok = k0 + k < D;
+      xr[i] = (kok && row0 + r < n) ? Xb[(int64_t)(row0 + r) * D + k0 + k] : 0.f;
+      orr[i] = (kok && r0 + r < R) ? om[(int64_t)(r0 + r) * D + k0 + k] : 0.f;
+    }
+  };
+  auto lstore = [&]() {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int e = tid + 256 * i, r = e / BK, k = e % BK;
+      Xs[k * LD + r] = xr[i];
+      Os[k * LD + r] = orr[i];
+    }
+  };
+
+  gload(rbeg, 0);
+  for (int r0 = rbeg; r0 < rend; r0 += BR) {
+    // 1. phases of 64 points x 64 frequencies; this wave: rows wr.., frequencies wf..
+    rf_f32x16 acc, tc, ts;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = tc[r] = ts[r] = 0.f;
+    for (int k0 = 0; k0 < D; k0 += BK) {
+      lstore();
+      __syncthreads();
+      int nk = k0 + BK, nr = r0;
+      if (nk >= D) { nk = 0; nr = r0 + BR; }
+      if (nr < rend) gload(nr, nk);
+#pragma unroll
+      for (int k = 0; k < BK; k += 2) {
+        const float af = Xs[(k + h) * LD + wr + l31];
+        const float bf = Os[(k + h) * LD + wf + l31];
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af, bf, acc, 0, 0, 0);
+      }
+      __syncthreads();
+    }
+
+    // 2. gout coef^T over the columns q = (c, k), QK at a time: tc against row r0 + f of coef, ts against row R + r0 + f
+    for (int q0 = 0; q0 < a.cols; q0 += QK) {
+      const int ql = tid & (QK - 1), il = tid / QK, q = q0 + ql;
+      const bool qok = q < a.cols;
+      const int qc = qok ? q / N : 0, qk = qok ? q - qc * N : 0;
+      const float* __restrict__ gq = a.gout + (b * a.Cc + qc) * n * N + qk;
+      const float* __restrict__ cq = a.coef + (b * a.Cc + qc) * 2 * R * N + qk;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int i = il + 16 * t;
+        Gs[ql * LD + i] = (qok && row0 + i < n) ? gq[(int64_t)(row0 + i) * N] : 0.f;
+      }
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        const int jl = il + 16 * t, f = r0 + (jl & (BR - 1));
+        const int64_t j = jl < BR ? f : (int64_t)R + f;
+        Cs[ql * LDC + jl] = (qok && f < R) ? cq[j * N] : 0.f;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < QK; k += 2) {
+        const float af = Gs[(k + h) * LD + wr + l31];
+        tc = __builtin_amdgcn_mfma_f32_32x32x2f32(af, Cs[(k + h) * LDC + wf + l31], tc, 0, 0, 0);
+        ts = __builtin_amdgcn_mfma_f32_32x32x2f32(af, Cs[(k + h) * LDC + BR + wf + l31], ts, 0, 0, 0);
+      }
+      __syncthreads();
+    }
+
+    // 3. h = gamma / sqrt(R) (cos p ts - sin p tc), in registers; to LDS as [frequency][point].  Frequencies >= R: coef entered
+    // as zeros, so h is zero there
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = wr + (r & 3) + 8 * (r >> 2) + 4 * h;
+      float sn, cs;
+      rff_sincos(acc[r], sn, cs);
+      hs[(wf + l31) * LD + row] = g * (cs * ts[r] - sn * tc[r]);
+    }
+    __syncthreads();
+
+    // 4. gacc += h om over the 64 frequencies of this step, JK at a time
+    for (int js = 0; js < BR; js += JK) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int jl = (tid + 256 * i) / BN, r = r0 + js + jl;
+        stage[jl * LDN + tid % BN] = (dq_ok && r < R) ? omd[(int64_t)r * D] : 0.f;
+      }
+      __syncthreads();
+#pragma unroll 8
+      for (int k = 0; k < JK; k += 2) {
+        const float af = hs[(js + k + h) * LD + wr + l31];
+#pragma unroll
+        for (int w = 0; w < WN; ++w)
+          gacc[w] = __builtin_amdgcn_mfma_f32_32x32x2f32(af, stage[(k + h) * LDN + wc + 32 * w + l31], gacc[w], 0, 0, 0);
+      }
+      __syncthreads();
+    }
+  }
+
+  // the only store: this (hyper-sample, piece of R)'s share of gX
+  const int Cx = a.shared ? 1 : a.C;
+  float* __restrict__ dst = a.dst + (((int64_t)s * a.KS + ks) * Cx + cc) * n * D;
+#pragma unroll
+  for (int w = 0; w < WN; ++w) {
+    const int d = col0 + wc + 32 * w + l31;
+    if (d >= D) continue;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = row0 + wr + (r & 3) + 8 * (r >> 2) + 4 * h;
+      if (row < n) dst[(int64_t)row * D + d] = gacc[w][r];
+    }
+  }
+}
+
+// gX[e] = sum_p part[p][e], p ascending: one summation order
+__global__ __launch_bounds__(256) void rff_bwd_reduce_kernel(const float* __restrict__ part, float* __restrict__ gX, int P,
+                                                             int64_t E) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= E) return;
+  float acc = part[e];
+  for (int p = 1; p < P; ++p) acc += part[(int64_t)p * E + e];
+  gX[e] = acc;
+}
+
 }  // namespace vargp
 
 using namespace vargp;
@@ -225,4 +424,67 @@ extern "C" int vargp_rff_paths(const float* theta, const float* X, const float* 
   else if (a.cols <= 128) hipLaunchKernelGGL((rff_paths_kernel<2>), dim3(cdiv(n, kRfBM), 1, nb), blk, 0, st, a);
   else hipLaunchKernelGGL((rff_paths_kernel<4>), dim3(cdiv(n, kRfBM), cdiv(a.cols, 256), nb), blk, 0, st, a);
   return check_launch("rff_paths");
+}
+
+// How the backward is cut: WN (the width of a D tile), the D tiles, and the pieces of R -- enough of them for about 512
+// workgroups, a function of the sizes alone, so that the summation order is too.
+struct RffBwdPlan {
+  int wn, dtiles, KS, steps;
+  int64_t E;                           // elements of gX
+  size_t part_floats;                  // the partial sums (none when S KS = 1)
+};
+
+static RffBwdPlan rff_bwd_plan(int S, int C, int n, int D, int R, int x_shared) {
+  RffBwdPlan p{};
+  p.wn = D <= 64 ? 1 : D <= 128 ? 2 : 4;
+  p.dtiles = cdiv(D, 64 * p.wn);
+  const int64_t wgs = (int64_t)cdiv(n, kRfBM) * p.dtiles * (x_shared ? S : (int64_t)S * C);
+  const int nsteps = cdiv(R, kRfBR);
+  const int want = (int)std::min<int64_t>(nsteps, std::max<int64_t>(1, (512 + wgs - 1) / wgs));
+  p.steps = cdiv(nsteps, want);
+  p.KS = cdiv(nsteps, p.steps);
+  p.E = (int64_t)(x_shared ? 1 : C) * n * D;
+  p.part_floats = (int64_t)S * p.KS > 1 ? (size_t)round_up((int64_t)S * p.KS * p.E, 64) : 0;
+  return p;
+}
+
+extern "C" size_t vargp_rff_paths_bwd_workspace_bytes(int S, int C, int n, int D, int R, int x_shared) {
+  if (S <= 0 || C <= 0 || n <= 0 || D <= 0 || R <= 0) return 0;
+  return (rff_ws_floats(S, D, R) + rff_bwd_plan(S, C, n, D, R, x_shared).part_floats) * sizeof(float) + 256;
+}
+
+extern "C" int vargp_rff_paths_bwd(const float* theta, const float* X, const float* omega, const float* coef, const float* gout,
+                                   float* gX, int S, int C, int n, int D, int R, int N, int x_shared, void* ws, size_t ws_bytes,
+                                   vargp_stream_t stream) {
+  VARGP_REQUIRE(theta && X && omega && coef && gout && gX && ws, "rff_paths_bwd: null pointer");
+  VARGP_REQUIRE(S > 0 && C > 0 && n > 0 && D > 0 && R > 0 && N > 0, "rff_paths_bwd: bad dims");
+  VARGP_REQUIRE(x_shared == 0 || x_shared == 1, "rff_paths_bwd: x_shared = %d (0 or 1)", x_shared);
+  VARGP_REQUIRE((int64_t)S * C <= 65535, "rff_paths_bwd: S C = %lld (at most 65535)", (long long)S * C);
+  VARGP_REQUIRE((int64_t)C * N <= (1 << 22), "rff_paths_bwd: C N = %lld (at most 2^22)", (long long)C * N);
+  VARGP_REQUIRE((int64_t)n * D < (1LL << 31) && (int64_t)R * D < (1LL << 31) && (int64_t)2 * R * N < (1LL << 31) &&
+                    (int64_t)n * N < (1LL << 31),
+                "rff_paths_bwd: n D, R D, 2 R N and n N must be below 2^31");
+  const RffBwdPlan p = rff_bwd_plan(S, C, n, D, R, x_shared);
+  VARGP_REQUIRE(p.E < (1LL << 31), "rff_paths_bwd: gX has %lld elements (below 2^31)", (long long)p.E);
+  VARGP_REQUIRE((int64_t)p.dtiles * p.KS <= 65535, "rff_paths_bwd: %d tiles of D x %d pieces of R (at most 65535)", p.dtiles,
+                p.KS);
+  VARGP_REQUIRE(ws_bytes >= vargp_rff_paths_bwd_workspace_bytes(S, C, n, D, R, x_shared), "rff_paths_bwd: workspace too small");
+  hipStream_t st = as_stream(stream);
+  float* om = reinterpret_cast<float*>(ws);
+  float* gs = om + round_up((int64_t)S * R * D, 64);
+  float* part = gs + round_up(S, 64);
+  const int P = S * p.KS;
+  ProfScope whole("rff_paths_bwd", st);
+  hipLaunchKernelGGL(rff_prep_kernel, dim3(cdiv((int64_t)S * R * D, 256)), dim3(256), 0, st, theta, omega, om, gs, S, D, R);
+  RffBwdArgs a{};
+  a.X = X; a.om = om; a.gs = gs; a.coef = coef; a.gout = gout; a.dst = P > 1 ? part : gX;
+  a.C = C; a.n = n; a.D = D; a.R = R; a.N = N;
+  a.shared = x_shared; a.Cc = x_shared ? C : 1; a.cols = a.Cc * N;
+  a.KS = p.KS; a.steps = p.steps;
+  const dim3 grid(cdiv(n, kRfBM), p.dtiles * p.KS, x_shared ? S : S * C), blk(256);
+  if (p.wn == 1) hipLaunchKernelGGL((rff_paths_bwd_kernel<1>), grid, blk, 0, st, a);
+  else if (p.wn == 2) hipLaunchKernelGGL((rff_paths_bwd_kernel<2>), grid, blk, 0, st, a);
+  else hipLaunchKernelGGL((rff_paths_bwd_kernel<4>), grid, blk, 0, st, a);
+  if (P > 1) hipLaunchKernelGGL(rff_bwd_reduce_kernel, dim3(cdiv(p.E, 256)), dim3(256), 0, st, part, gX, P, p.E);
+  return check_launch("rff_paths_bwd");
 }

@@ -523,6 +523,37 @@ def rff_paths(theta, X, omega, coef, x_shared):
     return out
 
 
+class _RffPathsX(Function):
+    @staticmethod
+    def forward(ctx, theta, X, omega, coef, x_shared):
+        out = rff_paths(theta, X, omega, coef, x_shared)
+        ctx.save_for_backward(*(t.detach().contiguous() for t in (theta, X, omega, coef)))
+        ctx.x_shared = bool(x_shared)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        theta, X, omega, coef = ctx.saved_tensors
+        gout = gout.contiguous()
+        S, D = theta.shape[0], theta.shape[1] - 1
+        R, C, N, n = omega.shape[0], coef.shape[1], coef.shape[3], X.shape[-2]
+        assert gout.dtype == torch.float32 and gout.shape == (S, C, n, N), (gout.dtype, gout.shape)
+        gX = torch.empty_like(X)
+        shared = int(ctx.x_shared)
+        ws = scratch(lib().vargp_rff_paths_bwd_workspace_bytes(S, C, n, D, R, shared), X.device)
+        check(lib().vargp_rff_paths_bwd(ptr(theta), ptr(X), ptr(omega), ptr(coef), ptr(gout), ptr(gX), S, C, n, D, R, N, shared,
+                                        ptr(ws), ws.numel() * 4, stream_ptr()), 'vargp_rff_paths_bwd')
+        return None, gX, None, None, None
+
+
+def rff_paths_x(theta, X, omega, coef, x_shared):
+    """rff_paths as an autograd node, differentiable in the points X only (theta, omega and coef get None): the forward is
+    rff_paths itself, bit for bit; the backward is ONE fused kernel (csrc/rff.hip, vargp_rff_paths_bwd) that stores neither the
+    phases, the features nor their gradient  ->  gX of X's shape.  Two backward calls are bitwise equal."""
+    return _RffPathsX.apply(theta, X, omega, coef, x_shared)
+
+
 # Lloyd's two steps for G sets of K centres over one data matrix (csrc/kmeans.hip -- not in the reference).  No autograd.
 
 def _kmeans_args(X, Z):

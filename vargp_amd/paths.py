@@ -12,7 +12,9 @@ For hyper-sample s and output c, with R frequencies omega (kernel.spectral_frequ
 
 with (m, S_u) the moments of q(u_<=t | theta) and Lz = chol(K(z, z) + eps I), the factors of VARGP.predict_f.  E f is
 predict_f's mean for any R; Cov f tends to predict_f's covariance less JITTER A A^T (A = P^T Lz^-1) as R grows.  The feature
-products g(z) and g(x) are ops.rff_paths (csrc/rff.hip): the features never reach memory.
+products g(z) and g(x) are ops.rff_paths (csrc/rff.hip): the features never reach memory.  PosteriorPaths.differentiable
+evaluates the same functions on the autograd graph of x (ops.rff_paths_x: a fused HIP backward in the points), which is
+what following one sampled function along its slope needs (PosteriorPaths.ascend).
 """
 import copy
 
@@ -73,3 +75,28 @@ class PosteriorPaths:
                 Kzx = self.kernel.compute(self.theta, self.z, xb)                                              # (S, C, Mt, b)
                 out.append(ops.matmul(Kzx.mT, self.V, D=g, beta=1.0))
             return torch.cat(out, dim=-2).permute(3, 0, 1, 2).contiguous()
+
+    def differentiable(self, x):
+        """The paths at x (B, D) -> (n_paths, S, C, B): the values of paths(x), attached to the autograd graph of x, so that
+        torch.autograd.grad(f[k, s, c].sum(), x) is the slope of ONE sampled function at all B points (row b of x enters
+        column b of f only).  Only x is differentiated: theta, omega, the weights, V, z and the kernel copy are frozen and never
+        receive a gradient.  No `tile` here: the graph keeps K(z, x), S C Mt B floats, until the backward has run, whatever
+        the blocks -- sweep x in blocks yourself where that is too much.  The feature product's backward is one fused kernel
+        (ops.rff_paths_x): the S B 2R features are not saved."""
+        theta, z, V = self.theta.detach(), self.z.detach(), self.V.detach()
+        g = ops.rff_paths_x(theta, self._features(x), self.omega, self.coef, True)                             # (S, C, B, N)
+        Kzx = self.kernel.compute(theta, z, x)                                                                 # (S, C, Mt, B)
+        return ops.matmul(Kzx.mT, V, D=g, beta=1.0).permute(3, 0, 1, 2).contiguous()
+
+    def ascend(self, x0, index, n_steps=100, step_size=1e-2):
+        """Plain gradient ascent of the single function f[index], index = (k, s, c): path k of hyper-sample s and output c.
+        x0 (B, D) is a set of starting points, one independent ascent per row, n_steps steps x <- x + step_size df/dx.
+        -> (x (B, D), f(x) (B,)), detached.  Each function costs its own backward pass: ascending several of them means one
+        call (and one backward per step) each."""
+        k, s, c = index
+        x = x0.detach().clone()
+        for _ in range(int(n_steps)):
+            x.requires_grad_(True)
+            grad, = torch.autograd.grad(self.differentiable(x)[k, s, c].sum(), x)
+            x = x.detach() + step_size * grad
+        return x, self(x)[k, s, c]
