@@ -119,11 +119,12 @@ def _batch3(shape, strides):
     return [1] * pad + list(shape), [0] * pad + list(strides)
 
 
-def bgemm(A, B, alpha=1.0, D=None, beta=0.0, triA=NONE, triB=NONE, triC=NONE, out=None):
-    """C = alpha * A @ B + beta * D on the MFMA GEMM; A: (..., M, K), B: (..., K, N) with
-    broadcasting over the leading dims (views with stride 0 and .mT views are consumed in place)."""
-    require_device(A, B, D)
-    assert A.dtype == torch.float32 and B.dtype == torch.float32
+def _gemm_desc(A, B, D, C, alpha, beta, triA, triB, triC):
+    """The GemmDesc of C = alpha * A @ B + beta * D, -> (desc, keep, C): layouts, leading dimensions, the three batch sizes and
+    strides (in elements) and the pointers.  `keep` = [A, B(, D)] as the descriptor addresses them -- the caller's own views
+    wherever the kernel can consume them in place, contiguous copies otherwise -- and has to outlive the launch.  C = None: the
+    result is allocated here.  No device check and no launch: the addressing is the same for host tensors, which is how the
+    suite checks it."""
     M, K = A.shape[-2:]
     K2, N = B.shape[-2:]
     assert K == K2, (A.shape, B.shape)
@@ -137,9 +138,12 @@ def bgemm(A, B, alpha=1.0, D=None, beta=0.0, triA=NONE, triB=NONE, triC=NONE, ou
         Be = Be.reshape(-1, K, N)
         Ae, tA, lda = _mat_layout(Ae)
         Be, tB, ldb = _mat_layout(Be)
-    C = out if out is not None else torch.empty(*bshape, M, N, dtype=torch.float32, device=A.device)
+    if C is None:
+        C = torch.empty(*bshape, M, N, dtype=torch.float32, device=A.device)
     assert tuple(C.shape) == (*bshape, M, N) and (C.stride(-1) == 1 or N == 1), 'bgemm: bad `out`'
-    Cv = C.reshape(-1, M, N) if len(bshape) > 3 else C
+    # (view, not reshape: where the batch dimensions of a strided `out` do not fold into one, reshape would hand back a copy,
+    #  and the product would be written there)
+    Cv = C.view(-1, M, N) if len(bshape) > 3 else C
     nbs, sA = _batch3(Ae.shape[:-2], Ae.stride()[:-2])
     _, sB = _batch3(Be.shape[:-2], Be.stride()[:-2])
     _, sC = _batch3(Cv.shape[:-2], Cv.stride()[:-2])
@@ -151,7 +155,9 @@ def bgemm(A, B, alpha=1.0, D=None, beta=0.0, triA=NONE, triB=NONE, triC=NONE, ou
     keep = [Ae, Be]
     if D is not None:
         De = D.expand(*bshape, M, N)
-        if De.stride(-1) != 1 and N > 1:
+        # the kernel reads D[row * ldd + col] with ldd >= N: a D broadcast over columns (stride(-1) == 0) or over rows
+        # (stride(-2) == 0 < N) has no such form
+        if (De.stride(-1) != 1 and N > 1) or (M > 1 and De.stride(-2) < N):
             De = De.contiguous()
         if len(bshape) > 3:
             De = De.reshape(-1, M, N)
@@ -166,7 +172,27 @@ def bgemm(A, B, alpha=1.0, D=None, beta=0.0, triA=NONE, triB=NONE, triC=NONE, ou
         d.sA[i], d.sB[i], d.sC[i], d.sD[i] = sA[i], sB[i], sC[i], sD[i]
     d.alpha, d.beta = float(alpha), float(beta)
     d.triA, d.triB, d.triC = triA, triB, triC
-    if M > 0 and N > 0 and C.numel() > 0:
+    return d, keep, C
+
+
+def bgemm(A, B, alpha=1.0, D=None, beta=0.0, triA=NONE, triB=NONE, triC=NONE, out=None):
+    """C = alpha * A @ B + beta * D on the MFMA GEMM; A: (..., M, K), B: (..., K, N) with
+    broadcasting over the leading dims (views with stride 0 and .mT views are consumed in place)."""
+    require_device(A, B, D)
+    assert A.dtype == torch.float32 and B.dtype == torch.float32
+    if A.shape[-1] == 0:
+        # an empty sum: nothing to launch (and empty operands have no address to hand over); C = beta * D, or zeros
+        M, N = A.shape[-2], B.shape[-1]
+        bshape = torch.broadcast_shapes(A.shape[:-2], B.shape[:-2], D.shape[:-2] if D is not None else ())
+        C = out if out is not None else torch.empty(*bshape, M, N, dtype=torch.float32, device=A.device)
+        assert B.shape[-2] == 0 and tuple(C.shape) == (*bshape, M, N), 'bgemm: bad `out`'
+        if D is not None:
+            torch.mul(D.expand(*bshape, M, N), float(beta), out=C)
+        else:
+            C.zero_()
+        return C
+    d, keep, C = _gemm_desc(A, B, D, out, alpha, beta, triA, triB, triC)
+    if d.M > 0 and d.N > 0 and C.numel() > 0:
         check(lib().vargp_bgemm(d, stream_ptr()), 'vargp_bgemm')
     return C
 
