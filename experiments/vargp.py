@@ -28,7 +28,7 @@ from torch.utils.data import ConcatDataset, DataLoader  # noqa: E402
 import vargp_amd  # noqa: E402
 from vargp_amd.datasets import PermutedMNIST, SplitMNIST, ToyDataset  # noqa: E402
 from vargp_amd.train import ElboTrainer  # noqa: E402
-from vargp_amd.train_utils import DeviceBatches, EarlyStopper, compute_accuracy, compute_lpd, set_seeds  # noqa: E402
+from vargp_amd.train_utils import DeviceBatches, EarlyStopper, compute_accuracy, compute_lpd, compute_uncertainty, set_seeds  # noqa: E402
 from vargp_amd.vargp import VARGP  # noqa: E402
 
 
@@ -52,7 +52,8 @@ def train(task_id, train_set, val_set, test_set, ep_var_mean=True, map_est_hyper
           epochs=1, M=20, n_f=10, n_var_samples=3, batch_size=512, lr=1e-2, beta=1.0,
           eval_interval=10, patience=20, prev_params=None, logger=None, device=None, graph=False, seed=None,
           retrain=False, eval_shared_hypers=False, dataloader=False, kernel='rbf', native_kernel=False,
-          likelihood='softmax', link='probit', lpd=False, z_init='random', kmeans_iters=20, lengthscale_init='default'):
+          likelihood='softmax', link='probit', lpd=False, z_init='random', kmeans_iters=20, lengthscale_init='default',
+          uncertainty=False):
     if retrain:      # the variant of experiments/vargp_retrain.py:14-19 (earlier tasks' inducing parameters re-optimised)
         from vargp_amd.vargp_retrain import VARGPRetrain
         assert kernel == 'rbf', '--retrain builds its model with the RBF kernel'
@@ -153,6 +154,9 @@ def train(task_id, train_set, val_set, test_set, ep_var_mean=True, map_est_hyper
             if lpd:      # --lpd: mean held-out log predictive density of the test set (every task seen so far)
                 loss_summary[f'task{task_id}/test/lpd'] = compute_lpd(test_set, gp, device=device,
                                                                       shared_hypers=eval_shared_hypers)
+            if uncertainty:      # --uncertainty: mean predictive entropy of the same test set and its epistemic part (nats)
+                ent, _, mi = compute_uncertainty(test_set, gp, device=device, shared_hypers=eval_shared_hypers)
+                loss_summary[f'task{task_id}/test/entropy'], loss_summary[f'task{task_id}/test/mi'] = ent, mi
             if logger is not None:
                 for k, v in dict(**loss_summary, **acc_summary).items():
                     logger.add_scalar(k, v, global_step=e + 1)
@@ -197,7 +201,8 @@ def toy(args):
                    link=args.link, prev_params=prev_params, logger=logger, device=device, patience=-1,
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed, retrain=args.retrain,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
-                   lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init)
+                   lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init,
+                   uncertainty=args.uncertainty)
         prev_params.append(sd)
     logger.close()
 
@@ -224,7 +229,8 @@ def split_mnist(args):
                    link=args.link, prev_params=prev_params, logger=logger, device=device,
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
-                   lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init)
+                   lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init,
+                   uncertainty=args.uncertainty)
         prev_params.append(sd)
     logger.close()
 
@@ -254,7 +260,8 @@ def permuted_mnist(args):
                    link=args.link, prev_params=prev_params, logger=logger,
                    device=device, eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
-                   lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init)
+                   lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init,
+                   uncertainty=args.uncertainty)
         prev_params.append(sd)
     logger.close()
 
@@ -314,6 +321,10 @@ def parse_args(argv=None):
         sp.add_argument('--lpd', action='store_true',
                         help='also log test/lpd at every evaluation: the mean held-out log predictive density per point of '
                              'the test set of the tasks seen so far (VARGP.log_prob)')
+        sp.add_argument('--uncertainty', action='store_true',
+                        help='also log test/entropy and test/mi at every evaluation: the mean predictive entropy per point of '
+                             'the test set of the tasks seen so far and its epistemic part, the mutual information of the '
+                             'label and the model (VARGP.uncertainty; nats)')
         if name == 'toy':
             sp.add_argument('--retrain', action='store_true',
                             help='VARGPRetrain (reference: experiments/vargp_retrain.py toy): re-optimise the earlier '

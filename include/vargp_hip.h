@@ -374,6 +374,45 @@ int vargp_studentt_lpd(const float* mu, const float* var, const float* y, int64_
                        float lognorm, float* lpd, float* lpd_out, int S, int C, int B, vargp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Predictive entropy of the classification likelihoods, split into noise and lack of knowledge (vargp_amd/csrc/uncertainty.hip).
+ * The reference has no counterpart.  mu, var [S, C, B]: the predictive moments of f under hyper-sample s.  All values in nats.
+ *     total    = H[ E p(y | theta, f) ]     the entropy of the predictive distribution
+ *     expected = E H[ p(y | theta, f) ]     the mean entropy of the samples' own distributions: noise (aleatoric)
+ *     mi       = max(total - expected, 0)   the mutual information of the label and (theta, f): lack of knowledge (epistemic)
+ *   total >= expected holds exactly (Jensen: both sides use the same samples / the same rule); the clamp removes rounding only.
+ *   softmax, eps [S, F, C, B]; the S F samples are p_sf = softmax_c(mu_s + sqrt(var_s) eps_sf):
+ *     probs[b,c]  = mean_sf p_sf[c,b]                            [B, C]  (the definition of vargp_softmax_predict; may be NULL)
+ *     total[b]    = - sum_c probs[b,c] log probs[b,c]            [B]     (0 log 0 = 0;  0 <= total <= log C)
+ *     expected[b] = mean_sf ( - sum_c p_sf[c,b] log p_sf[c,b] )  [B]     evaluated as Z - sum_c p_c f_c with Z the max-shifted
+ *                                                                        logsumexp_c f_c: log(0) is never evaluated
+ *     mi[b]                                                      [B]
+ *   Any C.  Nothing of size S F C B is written: ws holds S F B + B doubles, vargp_softmax_uncertainty_workspace_bytes(S, F, C, B)
+ *   bytes of 8-byte aligned device scratch used inside the call only.
+ *   bernoulli, link as in the Bernoulli section; the outputs are independent, so everything is per output (c, b).  With the
+ *   20-node Gauss-Hermite rule of that section (x_k, w^_k), which here too is the definition -- for the probit link as well, where
+ *   vargp_bernoulli_predict uses the closed form: probs differs from it by the rule's quadrature error -- f_k = mu + sqrt(2 var) x_k
+ *   and h(p) = - p log p - (1 - p) log(1 - p):
+ *     p_out[c,b]        = mean_s sum_k w^_k Lambda(f_k)          written to probs [B, C] (may be NULL)
+ *     total_out[c,b]    = h(p_out)                               [C, B]  (may be NULL)   the 1 - p_out in h is accumulated as
+ *                                                                        mean_s sum_k w^_k Lambda(-f_k), with its own digits
+ *     expected_out[c,b] = mean_s sum_k w^_k h(Lambda(f_k))       [C, B]  (may be NULL)   from log Lambda(f_k) and log Lambda(-f_k)
+ *                                                                        in fp64: finite and correct at |f| = 30 and beyond
+ *     mi_out[c,b]       = max(total_out - expected_out, 0)       [C, B]  (may be NULL)
+ *     total, expected, mi [B] = the sums over c of the three (required): the one-vs-rest score, an upper bound on the entropy
+ *     of the joint label vector.  No workspace.
+ * Deterministic: no float atomics, every sum in a fixed order (same inputs -> bitwise identical outputs).  Inputs and outputs are
+ * fp32; the element arithmetic, every sum and the subtraction in mi run in fp64, so each output is rounded once.  No gradients.
+ * Argument errors (NULL required pointer, non-positive size, bad link, workspace missing, misaligned or too small) return
+ * VARGP_EINVAL before any launch.
+ */
+size_t vargp_softmax_uncertainty_workspace_bytes(int S, int F, int C, int B);
+int vargp_softmax_uncertainty(const float* mu, const float* var, const float* eps, float* probs, float* total, float* expected,
+                              float* mi, int S, int F, int C, int B, float* ws, size_t ws_bytes, vargp_stream_t stream);
+int vargp_bernoulli_uncertainty(const float* mu, const float* var, int link, float* probs, float* total, float* expected,
+                                float* mi, float* total_out, float* expected_out, float* mi_out, int S, int C, int B,
+                                vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Yogi optimiser step, fused over one flat parameter buffer (reference call site:
  * experiments/vargp.py:23,37 -> torch_optimizer.Yogi; algorithm from Zaheer et al. 2018).
  * bias1/bias2 = 1 - beta^t; if `step` (device pointer to the step count t as a float) is not NULL

@@ -130,6 +130,9 @@ _SIGNATURES = {
     'vargp_bernoulli_lpd': (c_int, [_P, _P, _P, c_int64, _P, c_int, _P, _P, c_int, c_int, c_int, _P]),
     'vargp_poisson_lpd': (c_int, [_P, _P, _P, c_int64, _P, _P, c_int, c_int, c_int, _P]),
     'vargp_studentt_lpd': (c_int, [_P, _P, _P, c_int64, _P, c_float, c_float, _P, _P, c_int, c_int, c_int, _P]),
+    'vargp_softmax_uncertainty_workspace_bytes': (c_size_t, [c_int] * 4),
+    'vargp_softmax_uncertainty': (c_int, [_P] * 7 + [c_int] * 4 + [_P, c_size_t, _P]),
+    'vargp_bernoulli_uncertainty': (c_int, [_P, _P, c_int] + [_P] * 7 + [c_int, c_int, c_int, _P]),
     'vargp_yogi_step_multi': (c_int, [c_int, _P, _P, _P, _P, _P] + [c_float] * 4 + [_P, c_int, _P]),
     'vargp_yogi_step_multi_hyper': (c_int, [c_int, _P, _P, _P, _P, _P] + [c_float] * 4 + [_P, c_int, POINTER(HyperGradDesc), c_int,
                                             c_int, _P]),

@@ -1,5 +1,6 @@
 // What the kernels of the independent-output likelihoods share (indep_lik.hip: the ELBO term E_q[log p] and its gradients;
-// lpd.hip: the held-out log predictive density): the quadrature table, the target readers and one struct per likelihood.
+// lpd.hip: the held-out log predictive density; uncertainty.hip: the predictive entropy and its parts): the quadrature table,
+// the target readers and one struct per likelihood.
 //   Bernoulli   p(t | f) = Lambda(s f), s = 2 t - 1, Lambda = Phi (probit) or the logistic function (logit)
 //   Poisson     p(y | f) = exp(y f - exp(f)) / y!                                                (log link: counts)
 //   Student-t   p(y | f) = t_nu((y - f) / sigma_c) / sigma_c,  sigma_c = exp(log_scale[c])       (fixed nu: outliers)
@@ -73,7 +74,7 @@ struct Target {
   __device__ __forceinline__ float at(int c, size_t b) const { return y[(size_t)c * (size_t)ldy + b]; }
 };
 
-// A link: eval(z, lp, dlp) = log Lambda(z) and its derivative; prob(z) = Lambda(z).  fp32.
+// A link: eval(z, lp, dlp) = log Lambda(z) and its derivative; prob(z) = Lambda(z).  fp32.  logp(z) = log Lambda(z) in fp64.
 struct LinkProbit {
   // With a = |z| / sqrt2 and the scaled complementary error function erfcx(a) = exp(a^2) erfc(a) (finite and accurate for every
   // a >= 0):  z < 0:  Phi(z) = erfcx(a) exp(-a^2) / 2  ->  log Phi = log(erfcx(a) / 2) - a^2,  phi / Phi = sqrt(2 / pi) / erfcx(a)
@@ -92,6 +93,11 @@ struct LinkProbit {
     }
   }
   static __device__ __forceinline__ float prob(float z) { return 0.5f * erfcf(-z * (float)kInvSqrt2); }
+  // log Phi(z) in fp64, the two branches of eval: finite for every finite z (uncertainty.hip)
+  static __device__ __forceinline__ double logp(double z) {
+    const double a = fabs(z) * kInvSqrt2, ex = erfcx(a);
+    return z < 0.0 ? log(0.5 * ex) - a * a : log1p(-0.5 * ex * exp(-a * a));
+  }
 };
 struct LinkLogit {
   // log sigma(z) = -softplus(-z) = min(z, 0) - log1p(exp(-|z|));  (log sigma)' = sigma(-z)
@@ -106,6 +112,8 @@ struct LinkLogit {
     const float t = expf(-fabsf(z)), r = 1.f / (1.f + t);
     return z < 0.f ? t * r : r;
   }
+  // log sigma(z) in fp64 (uncertainty.hip)
+  static __device__ __forceinline__ double logp(double z) { return fmin(z, 0.0) - log1p(exp(-fabs(z))); }
 };
 
 // ell = sum_k w^_k log Lambda(s (mu + sqrt(2 var) x_k)) in fp32;

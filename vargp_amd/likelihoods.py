@@ -13,11 +13,29 @@ All but the softmax are "external" (_ExternalLikelihood): the native ELBO progra
 Every class names the layout of what its `predict` returns in `predict_batch_dim`: the dim that runs over the data points
 (0 for probabilities (B, C), -1 for per-sample values (S, C, B)) -- what a tiled prediction concatenates along.
 Every class has `log_prob(mu, var, y, per_output=False)`: the held-out log predictive density per point (B,), log E_q[p(y)] -- the
-mixture over the hyper-samples of the marginal likelihood of the point's targets (csrc/lpd.hip; not in the reference, no gradients)."""
+mixture over the hyper-samples of the marginal likelihood of the point's targets (csrc/lpd.hip; not in the reference, no gradients).
+The classification likelihoods (softmax, Bernoulli) have `uncertainty(mu, var, per_output=False)`: the predictive entropy per point
+split into noise and lack of knowledge (Uncertainty; csrc/uncertainty.hip; not in the reference, no gradients); the regression
+likelihoods raise ValueError."""
+from collections import namedtuple
+
 import torch
 import torch.nn as nn
 
 from . import noise, ops
+
+
+Uncertainty = namedtuple('Uncertainty', 'probs total aleatoric epistemic total_out aleatoric_out epistemic_out', defaults=(None,) * 3)
+Uncertainty.__doc__ = """Predictive entropy per point, in nats: probs (B, C), the predictive probabilities the entropies belong to;
+total (B,) = H[E p(y | theta, f)]; aleatoric (B,) = E H[p(y | theta, f)], the noise every sample agrees on; epistemic (B,) =
+max(total - aleatoric, 0), the mutual information of the label and the model's random variables.  The three *_out (C, B): the
+per-output values of independent outputs, whose sums over the outputs the (B,) arrays are; None unless asked for."""
+
+
+def cat_uncertainty(parts):
+    """One Uncertainty from those of consecutive blocks of points: probs (B, C) and the (B,) entropies run over the points in
+    dim 0, the per-output arrays (C, B) in dim 1."""
+    return Uncertainty(*(None if f[0] is None else torch.cat(f, dim=0 if k < 4 else 1) for k, f in enumerate(zip(*parts))))
 
 
 class MulticlassSoftmax(nn.Module):
@@ -53,6 +71,15 @@ class MulticlassSoftmax(nn.Module):
             raise ValueError('MulticlassSoftmax.log_prob: the softmax has no per-output marginals (per_output=True)')
         return ops.softmax_lpd(mu, var, self._eps(mu), y)
 
+    def uncertainty(self, mu, var, per_output=False):
+        """Uncertainty(probs (B, C), total, aleatoric, epistemic (B,)) of the S F samples p_sf = softmax(mu + sqrt(var) eps), eps
+        drawn as predict draws it: probs = mean_sf p_sf (predict's definition), total = the entropy of probs, aleatoric =
+        mean_sf of the entropy of p_sf, epistemic = max(total - aleatoric, 0); nats, 0 <= epistemic <= total <= log C.  The
+        classes share one normaliser: there are no per-output parts (per_output=True: ValueError).  No gradients."""
+        if per_output:
+            raise ValueError('MulticlassSoftmax.uncertainty: the softmax has no per-output parts (per_output=True)')
+        return Uncertainty(*ops.softmax_uncertainty(mu, var, self._eps(mu)))
+
 
 class _ExternalLikelihood(nn.Module):
     """A likelihood with independent outputs on the uniform `vargp_<kind>_*` entries (ops.lik_nll_fwd / lik_nll_bwd / lik_lpd).
@@ -83,6 +110,12 @@ class _ExternalLikelihood(nn.Module):
         target under f ~ N(mu, var); per_output: (lpd, lpd_out (C, B)) with the per-output marginals.  Not in the reference.
         No gradients."""
         return ops.lik_lpd(self.kind, mu, var, y, self._extra(), per_output)
+
+    def uncertainty(self, mu, var, per_output=False):
+        """The split of the predictive entropy into noise and lack of knowledge: classification likelihoods only
+        (BernoulliLikelihood overrides this).  The entropy of a predictive mixture of densities has no closed form."""
+        raise ValueError(f'{type(self).__name__}.uncertainty: the predictive entropy split is defined for the classification '
+                         'likelihoods (MulticlassSoftmax, BernoulliLikelihood) only')
 
     # -- the native programs' ext_lik route ------------------------------------------------------------------------------------
     def ext_target(self, y, C, B):
@@ -163,6 +196,16 @@ class BernoulliLikelihood(_ExternalLikelihood):
         The outputs are independent: a row is NOT normalised over c.  Probit: Phi(mu / sqrt(1 + var)) in closed form; logit:
         the 20-node rule on the logistic function."""
         return ops.bernoulli_predict(mu, var, self.link)
+
+    def uncertainty(self, mu, var, per_output=False):
+        """Uncertainty(probs (B, C), total, aleatoric, epistemic (B,)) in nats, per output on the class's 20-node rule with
+        h(p) = -p log p - (1 - p) log(1 - p): p_out = mean_s sum_k w_k Lambda(f_k), total_out = h(p_out), aleatoric_out =
+        mean_s sum_k w_k h(Lambda(f_k)), epistemic_out = max(total_out - aleatoric_out, 0); the (B,) values are the sums over
+        the outputs (the one-vs-rest score, an upper bound on the joint quantity).  per_output=True: the three (C, B) arrays
+        are filled in too.  probs uses the rule for the probit link as well (one rule on both sides of Jensen's
+        inequality): it differs from predict's closed form by the rule's quadrature error, documented on the class.  No
+        gradients."""
+        return Uncertainty(*ops.bernoulli_uncertainty(mu, var, self.link, per_output=per_output))
 
     def _consts(self):
         return (self._link,)

@@ -957,6 +957,49 @@ def studentt_lpd(mu, var, y, log_scale, df=4.0, per_output=False):
     return lik_lpd('studentt', mu, var, y, (log_scale, float(df), studentt_lognorm(df)), per_output)
 
 
+def _unc_moments(mu, var, *others):
+    """_lpd_moments with the shape and dtype asserted BEFORE the device: a malformed call fails the same way on any tensor."""
+    assert mu.dim() == 3 and var.shape == mu.shape and mu.dtype == torch.float32 and var.dtype == torch.float32, \
+        (mu.shape, var.shape, mu.dtype, var.dtype)
+    assert all(d > 0 for d in mu.shape), mu.shape
+    return _lpd_moments(mu, var, *others)
+
+
+def softmax_uncertainty(mu, var, eps):
+    """The predictive entropy of the softmax and its two parts (csrc/uncertainty.hip; nats, no autograd): mu, var (S, C, B),
+    eps (S, F, C, B)  ->  probs (B, C) = mean_{s,f} softmax_c(mu + sqrt(var) eps), the definition of softmax_predict;
+    total (B,) = the entropy of probs; expected (B,) = the mean entropy of the S F samples; mi (B,) = max(total - expected, 0),
+    subtracted in fp64 before rounding.  The (S, F, C, B) probabilities are never stored (pooled scratch: (S F + 1) B doubles)."""
+    assert eps.dim() == 4 and eps.dtype == torch.float32, (eps.shape, eps.dtype)
+    S, F, C, B = eps.shape
+    assert tuple(mu.shape) == (S, C, B), (mu.shape, eps.shape)
+    mu, var = _unc_moments(mu, var, eps)
+    eps = eps.detach().contiguous()
+    probs = torch.empty(B, C, dtype=torch.float32, device=mu.device)
+    total, expected, mi = (torch.empty(B, dtype=torch.float32, device=mu.device) for _ in range(3))
+    ws = scratch(lib().vargp_softmax_uncertainty_workspace_bytes(S, F, C, B), mu.device)
+    check(lib().vargp_softmax_uncertainty(ptr(mu), ptr(var), ptr(eps), ptr(probs), ptr(total), ptr(expected), ptr(mi), S, F, C, B,
+                                          ptr(ws), ws.numel() * 4, stream_ptr()), 'vargp_softmax_uncertainty')
+    return probs, total, expected, mi
+
+
+def bernoulli_uncertainty(mu, var, link='probit', per_output=False):
+    """The predictive entropy of independent Bernoulli outputs and its two parts (csrc/uncertainty.hip; nats, no autograd), on the
+    20-node Gauss-Hermite rule for either link: mu, var (S, C, B)  ->  probs (B, C) = mean_s sum_k w_k Lambda(f_k);
+    total, expected, mi (B,), the sums over the outputs of h(p_out), mean_s sum_k w_k h(Lambda(f_k)) and max of their difference
+    and 0; per_output: also total_out, expected_out, mi_out (C, B).  For the probit link probs differs from bernoulli_predict
+    (closed form) by the rule's quadrature error."""
+    link = bernoulli_link(link)
+    mu, var = _unc_moments(mu, var)
+    S, C, B = mu.shape
+    probs = torch.empty(B, C, dtype=torch.float32, device=mu.device)
+    total, expected, mi = (torch.empty(B, dtype=torch.float32, device=mu.device) for _ in range(3))
+    outs = tuple(torch.empty(C, B, dtype=torch.float32, device=mu.device) for _ in range(3)) if per_output else (None,) * 3
+    check(lib().vargp_bernoulli_uncertainty(ptr(mu), ptr(var), link, ptr(probs), ptr(total), ptr(expected), ptr(mi),
+                                            *(ptr(o) for o in outs), S, C, B, stream_ptr()), 'vargp_bernoulli_uncertainty')
+    return (probs, total, expected, mi) + (outs if per_output else ())
+
+
 # ------------------------------------------------------------------------------------------------
 # variational hyper-parameters
 # ------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """Training utilities of the driver (counterparts of the reference's `var_gp/train_utils.py`:
 set_seeds :13-18, compute_accuracy :21-35, compute_acc_ent :38-56, compute_bwt :59-65, EarlyStopper :69-98)."""
+import math
 import random
 
 import numpy as np
@@ -114,6 +115,28 @@ def compute_lpd(dataset, gp, batch_size=512, device=None, shared_hypers=False):
         total, bad = torch.stack([total, bad.double()]).tolist()                      # the one host sync
     assert not bad, 'Found NaNs'
     return total / len(dataset)
+
+
+def compute_uncertainty(dataset, gp, batch_size=512, device=None, shared_hypers=False):
+    """(mean total, mean aleatoric, mean epistemic) predictive entropy per point in nats, the means of gp.uncertainty(x) over
+    `dataset` (not in the reference), alongside compute_lpd: how unsure the model is about the set, and how much of that is
+    noise and how much lack of knowledge.  Classification likelihoods only (the others: the likelihood's ValueError).
+    Accumulated on the device: ONE host sync per data set; asserts on NaN.  shared_hypers: ONE uncertainty(x, tile=batch_size)
+    call -- one hyper-parameter draw and one factorisation for the sweep instead of one per batch."""
+    loader = DataLoader(dataset, batch_size=batch_size)
+    with torch.no_grad():
+        if shared_hypers:
+            parts = [gp.uncertainty(torch.cat([x for x, _ in loader]).to(device), tile=batch_size)]
+        else:
+            parts = (gp.uncertainty(x.to(device)) for x, _ in loader)
+        sums = None
+        for u in parts:
+            t = torch.stack([u.total.double().sum(), u.aleatoric.double().sum(), u.epistemic.double().sum()])
+            sums = t if sums is None else sums + t
+        total, aleatoric, epistemic = sums.tolist()                                   # the one host sync
+    assert not any(math.isnan(v) for v in (total, aleatoric, epistemic)), 'Found NaNs'
+    n = len(dataset)
+    return total / n, aleatoric / n, epistemic / n
 
 
 def compute_bwt(acc_mat):

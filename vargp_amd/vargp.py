@@ -23,7 +23,7 @@ from . import fused, gp_utils, init, noise, ops
 from .gp_utils import vec2tril, mat2trilvec, cholesky, rev_cholesky, gp_cond, block_joint, linear_marginal_diag
 from .kernels import RBFKernel, DeepRBFKernel, MaternKernel, native_code
 from .likelihoods import (BernoulliLikelihood, GaussianLikelihood, MulticlassSoftmax, PoissonLikelihood, StudentTLikelihood,
-                          is_external, n_f, predict_batch_dim)
+                          cat_uncertainty, is_external, n_f, predict_batch_dim)
 from .ops import LOWER
 from .paths import PosteriorPaths
 
@@ -511,6 +511,28 @@ class VARGP(nn.Module):
             if per_output:
                 return torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out], dim=-1)
             return torch.cat(out)
+
+    def uncertainty(self, x, tile=None, per_output=False):
+        """Why the model is unsure about each point of x (N, D): likelihoods.Uncertainty(probs (N, C), total, aleatoric,
+        epistemic (N,)), entropies in nats (likelihood.uncertainty; csrc/uncertainty.hip).  Over the model's samples (theta_s,
+        f_sf) of the class distribution p(y | theta, f):
+            total     = H[ E p(y | theta, f) ]      the entropy of the predictive distribution (of probs)
+            aleatoric = E H[ p(y | theta, f) ]      noise: every sample agrees that the point is ambiguous (a class boundary)
+            epistemic = max(total - aleatoric, 0)   the mutual information of the label and (theta, f): the samples disagree
+                                                    with each other (an unseen class) -- the BALD score
+        MulticlassSoftmax: 0 <= epistemic <= total <= log C; probs is predict's.  BernoulliLikelihood: per output on the 20-node
+        rule, summed over the outputs (the one-vs-rest score, an upper bound on the joint quantity; total <= C log 2);
+        per_output=True fills total_out, aleatoric_out, epistemic_out (C, N) too (ValueError for the softmax, which has no
+        per-output parts).  For the probit link probs comes from the rule as well, not from predict's closed form
+        Phi(mu / sqrt(1 + var)): the two differ by the rule's quadrature error (BernoulliLikelihood's docstring).  The
+        regression likelihoods raise ValueError.
+        Evaluated under torch.no_grad() from the moment routes of predict / log_prob: one self(x) call, or with `tile` and
+        N > tile the same sweep (one hyper-sample draw and one factorisation for all tiles)."""
+        with torch.no_grad():
+            if tile is None or x.size(0) <= tile:
+                return self.likelihood.uncertainty(*self(x), per_output=per_output)
+            return cat_uncertainty([self.likelihood.uncertainty(mu, var, per_output=per_output)
+                                    for _, mu, var in self._moment_sweep(x, tile)])
 
     def predict_f(self, x, full_cov=False):
         """The posterior over the latent functions at x (B, D), under torch.no_grad().  full_cov=False: what self(x) returns,

@@ -16,7 +16,7 @@ import torch.nn as nn
 from . import gp_utils, noise, ops
 from .gp_utils import vec2tril, rev_cholesky, linear_marginal_diag
 from .kernels import RBFKernel
-from .likelihoods import predict_batch_dim
+from .likelihoods import cat_uncertainty, predict_batch_dim
 from .ops import LOWER
 
 _HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
@@ -183,6 +183,16 @@ class VARGPRetrain(nn.Module):
                     return torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out], dim=-1)
                 return torch.cat(out)
             return self.likelihood.log_prob(*self(x), y, per_output=per_output)
+
+    def uncertainty(self, x, tile=None, per_output=False):
+        """The predictive entropy per point split into noise and lack of knowledge, likelihoods.Uncertainty: the signature and
+        meaning of VARGP.uncertainty.  `tile`: chunks of `tile` points, every chunk with its own hyper-parameter sample, as
+        predict."""
+        with torch.no_grad():
+            if tile is not None and x.size(0) > tile:
+                return cat_uncertainty([self.uncertainty(x[i:i + tile], per_output=per_output)
+                                        for i in range(0, x.size(0), tile)])
+            return self.likelihood.uncertainty(*self(x), per_output=per_output)
 
     @staticmethod
     def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None, likelihood='softmax', link='probit'):
