@@ -129,6 +129,27 @@ __device__ __forceinline__ T block_sum(T v, T* red /* >= NT/64 values of LDS */)
   return t;
 }
 
+// ---- stores of single-use outputs -------------------------------------------------------------
+// An output that its kernel writes once, never loads, and that only a LATER launch consumes.  Stored
+// plainly such lines sit dirty in the XCD's L2 until the kernel ends and are written back behind the last workgroup, where
+// nothing overlaps the drain; the gap in front of the next launch grows with them.  store_once writes through instead (`sc1`,
+// agent scope: the line leaves this XCD's L2 as the store is issued).  Used where it measured faster: P and W of
+// t0_fwd_fused_kernel, W_uf of t0_bwd_mid_kernel; not K_uf and P_uf, whose dword-per-lane epilogues lose more than the gap gains.
+// Never for anything accumulated with atomics or loaded inside the same launch.
+#ifdef __HIPCC__
+__device__ __forceinline__ void store_once(float* p, float v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // global_store_dword ... sc1
+}
+__device__ __forceinline__ void store_once(float4* p, float4 v) {      // p: 16-byte aligned
+  typedef float f32x4_ __attribute__((ext_vector_type(4)));
+  const f32x4_ x = {v.x, v.y, v.z, v.w};
+  // (no 16-byte atomic store to lower to `sc1`: the instruction itself.  The compiler's hazard recogniser does not see a store
+  // inside an asm string: a store wider than 8 bytes needs one wait state before a VALU write of its data registers, hence the
+  // s_nop INSIDE the string.  Nothing waits for the store's completion but the end of the kernel.)
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");
+}
+#endif
+
 // internal GEMM parameter block (superset of vargp_gemm_desc: adds the fused RBF epilogue)
 struct GemmParams {
   const float* A;

@@ -64,6 +64,7 @@ static T0Ws carve_t0(void* ws, int S, int C, int M, int D, int B, int F) {
   float* p = reinterpret_cast<float*>(ws);
   auto take = [&](int64_t n) { float* q = p; p += round_up(n, 64); return q; };
   // theta, eps_theta, eps_f first, in this order (vargp_amd/fused.py exposes them as views)
+  // (tests/test_hip_front_roles.py: _ws_offsets mirrors the layout up to LL to read S_u and L_S back)
   o.theta = take(S * D1); o.eps_theta = take(S * D1); o.eps_f = take((int64_t)S * F * C * B);
   o.w = take(S * o.Dp); o.g2 = take(S); o.kd = take(SC); o.queue = take(8);
   o.na = take(SC * M); o.nb = take((int64_t)S * B);
@@ -593,7 +594,7 @@ __global__ __launch_bounds__(256) void t0_fwd_fused_kernel(const float* __restri
       const int m = 32 * rbs[u] + (r & 3) + 8 * (r >> 2) + 4 * lh;
       const float v = accP[u][r];
       if (m < kFusedK) sK[m * kFusedKS + 32 * cb + li] = v;
-      if (m < M && col < B) *reinterpret_cast<float*>(Pout_b + 4u * (__umul24((unsigned)m, (unsigned)LD) + (unsigned)col)) = v;   // (32-bit byte offset)
+      if (m < M && col < B) store_once(reinterpret_cast<float*>(Pout_b + 4u * (__umul24((unsigned)m, (unsigned)LD) + (unsigned)col)), v);   // (32-bit byte offset)
       s_mu = fmaf(v, sav[r], s_mu);
       s_p2 = fmaf(v, v, s_p2);
     }
@@ -621,7 +622,7 @@ __global__ __launch_bounds__(256) void t0_fwd_fused_kernel(const float* __restri
         const int m = 32 * rb + (r & 3) + 8 * (r >> 2) + 4 * lh;
         if (m < M) {
           const float v = accW[u][r];
-          if (col < B) *reinterpret_cast<float*>(Wb_b + 4u * (__umul24((unsigned)m, (unsigned)B) + (unsigned)col)) = v;
+          if (col < B) store_once(reinterpret_cast<float*>(Wb_b + 4u * (__umul24((unsigned)m, (unsigned)B) + (unsigned)col)), v);
           s_w2 = fmaf(v, v, s_w2);
         }
       }
@@ -908,6 +909,7 @@ static T0Plan t0_plan(const vargp_elbo_t0_desc* d, const T0Ws& o, int cus) {
   // building their matrix and the norm role in front of the (now short) prologue roles -- front launch 22.5 -> 19.0 us, the merged
   // launch 35.2 -> 37.1 (the S_u chains become its longest); a workgroup per class inside the front launch instead: 5019 (its
   // packed-vector loads are slow, and the heavier kernel costs the front launch a workgroup slot per SIMD)
+  // (a second attempt at that, with the slot kept: DESIGN_HISTORY.md)
   p.su_in_chain = VARGP_CHOL_BLK16 && tune.su && tune.chol_f32 && p.merge_chol && M > 64 && (M % 4) == 0 && M <= 100;
 
   // LDS-resident middles, at most tune.units (sample, class, 64-column) tile units (beyond: the round-2 sequences / the block

@@ -532,7 +532,9 @@ __global__ __launch_bounds__(256) void t0_bwd_mid_kernel(const float* __restrict
     for (int u = 0; u < kBmNT; ++u) {
       const int e = tid + 256 * u, m = e >> 4;
       if (e < kBmKP * 16) { cs.x += wv4[u].x; cs.y += wv4[u].y; cs.z += wv4[u].z; cs.w += wv4[u].w; }
-      if (m < M && n0 + n4 < B) *reinterpret_cast<float4*>(&Gout[(int64_t)m * LD + n4]) = wv4[u];
+      // (store_once: W_uf goes to the K_uf block of gRK -- a buffer of its own, which this launch never loads: the K_uf tile the
+      //  workgroup staged came from RK -- and is read by the NEXT launch's P_uf product only)
+      if (m < M && n0 + n4 < B) store_once(reinterpret_cast<float4*>(&Gout[(int64_t)m * LD + n4]), wv4[u]);
     }
     atomicAdd(&scs[n4], cs.x); atomicAdd(&scs[n4 + 1], cs.y); atomicAdd(&scs[n4 + 2], cs.z); atomicAdd(&scs[n4 + 3], cs.w);
     // row sums: thread (m, h) = (tid / 2, tid % 2) sums columns [32 h, 32 h + 32) of row m
