@@ -327,6 +327,176 @@ __device__ __forceinline__ void ff_product_w(f32x16_t (&acc)[2], const float* __
   });
 }
 
+// ---- FOLD (T0Plan::fold_small): the small-column product QP[:, :NR] = T [m | L_S | L_u] without a launch of its own ----------
+// Every tile workgroup of an (s, c) stages L_S[c] where it used to stage G and forms G = T L_S itself: the ten lower 32 x 32
+// blocks at once -- block (ib, jb) sums over the k-groups 4 jb .. min(13, 4 ib + 4), no block needs another one -- shared out so
+// that every wave carries 17 k-groups; then a barrier, G into L_S's place, a barrier.  a = T m is a mat-vec on the staged T.
+// The tile-0 workgroup stores a and G into QP for the backward (all tile workgroups hold identical values).  G2 = T L_u feeds
+// only the KL of q(u) and the backward: workgroups on the CUs the tiles leave free (ff_small_role) form it the same way, store
+// it and add the whole kl[s, c].  No workgroup waits for another one.
+struct FgBlk { int ib, jb; };
+constexpr FgBlk kFgBlk[4][3] = {{{3, 0}, {0, 0}, {-1, 0}}, {{2, 0}, {3, 2}, {-1, 0}}, {{3, 1}, {1, 1}, {2, 2}}, {{1, 0}, {2, 1}, {3, 3}}};
+// one block: acc += T[32 IB .., k] L[k, 32 JB ..] (sT K-contiguous, sL k-major with row stride kFusedGS); two accumulator
+// chains (even / odd k-pairs), summed at the end
+template <int IB, int JB>
+__device__ __forceinline__ void fg_block(f32x16_t& acc, const float* __restrict__ sT, const float* __restrict__ sL, int li, int lh) {
+  constexpr int G0 = 4 * JB, G1 = bm_min(kFusedK / 8, 4 * IB + 4);
+  const float* arow = sT + (32 * IB + li) * kFusedTS + 4 * lh;
+  const float* bcol = sL + (4 * lh) * kFusedGS + 32 * JB + li;
+  f32x16_t e, o;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { e[r] = 0.f; o[r] = 0.f; }
+  float4 a = bm_frag_kc(arow, 8 * G0), b = bm_frag_km(bcol, 8 * G0, kFusedGS);
+  bm_for<G0, G1>([&](auto gi) {
+    constexpr int g = decltype(gi)::value;
+    const float4 ca = a, cb = b;
+    if constexpr (g + 1 < G1) { a = bm_frag_kc(arow, 8 * (g + 1)); b = bm_frag_km(bcol, 8 * (g + 1), kFusedGS); }
+    e = __builtin_amdgcn_mfma_f32_32x32x2f32(ca.x, cb.x, e, 0, 0, 0);
+    o = __builtin_amdgcn_mfma_f32_32x32x2f32(ca.y, cb.y, o, 0, 0, 0);
+    e = __builtin_amdgcn_mfma_f32_32x32x2f32(ca.z, cb.z, e, 0, 0, 0);
+    o = __builtin_amdgcn_mfma_f32_32x32x2f32(ca.w, cb.w, o, 0, 0, 0);
+  });
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = e[r] + o[r];
+}
+template <int W>
+__device__ __forceinline__ void fg_wave_product(f32x16_t (&acc)[3], const float* sT, const float* sL, int li, int lh) {
+  bm_for<0, 3>([&](auto ui) {
+    constexpr int u = decltype(ui)::value;
+    if constexpr (kFgBlk[W][u].ib >= 0) fg_block<kFgBlk[W][u].ib, kFgBlk[W][u].jb>(acc[u], sT, sL, li, lh);
+  });
+}
+// the wave's blocks into sG ([k][i], rows < kFusedK; rows >= M are zero: T is zero-padded).  Returns the sum of their squares
+template <int W>
+__device__ __forceinline__ float fg_wave_dump(const f32x16_t (&acc)[3], float* sG, int li, int lh) {
+  float ss = 0.f;
+  bm_for<0, 3>([&](auto ui) {
+    constexpr int u = decltype(ui)::value;
+    if constexpr (kFgBlk[W][u].ib >= 0) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = 32 * kFgBlk[W][u].ib + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        if (m < kFusedK) sG[m * kFusedGS + 32 * kFgBlk[W][u].jb + li] = acc[u][r];
+        ss = fmaf(acc[u][r], acc[u][r], ss);
+      }
+    }
+  });
+  return ss;
+}
+__device__ __forceinline__ void fg_product(f32x16_t (&acc)[3], const float* sT, const float* sL, int wave, int li, int lh) {
+  switch (wave) {
+    case 0: fg_wave_product<0>(acc, sT, sL, li, lh); break;
+    case 1: fg_wave_product<1>(acc, sT, sL, li, lh); break;
+    case 2: fg_wave_product<2>(acc, sT, sL, li, lh); break;
+    default: fg_wave_product<3>(acc, sT, sL, li, lh); break;
+  }
+}
+__device__ __forceinline__ float fg_dump(const f32x16_t (&acc)[3], float* sG, int wave, int li, int lh) {
+  switch (wave) {
+    case 0: return fg_wave_dump<0>(acc, sG, li, lh);
+    case 1: return fg_wave_dump<1>(acc, sG, li, lh);
+    case 2: return fg_wave_dump<2>(acc, sG, li, lh);
+    default: return fg_wave_dump<3>(acc, sG, li, lh);
+  }
+}
+// a = T m on the staged T (sv: m, zero beyond M, 16-byte aligned): two threads per row take alternate float4 of k
+__device__ __forceinline__ void fg_matvec(const float* sT, const float* sv, float* sa, int tid) {
+  const int i = tid >> 1, h = tid & 1;
+  float acc = 0.f;
+#pragma unroll
+  for (int q = 0; q < kFusedK / 8; ++q) {
+    const float4 t = *reinterpret_cast<const float4*>(&sT[i * kFusedTS + 8 * q + 4 * h]);
+    const float4 v = *reinterpret_cast<const float4*>(&sv[8 * q + 4 * h]);
+    acc = fmaf(t.x, v.x, acc); acc = fmaf(t.y, v.y, acc); acc = fmaf(t.z, v.z, acc); acc = fmaf(t.w, v.w, acc);
+  }
+  acc += __shfl_xor(acc, 1, 64);
+  if (h == 0) sa[i] = acc;
+}
+// the M x M block staged in sG ([k][i], upper triangle zero) -> M columns of QP from dst on (row stride LD)
+__device__ __forceinline__ void fg_copy_out(const float* sG, float* __restrict__ dst, int M, int LD, int tid) {
+  const int j = (tid & 31) * 4;
+  if (j < M)
+    for (int i = tid >> 5; i < M; i += 8)
+      *reinterpret_cast<float4*>(dst + (int64_t)i * LD + j) = *reinterpret_cast<const float4*>(&sG[i * kFusedGS + j]);
+}
+// T[b] -> registers (lower triangular: a float4 wholly above the diagonal is not fetched, bm_load_mat<true>) and -> sT
+constexpr int kFfNT = 128 * (kFusedK / 4) / 256;          // 13 float4 per thread
+constexpr int kFfNG = kFusedK * 32 / 256;                 // 13
+__device__ __forceinline__ void ff_load_t(const char* Tbb, int M, int tid, float4 (&rt)[kFfNT]) {
+#pragma unroll
+  for (int u = 0; u < kFfNT; ++u) {
+    const int e = tid + 256 * u;
+    const int i = e / (kFusedK / 4), k = (e - i * (kFusedK / 4)) * 4;
+    const int ic = min(i, M - 1);
+    rt[u] = *reinterpret_cast<const float4*>(Tbb + 4u * (__umul24((unsigned)ic, (unsigned)M) + (unsigned)min(k, min(M - 4, ic & ~3))));
+  }
+}
+__device__ __forceinline__ void ff_store_t(float* sT, int M, int tid, const float4 (&rt)[kFfNT]) {
+#pragma unroll
+  for (int u = 0; u < kFfNT; ++u) {
+    const int e = tid + 256 * u;
+    const int i = e / (kFusedK / 4), k = (e - i * (kFusedK / 4)) * 4;
+    const bool ok = i < M && k < M && k <= i;
+    *reinterpret_cast<float4*>(&sT[i * kFusedTS + k]) = ok ? rt[u] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+// a lower-triangular M x M block of QP or RK (row stride LD, from column `col0` on: G, L_S or L_u) likewise, into sG's layout
+__device__ __forceinline__ void ff_load_g(const char* Qbb, unsigned col0, int M, int LD, int tid, float4 (&rg)[kFfNG]) {
+#pragma unroll
+  for (int u = 0; u < kFfNG; ++u) {
+    const int e = tid + 256 * u;
+    const int k = e >> 5, i = (e & 31) * 4;
+    const int kc = min(k, M - 1);
+    rg[u] = *reinterpret_cast<const float4*>(Qbb + 4u * (__umul24((unsigned)kc, (unsigned)LD) + col0 + (unsigned)min(i, min(M - 4, kc & ~3))));
+  }
+}
+__device__ __forceinline__ void ff_store_g(float* sG, int M, int tid, const float4 (&rg)[kFfNG]) {
+#pragma unroll
+  for (int u = 0; u < kFfNG; ++u) {
+    const int e = tid + 256 * u;
+    const int k = e >> 5, i = (e & 31) * 4;
+    *reinterpret_cast<float4*>(&sG[k * kFusedGS + i]) = (k < M && i < M && i <= k) ? rg[u] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+// The role on the CUs the tile workgroups leave free: for the matrices b = first, first + step, ... G2 = T L_u into QP and
+//   kl[s,c] = sum log diag Lz - sum log diag Lu + (|G2|_F^2 + |a|^2 - M) / 2,   kl_u += kl[s,c] / S      (vargp.py:182-190)
+__device__ __forceinline__ void ff_small_role(const float* __restrict__ TT, float* __restrict__ QP, const float* __restrict__ RK,
+                                              const float* __restrict__ Lz, const float* __restrict__ Lu, float* __restrict__ kl_u,
+                                              int S, int C, int M, int NR, int LD, int first, int step, float* lds_f) {
+  float* sT = lds_f;
+  float* sG = sT + 128 * kFusedTS;
+  float* sm = sG + kFusedK * kFusedGS;            // m, in the K_uf tile's place
+  float* sa = sm + kFusedK * kFusedKS;
+  float* red = sa + 128;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
+  const int64_t MM = (int64_t)M * M, MLD = (int64_t)M * LD;
+  for (int64_t b = first; b < (int64_t)S * C; b += step) {
+    const int c = b % C;
+    const char* Rbb = reinterpret_cast<const char*>(RK + b * MLD);
+    float4 rt[kFfNT], rg[kFfNG];
+    ff_load_t(reinterpret_cast<const char*>(TT + b * MM), M, tid, rt);
+    ff_load_g(Rbb, 4u + (unsigned)M, M, LD, tid, rg);
+    const int ic = min(tid, M - 1);
+    const float mv = *reinterpret_cast<const float*>(Rbb + 4u * __umul24((unsigned)ic, (unsigned)LD));
+    const float dlz = Lz[(b * M + ic) * M + ic], dlu = Lu[((int64_t)c * M + ic) * M + ic];
+    ff_store_t(sT, M, tid, rt);
+    ff_store_g(sG, M, tid, rg);
+    if (tid < 128) sm[tid] = tid < M ? mv : 0.f;
+    __syncthreads();
+    fg_matvec(sT, sm, sa, tid);
+    f32x16_t acc[3];
+    fg_product(acc, sT, sG, wave, li, lh);
+    __syncthreads();                                // everybody is done with L_u
+    float kl_acc = fg_dump(acc, sG, wave, li, lh);
+    if (tid < M) kl_acc += fmaf(sa[tid], sa[tid], 2.f * (logf(dlz) - logf(dlu)) - 1.f);
+    __syncthreads();
+    fg_copy_out(sG, QP + b * MLD + 4 + M, M, LD, tid);
+    const float tkl = block_sum<256>(kl_acc, red);
+    if (tid == 0) atomicAdd(kl_u, 0.5f * tkl / (float)S);
+    __syncthreads();                                // the next matrix restages
+  }
+}
+
 // MULTI (throughput-bound shapes: more (s, c, tile) units than the chip has CUs): a workgroup takes `ntile / nparts` consecutive
 // tiles of its (s, c) -- T, G and a are staged ONCE per workgroup instead of once per tile (80 of the 106 KB a tile workgroup
 // pulls), and the next tile's K_uf loads are in flight under the current tile's products.  nparts = workgroups per (s, c)
@@ -337,14 +507,15 @@ template <bool MULTI>
 __device__ __forceinline__ void ff_barrier() {
   if constexpr (MULTI) bmm_lds_barrier(); else __syncthreads();
 }
-template <bool VEC4, bool MULTI = false>
+template <bool VEC4, bool MULTI = false, bool FOLD = false>
 __global__ __launch_bounds__(256) void t0_fwd_fused_kernel(const float* __restrict__ TT, float* __restrict__ QP,
                                                            const float* __restrict__ RK, float* __restrict__ W,
                                                            const float* __restrict__ kd, const float* __restrict__ Lz,
                                                            const float* __restrict__ Lu, float* __restrict__ mu,
                                                            float* __restrict__ var, float* __restrict__ kl_u, int S, int C,
                                                            int M, int B, int NR, int LD, int ntile, uint32_t* rng_counter,
-                                                           int nparts) {
+                                                           int nparts, int nrole) {
+  static_assert(!FOLD || (VEC4 && !MULTI), "the folded small-column product: single-tile form, B % 4 == 0");
   extern __shared__ __attribute__((aligned(16))) float lds_f[];
   STEP_SPAN(t0, 3);
   float* sT = lds_f;                              // [128][TS]   T[i][k]
@@ -359,8 +530,20 @@ __global__ __launch_bounds__(256) void t0_fwd_fused_kernel(const float* __restri
   const int64_t b = (int64_t)(idx / nparts) * 8 + xcd;
   const int64_t MM = (int64_t)M * M, MLD = (int64_t)M * LD;
   if (rng_counter && blockIdx.x == 0 && tid == 0) rng_counter[0] += 1u;   // this step's noise has been drawn
-  if (b >= (int64_t)S * C) return;
   const int part = idx % nparts;
+  if constexpr (FOLD) {
+    // the G2 / KL role (ff_small_role): the surplus workgroups of the tile map first -- they are the ones on the XCDs with CUs
+    // to spare -- then the ones the launch appends; role r takes the matrices r, r + nrole, ...
+    const int SC = S * C, gt = 8 * ((SC + 7) >> 3) * nparts;
+    int role = -1;
+    if ((int)blockIdx.x >= gt) role = ((SC & 7) ? (8 - (SC & 7)) * nparts : 0) + (int)blockIdx.x - gt;
+    else if (b >= SC) role = (xcd - (SC & 7)) * nparts + part;
+    if (role >= 0) {
+      ff_small_role(TT, QP, RK, Lz, Lu, kl_u, S, C, M, NR, LD, role, nrole, lds_f);
+      return;
+    }
+  }
+  if (b >= (int64_t)S * C) return;
   // this workgroup's tiles [tile_x, tile_end) of the (s, c) (single-tile form: one)
   int tile_x = MULTI ? (part * ntile) / nparts : part;
   const int tile_end = MULTI ? ((part + 1) * ntile) / nparts : part + 1;
@@ -397,8 +580,12 @@ __global__ __launch_bounds__(256) void t0_fwd_fused_kernel(const float* __restri
     const int e = tid + 256 * u;
     const int k = e >> 5, i = (e & 31) * 4;
     const int kc = min(k, M - 1);      // (G = T L_S likewise: G[k][i] = 0 for i > k)
-    rg[u] = *reinterpret_cast<const float4*>(Qbb + 4u * (__umul24((unsigned)kc, (unsigned)LD) + 4u + (unsigned)min(i, min(M - 4, kc & ~3))));
+    // (FOLD: L_S[c] from RK's copy, same place and byte count -- G is formed below)
+    rg[u] = *reinterpret_cast<const float4*>((FOLD ? Kbb - 4 * NR : Qbb) + 4u * (__umul24((unsigned)kc, (unsigned)LD) + 4u + (unsigned)min(i, min(M - 4, kc & ~3))));
   }
+  // (FOLD: m in a's place, in front of the K_uf loads -- those stay in flight under the product G = T L_S)
+  float av = 0.f;
+  if constexpr (FOLD) av = *reinterpret_cast<const float*>(Kbb - 4 * NR + 4u * __umul24((unsigned)min(tid, M - 1), (unsigned)LD));
   // K_uf tile.  B % 4 == 0 (VEC4; every BASELINE shape): a float4 lies wholly inside or outside the matrix, so the column is
   // clamped and the padding selected in when the value is stored -- NO branch: the previous form, `if (full) float4 else
   // per-element`, left a branch around every one of the seven loads, and the compiler put an s_waitcnt vmcnt(0) at each join:
@@ -421,24 +608,28 @@ __global__ __launch_bounds__(256) void t0_fwd_fused_kernel(const float* __restri
     }
   };
   load_ktile(n0);
-  const float av = tid < 128 ? *reinterpret_cast<const float*>(Qbb + 4u * __umul24((unsigned)min(tid, M - 1), (unsigned)LD)) : 0.f;
+  if constexpr (!FOLD) av = tid < 128 ? *reinterpret_cast<const float*>(Qbb + 4u * __umul24((unsigned)min(tid, M - 1), (unsigned)LD)) : 0.f;
   // ---- KL of q(u) against p(u) for this (s, c) (vargp.py:182-190), its rows shared out over the tile workgroups:
   //      kl[s,c] = sum log diag Lz - sum log diag Lu + (|G2|_F^2 + |a|^2 - M) / 2,   kl_u = (1/S) sum kl[s,c]
   const int c_kl = b % C;
   const int per = (M + nparts - 1) / nparts, i0 = part * per, i1 = min(M, i0 + per);
   const int nkl = max((i1 - i0) * M, 0);
   const unsigned mdiv = ((1u << 20) + (unsigned)M - 1u) / (unsigned)M;      // (uniform: one scalar division instead of eight per thread)
-  float kv[8];                                            // first round of G2 entries (clamped; eight loads in flight per round)
+  // (FOLD: none of it -- the whole kl[s, c] comes from ff_small_role)
+  float kv[8] = {};                                       // first round of G2 entries (clamped; eight loads in flight per round)
 #pragma unroll
-  for (int u = 0; u < 8; ++u) {
+  for (int u = 0; u < (FOLD ? 0 : 8); ++u) {
     const int e = min(tid + 256 * u, max(nkl - 1, 0));
     const int ei = (int)(((unsigned)e * mdiv) >> 20);     // e / M (exact: e < 2^11, M <= 104, mdiv = ceil(2^20 / M))
     kv[u] = *reinterpret_cast<const float*>(Qbb + 4u * (__umul24((unsigned)min(i0 + ei, M - 1), (unsigned)LD) + 4u + (unsigned)M + (unsigned)(e - ei * M)));
   }
   // the diagonal terms: thread t < i1 - i0 takes row i0 + t (rows beyond: clamped loads, masked)
   const int idg = min(i0 + tid, M - 1);
-  const float dga = *reinterpret_cast<const float*>(Qbb + 4u * __umul24((unsigned)idg, (unsigned)LD));
-  const float dlz = Lz[(b * M + idg) * M + idg], dlu = Lu[((int64_t)c_kl * M + idg) * M + idg];
+  float dga = 0.f, dlz = 1.f, dlu = 1.f;
+  if constexpr (!FOLD) {
+    dga = *reinterpret_cast<const float*>(Qbb + 4u * __umul24((unsigned)idg, (unsigned)LD));
+    dlz = Lz[(b * M + idg) * M + idg]; dlu = Lu[((int64_t)c_kl * M + idg) * M + idg];
+  }
   FF_STAMP(10);
   // ---- LDS stores (zero-padded: rows / inner indices >= M, columns >= B)
 #pragma unroll
@@ -455,18 +646,30 @@ __global__ __launch_bounds__(256) void t0_fwd_fused_kernel(const float* __restri
     const int k = e >> 5, i = (e & 31) * 4;
     *reinterpret_cast<float4*>(&sG[k * kFusedGS + i]) = (k < M && i < M && i <= k) ? rg[u] : make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  if (tid < 128) sa[tid] = tid < M ? av : 0.f;
+  if constexpr (!FOLD) { if (tid < 128) sa[tid] = tid < M ? av : 0.f; }
   if (tid < 192) red[tid] = 0.f;
+  if constexpr (FOLD) {
+    // ---- G = T L_S into L_S's place and a = T m, with the K_uf loads still in flight (LDS-only barriers)
+    if (tid < 128) sK[tid] = tid < M ? av : 0.f;      // m, in the tile's place until the tile is stored
+    bmm_lds_barrier();
+    FF_STAMP(14);
+    fg_matvec(sT, sK, sa, tid);
+    f32x16_t accG[3];
+    fg_product(accG, sT, sG, wave, li, lh);
+    bmm_lds_barrier();                                // everybody is done with L_S and m
+    fg_dump(accG, sG, wave, li, lh);
+    FF_STAMP(15);
+  }
   // ---- KL arithmetic (further rounds of loads only when a workgroup's share exceeds 2048 entries)
   float kl_acc = 0.f;
 #pragma unroll
-  for (int u = 0; u < 8; ++u) {
+  for (int u = 0; u < (FOLD ? 0 : 8); ++u) {
     const int e = tid + 256 * u;
     const int ei = (int)(((unsigned)e * mdiv) >> 20);
     const int i = i0 + ei, j = e - ei * M;
     kl_acc = fmaf((e < nkl && j <= i) ? kv[u] : 0.f, kv[u], kl_acc);      // upper entries are stored zeros
   }
-  for (int e0 = 8 * 256; e0 < nkl; e0 += 8 * 256) {
+  for (int e0 = 8 * 256; !FOLD && e0 < nkl; e0 += 8 * 256) {
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int e = min(e0 + tid + 256 * u, nkl - 1);
@@ -479,7 +682,7 @@ __global__ __launch_bounds__(256) void t0_fwd_fused_kernel(const float* __restri
       kl_acc = fmaf((e < nkl && j <= i) ? kv[u] : 0.f, kv[u], kl_acc);
     }
   }
-  {
+  if constexpr (!FOLD) {
     const bool dok = i0 + tid < i1;
     float t = fmaf(dga, dga, 2.f * (logf(dlz) - logf(dlu)) - 1.f);
     kl_acc += dok ? t : 0.f;
@@ -644,10 +847,18 @@ __global__ __launch_bounds__(256) void t0_fwd_fused_kernel(const float* __restri
   FF_STAMP(8);
   }
   } while (MULTI && tile_x < tile_end);
+  if constexpr (FOLD) {
+    // ---- a and G for the backward: the tile-0 workgroup's copy (columns 1 .. 3 of QP: zero, as the product wrote them)
+    if (part == 0) {
+      if (tid < M) *reinterpret_cast<float4*>(QP + b * MLD + (int64_t)tid * LD) = make_float4(sa[tid], 0.f, 0.f, 0.f);
+      fg_copy_out(sG, QP + b * MLD + 4, M, LD, tid);
+    }
+  } else {
   // ---- KL (partial sum from the top of the kernel)
   __syncthreads();
   const float tkl = block_sum<256>(kl_acc, red);
   if (tid == 0) atomicAdd(kl_u, 0.5f * tkl / (float)S);
+  }
   FF_STAMP(9);
 }
 
@@ -818,6 +1029,7 @@ struct T0Tune {
   int unmerge = env("VARGP_T0_UNMERGE", -1), side = env("VARGP_T0_SIDE", 1);
   int multi = env("VARGP_T0_MULTI", 0), parts = env("VARGP_T0_PARTS", 0);
   int fused = env("VARGP_T0_FUSED", 1), fused_bwd = env("VARGP_T0_FUSED_BWD", 1), mat_bwd = env("VARGP_T0_MAT_BWD", 1);
+  int fold_small = env("VARGP_T0_FOLD_SMALL", 1);
   int front = env("VARGP_T0_FRONT", 1), gram_in_chain = env("VARGP_T0_GRAM_IN_CHAIN", -1), su = env("VARGP_T0_SU", 1);
   int tail = env("VARGP_T0_TAIL", 1), tail_lds = env("VARGP_T0_TAIL_LDS", kTailLdsDefault);
   int kuf_tile = env("VARGP_T0_KUF_TILE", 0), puf_tile = env("VARGP_T0_PUF_TILE", 0), puu_tile = env("VARGP_T0_PUU_TILE", 0);
@@ -854,6 +1066,8 @@ struct T0Plan {
   bool unmerge, side;                                                                                 // both
   bool fused_bwd, mat_bwd, bwd_multi, fused_tail, tail_lds;                                           // backward
   int kuf_tile, puf_tile, puu_tile;          // tile form of the products that run as launches of their own (0: launch_gemm's choice)
+  bool fold_small;                           // forward: QP[:, :NR] formed inside the fused middle, no launch of its own
+  int fold_roles, fold_extra;                // ... its G2 / KL role workgroups (ff_small_role), and how many of them the launch appends
   int ksp, ntile, fwd_parts, bwd_parts;      // K-splits of K_uu, 64-column tiles of the minibatch, workgroups per (s, c) of the middles
 };
 static T0Plan t0_plan(const vargp_elbo_t0_desc* d, const T0Ws& o, int cus) {
@@ -920,6 +1134,20 @@ static T0Plan t0_plan(const vargp_elbo_t0_desc* d, const T0Ws& o, int cus) {
   p.fwd_parts = t0_tile_parts(SC, p.ntile, cus, kFwdMidSetup, tune.parts);
   p.fwd_multi = p.fwd_parts < p.ntile || tune.multi == 1;
   p.w_vec4 = B % 4 == 0;      // float4 rows of W in t0_fwd_fused_kernel
+  // The small-column product QP[:, :NR] = T [m | L_S | L_u] inside the single-tile fused middle instead of a launch of its own
+  // (a 64-tile GEMM of 0.03 GFLOP: 6.8 us behind a 2.9 us gap at Cfg2): every tile workgroup recomputes G = T L_S and a = T m on
+  // its staged T; G2 = T L_u and the whole KL of q(u) go to role workgroups on the CUs the tiles leave free, at most two matrices
+  // each -- the surplus workgroups of the XCD-aware tile map (b >= S C: they sit on the XCDs with CUs to spare) and, where those
+  // are too few, fold_extra appended ones.  Only where tiles and roles find a CU each in one round; not with the launches taken
+  // apart (unmerge).  VARGP_T0_FOLD_SMALL=0: the launch
+  {
+    const int nsur = (int)(8 * cdiv(SC, 8) - SC) * p.ntile, need = (int)cdiv(SC, 2);
+    p.fold_extra = nsur >= need ? 0 : (int)round_up(need - nsur, 8);
+    p.fold_roles = nsur + p.fold_extra;
+    p.fold_small = tune.fold_small && p.fused_mid && !p.fwd_multi && p.w_vec4 && !p.unmerge && M >= 4 &&
+                   SC * p.ntile + std::min<int64_t>(p.fold_roles, SC) <= cus;
+    if (!p.fold_small) p.fold_roles = p.fold_extra = 0;
+  }
   // LDS-resident backward middle (t0_bwd_mid.h): same shapes as the forward's fused middle, plus B % 4 == 0 (float4 rows of W)
   p.fused_bwd = tune.fused_bwd && M <= kBmKP && M >= 4 && (M % 4) == 0 && (LD % 4) == 0 && (B % 4) == 0 && units_ok;
   // ... and everything per matrix after it (small columns of gT / gRK, Cholesky adjoint, W_uu) as one LDS-resident workgroup
@@ -1164,20 +1392,23 @@ int T0::fwd() const {
   }
   uint32_t* rngc = plan.native ? d->rng_counter : nullptr;
   if (plan.fused_mid) {
-    // small columns first (one M x NR x M product per (s, c)), then the LDS-resident kernel
-    rc = qp_gemm(NR).run(st);
-    if (rc) return rc;
-    static std::atomic<unsigned> attr_set_mask[4][2] = {};      // 64 device ordinals per instantiation
-    const dim3 grid(8 * cdiv(SC, 8) * plan.fwd_parts);
-#define VARGP_FF(V4, MT, SLOT)                                                                                                  \
+    // small columns first (one M x NR x M product per (s, c)), then the LDS-resident kernel -- or, fold_small, inside it
+    if (!plan.fold_small) {
+      rc = qp_gemm(NR).run(st);
+      if (rc) return rc;
+    }
+    static std::atomic<unsigned> attr_set_mask[5][2] = {};      // 64 device ordinals per instantiation
+    const dim3 grid(8 * cdiv(SC, 8) * plan.fwd_parts + plan.fold_extra);
+#define VARGP_FF(V4, MT, SLOT, ...)                                                                                                \
   do {                                                                                                                          \
-    rc = ensure_dynamic_lds(reinterpret_cast<const void*>(t0_fwd_fused_kernel<V4, MT>), kFusedLdsBytes, attr_set_mask[SLOT],    \
+    rc = ensure_dynamic_lds(reinterpret_cast<const void*>(t0_fwd_fused_kernel<V4, MT, ##__VA_ARGS__>), kFusedLdsBytes, attr_set_mask[SLOT], \
                             "elbo_t0_fwd");                                                                                     \
     if (rc) return rc;                                                                                                          \
-    hipLaunchKernelGGL((t0_fwd_fused_kernel<V4, MT>), grid, dim3(256), kFusedLdsBytes, st, o.TT, o.QP, o.RK, o.W, o.kd, o.LL,   \
-                       o.Lu, o.mu, o.var, d->scalars + 1, S, C, M, B, NR, LD, plan.ntile, rngc, plan.fwd_parts);                  \
+    hipLaunchKernelGGL((t0_fwd_fused_kernel<V4, MT, ##__VA_ARGS__>), grid, dim3(256), kFusedLdsBytes, st, o.TT, o.QP, o.RK, o.W, o.kd, o.LL,   \
+                       o.Lu, o.mu, o.var, d->scalars + 1, S, C, M, B, NR, LD, plan.ntile, rngc, plan.fwd_parts, plan.fold_roles);  \
   } while (0)
-    if (plan.w_vec4) { if (plan.fwd_multi) VARGP_FF(true, true, 0); else VARGP_FF(true, false, 1); }
+    if (plan.fold_small) VARGP_FF(true, false, 4, true);
+    else if (plan.w_vec4) { if (plan.fwd_multi) VARGP_FF(true, true, 0); else VARGP_FF(true, false, 1); }
     else { if (plan.fwd_multi) VARGP_FF(false, true, 2); else VARGP_FF(false, false, 3); }
 #undef VARGP_FF
   } else {
