@@ -489,6 +489,14 @@ int vargp_elbo_t0_fwd(const vargp_elbo_t0_desc* d, vargp_stream_t stream);
 /* Where the program keeps the predictive moments mu, var (S, C, B) of its last fwd and the likelihood gradients gmu, gvar
  * (S, C, B) its bwd reads (pointers into d->ws; any of the four outputs may be NULL). */
 int vargp_elbo_t0_lik_buffers(const vargp_elbo_t0_desc* d, float** mu, float** var, float** gmu, float** gvar);
+/* Which launch sequence fwd and bwd take for this descriptor on a device of `cus` compute units (cus <= 0: the current
+ * device's): every member of the program's plan (T0Plan, csrc/elbo_t0.hip), evaluated by the same code the two calls use, as
+ * text in out -- one `name=value` line per member, a flag as true / false, a count as a decimal integer, NUL-terminated
+ * (VARGP_EINVAL if out_bytes is too small; 1024 is plenty).  Read-only host arithmetic: with cus > 0 the device is not
+ * touched, so it runs on a machine without one.  It reads the dimensions, map_est / defer_softmax / ext_lik, whether eps_f is
+ * NULL (native noise) and the ALIGNMENT of z, x, eps_f and ws as given -- the pointers need not be valid (ws may be NULL) -- and
+ * the VARGP_T0_* tuning switches as fwd and bwd see them (read once per process). */
+int vargp_elbo_t0_plan(const vargp_elbo_t0_desc* d, int cus, char* out, size_t out_bytes);
 /* ONE vargp_elbo_t0_bwd per vargp_elbo_t0_fwd: for the shapes of the LDS-resident backward (M <= 104, M % 4 == 0, B % 4 == 0,
  * D % 4 == 0, S <= 64) the forward clears the accumulators the backward adds into (and the tile counters of the backward's
  * persistent product workgroups) -- there is no clearing launch in bwd.

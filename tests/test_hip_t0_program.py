@@ -1,5 +1,6 @@
 """GPU: the native first-task ELBO program (vargp_elbo_t0_fwd / _bwd) against the fp64 oracle on shapes that hit
-its edge paths, and the trainer's direct use of it against the autograd route."""
+its edge paths, and the trainer's direct use of it against the autograd route.  (tests/test_t0_plan.py asserts, without a
+GPU, that every shape of SHAPES takes the path its comment names on 256 CUs.)"""
 import numpy as np
 import pytest
 import torch
@@ -24,14 +25,15 @@ SHAPES = [(2, 3, 3, 33, 40, 50), (3, 2, 4, 20, 64, 37), (2, 2, 18, 12, 36, 24), 
           # M = 64 and M = 65 (the two register-slot layouts of the factorisation kernel), M = 100 with B % 4 != 0
           (1, 1, 1, 3, 33, 2), (2, 2, 2, 64, 40, 33), (2, 2, 2, 65, 40, 32), (1, 2, 2, 100, 36, 50), (1, 2, 3, 51, 36, 8),
           # the LDS-resident backward (t0_bwd_mid.h / t0_bwd_mat.h: M % 4 == 0, M <= 104, B % 4 == 0, D % 4 == 0): ragged last
-          # 64-column tile, M = 104 (no padding left), M = 4, four / five / eight / sixteen hyper-samples (the S_u chains redo S products), seventeen
-          # (the tile kernel without the per-matrix chains), several full tiles
+          # 64-column tile, M = 104 (no padding left), M = 4, four / five / eight / sixteen / seventeen hyper-samples (the S_u chains
+          # redo S products; more than four: the tail's operands staged through LDS), several full tiles
           (3, 2, 3, 100, 40, 72), (4, 2, 2, 104, 36, 64), (5, 2, 2, 52, 36, 40), (2, 2, 2, 4, 36, 8), (2, 3, 3, 96, 48, 200),
           (3, 2, 2, 100, 36, 132), (8, 2, 2, 100, 36, 64), (16, 1, 2, 100, 36, 64), (17, 2, 2, 52, 36, 40),
           # the persistent P_uf role of the backward's merged launch (gemm_persist_body: more tiles than free CUs, B % 64 == 0,
           # B >= 256): static tile lists with four (the minimum) and five slabs per tile, and the work queue that the finished
-          # matrix chains join (many tiles per CU: 8 hyper-samples)
-          (3, 2, 10, 100, 784, 256), (3, 2, 10, 100, 784, 320), (8, 2, 10, 100, 384, 256),
+          # matrix chains join (more than four tiles per free CU: 7 x 16 x 7 = 784 tiles for 256 - 80 CUs; seven hyper-samples keep
+          # the S C + C = 80 chains below the third of the CU count from which the launches are taken apart)
+          (3, 2, 10, 100, 784, 256), (3, 2, 10, 100, 784, 320), (7, 2, 10, 100, 448, 256),
           # more (s, c, tile) units than CUs: the multi-tile form of the LDS-resident tile kernels (a workgroup walks several tiles
           # of its (s, c): T / G staged once, M x M accumulators kept across tiles) -- uneven tile shares (8 tiles over 3
           # workgroups), a ragged last tile, B % 4 != 0 (the per-element K_uf loads), and one workgroup for all tiles of a matrix

@@ -145,6 +145,7 @@ _SIGNATURES = {
     'vargp_elbo_t0_workspace_bytes': (c_size_t, [c_int] * 6),
     'vargp_elbo_t0_fwd': (c_int, [POINTER(ElboT0Desc), _P]),
     'vargp_elbo_t0_lik_buffers': (c_int, [POINTER(ElboT0Desc)] + [POINTER(c_void_p)] * 4),
+    'vargp_elbo_t0_plan': (c_int, [POINTER(ElboT0Desc), c_int, c_char_p, c_size_t]),
     'vargp_elbo_tn_lik_buffers': (c_int, [POINTER(ElboTnDesc)] + [POINTER(c_void_p)] * 4),
     'vargp_elbo_t0_bwd': (c_int, [POINTER(ElboT0Desc)] + [_P] * 7),
     'vargp_bias_act_fwd': (c_int, [_P, _P, _P, c_int64, c_int, c_int, _P]),

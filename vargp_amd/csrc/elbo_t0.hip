@@ -1174,6 +1174,35 @@ static T0Plan t0_plan(const vargp_elbo_t0_desc* d, const T0Ws& o, int cus) {
   return p;
 }
 
+// The plan as text, one `name=value` line per member of T0Plan (bool: true / false) -- vargp_elbo_t0_plan.  -> characters the
+// text needs (as snprintf), or -1 if a member of T0Plan has no line here.
+static int t0_plan_text(const T0Plan& p, char* out, size_t cap) {
+  size_t n = 0;
+  int lines = 0;
+  auto put = [&](const char* name, const char* fmt, auto v) {
+    const int k = snprintf(out && n < cap ? out + n : nullptr, out && n < cap ? cap - n : 0, fmt, name, v);
+    n += k > 0 ? k : 0;
+    ++lines;
+  };
+#define T0_PLAN_BOOL(m) put(#m, "%s=%s\n", p.m ? "true" : "false")
+#define T0_PLAN_INT(m) put(#m, "%s=%d\n", (int)p.m)
+  T0_PLAN_BOOL(native); T0_PLAN_BOOL(generic_lik); T0_PLAN_BOOL(unscaled_lik_grad); T0_PLAN_BOOL(defer_softmax);
+  T0_PLAN_BOOL(fwd_softmax16);
+  T0_PLAN_BOOL(direct_gram); T0_PLAN_BOOL(merge_chol); T0_PLAN_BOOL(split_kuu); T0_PLAN_BOOL(front); T0_PLAN_BOOL(gram_in_chain);
+  T0_PLAN_BOOL(su_in_chain); T0_PLAN_BOOL(fused_mid); T0_PLAN_BOOL(fwd_multi); T0_PLAN_BOOL(w_vec4);
+  T0_PLAN_BOOL(unmerge); T0_PLAN_BOOL(side);
+  T0_PLAN_BOOL(fused_bwd); T0_PLAN_BOOL(mat_bwd); T0_PLAN_BOOL(bwd_multi); T0_PLAN_BOOL(fused_tail); T0_PLAN_BOOL(tail_lds);
+  T0_PLAN_INT(kuf_tile); T0_PLAN_INT(puf_tile); T0_PLAN_INT(puu_tile);
+  T0_PLAN_BOOL(fold_small); T0_PLAN_INT(fold_roles); T0_PLAN_INT(fold_extra);
+  T0_PLAN_INT(ksp); T0_PLAN_INT(ntile); T0_PLAN_INT(fwd_parts); T0_PLAN_INT(bwd_parts);
+#undef T0_PLAN_BOOL
+#undef T0_PLAN_INT
+  // (a structured binding names every member: one added to T0Plan without a line above does not compile here / fails the count)
+  [[maybe_unused]] const auto& [m0, m1, m2, m3, m4, m5, m6, m7, m8, m9, m10, m11, m12, m13, m14, m15, m16, m17, m18, m19, m20, m21,
+                                m22, m23, m24, m25, m26, m27, m28, m29, m30] = p;
+  return lines == 31 ? (int)n : -1;
+}
+
 // One backward per forward on the LDS-resident path (the forward clears what the backward adds into).  The C ABI enforces it
 // itself: host-side state per workspace, updated when a call is ISSUED (which is also when a hipGraph capture records it, so a
 // captured fwd -> bwd sequence is checked once and replays as recorded).  kT0Cleared: a forward has cleared the accumulators
@@ -1613,6 +1642,18 @@ using namespace vargp;
 
 extern "C" size_t vargp_elbo_t0_workspace_bytes(int S, int C, int M, int D, int B, int F) {
   return carve_t0(nullptr, S, C, M, D, B, F).bytes + 256;
+}
+
+// Host arithmetic only (the device is asked for its CU count when cus <= 0, and for nothing else): none of check_desc's pointer
+// requirements -- the plan reads the dimensions, the flags and the ALIGNMENT of z, x, eps_f and ws, never what they point to.
+extern "C" int vargp_elbo_t0_plan(const vargp_elbo_t0_desc* d, int cus, char* out, size_t out_bytes) {
+  VARGP_REQUIRE(d && out && out_bytes > 0, "elbo_t0_plan: null pointer");
+  VARGP_REQUIRE(d->S > 0 && d->C > 0 && d->M > 0 && d->D > 0 && d->B > 0 && d->F > 0, "elbo_t0_plan: bad dims");
+  const T0Ws o = carve_t0(d->ws, d->S, d->C, d->M, d->D, d->B, d->F);
+  const int n = t0_plan_text(t0_plan(d, o, cus > 0 ? cus : vargp_cu_count()), out, out_bytes);
+  VARGP_REQUIRE(n >= 0, "elbo_t0_plan: a member of T0Plan has no line in t0_plan_text");
+  VARGP_REQUIRE((size_t)n < out_bytes, "elbo_t0_plan: the text needs %d bytes, the buffer has %zu", n + 1, out_bytes);
+  return VARGP_OK;
 }
 
 extern "C" int vargp_elbo_t0_lik_buffers(const vargp_elbo_t0_desc* d, float** mu, float** var, float** gmu, float** gvar) {

@@ -252,6 +252,32 @@ class T0Program(_Program):
                              eps_f, bump, ext_lik)
 
 
+    def plan(self, cus=None):
+        """The launch plan (T0Plan, csrc/elbo_t0.hip) of this program's descriptor as it stands -- after a forward: of that
+        forward and its backward -- as {member: bool | int}.  cus: CU count to plan for (None: the current device's)."""
+        return _plan_of(self.desc, cus)
+
+
+def _plan_of(desc, cus):
+    buf = ctypes.create_string_buffer(2048)
+    check(lib().vargp_elbo_t0_plan(ctypes.byref(desc), int(cus or 0), buf, len(buf)), 'vargp_elbo_t0_plan')
+    plan = {}
+    for line in buf.value.decode().splitlines():
+        name, _, value = line.partition('=')
+        plan[name] = value == 'true' if value in ('true', 'false') else int(value)
+    return plan
+
+
+def t0_plan(S, C, M, D, B, F, cus=None, defer_softmax=False, ext_lik=False, native=False, map_est=False):
+    """The launch plan the first-task program takes for these dimensions and flags (vargp_elbo_t0_plan: the library's own
+    t0_plan, not a copy of its rules) as {member: bool | int}, with every operand on a 16-byte boundary.  native: the program
+    draws its own noise (eps_f = NULL).  Host arithmetic: with `cus` given no device is needed."""
+    aligned = 4096                                        # (only the alignment of z, x and eps_f is read)
+    desc = ElboT0Desc(S=S, C=C, M=M, D=D, B=B, F=F, map_est=int(bool(map_est)), jitter=JITTER, z=aligned, x=aligned,
+                      eps_f=None if native else aligned, defer_softmax=int(bool(defer_softmax)), ext_lik=int(bool(ext_lik)))
+    return _plan_of(desc, cus)
+
+
 def _claim(prog, owner):
     """`owner` (an autograd ctx, a lazy.PendingForward) takes the workspace of `prog` until its backward has run -- or until it
     dies without one (validation ELBO under no_grad: no graph is recorded and the ctx is released as soon as apply() returns; a
