@@ -53,7 +53,7 @@ def train(task_id, train_set, val_set, test_set, ep_var_mean=True, map_est_hyper
           eval_interval=10, patience=20, prev_params=None, logger=None, device=None, graph=False, seed=None,
           retrain=False, eval_shared_hypers=False, dataloader=False, kernel='rbf', native_kernel=False,
           likelihood='softmax', link='probit', lpd=False, z_init='random', kmeans_iters=20, lengthscale_init='default',
-          uncertainty=False):
+          uncertainty=False, greedy_candidates=4096):
     if retrain:      # the variant of experiments/vargp_retrain.py:14-19 (earlier tasks' inducing parameters re-optimised)
         from vargp_amd.vargp_retrain import VARGPRetrain
         assert kernel == 'rbf', '--retrain builds its model with the RBF kernel'
@@ -65,7 +65,8 @@ def train(task_id, train_set, val_set, test_set, ep_var_mean=True, map_est_hyper
         gp = VARGP.create_clf(train_set, M=M, n_f=n_f, n_var_samples=n_var_samples, prev_params=prev_params,
                               ep_var_mean=ep_var_mean, map_est_hypers=map_est_hypers, dkl=dkl, kernel=kernel,
                               native_kernel=native_kernel, likelihood=likelihood, link=link, z_init=z_init,
-                              kmeans_iters=kmeans_iters, lengthscale_init=lengthscale_init).to(device)
+                              kmeans_iters=kmeans_iters, lengthscale_init=lengthscale_init,
+                              greedy_candidates=greedy_candidates).to(device)
     stopper = EarlyStopper(patience=patience)
     N = len(train_set)
     # the program's counter-based noise generator is keyed by the run's seed (the reference draws from the torch global
@@ -202,7 +203,7 @@ def toy(args):
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed, retrain=args.retrain,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
                    lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init,
-                   uncertainty=args.uncertainty)
+                   uncertainty=args.uncertainty, greedy_candidates=args.greedy_candidates)
         prev_params.append(sd)
     logger.close()
 
@@ -230,7 +231,7 @@ def split_mnist(args):
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
                    lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init,
-                   uncertainty=args.uncertainty)
+                   uncertainty=args.uncertainty, greedy_candidates=args.greedy_candidates)
         prev_params.append(sd)
     logger.close()
 
@@ -261,7 +262,7 @@ def permuted_mnist(args):
                    device=device, eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
                    lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init,
-                   uncertainty=args.uncertainty)
+                   uncertainty=args.uncertainty, greedy_candidates=args.greedy_candidates)
         prev_params.append(sd)
     logger.close()
 
@@ -295,9 +296,12 @@ def parse_args(argv=None):
                              'Bernoulli outputs (deterministic 20-node Gauss-Hermite rule; not stored in checkpoints)')
         sp.add_argument('--link', choices=('probit', 'logit'), default='probit',
                         help='link function of --likelihood bernoulli')
-        sp.add_argument('--z_init', choices=('random', 'kmeans'), default='random',
-                        help="inducing points of a new task: M random data points per output (the reference's), or the "
-                             'k-means centres of the task found from them on the device')
+        sp.add_argument('--z_init', choices=('random', 'kmeans', 'greedy'), default='random',
+                        help="inducing points of a new task: M random data points per output (the reference's), the "
+                             'k-means centres of the task found from them on the device, or greedy conditional-variance '
+                             "selection under the model's kernel, started from the earlier tasks' inducing points (not with --dkl)")
+        sp.add_argument('--greedy_candidates', type=int, default=4096,
+                        help='random data points per output that --z_init greedy selects among (at most)')
         sp.add_argument('--kmeans_iters', type=int, default=20, help='Lloyd iterations of --z_init kmeans (at most)')
         sp.add_argument('--lengthscale_init', choices=('default', 'median'), default='default',
                         help="lengthscales of the first task: 0.5 (the reference's), or the median distance between pairs of "

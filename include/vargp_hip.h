@@ -219,6 +219,32 @@ int vargp_kmeans_update(const float* X, const int32_t* label, float* Z, int32_t*
                         size_t ws_bytes, vargp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Greedy conditional-variance selection of inducing points: a pivoted Cholesky of K(X_cand, X_cand) for G independent candidate
+ * sets over one data matrix X [N, D] and ONE hyper vector theta [D + 1] (log lengthscale_1..D, log gamma).  Not in the reference.
+ *   k(x, y) = gamma^2 f(r), r^2 = sum_d ((x_d - y_d) / lengthscale_d)^2 formed directly at every D (coincident points give exactly
+ *   gamma^2); f by nu2: 0 = RBF, 1 | 3 | 5 = Matern nu = nu2 / 2, as the gram entries define it.
+ *   cand [G, Nc]: row numbers into X (numbers outside [0, N) are clamped into it), or NULL = rows 0..Nc-1 for every set (Nc <= N).
+ *   LT [G, k0 + M, Nc], k-major: row k is the k-th Cholesky column over the candidates.  d [G, Nc]: residual variances.
+ *   k0 == 0: the call sets d = gamma^2.  k0 > 0: rows 0..k0-1 of LT and all of d are the caller's (a factorisation already begun,
+ *   e.g. from earlier tasks' inducing points: LT0 = chol(K(z, z) + eps I)^-1 K(z, x_cand), d = gamma^2 - colsum(LT0^2)).  Nothing is
+ *   marked selected on entry in either case.
+ *   Step k = 0..M-1 per set: the key of an unselected candidate is d_i if d_i > eps, else 0; p = the unselected candidate with the
+ *   largest key, the lowest position on a tie (so step 0 of an empty start picks position 0); pick[k] = p (a POSITION in the
+ *   candidate list), pivot[k] = d_p before its downdate.  If d_p > eps, for every candidate i:
+ *   c_i = k(x_i, x_p) - sum_{j < k0 + k} LT[j, i] LT[j, p], LT[k0 + k, i] = c_i / sqrt(d_p), d_i = max(d_i - LT[k0 + k, i]^2, 0);
+ *   otherwise the set is exhausted: row k0 + k is zeros and d stays.  p is marked selected (the mask lives in the workspace).
+ * M + 1 launches on `stream` and no host synchronisation; no cooperative launch and no waiting between workgroups: each step's
+ * workgroups leave their tile's best in a table that the next launch's workgroups reduce.  Deterministic (no atomics): two calls
+ * on the same input are bitwise equal.  The workspace is linear in Nc (a mask, the table, exp(-2 theta)); 0 for G == 0.
+ * VARGP_EINVAL before any launch: a null pointer other than cand, a size < 1, k0 < 0, M > Nc, cand == NULL with Nc > N, nu2 not
+ * one of the four, G > 65535, a short workspace.  eps: the jitter the Cholesky of K(z, z) will add.
+ */
+size_t vargp_greedy_workspace_bytes(int G, int Nc, int D, int Mtot);
+int vargp_greedy_select(const float* theta, const float* X, const int32_t* cand, float* LT, float* d, int32_t* pick, float* pivot,
+                        int G, int Nc, int N, int D, int k0, int M, int nu2, float eps, void* ws, size_t ws_bytes,
+                        vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * KL(N(mu_q, Lq Lq^T) || N(mu_p, Lp Lp^T)) from its triangular ingredients (reference:
  * torch.distributions kl_divergence(MVN, MVN) as called from var_gp/vargp.py:182-190):
  *   kl = logdet_p - logdet_q + 0.5 * (|G|_F^2 + |d|^2 - M),  G = Lp^-1 Lq [nb, M, M],

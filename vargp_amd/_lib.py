@@ -104,6 +104,8 @@ _SIGNATURES = {
     'vargp_kmeans_workspace_bytes': (c_size_t, [c_int] * 4),
     'vargp_kmeans_assign': (c_int, [_P] * 4 + [c_int] * 4 + [_P, c_size_t, _P]),
     'vargp_kmeans_update': (c_int, [_P] * 4 + [c_int] * 4 + [_P, c_size_t, _P]),
+    'vargp_greedy_workspace_bytes': (c_size_t, [c_int] * 4),
+    'vargp_greedy_select': (c_int, [_P] * 7 + [c_int] * 7 + [c_float, _P, c_size_t, _P]),
     'vargp_mvn_kl_fwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),
     'vargp_mvn_kl_bwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),
     'vargp_logdet_tril_fwd': (c_int, [_P, _P, c_int, c_int, _P]),

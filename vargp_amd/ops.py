@@ -616,6 +616,47 @@ def kmeans_update(X, label, Z):
     return Z_new, count
 
 
+# Greedy conditional-variance selection: a pivoted Cholesky over G candidate sets (csrc/greedy.hip -- not in the reference).
+# No autograd.
+
+def greedy_select(theta, X, cand=None, LT0=None, d0=None, M=None, nu2=0, eps=JITTER, n_sets=None):
+    """theta (D+1,): ONE hyper vector; X (N, D); cand int32 (G, Nc): row numbers into X, or None = rows 0..N-1 for each of
+    n_sets sets (default 1, or LT0's).  LT0 (G, k0, Nc) with d0 (G, Nc): a factorisation already begun (both or neither).
+    -> (pick int32 (G, M): POSITIONS in the candidate list, pivot (G, M): the residual variance at each pick before its
+    downdate, LT (G, k0 + M, Nc): row k = the k-th Cholesky column over the candidates, d (G, Nc): the residual variances left).
+    nu2: 0 = RBF, 1 | 3 | 5 = Matern.  eps: a candidate whose residual variance is not above it is never preferred and ends the
+    selection when it is the best left (rows of zeros from there on); the default is the jitter chol_inv adds, below which a
+    point adds nothing that factorisation can see.  M + 1 launches, no host synchronisation; bitwise reproducible."""
+    require_device(theta, X, cand, LT0, d0)
+    assert (LT0 is None) == (d0 is None), 'greedy_select: LT0 and d0 go together'
+    assert M is not None, 'greedy_select: M'
+    theta, X = theta.detach().contiguous().view(-1), X.detach().contiguous()
+    assert X.dim() == 2 and theta.numel() == X.shape[1] + 1, (theta.shape, X.shape)
+    assert X.dtype == torch.float32 and theta.dtype == torch.float32, (X.dtype, theta.dtype)
+    N, D = X.shape
+    if cand is not None:
+        cand = cand.detach().contiguous()
+        assert cand.dim() == 2 and cand.dtype == torch.int32, (cand.shape, cand.dtype)
+        G, Nc = cand.shape
+    else:
+        G, Nc = int(n_sets if n_sets is not None else (LT0.shape[0] if LT0 is not None else 1)), N
+    k0 = 0 if LT0 is None else LT0.shape[1]
+    M = int(M)
+    LT = torch.empty(G, k0 + M, Nc, dtype=torch.float32, device=X.device)
+    d = torch.empty(G, Nc, dtype=torch.float32, device=X.device)
+    if k0:
+        assert tuple(LT0.shape) == (G, k0, Nc) and tuple(d0.shape) == (G, Nc), (LT0.shape, d0.shape, G, Nc)
+        assert LT0.dtype == torch.float32 and d0.dtype == torch.float32, (LT0.dtype, d0.dtype)
+        LT[:, :k0].copy_(LT0.detach())
+        d.copy_(d0.detach())
+    pick = torch.empty(G, M, dtype=torch.int32, device=X.device)
+    pivot = torch.empty(G, M, dtype=torch.float32, device=X.device)
+    ws = scratch(lib().vargp_greedy_workspace_bytes(G, Nc, D, k0 + M), X.device)
+    check(lib().vargp_greedy_select(ptr(theta), ptr(X), ptr(cand), ptr(LT), ptr(d), ptr(pick), ptr(pivot), G, Nc, N, D, k0, M,
+                                    int(nu2), float(eps), ptr(ws), ws.numel() * 4, stream_ptr()), 'vargp_greedy_select')
+    return pick, pivot, LT, d
+
+
 class _LogdetTril(Function):
     @staticmethod
     def forward(ctx, L):

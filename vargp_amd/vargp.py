@@ -63,7 +63,7 @@ def _hand_over_hyper_prior(prev_params):
     return prior
 
 
-_Z_INITS = ('kmeans', 'random')                    # create_clf / create_reg (z_init=)
+_Z_INITS = ('greedy', 'kmeans', 'random')                  # create_clf / create_reg (z_init=)
 _LENGTHSCALE_INITS = ('default', 'median')        # (lengthscale_init=)
 
 
@@ -84,6 +84,35 @@ def _init_inducing(dataset, out_size, M, z_init, kmeans_iters):
     x = dataset[torch.arange(N)][0]
     xd = x.to(device=torch.device('cuda', torch.cuda.current_device()), dtype=torch.float32)
     return init.kmeans_inducing(xd, out_size, M, n_iter=kmeans_iters).to(device=x.device, dtype=x.dtype)
+
+
+def _greedy_candidates(dataset, out_size, M, n_candidates, who):
+    """z_init='greedy', first half, at the point where the random route draws: the candidate rows of every output, one
+    torch.randperm(N) each on the global generator (init.draw_candidates).  -> (x (N, D) as the dataset holds it, cand)."""
+    N = len(dataset)
+    cand = init.draw_candidates(N, out_size, n_candidates)
+    if M > cand.shape[1]:
+        raise ValueError(f"{who}: z_init='greedy' picks M = {M} inducing points from {cand.shape[1]} candidates "
+                         f'(min(len(dataset), greedy_candidates))')
+    return dataset[torch.arange(N)][0], cand
+
+
+def _greedy_inducing(x, cand, M, kern, prior_log_mean, prev_params):
+    """z_init='greedy', second half, once the kernel stands (not in the reference): greedy conditional-variance selection among
+    the candidates on the current CUDA device (init.greedy_inducing).  Hyper vector: the kernel's own log_mean for a first task
+    (after lengthscale_init, so 'median' and 'greedy' compose); for a later task the handed-over prior_log_mean -- the last
+    task's trained hyper-posterior mean, the only informed value at that point -- and the selection starts from the previous
+    tasks' inducing points.  The kernel code comes from the kernel's class whatever its route.  z returns on the dataset's
+    device and dtype."""
+    dev = torch.device('cuda', torch.cuda.current_device())
+    theta = kern.log_mean.detach() if not prev_params or prior_log_mean is None else prior_log_mean
+    nu2 = int(round(2 * kern.nu)) if isinstance(kern, MaternKernel) else 0
+    z_prev = None
+    if prev_params:
+        z_prev = torch.cat([p['z'].detach().to(device=dev, dtype=torch.float32) for p in prev_params], dim=-2)
+    xd = x.to(device=dev, dtype=torch.float32)
+    z = init.greedy_inducing(xd, cand.shape[0], M, theta.to(dev), nu2=nu2, z_prev=z_prev, cand=cand)
+    return z.to(device=x.device, dtype=x.dtype)
 
 
 def _init_lengthscale(kern, dataset, lengthscale_init, first_task):
@@ -584,7 +613,8 @@ class VARGP(nn.Module):
     @staticmethod
     def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None,
                    ep_var_mean=True, map_est_hypers=False, dkl=False, kernel='rbf', native_kernel=False,
-                   likelihood='softmax', link='probit', z_init='random', kmeans_iters=20, lengthscale_init='default'):
+                   likelihood='softmax', link='probit', z_init='random', kmeans_iters=20, lengthscale_init='default',
+                   greedy_candidates=4096):
         """Factory used by the experiment driver (vargp.py:200-243): inducing points at random data
         points per class, hyper-prior = previous task's hyper-posterior (popped from prev_params[-1],
         which is mutated like the reference does).  kernel: 'rbf' (the reference's), or 'matern12' / 'matern32' /
@@ -593,13 +623,18 @@ class VARGP(nn.Module):
         reference's MulticlassSoftmax(n_f)) or 'bernoulli' (BernoulliLikelihood(link), the integer labels read as one-vs-rest
         targets; n_f is then unused), with any kernel choice.  None of these is part of a checkpoint: give them again on reload.
         z_init: 'random' (the reference's) or 'kmeans' (k-means centres of the task's data from those random points, at most
-        kmeans_iters Lloyd iterations on the current CUDA device).  lengthscale_init: 'default' (0.5, the reference's) or 'median'
+        kmeans_iters Lloyd iterations on the current CUDA device) or 'greedy' (greedy conditional-variance selection among
+        min(len(dataset), greedy_candidates) random data points per output under the model's own kernel, started from the
+        previous tasks' inducing points when there are any: init.greedy_inducing; not with dkl).  lengthscale_init: 'default' (0.5, the reference's) or 'median'
         (the median pair distance of the task's data, first task only; not with dkl, whose features are untrained)."""
         lik = make_clf_likelihood(likelihood, n_f, link)
         _check_init_names('create_clf', z_init, lengthscale_init)
         if dkl and lengthscale_init == 'median':
             raise ValueError("create_clf: lengthscale_init='median' measures distances between inputs; with dkl=True the kernel "
                              'acts on the features of an untrained network')
+        if dkl and z_init == 'greedy':
+            raise ValueError("create_clf: z_init='greedy' selects by the kernel between inputs; with dkl=True the kernel acts on "
+                             'the features of an untrained network')
         if kernel not in _KERNEL_NU:
             raise ValueError(f'create_clf: kernel must be one of {sorted(_KERNEL_NU)}, got {kernel!r}')
         if dkl and kernel != 'rbf':
@@ -608,7 +643,12 @@ class VARGP(nn.Module):
             raise ValueError('create_clf: native_kernel=True selects the native route of a Matern kernel (kernel="matern12" / '
                              '"matern32" / "matern52", dkl=False); the RBF kernel is always native, DeepRBFKernel never')
         out_size = torch.unique(dataset.targets).size(0)
-        z = _init_inducing(dataset, out_size, M, z_init, kmeans_iters)
+        if z_init == 'greedy':
+            x_all, cand = _greedy_candidates(dataset, out_size, M, greedy_candidates, 'create_clf')
+            in_size = x_all.size(-1)
+        else:
+            z = _init_inducing(dataset, out_size, M, z_init, kmeans_iters)
+            in_size = z.size(-1)
 
         first_task = not prev_params
         prior_log_mean, prior_log_logvar, phi_params = None, None, None
@@ -621,30 +661,32 @@ class VARGP(nn.Module):
                 for k in [k for k in p if k.startswith('kernel')]:
                     p.pop(k)
         if dkl:
-            kern = DeepRBFKernel(z.size(-1), prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
+            kern = DeepRBFKernel(in_size, prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
                                  map_est=map_est_hypers)
             if phi_params:
                 kern.phi.load_state_dict(phi_params)
         elif kernel != 'rbf':
-            kern = MaternKernel(z.size(-1), nu=_KERNEL_NU[kernel], prior_log_mean=prior_log_mean,
+            kern = MaternKernel(in_size, nu=_KERNEL_NU[kernel], prior_log_mean=prior_log_mean,
                                 prior_log_logvar=prior_log_logvar, map_est=map_est_hypers, native=bool(native_kernel))
         else:
-            kern = RBFKernel(z.size(-1), prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
+            kern = RBFKernel(in_size, prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
                              map_est=map_est_hypers)
         _init_lengthscale(kern, dataset, lengthscale_init, first_task)
+        if z_init == 'greedy':
+            z = _greedy_inducing(x_all, cand, M, kern, prior_log_mean, prev_params)
         return VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean,
                      prev_params=prev_params)
 
     @staticmethod
     def create_reg(dataset, M=20, n_var_samples=3, likelihood='gaussian', df=4.0, prev_params=None, ep_var_mean=True,
                    map_est_hypers=False, kernel='rbf', native_kernel=False, z_init='random', kmeans_iters=20,
-                   lengthscale_init='default'):
+                   lengthscale_init='default', greedy_candidates=4096):
         """Regression / count factory, the counterpart of create_clf (not in the reference): dataset[i] -> (x, y), dataset.targets
         (N,) (one output) or (N, C); inducing points at M random data points per output; hyper-prior = the previous task's
         hyper-posterior (popped from prev_params[-1], which is mutated as in create_clf).  likelihood: 'gaussian'
         (GaussianLikelihood), 'studentt' (StudentTLikelihood(df=df): robust to outliers) or 'poisson' (PoissonLikelihood:
         non-negative counts, log link; df is unused by the other two).  kernel / native_kernel / z_init / kmeans_iters /
-        lengthscale_init: as create_clf, without dkl.
+        lengthscale_init / greedy_candidates: as create_clf, without dkl.
         None of likelihood, df, kernel and native_kernel is part of a checkpoint: give them again on reload.  A minibatch's
         targets go to loss() as (C, B) -- y.t() of a (B, C) batch -- or (B,)."""
         if kernel not in _KERNEL_NU:
@@ -658,14 +700,21 @@ class VARGP(nn.Module):
             raise ValueError(f'create_reg: dataset.targets must have shape (N,) or (N, C), got {tuple(targets.shape)}')
         out_size = 1 if targets.dim() == 1 else targets.size(1)
         lik = make_reg_likelihood(likelihood, out_size, df)
-        z = _init_inducing(dataset, out_size, M, z_init, kmeans_iters)
+        if z_init == 'greedy':
+            x_all, cand = _greedy_candidates(dataset, out_size, M, greedy_candidates, 'create_reg')
+            in_size = x_all.size(-1)
+        else:
+            z = _init_inducing(dataset, out_size, M, z_init, kmeans_iters)
+            in_size = z.size(-1)
         first_task = not prev_params
         prior_log_mean, prior_log_logvar = _hand_over_hyper_prior(prev_params)
         if kernel != 'rbf':
-            kern = MaternKernel(z.size(-1), nu=_KERNEL_NU[kernel], prior_log_mean=prior_log_mean,
+            kern = MaternKernel(in_size, nu=_KERNEL_NU[kernel], prior_log_mean=prior_log_mean,
                                 prior_log_logvar=prior_log_logvar, map_est=map_est_hypers, native=bool(native_kernel))
         else:
-            kern = RBFKernel(z.size(-1), prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
+            kern = RBFKernel(in_size, prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
                              map_est=map_est_hypers)
         _init_lengthscale(kern, dataset, lengthscale_init, first_task)
+        if z_init == 'greedy':
+            z = _greedy_inducing(x_all, cand, M, kern, prior_log_mean, prev_params)
         return VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean, prev_params=prev_params)
