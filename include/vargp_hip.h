@@ -245,6 +245,28 @@ int vargp_greedy_select(const float* theta, const float* X, const int32_t* cand,
                         vargp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Weighted moments of the cross-kernel over a data set, for G outputs over one data matrix X [N, D] and ONE hyper vector theta
+ * [D + 1] (log lengthscale_1..D, log gamma) -- what the closed-form optimal q(u) of a Gaussian likelihood needs of the data
+ * (vargp_amd/collapsed.py).  Not in the reference.  With k_n = k_theta(Z_g, x_n), an Mt-vector of the kernel of gram (nu2 = 0: RBF;
+ * 1, 3, 5: Matern nu = nu2 / 2; D <= 32: the direct distance form):
+ *   Phi[g] = sum_n w[g, n] k_n k_n^T  (Mt x Mt, bitwise symmetric),   c[g] = sum_n w[g, n] y[g, n] k_n,
+ *   sums[g] = (sum_n w[g, n], sum_n w[g, n] y[g, n]^2);   w == NULL: every weight is 1.
+ * K(Z, X) is never stored: 64-column tiles of it live in LDS and feed an f32-MFMA rank update.  The points are cut into
+ * vargp_gram_moments_chunks(G, Mt, N, D) chunks -- a function of the shapes alone, at most 1024 and no more than give the launch
+ * about 1024 workgroups -- each accumulated in fp32; a second launch adds the chunks in ascending order in fp64 and rounds once.
+ * No atomics: two calls on the same input are bitwise equal.  A zero weight contributes exactly nothing; nothing is read
+ * behind row N of X.
+ * Workspace: per-chunk partial sums only -- with nt = ceil(Mt / 64) and ntri = nt (nt + 1) / 2, chunks x G x (ntri 16384 + nt 256
+ * + 8) bytes and padding, chunks x G x ntri <= 1024 + G ntri: at most (1024 + G ntri) x 16.6 KB, whatever N is.
+ * Any G, Mt, N, D >= 1, G <= 65535.  VARGP_EINVAL before any launch: a null pointer other than w, a size < 1, nu2 not one of the
+ * four, G > 65535, a short workspace.  The two queries return 0 for a size < 1.
+ */
+size_t vargp_gram_moments_workspace_bytes(int G, int Mt, int N, int D);
+int vargp_gram_moments_chunks(int G, int Mt, int N, int D);
+int vargp_gram_moments(const float* theta, const float* Z, const float* X, const float* w, const float* y, float* Phi, float* c,
+                       float* sums, int G, int Mt, int N, int D, int nu2, void* ws, size_t ws_bytes, vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * KL(N(mu_q, Lq Lq^T) || N(mu_p, Lp Lp^T)) from its triangular ingredients (reference:
  * torch.distributions kl_divergence(MVN, MVN) as called from var_gp/vargp.py:182-190):
  *   kl = logdet_p - logdet_q + 0.5 * (|G|_F^2 + |d|^2 - M),  G = Lp^-1 Lq [nb, M, M],

@@ -106,6 +106,9 @@ _SIGNATURES = {
     'vargp_kmeans_update': (c_int, [_P] * 4 + [c_int] * 4 + [_P, c_size_t, _P]),
     'vargp_greedy_workspace_bytes': (c_size_t, [c_int] * 4),
     'vargp_greedy_select': (c_int, [_P] * 7 + [c_int] * 7 + [c_float, _P, c_size_t, _P]),
+    'vargp_gram_moments_workspace_bytes': (c_size_t, [c_int] * 4),
+    'vargp_gram_moments_chunks': (c_int, [c_int] * 4),
+    'vargp_gram_moments': (c_int, [_P] * 8 + [c_int] * 5 + [_P, c_size_t, _P]),
     'vargp_mvn_kl_fwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),
     'vargp_mvn_kl_bwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),
     'vargp_logdet_tril_fwd': (c_int, [_P, _P, c_int, c_int, _P]),

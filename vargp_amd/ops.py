@@ -657,6 +657,37 @@ def greedy_select(theta, X, cand=None, LT0=None, d0=None, M=None, nu2=0, eps=JIT
     return pick, pivot, LT, d
 
 
+# Weighted moments of the cross-kernel over a data set (csrc/moments.hip -- not in the reference).  No autograd.
+
+def gram_moments_chunks(G, Mt, N, D):
+    """The number of chunks ops.gram_moments cuts N points into for this shape (= partials per output tile); the shapes alone
+    decide it."""
+    return int(lib().vargp_gram_moments_chunks(int(G), int(Mt), int(N), int(D)))
+
+
+def gram_moments(theta, Z, X, w, y, nu2=0):
+    """theta (D+1,): ONE hyper vector; Z (G, Mt, D); X (N, D) shared by the G outputs; w (G, N) or None = 1; y (G, N).  With
+    k_n = k(Z_g, x_n): -> (Phi (G, Mt, Mt) = sum_n w_n k_n k_n^T, exactly symmetric; c (G, Mt) = sum_n w_n y_n k_n; sums (G, 2) =
+    (sum_n w_n, sum_n w_n y_n^2)).  nu2: 0 = RBF, 1 | 3 | 5 = Matern.  K(Z, X) is never stored and the scratch does not grow with
+    N; fp32 within a chunk of points, fp64 across chunks; bitwise reproducible."""
+    require_device(theta, Z, X, w, y)
+    theta, Z, X, y = theta.detach().contiguous().view(-1), Z.detach().contiguous(), X.detach().contiguous(), y.detach().contiguous()
+    assert Z.dim() == 3 and X.dim() == 2 and Z.shape[-1] == X.shape[1] and theta.numel() == X.shape[1] + 1, (theta.shape, Z.shape, X.shape)
+    (G, Mt, D), N = Z.shape, X.shape[0]
+    assert tuple(y.shape) == (G, N), (y.shape, G, N)
+    if w is not None:
+        w = w.detach().contiguous()
+        assert tuple(w.shape) == (G, N) and w.dtype == torch.float32, (w.shape, w.dtype)
+    assert all(t.dtype == torch.float32 for t in (theta, Z, X, y)), (theta.dtype, Z.dtype, X.dtype, y.dtype)
+    Phi = torch.empty(G, Mt, Mt, dtype=torch.float32, device=X.device)
+    c = torch.empty(G, Mt, dtype=torch.float32, device=X.device)
+    sums = torch.empty(G, 2, dtype=torch.float32, device=X.device)
+    ws = scratch(lib().vargp_gram_moments_workspace_bytes(G, Mt, N, D), X.device)
+    check(lib().vargp_gram_moments(ptr(theta), ptr(Z), ptr(X), ptr(w), ptr(y), ptr(Phi), ptr(c), ptr(sums), G, Mt, N, D, int(nu2),
+                                   ptr(ws), ws.numel() * 4, stream_ptr()), 'vargp_gram_moments')
+    return Phi, c, sums
+
+
 class _LogdetTril(Function):
     @staticmethod
     def forward(ctx, L):

@@ -19,7 +19,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import fused, gp_utils, init, noise, ops
+from . import collapsed, fused, gp_utils, init, noise, ops
 from .gp_utils import vec2tril, mat2trilvec, cholesky, rev_cholesky, gp_cond, block_joint, linear_marginal_diag
 from .kernels import RBFKernel, DeepRBFKernel, MaternKernel, native_code
 from .likelihoods import (BernoulliLikelihood, GaussianLikelihood, MulticlassSoftmax, PoissonLikelihood, StudentTLikelihood,
@@ -65,6 +65,7 @@ def _hand_over_hyper_prior(prev_params):
 
 _Z_INITS = ('greedy', 'kmeans', 'random')                  # create_clf / create_reg (z_init=)
 _LENGTHSCALE_INITS = ('default', 'median')        # (lengthscale_init=)
+_Q_INITS = ('default', 'optimal')                 # create_reg (q_init=)
 
 
 def _check_init_names(who, z_init, lengthscale_init):
@@ -585,6 +586,19 @@ class VARGP(nn.Module):
             mu, P, W = gp_utils.marginal_apply_full(prep, self.kernel.compute(theta, z_leq_t, x))
             return mu, self.kernel.compute_cov(theta, x, P, W)
 
+    def fit_q_(self, x, y, weights=None, temper=1.0):
+        """Set q(u) of the current task to its closed-form optimum for the data x (N, D), y (N,) or (C, N) as loss() takes it
+        (Titsias' collapsed bound; collapsed.fit_q_, not in the reference): u_mean and u_tril_vec are overwritten in place under
+        torch.no_grad(), everything else is read at theta = kernel.log_mean.  One pass over the data on the device (ops.gram_moments:
+        K(z, x) is never stored), first-task models and models with prev_params alike.  weights: None, (N,) or (C, N) per-point
+        weights; temper: a factor on the likelihood.  -> collapsed.CollapsedFit(bound (C,) float64: the variational bound of this
+        data at the optimum, per output; n_chunks).  GaussianLikelihood and ep_var_mean=True only (ValueError otherwise); RBFKernel,
+        MaternKernel (any `native`) and DeepRBFKernel.
+        The bound is the standard one, E_q log N(y | f, sigma^2) - KL(q(u_t) || p(u_t | u_<t)).  GaussianLikelihood.loss is the
+        reference's -log N(y | mu, var + sigma^2) instead, so the fitted q(u) maximises this bound and is close to, but not exactly,
+        the minimiser of kl_u + nll as VARGP.loss reports them; kl_u itself is the KL term of the bound."""
+        return collapsed.fit_q_(self, x, y, weights=weights, temper=temper)
+
     def sample_f(self, x, n_samples=1):
         """Joint draws of the latent functions at x (B, D): (n_samples, S, C, B), f = mu + chol(cov + JITTER I) eps with
         (mu, cov) = predict_f(x, full_cov=True) and eps = noise.draw('eps_fs', (n_samples, S, C, B)) (noise.inject can supply
@@ -680,15 +694,23 @@ class VARGP(nn.Module):
     @staticmethod
     def create_reg(dataset, M=20, n_var_samples=3, likelihood='gaussian', df=4.0, prev_params=None, ep_var_mean=True,
                    map_est_hypers=False, kernel='rbf', native_kernel=False, z_init='random', kmeans_iters=20,
-                   lengthscale_init='default', greedy_candidates=4096):
+                   lengthscale_init='default', greedy_candidates=4096, q_init='default'):
         """Regression / count factory, the counterpart of create_clf (not in the reference): dataset[i] -> (x, y), dataset.targets
         (N,) (one output) or (N, C); inducing points at M random data points per output; hyper-prior = the previous task's
         hyper-posterior (popped from prev_params[-1], which is mutated as in create_clf).  likelihood: 'gaussian'
         (GaussianLikelihood), 'studentt' (StudentTLikelihood(df=df): robust to outliers) or 'poisson' (PoissonLikelihood:
         non-negative counts, log link; df is unused by the other two).  kernel / native_kernel / z_init / kmeans_iters /
         lengthscale_init / greedy_candidates: as create_clf, without dkl.
+        q_init: 'default' (u_mean ~ N(0, 0.25), u_tril = the softplus identity, as the reference starts) or 'optimal' (Gaussian
+        likelihood only): once the inducing points and the lengthscale stand, fit_q_ on the whole data set on the current CUDA
+        device -- q(u) starts at its closed-form optimum and the trainer only has to move hyper-parameters and inducing points; the
+        model returns on the device the default route returns it on.
         None of likelihood, df, kernel and native_kernel is part of a checkpoint: give them again on reload.  A minibatch's
         targets go to loss() as (C, B) -- y.t() of a (B, C) batch -- or (B,)."""
+        if q_init not in _Q_INITS:
+            raise ValueError(f'create_reg: q_init must be one of {sorted(_Q_INITS)}, got {q_init!r}')
+        if q_init == 'optimal' and likelihood != 'gaussian':
+            raise ValueError(f"create_reg: q_init='optimal' is the closed form of likelihood='gaussian', got {likelihood!r}")
         if kernel not in _KERNEL_NU:
             raise ValueError(f'create_reg: kernel must be one of {sorted(_KERNEL_NU)}, got {kernel!r}')
         if native_kernel and kernel == 'rbf':
@@ -717,4 +739,12 @@ class VARGP(nn.Module):
         _init_lengthscale(kern, dataset, lengthscale_init, first_task)
         if z_init == 'greedy':
             z = _greedy_inducing(x_all, cand, M, kern, prior_log_mean, prev_params)
-        return VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean, prev_params=prev_params)
+        gp = VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean, prev_params=prev_params)
+        if q_init == 'optimal':
+            collapsed.check_supported(gp, 'create_reg(q_init="optimal")')
+            home, dev = gp.z.device, torch.device('cuda', torch.cuda.current_device())
+            x = dataset[torch.arange(len(dataset))][0]
+            y = targets if targets.dim() == 1 else targets.t()
+            gp.to(dev).fit_q_(x.to(device=dev, dtype=torch.float32), y.to(device=dev, dtype=torch.float32))
+            gp.to(home)
+        return gp
