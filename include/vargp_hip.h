@@ -266,6 +266,28 @@ int vargp_gram_moments_chunks(int G, int Mt, int N, int D);
 int vargp_gram_moments(const float* theta, const float* Z, const float* X, const float* w, const float* y, float* Phi, float* c,
                        float* sums, int G, int Mt, int N, int D, int nu2, void* ws, size_t ws_bytes, vargp_stream_t stream);
 
+/* The backward of vargp_gram_moments for theta and Z (X, w and y get no gradient), in one fused pass over the data.  gPhi
+ * [G, Mt, Mt] is ANY matrix (it is symmetrised inside: S = gPhi + gPhi^T), gc [G, Mt].  With gK = (S K + gc y^T) diag(w) and
+ * V = gK o (-2 dk/dd2) (RBF: gK o K; Matern: matern_w; 0 at a zero distance for nu = 1/2), neither ever stored:
+ *   r = V 1, cn = V^T 1, P = V X, wl_d = exp(-2 theta_d),
+ *   gZ[g, i]  = -wl o (r_i z_i - P_i)                                                          [G, Mt, D]
+ *   gtheta[d] = wl_d sum_g [sum_i z_id (r_i z_id - 2 P_id) + sum_n cn_n x_nd^2]                 d < D.
+ * gtheta has D + 1 entries; entry D is LEFT TO THE CALLER: it needs no pass over the data,
+ *   gtheta[D] = sum_g 4 <gPhi_g, Phi_g> + 2 <gc_g, c_g>   with the forward's outputs.
+ * A workgroup owns (g, a 64-row panel of Z, a chunk of N, a group of at most 448 values of d); the contract of the forward holds:
+ * masked columns behind a chunk's end, a zero weight adds exactly nothing, no atomics, the chunks' partials added in ascending
+ * order in fp64 by a last launch and rounded once, two calls bitwise equal.  vargp_gram_moments_bwd_chunks(G, Mt, N, D): the
+ * chunk count, a function of the shapes alone -- as the forward's (about 1024 workgroups, >= 256 columns, <= 1024 chunks) and
+ * capped so that the partials of r and P, chunks x G x ceil(Mt / 64) x 64 (D + 1) floats, stay below 64 MiB (one chunk is always
+ * allowed).  Workspace: those partials, chunks x G x ceil(Mt / 64) x D floats for the theta sums, G Mt^2 floats for S, and padding;
+ * it does not grow with N.  VARGP_EINVAL before any launch as for the forward (every pointer but w is required).
+ */
+size_t vargp_gram_moments_bwd_workspace_bytes(int G, int Mt, int N, int D);
+int vargp_gram_moments_bwd_chunks(int G, int Mt, int N, int D);
+int vargp_gram_moments_bwd(const float* theta, const float* Z, const float* X, const float* w, const float* y, const float* gPhi,
+                           const float* gc, float* gZ, float* gtheta, int G, int Mt, int N, int D, int nu2, void* ws,
+                           size_t ws_bytes, vargp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * KL(N(mu_q, Lq Lq^T) || N(mu_p, Lp Lp^T)) from its triangular ingredients (reference:
  * torch.distributions kl_divergence(MVN, MVN) as called from var_gp/vargp.py:182-190):

@@ -109,6 +109,9 @@ _SIGNATURES = {
     'vargp_gram_moments_workspace_bytes': (c_size_t, [c_int] * 4),
     'vargp_gram_moments_chunks': (c_int, [c_int] * 4),
     'vargp_gram_moments': (c_int, [_P] * 8 + [c_int] * 5 + [_P, c_size_t, _P]),
+    'vargp_gram_moments_bwd_workspace_bytes': (c_size_t, [c_int] * 4),
+    'vargp_gram_moments_bwd_chunks': (c_int, [c_int] * 4),
+    'vargp_gram_moments_bwd': (c_int, [_P] * 9 + [c_int] * 5 + [_P, c_size_t, _P]),
     'vargp_mvn_kl_fwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),
     'vargp_mvn_kl_bwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),
     'vargp_logdet_tril_fwd': (c_int, [_P, _P, c_int, c_int, _P]),

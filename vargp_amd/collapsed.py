@@ -1,6 +1,8 @@
 """The optimal q(u) of a Gaussian-likelihood model in closed form (Titsias' collapsed bound, SGPR) -- not in the reference, whose
 q(u) is only ever moved by gradient steps.  `fit_q_` (VARGP.fit_q_, create_reg(q_init='optimal')) writes it into u_mean and
 u_tril_vec and returns the bound's value at the optimum; for a Gaussian likelihood this is one natural-gradient step of length 1.
+`collapsed_bound` is the same value on the autograd graph of z, kernel.log_mean and obs_log_var, and `fit_collapsed_` climbs it
+(SGPR: no q(u) parameter; VARGP.collapsed_bound, VARGP.fit_collapsed_, create_reg(q_init='collapsed')).
 
 Everything happens at ONE hyper vector, theta = kernel.log_mean, in the whitened coordinates of gp_utils.block_joint: with
 K' = K(z_<=t) + eps I = L L^T, T = L^-1 and v = T u, the posterior is q(v) = N(a, H H^T) with block-diagonal H, the blocks of the
@@ -63,6 +65,68 @@ def inv_softplus(d):
     return torch.where(d > 20.0, d, torch.log(torch.expm1(d.clamp_max(20.0))))
 
 
+def _whitened_bound(gp, x, y, weights, temper):
+    """The module docstring's formulas, once, for fit_q_ and collapsed_bound alike: every step is a differentiable op (or fp64
+    elementwise torch), so under no_grad this is the plain computation and otherwise the bound sits on the autograd graph of gp.z,
+    kernel.log_mean and obs_log_var.  -> (bound (C,) float64, n_chunks, what fit_q_ needs for q(u_t): beta, L_tt, G, G64, gb)."""
+    kern = gp.kernel
+    C, M, N = gp.z.size(0), gp.M, x.size(0)
+    theta = kern.log_mean.to(torch.float32).contiguous()
+    prev = [gp._prev(i) for i in range(len(gp.prev_params))]
+    z_all = torch.cat([p['z'] for p in prev] + [gp.z], dim=-2).contiguous()
+    Mt = z_all.size(-2)
+    n_lt = Mt - M
+    yt, ldy = ops.reg_target(y, C, N)
+    yt = yt.expand(C, N).contiguous() if ldy == 0 else yt
+    wt = None
+    if weights is not None:
+        wt, ldw = ops.reg_target(weights, C, N)
+        wt = wt.expand(C, N).contiguous() if ldw == 0 else wt
+    deep = isinstance(kern, DeepRBFKernel)
+    zf, xf = (kern.features(z_all), kern.features(x)) if deep else (z_all, x)
+    nu2 = int(round(2 * kern.nu)) if isinstance(kern, MaternKernel) else 0
+
+    # the only pass over the data (and, in the backward, the only other one)
+    Phi, c, sums = ops.gram_moments_diff(theta, zf, xf, wt, yt, nu2)
+    n_chunks = ops.gram_moments_chunks(C, Mt, N, zf.size(-1))
+
+    L, T = ops.chol_inv(kern.compute(theta.unsqueeze(0), z_all)[0])                  # (C, Mt, Mt): as block_joint factorises
+    A = ops.matmul(ops.matmul(T, Phi, triA=LOWER), T.mT, triB=UPPER).double()
+    A = 0.5 * (A + A.mT)
+    tc = ops.matmul(T, c.unsqueeze(-1), triA=LOWER).squeeze(-1).double()
+    sw, syy = sums[:, 0].double(), sums[:, 1].double()
+    beta = float(temper) * (-gp.likelihood.obs_log_var.double()).exp()               # (C,)
+    g2 = (2.0 * theta[-1].double()).exp()
+
+    # the frozen tasks: a_< and sum_i tr(H_i^T A_ii H_i)
+    a_lt, trHAH, o = [], torch.zeros(C, dtype=torch.float64, device=x.device), 0
+    for p in prev:
+        n = p['z'].size(-2)
+        T_ii = T[:, o:o + n, o:o + n].contiguous()
+        a_lt.append(ops.matmul(T_ii, p['u_mean'], triA=LOWER).squeeze(-1).double())
+        H = ops.matmul(T_ii, p['u_tril'], triA=LOWER, triB=LOWER).double().tril()
+        A_ii = A[:, o:o + n, o:o + n]
+        trHAH = trHAH + ((A_ii.unsqueeze(-1) * H.unsqueeze(-3)).sum(-2) * H).sum((-2, -1))
+        o += n
+    a_lt = torch.cat(a_lt, dim=-1) if a_lt else tc.new_zeros(C, 0)
+    A_ll, A_tl, A_tt = A[:, :n_lt, :n_lt], A[:, n_lt:, :n_lt], A[:, n_lt:, n_lt:]
+    b_t = tc[:, n_lt:] - _mv(A_tl, a_lt)
+
+    # I + beta A_tt = U U^T, U upper: the Cholesky factor of the reversed matrix, reversed back; G = U^-T is lower
+    Bm = torch.eye(M, dtype=torch.float64, device=x.device) + beta.view(C, 1, 1) * A_tt
+    Lr, Tr = ops.chol_inv(Bm.flip(-2, -1).float().contiguous(), 0.0)
+    G = Tr.mT.flip(-2, -1).contiguous()                                               # Sigma_t = G G^T
+    G64 = G.double().tril()
+    gb = _mv(G64.mT, b_t)
+    quad = gb.square().sum(-1)                                                        # b_t^T Sigma_t b_t
+    logdet = 2.0 * Lr.diagonal(dim1=-2, dim2=-1).double().log().sum(-1)
+
+    fixed = syy - 2.0 * (a_lt * tc[:, :n_lt]).sum(-1) + (a_lt * _mv(A_ll, a_lt)).sum(-1) + g2 * sw \
+        - A.diagonal(dim1=-2, dim2=-1).sum(-1) + trHAH
+    bound = -0.5 * sw * (2.0 * math.pi / beta).log() - 0.5 * beta * fixed + 0.5 * beta.square() * quad - 0.5 * logdet
+    return bound, n_chunks, (beta, L[:, n_lt:, n_lt:].contiguous(), G, G64, gb)
+
+
 def fit_q_(gp, x, y, weights=None, temper=1.0):
     """Set q(u_t) of the VARGP model `gp` to its optimum for the data x (N, D), y (N,) or (C, N) (as loss() takes it), in place and
     under no_grad; weights None, (N,) or (C, N), >= 0: per-point weights of the log-likelihood; temper: a factor on all of them
@@ -70,62 +134,11 @@ def fit_q_(gp, x, y, weights=None, temper=1.0):
     obs_log_var are read, not changed.  -> CollapsedFit(bound (C,) float64, n_chunks).  See the module docstring for the formulas
     and for how the bound relates to VARGP.loss."""
     check_supported(gp)
-    kern = gp.kernel
     ops.require_device(gp.z, x, y, weights)
     with torch.no_grad():
-        C, M, N = gp.z.size(0), gp.M, x.size(0)
-        theta = kern.log_mean.detach().to(torch.float32).contiguous()
-        prev = [gp._prev(i) for i in range(len(gp.prev_params))]
-        z_all = torch.cat([p['z'] for p in prev] + [gp.z.detach()], dim=-2).contiguous()
-        Mt = z_all.size(-2)
-        n_lt = Mt - M
-        yt, ldy = ops.reg_target(y, C, N)
-        yt = yt.expand(C, N).contiguous() if ldy == 0 else yt
-        wt = None
-        if weights is not None:
-            wt, ldw = ops.reg_target(weights, C, N)
-            wt = wt.expand(C, N).contiguous() if ldw == 0 else wt
-        deep = isinstance(kern, DeepRBFKernel)
-        zf, xf = (kern.features(z_all), kern.features(x)) if deep else (z_all, x)
-        nu2 = int(round(2 * kern.nu)) if isinstance(kern, MaternKernel) else 0
-
-        # the only pass over the data
-        Phi, c, sums = ops.gram_moments(theta, zf, xf, wt, yt, nu2)
-        n_chunks = ops.gram_moments_chunks(C, Mt, N, zf.size(-1))
-
-        L, T = ops.chol_inv(kern.compute(theta.unsqueeze(0), z_all)[0])                  # (C, Mt, Mt): as block_joint factorises
-        A = ops.bgemm(ops.bgemm(T, Phi, triA=LOWER), T.mT, triB=UPPER).double()
-        A = 0.5 * (A + A.mT)
-        tc = ops.bgemm(T, c.unsqueeze(-1), triA=LOWER).squeeze(-1).double()
-        sw, syy = sums[:, 0].double(), sums[:, 1].double()
-        beta = float(temper) * (-gp.likelihood.obs_log_var.detach().double()).exp()      # (C,)
-        g2 = (2.0 * theta[-1].double()).exp()
-
-        # the frozen tasks: a_< and sum_i tr(H_i^T A_ii H_i)
-        a_lt, trHAH, o = [], torch.zeros(C, dtype=torch.float64, device=x.device), 0
-        for p in prev:
-            n = p['z'].size(-2)
-            T_ii = T[:, o:o + n, o:o + n].contiguous()
-            a_lt.append(ops.bgemm(T_ii, p['u_mean'], triA=LOWER).squeeze(-1).double())
-            H = ops.bgemm(T_ii, p['u_tril'], triA=LOWER, triB=LOWER).double().tril()
-            A_ii = A[:, o:o + n, o:o + n]
-            trHAH = trHAH + ((A_ii.unsqueeze(-1) * H.unsqueeze(-3)).sum(-2) * H).sum((-2, -1))
-            o += n
-        a_lt = torch.cat(a_lt, dim=-1) if a_lt else tc.new_zeros(C, 0)
-        A_ll, A_tl, A_tt = A[:, :n_lt, :n_lt], A[:, n_lt:, :n_lt], A[:, n_lt:, n_lt:]
-        b_t = tc[:, n_lt:] - _mv(A_tl, a_lt)
-
-        # I + beta A_tt = U U^T, U upper: the Cholesky factor of the reversed matrix, reversed back; G = U^-T is lower
-        Bm = torch.eye(M, dtype=torch.float64, device=x.device) + beta.view(C, 1, 1) * A_tt
-        Lr, Tr = ops.chol_inv(Bm.flip(-2, -1).float().contiguous(), 0.0)
-        G = Tr.mT.flip(-2, -1).contiguous()                                               # Sigma_t = G G^T
-        G64 = G.double().tril()
-        gb = _mv(G64.mT, b_t)
-        quad = gb.square().sum(-1)                                                        # b_t^T Sigma_t b_t
+        M = gp.M
+        bound, n_chunks, (beta, L_tt, G, G64, gb) = _whitened_bound(gp, x, y, weights, temper)
         a_t = beta.unsqueeze(-1) * _mv(G64, gb)
-        logdet = 2.0 * Lr.diagonal(dim1=-2, dim2=-1).double().log().sum(-1)
-
-        L_tt = L[:, n_lt:, n_lt:].contiguous()
         u_mean = _mv(L_tt.double().tril(), a_t).unsqueeze(-1)
         u_tril = ops.bgemm(L_tt, G, triA=LOWER, triB=LOWER).tril()
         vec = ops.mat2trilvec(u_tril)
@@ -133,10 +146,62 @@ def fit_q_(gp, x, y, weights=None, temper=1.0):
         diag = idx * (idx + 1) // 2 + idx
         vec[:, diag] = inv_softplus(vec[:, diag].double()).float()
 
-        fixed = syy - 2.0 * (a_lt * tc[:, :n_lt]).sum(-1) + (a_lt * _mv(A_ll, a_lt)).sum(-1) + g2 * sw \
-            - A.diagonal(dim1=-2, dim2=-1).sum(-1) + trHAH
-        bound = -0.5 * sw * (2.0 * math.pi / beta).log() - 0.5 * beta * fixed + 0.5 * beta.square() * quad - 0.5 * logdet
-
         gp.u_mean.copy_(u_mean.to(gp.u_mean.dtype))
         gp.u_tril_vec.copy_(vec.to(gp.u_tril_vec.dtype))
     return CollapsedFit(bound, n_chunks)
+
+
+def check_differentiable(gp, who):
+    """check_supported, and exactly RBFKernel or MaternKernel: the bound's gradient for a DeepRBFKernel needs the gradient of the
+    moments for X (the feature map), which ops.gram_moments_diff does not produce."""
+    if isinstance(gp.kernel, DeepRBFKernel):
+        raise ValueError(f'{who}: DeepRBFKernel is not supported (the feature map needs the gradient of the moments for their '
+                         'inputs X, which the fused backward does not produce); fit_q_ supports it')
+    check_supported(gp, who)
+    if type(gp.kernel) not in (RBFKernel, MaternKernel):
+        raise ValueError(f'{who}: supported kernels are exactly RBFKernel and MaternKernel, got {type(gp.kernel).__name__}')
+
+
+def collapsed_bound(gp, x, y, weights=None, temper=1.0):
+    """Titsias' collapsed bound of the data x (N, D), y (N,) or (C, N) -- the value fit_q_ returns, the variational bound at the
+    optimal q(u_t) -- as a (C,) float64 tensor ON THE AUTOGRAD GRAPH of gp.z, gp.kernel.log_mean and gp.likelihood.obs_log_var
+    (the module docstring's formulas; the frozen tasks' inducing points and q(u) are constants).  q(u_t) itself is neither read
+    nor written.  x, y and weights get no gradient.  One fused pass over the data forward and one backward
+    (ops.gram_moments_diff): K(z, x) is never stored in either.  GaussianLikelihood, ep_var_mean=True, exactly RBFKernel or
+    MaternKernel; a DeepRBFKernel is refused (ValueError).  The hyper-prior (kl_hypers) is NOT part of the bound."""
+    check_differentiable(gp, 'collapsed_bound')
+    ops.require_device(gp.z, x, y, weights)
+    return _whitened_bound(gp, x, y, weights, temper)[0]
+
+
+def fit_collapsed_(gp, x, y, n_steps=200, lr=1e-2, weights=None, temper=1.0, params=('z', 'kernel', 'noise')):
+    """Full-batch ascent of sum_c collapsed_bound over the chosen subset of {'z': gp.z, 'kernel': gp.kernel.log_mean, 'noise':
+    gp.likelihood.obs_log_var} with the project's Yogi (optim.py), n_steps deterministic steps without any q(u) parameter, then
+    fit_q_ once at the parameters reached.  The objective is the bound alone: the hyper-prior (kl_hypers) is NOT in it, so this
+    is maximum likelihood (type II) for the hyper-parameters, not the MAP / variational treatment of VARGP.loss.
+    -> the bound per step, float64 (n_steps + 1, C) on the host: row k is the bound BEFORE step k + 1, the last row the bound
+    fit_q_ reports at the final parameters.  One device synchronisation, at the end."""
+    from .optim import Yogi
+    check_differentiable(gp, 'fit_collapsed_')
+    named = dict(z=gp.z, kernel=gp.kernel.log_mean, noise=gp.likelihood.obs_log_var)
+    unknown = [p for p in params if p not in named]
+    if unknown or not params:
+        raise ValueError(f'fit_collapsed_: params must be a non-empty subset of {sorted(named)}, got {tuple(params)!r}')
+    n_steps = int(n_steps)
+    if n_steps < 0:
+        raise ValueError(f'fit_collapsed_: n_steps must be >= 0, got {n_steps}')
+    ops.require_device(gp.z, x, y, weights)
+    chosen = [named[p] for p in dict.fromkeys(params)]
+    opt = Yogi(chosen, lr=lr)
+    trace = []
+    for _ in range(n_steps):
+        bound = collapsed_bound(gp, x, y, weights=weights, temper=temper)
+        grads = torch.autograd.grad(-bound.sum(), chosen)
+        for p, g in zip(chosen, grads):
+            p.grad = g.to(p.dtype)
+        opt.step()
+        trace.append(bound.detach())
+    for p in chosen:
+        p.grad = None
+    trace.append(fit_q_(gp, x, y, weights=weights, temper=temper).bound)
+    return torch.stack(trace).cpu()

@@ -688,6 +688,58 @@ def gram_moments(theta, Z, X, w, y, nu2=0):
     return Phi, c, sums
 
 
+def gram_moments_bwd_chunks(G, Mt, N, D):
+    """The number of chunks the backward of ops.gram_moments_diff cuts N points into; the shapes alone decide it."""
+    return int(lib().vargp_gram_moments_bwd_chunks(int(G), int(Mt), int(N), int(D)))
+
+
+def gram_moments_bwd(theta, Z, X, w, y, gPhi, gc, nu2=0):
+    """The fused backward of gram_moments (csrc/moments.hip, vargp_gram_moments_bwd) for contiguous fp32 operands: gPhi (G, Mt,
+    Mt), any matrix, and gc (G, Mt) -> (gZ (G, Mt, D), gtheta (D + 1,)) with gtheta[D] NOT written (it needs the forward's outputs:
+    _GramMoments.backward).  K(Z, X) and its gradient are never stored; bitwise reproducible."""
+    (G, Mt, D), N = Z.shape, X.shape[0]
+    gZ = torch.empty_like(Z)
+    gtheta = torch.empty(D + 1, dtype=torch.float32, device=Z.device)
+    ws = scratch(lib().vargp_gram_moments_bwd_workspace_bytes(G, Mt, N, D), Z.device)
+    check(lib().vargp_gram_moments_bwd(ptr(theta), ptr(Z), ptr(X), ptr(w), ptr(y), ptr(gPhi), ptr(gc), ptr(gZ), ptr(gtheta),
+                                       G, Mt, N, D, int(nu2), ptr(ws), ws.numel() * 4, stream_ptr()), 'vargp_gram_moments_bwd')
+    return gZ, gtheta
+
+
+class _GramMoments(Function):
+    @staticmethod
+    def forward(ctx, theta, Z, X, w, y, nu2):
+        Phi, c, sums = gram_moments(theta, Z, X, w, y, nu2)
+        det = lambda t: None if t is None else t.detach().contiguous()
+        ctx.save_for_backward(det(theta).view(-1), det(Z), det(X), det(w), det(y), Phi, c)
+        ctx.nu2, ctx.theta_shape = int(nu2), theta.shape
+        ctx.mark_non_differentiable(sums)
+        return Phi, c, sums
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gPhi, gc, _gsums):
+        theta, Z, X, w, y, Phi, c = ctx.saved_tensors
+        gPhi = torch.zeros_like(Phi) if gPhi is None else gPhi.to(torch.float32).contiguous()
+        gc = torch.zeros_like(c) if gc is None else gc.to(torch.float32).contiguous()
+        gZ, gtheta = gram_moments_bwd(theta, Z, X, w, y, gPhi, gc, ctx.nu2)
+        # the log-gamma entry needs no pass over the data: K is gamma^2 times a function of the distances, so
+        # gtheta_D = 2 sum gK o K = 4 <gPhi, Phi> + 2 <gc, c>
+        gtheta[-1] = (4.0 * (gPhi.double() * Phi.double()).sum() + 2.0 * (gc.double() * c.double()).sum()).float()
+        return gtheta.view(ctx.theta_shape), gZ, None, None, None, None
+
+
+def gram_moments_diff(theta, Z, X, w, y, nu2=0):
+    """ops.gram_moments on the autograd graph of theta (D+1,) and Z (G, Mt, D): the same forward call and outputs (Phi, c, sums),
+    with a fused backward that never stores K(Z, X) either (gram_moments_bwd).  gPhi may be any matrix (it is not assumed
+    symmetric).  No gradients are produced for X, w and y: a ValueError if one of them requires grad.  sums depends on w and y
+    alone and is not differentiable."""
+    for name, t in (('X', X), ('w', w), ('y', y)):
+        if t is not None and t.requires_grad:
+            raise ValueError(f'gram_moments_diff: {name} requires grad, but gradients are produced for theta and Z only')
+    return _GramMoments.apply(theta, Z, X, w, y, nu2)
+
+
 class _LogdetTril(Function):
     @staticmethod
     def forward(ctx, L):

@@ -65,7 +65,7 @@ def _hand_over_hyper_prior(prev_params):
 
 _Z_INITS = ('greedy', 'kmeans', 'random')                  # create_clf / create_reg (z_init=)
 _LENGTHSCALE_INITS = ('default', 'median')        # (lengthscale_init=)
-_Q_INITS = ('default', 'optimal')                 # create_reg (q_init=)
+_Q_INITS = ('default', 'optimal', 'collapsed')                # create_reg (q_init=)
 
 
 def _check_init_names(who, z_init, lengthscale_init):
@@ -599,6 +599,22 @@ class VARGP(nn.Module):
         the minimiser of kl_u + nll as VARGP.loss reports them; kl_u itself is the KL term of the bound."""
         return collapsed.fit_q_(self, x, y, weights=weights, temper=temper)
 
+    def collapsed_bound(self, x, y, weights=None, temper=1.0):
+        """The bound fit_q_ returns -- the variational bound of x (N, D), y (N,) or (C, N) at the optimal q(u) of the current
+        task -- as a (C,) float64 tensor on the autograd graph of z, kernel.log_mean and likelihood.obs_log_var
+        (collapsed.collapsed_bound): maximise it to place inducing points and fit lengthscales and noise without any q(u)
+        parameter (SGPR).  One fused pass over the data forward and one backward; K(z, x) is never stored.  q(u) is not touched;
+        the frozen tasks are constants; x, y and weights get no gradient.  GaussianLikelihood, ep_var_mean=True, exactly
+        RBFKernel or MaternKernel (a DeepRBFKernel is refused: ValueError).  The hyper-prior is not part of the bound."""
+        return collapsed.collapsed_bound(self, x, y, weights=weights, temper=temper)
+
+    def fit_collapsed_(self, x, y, n_steps=200, lr=1e-2, weights=None, temper=1.0, params=('z', 'kernel', 'noise')):
+        """n_steps full-batch Yogi steps up sum_c collapsed_bound over the chosen subset of {'z', 'kernel' (kernel.log_mean),
+        'noise' (obs_log_var)}, then fit_q_ once (collapsed.fit_collapsed_).  The objective is the bound alone, WITHOUT the
+        hyper-prior (kl_hypers): type-II maximum likelihood, not what VARGP.loss optimises.  -> the bound per step, float64
+        (n_steps + 1, C) on the host, the last row being fit_q_'s at the final parameters; one synchronisation, at the end."""
+        return collapsed.fit_collapsed_(self, x, y, n_steps=n_steps, lr=lr, weights=weights, temper=temper, params=params)
+
     def sample_f(self, x, n_samples=1):
         """Joint draws of the latent functions at x (B, D): (n_samples, S, C, B), f = mu + chol(cov + JITTER I) eps with
         (mu, cov) = predict_f(x, full_cov=True) and eps = noise.draw('eps_fs', (n_samples, S, C, B)) (noise.inject can supply
@@ -694,7 +710,7 @@ class VARGP(nn.Module):
     @staticmethod
     def create_reg(dataset, M=20, n_var_samples=3, likelihood='gaussian', df=4.0, prev_params=None, ep_var_mean=True,
                    map_est_hypers=False, kernel='rbf', native_kernel=False, z_init='random', kmeans_iters=20,
-                   lengthscale_init='default', greedy_candidates=4096, q_init='default'):
+                   lengthscale_init='default', greedy_candidates=4096, q_init='default', collapsed_steps=200):
         """Regression / count factory, the counterpart of create_clf (not in the reference): dataset[i] -> (x, y), dataset.targets
         (N,) (one output) or (N, C); inducing points at M random data points per output; hyper-prior = the previous task's
         hyper-posterior (popped from prev_params[-1], which is mutated as in create_clf).  likelihood: 'gaussian'
@@ -704,13 +720,15 @@ class VARGP(nn.Module):
         q_init: 'default' (u_mean ~ N(0, 0.25), u_tril = the softplus identity, as the reference starts) or 'optimal' (Gaussian
         likelihood only): once the inducing points and the lengthscale stand, fit_q_ on the whole data set on the current CUDA
         device -- q(u) starts at its closed-form optimum and the trainer only has to move hyper-parameters and inducing points; the
-        model returns on the device the default route returns it on.
+        model returns on the device the default route returns it on.  'collapsed' (Gaussian likelihood, RBF / Matern kernel):
+        fit_collapsed_(n_steps=collapsed_steps) instead -- inducing points, lengthscales and noise variance are first moved up
+        the collapsed bound (without the hyper-prior), then q(u) is fitted.
         None of likelihood, df, kernel and native_kernel is part of a checkpoint: give them again on reload.  A minibatch's
         targets go to loss() as (C, B) -- y.t() of a (B, C) batch -- or (B,)."""
         if q_init not in _Q_INITS:
             raise ValueError(f'create_reg: q_init must be one of {sorted(_Q_INITS)}, got {q_init!r}')
-        if q_init == 'optimal' and likelihood != 'gaussian':
-            raise ValueError(f"create_reg: q_init='optimal' is the closed form of likelihood='gaussian', got {likelihood!r}")
+        if q_init != 'default' and likelihood != 'gaussian':
+            raise ValueError(f"create_reg: q_init={q_init!r} is the closed form of likelihood='gaussian', got {likelihood!r}")
         if kernel not in _KERNEL_NU:
             raise ValueError(f'create_reg: kernel must be one of {sorted(_KERNEL_NU)}, got {kernel!r}')
         if native_kernel and kernel == 'rbf':
@@ -740,11 +758,16 @@ class VARGP(nn.Module):
         if z_init == 'greedy':
             z = _greedy_inducing(x_all, cand, M, kern, prior_log_mean, prev_params)
         gp = VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean, prev_params=prev_params)
-        if q_init == 'optimal':
-            collapsed.check_supported(gp, 'create_reg(q_init="optimal")')
+        if q_init != 'default':
+            check = collapsed.check_supported if q_init == 'optimal' else collapsed.check_differentiable
+            check(gp, f'create_reg(q_init="{q_init}")')
             home, dev = gp.z.device, torch.device('cuda', torch.cuda.current_device())
             x = dataset[torch.arange(len(dataset))][0]
             y = targets if targets.dim() == 1 else targets.t()
-            gp.to(dev).fit_q_(x.to(device=dev, dtype=torch.float32), y.to(device=dev, dtype=torch.float32))
+            x, y = x.to(device=dev, dtype=torch.float32), y.to(device=dev, dtype=torch.float32)
+            if q_init == 'optimal':
+                gp.to(dev).fit_q_(x, y)
+            else:
+                gp.to(dev).fit_collapsed_(x, y, n_steps=collapsed_steps)
             gp.to(home)
         return gp
