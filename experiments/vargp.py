@@ -53,11 +53,12 @@ def train(task_id, train_set, val_set, test_set, ep_var_mean=True, map_est_hyper
           eval_interval=10, patience=20, prev_params=None, logger=None, device=None, graph=False, seed=None,
           retrain=False, eval_shared_hypers=False, dataloader=False, kernel='rbf', native_kernel=False,
           likelihood='softmax', link='probit', lpd=False, z_init='random', kmeans_iters=20, lengthscale_init='default',
-          uncertainty=False, greedy_candidates=4096):
+          uncertainty=False, greedy_candidates=4096, q_init='default', newton_iters=20):
     if retrain:      # the variant of experiments/vargp_retrain.py:14-19 (earlier tasks' inducing parameters re-optimised)
         from vargp_amd.vargp_retrain import VARGPRetrain
         assert kernel == 'rbf', '--retrain builds its model with the RBF kernel'
         assert z_init == 'random' and lengthscale_init == 'default', "--retrain builds its model with the reference's initialisation"
+        assert q_init == 'default', "--retrain builds its model with the reference's initialisation"
         gp = VARGPRetrain.create_clf(train_set, M=M, n_f=n_f, n_var_samples=n_var_samples, prev_params=prev_params,
                                      likelihood=likelihood, link=link).to(device)
         graph = False
@@ -66,7 +67,7 @@ def train(task_id, train_set, val_set, test_set, ep_var_mean=True, map_est_hyper
                               ep_var_mean=ep_var_mean, map_est_hypers=map_est_hypers, dkl=dkl, kernel=kernel,
                               native_kernel=native_kernel, likelihood=likelihood, link=link, z_init=z_init,
                               kmeans_iters=kmeans_iters, lengthscale_init=lengthscale_init,
-                              greedy_candidates=greedy_candidates).to(device)
+                              greedy_candidates=greedy_candidates, q_init=q_init, newton_iters=newton_iters).to(device)
     stopper = EarlyStopper(patience=patience)
     N = len(train_set)
     # the program's counter-based noise generator is keyed by the run's seed (the reference draws from the torch global
@@ -202,7 +203,8 @@ def toy(args):
                    link=args.link, prev_params=prev_params, logger=logger, device=device, patience=-1,
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed, retrain=args.retrain,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
-                   lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init,
+                   lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init, q_init=args.q_init,
+                   newton_iters=args.newton_iters,
                    uncertainty=args.uncertainty, greedy_candidates=args.greedy_candidates)
         prev_params.append(sd)
     logger.close()
@@ -230,7 +232,8 @@ def split_mnist(args):
                    link=args.link, prev_params=prev_params, logger=logger, device=device,
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
-                   lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init,
+                   lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init, q_init=args.q_init,
+                   newton_iters=args.newton_iters,
                    uncertainty=args.uncertainty, greedy_candidates=args.greedy_candidates)
         prev_params.append(sd)
     logger.close()
@@ -261,7 +264,8 @@ def permuted_mnist(args):
                    link=args.link, prev_params=prev_params, logger=logger,
                    device=device, eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
-                   lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init,
+                   lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init, q_init=args.q_init,
+                   newton_iters=args.newton_iters,
                    uncertainty=args.uncertainty, greedy_candidates=args.greedy_candidates)
         prev_params.append(sd)
     logger.close()
@@ -306,6 +310,10 @@ def parse_args(argv=None):
         sp.add_argument('--lengthscale_init', choices=('default', 'median'), default='default',
                         help="lengthscales of the first task: 0.5 (the reference's), or the median distance between pairs of "
                              'its points (not with --dkl)')
+        sp.add_argument('--q_init', choices=('default', 'newton'), default='default',
+                        help="q(u) of each task: the reference's start, or fit_q_newton_ on the task's whole training set "
+                             '(--likelihood bernoulli only)')
+        sp.add_argument('--newton_iters', type=int, default=20, help='iterations of --q_init newton (at most)')
         sp.add_argument('--seed', type=int, default=None)
         sp.add_argument('--eval_interval', type=int, default=10)
         sp.add_argument('--log_dir', default=os.path.join('runs', f'{name}-{int(time.time())}'))

@@ -289,6 +289,42 @@ int vargp_gram_moments_bwd(const float* theta, const float* Z, const float* X, c
                            size_t ws_bytes, vargp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Gaussian sites of a non-Gaussian likelihood over a data set, for G independent outputs over one data matrix X [N, D] and ONE
+ * hyper vector theta [D + 1] -- what one natural-gradient (conjugate-computation) iteration on q(u) needs of the data
+ * (vargp_amd/sites.py).  Not in the reference.  q(u) enters through alpha [G, Mt] and a symmetric Q [G, Mt, Mt] (only its
+ * symmetric part matters).  With k_n = k_theta(Z_g, x_n), the kernel of vargp_gram_moments (nu2, the two distance forms):
+ *   mu_n = alpha[g] . k_n,   var_n = max(gamma^2 - k_n^T Q[g] k_n, 0)
+ *   (ell, dmu, dvar) = E_{f ~ N(mu_n, var_n)} log p(y[g, n] | f) and its derivatives for (mu, var), as the vargp_<kind>_nll_bwd
+ *   entries evaluate them (fp32 for Bernoulli, fp64 for the others; the 20-node Gauss-Hermite rule where there is no closed form)
+ *   lam2[g, n] = w[g, n] max(-2 dvar, 0),   lam1 = w[g, n] dmu + lam2[g, n] mu_n
+ *   c[g] = sum_n lam1 k_n   [G, Mt]
+ *   sums[g] = (sum_n w ell, sum_n lam2, the number of points with w != 0 whose -2 dvar < 0 was clamped to 0, sum_n w)   [G, 4]
+ * kind: VARGP_SITE_*.  y with row stride ldy (>= N), or ldy = 0: one row shared by every output; Bernoulli reads targets in
+ * {0, 1} (no class-index form here).  log_scale [G], df, lognorm: Student-t only, as vargp_studentt_nll_fwd takes them (ignored,
+ * and log_scale may be NULL, for the other kinds).  w == NULL: every weight is 1.  A point of weight 0 is not evaluated: it adds
+ * exactly nothing to c and sums and gets lam2 = 0, whatever its row of X and its target hold.
+ * K(Z, X) is never stored: all Mt rows of 64 columns of it live in LDS, so Mt <= 256 (VARGP_EINVAL above: the caller composes the
+ * same quantities from the per-op entries).  Q K runs on the f32 MFMA.  The points are cut into vargp_site_moments_chunks(G, Mt,
+ * N, D) chunks -- a function of the shapes alone: at most 1024, at least 256 columns each, about 1024 workgroups -- each
+ * accumulated in fp32 (sums: fp64); a second launch adds the chunks in ascending order in fp64 and rounds once.  No atomics: two
+ * calls on the same input are bitwise equal.  Nothing is read behind row N of X.
+ * Workspace: per-chunk partials only, chunks x G x (ceil(Mt / 64) 256 + 32) bytes and padding, 8-byte aligned; it does not grow
+ * with N beyond the chunk count.  VARGP_EINVAL before any launch: a null pointer other than w (and log_scale unless Student-t),
+ * a size < 1, Mt > 256, G > 65535, an unknown kind or nu2, ldy in (0, N), df <= 0 for Student-t, a short or misaligned
+ * workspace.  The two queries return 0 for a size < 1.
+ */
+#define VARGP_SITE_BERNOULLI_PROBIT 0
+#define VARGP_SITE_BERNOULLI_LOGIT 1
+#define VARGP_SITE_POISSON 2
+#define VARGP_SITE_STUDENTT 3
+size_t vargp_site_moments_workspace_bytes(int G, int Mt, int N, int D);
+int vargp_site_moments_chunks(int G, int Mt, int N, int D);
+int vargp_site_moments(const float* theta, const float* Z, const float* X, const float* alpha, const float* Q, const float* y,
+                       int64_t ldy, const float* w, int kind, const float* log_scale, float df, float lognorm, float* lam2,
+                       float* c, float* sums, int G, int Mt, int N, int D, int nu2, void* ws, size_t ws_bytes,
+                       vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * KL(N(mu_q, Lq Lq^T) || N(mu_p, Lp Lp^T)) from its triangular ingredients (reference:
  * torch.distributions kl_divergence(MVN, MVN) as called from var_gp/vargp.py:182-190):
  *   kl = logdet_p - logdet_q + 0.5 * (|G|_F^2 + |d|^2 - M),  G = Lp^-1 Lq [nb, M, M],

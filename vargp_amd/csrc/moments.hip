@@ -17,19 +17,11 @@
 // entry (i, j), j <= i, to both triangles: Phi is bitwise symmetric and two calls on the same input are bitwise equal.
 // The chunking depends on the shapes alone (mom_plan): at most kMoMaxChunks chunks of at least kMoMinChunk columns, as many as
 // give the launch about kMoTargetWg workgroups.
-#include "common.h"
+#include "moments_plan.h"      // kMoT and the other tiling / chunking constants (shared with sites.hip)
 
 namespace vargp {
 
 typedef float mo_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kMoT = 64;               // tile side of Phi = columns of X per step
-constexpr int kMoLD = kMoT + 1;
-constexpr int kMoBK = 32;              // values of d per slab (D > kRbfDirectD)
-constexpr int kMoDl = kRbfDirectD | 1; // row stride of the staged points (direct form)
-constexpr int kMoTargetWg = 1024;
-constexpr int kMoMinChunk = 256;
-constexpr int kMoMaxChunks = 1024;
 
 struct MomPlan {
   int nt, ntri, nch;         // tiles per side, lower-triangle tiles, chunks

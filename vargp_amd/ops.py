@@ -740,6 +740,61 @@ def gram_moments_diff(theta, Z, X, w, y, nu2=0):
     return _GramMoments.apply(theta, Z, X, w, y, nu2)
 
 
+# Gaussian sites of a non-Gaussian likelihood over a data set (csrc/sites.hip -- not in the reference).  No autograd.
+SITE_MAX_MT = 256                # kSiMaxMt (csrc/moments_plan.h): the fused pass holds all Mt rows of a K block in LDS
+_SITE_KINDS = {('bernoulli', 0): 0, ('bernoulli', 1): 1, ('poisson', None): 2, ('studentt', None): 3}
+
+
+def site_kind(kind, extra):
+    """The VARGP_SITE_* code of a likelihood kind with its `extra` (as ops.lik_nll_fwd takes it) -> (code, log_scale, df,
+    lognorm); ValueError for a kind without independent non-Gaussian sites."""
+    if kind == 'bernoulli':
+        return _SITE_KINDS[(kind, int(extra[0]))], None, 0.0, 0.0
+    if kind == 'poisson':
+        return _SITE_KINDS[(kind, None)], None, 0.0, 0.0
+    if kind == 'studentt':
+        return _SITE_KINDS[(kind, None)], extra[0], float(extra[1]), float(extra[2])
+    raise ValueError(f"site_moments: kind must be 'bernoulli', 'poisson' or 'studentt', got {kind!r}")
+
+
+def site_moments_chunks(G, Mt, N, D):
+    """The number of chunks ops.site_moments cuts N points into for this shape; the shapes alone decide it."""
+    return int(lib().vargp_site_moments_chunks(int(G), int(Mt), int(N), int(D)))
+
+
+def site_moments(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0):
+    """theta (D+1,): ONE hyper vector; Z (G, Mt, D), Mt <= SITE_MAX_MT; X (N, D) shared by the G outputs; alpha (G, Mt) and a
+    symmetric Q (G, Mt, Mt): q(f_n) = N(alpha . k_n, max(gamma^2 - k_n^T Q k_n, 0)), k_n = k(Z_g, x_n); y (G, N) or (N,) (one row
+    for every output), targets as the kind's nll reads float targets; w (G, N) or None = 1; kind / extra: as ops.lik_nll_fwd
+    names the likelihood ('bernoulli' (link code,), 'poisson' (), 'studentt' (log_scale (G,), df, lognorm)).
+    -> (lam2 (G, N) = w max(-2 d ell / d var, 0); c (G, Mt) = sum_n (w d ell / d mu + lam2 mu_n) k_n; sums (G, 4) = (sum w ell,
+    sum lam2, clamped points, sum w)).  K(Z, X) is never stored and the scratch does not grow with N beyond the chunk count;
+    bitwise reproducible; a point of weight 0 adds exactly nothing."""
+    require_device(theta, Z, X, alpha, Q, y, w)
+    code, log_scale, df, lognorm = site_kind(kind, extra)
+    det = lambda t: t.detach().contiguous()
+    theta, Z, X, alpha, Q = det(theta).view(-1), det(Z), det(X), det(alpha), det(Q)
+    assert Z.dim() == 3 and X.dim() == 2 and Z.shape[-1] == X.shape[1] and theta.numel() == X.shape[1] + 1, (theta.shape, Z.shape, X.shape)
+    (G, Mt, D), N = Z.shape, X.shape[0]
+    assert tuple(alpha.shape) == (G, Mt) and tuple(Q.shape) == (G, Mt, Mt), (alpha.shape, Q.shape, G, Mt)
+    yt, ldy = reg_target(y, G, N)
+    if w is not None:
+        w = det(w)
+        assert tuple(w.shape) == (G, N) and w.dtype == torch.float32, (w.shape, w.dtype)
+    if log_scale is not None:
+        log_scale = det(log_scale)
+        assert tuple(log_scale.shape) == (G,) and log_scale.dtype == torch.float32, (log_scale.shape, log_scale.dtype)
+    assert all(t.dtype == torch.float32 for t in (theta, Z, X, alpha, Q)), (theta.dtype, Z.dtype, X.dtype, alpha.dtype, Q.dtype)
+    lam2 = torch.empty(G, N, dtype=torch.float32, device=X.device)
+    c = torch.empty(G, Mt, dtype=torch.float32, device=X.device)
+    sums = torch.empty(G, 4, dtype=torch.float32, device=X.device)
+    ws = scratch(lib().vargp_site_moments_workspace_bytes(G, Mt, N, D), X.device)
+    check(lib().vargp_site_moments(ptr(theta), ptr(Z), ptr(X), ptr(alpha), ptr(Q), ptr(yt), ldy, ptr(w), code, ptr(log_scale), df,
+                                   lognorm, ptr(lam2), ptr(c), ptr(sums), G, Mt, N, D, int(nu2), ptr(ws), ws.numel() * 4,
+                                   stream_ptr()), 'vargp_site_moments')
+    return lam2, c, sums
+
+
 class _LogdetTril(Function):
     @staticmethod
     def forward(ctx, L):

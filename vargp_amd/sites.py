@@ -1,0 +1,321 @@
+"""Natural-gradient fit of q(u) for the non-Gaussian likelihoods with independent outputs -- Bernoulli (probit / logit), Poisson,
+Student-t -- by conjugate-computation variational inference (Khan & Lin 2017); not in the reference, whose q(u) is only ever moved
+by minibatch gradient steps.  `fit_q_newton_` (VARGP.fit_q_newton_, create_clf / create_reg(q_init='newton')) is the counterpart
+of collapsed.fit_q_: a stand-alone, full-batch call under no_grad that overwrites u_mean and u_tril_vec.
+
+Everything happens at ONE hyper vector, theta = kernel.log_mean, in the whitened coordinates of collapsed.py's docstring:
+K' = K(z_<=t) + eps I = L L^T, T = L^-1, v = T u, q(v) = N(a, H H^T) with a = (a_<, a_t) and block-diagonal H, the blocks of the
+frozen tasks being a_i = T_ii m_i, H_i = T_ii Lu_i.  The new block starts at the model's current q(u_t): a_t = T_tt u_mean,
+H_t = T_tt L_u, and is carried in natural parameters P = Sigma_t^-1, h = P a_t.  One iteration, with k_n = k(z_<=t, x_n):
+
+    alpha = T^T a,   Q = T^T (I - H H^T) T                          (so that q(f_n) = N(alpha . k_n, gamma^2 - k_n^T Q k_n))
+    mu_n = alpha . k_n,   var_n = max(gamma^2 - k_n^T Q k_n, 0)
+    (ell, dmu, dvar) = E_{N(mu_n, var_n)} log p(y_n | f) and its derivatives for (mu_n, var_n)      (csrc/lik.h)
+    lam2_n = w_n max(-2 dvar, 0),   lam1_n = w_n dmu + lam2_n mu_n                                  (the Gaussian site of point n)
+    c = sum_n lam1_n k_n,   Phi = sum_n lam2_n k_n k_n^T,   A = T Phi T^T,   tc = T c
+    P' = (1 - rho) P + rho (I + A_tt),   h' = (1 - rho) h + rho (tc_t - A_{t,<} a_<)
+    Sigma_t = P'^-1 = G G^T,   a_t = Sigma_t h'
+    bound = sum_n w_n ell - 1/2 (|a_t|^2 + tr Sigma_t - M - logdet Sigma_t)
+
+The first two lines of data terms are ONE fused pass over the data (ops.site_moments, csrc/sites.hip: K(z, X) and the (C, N)
+moments never reach memory), Phi a second one (ops.gram_moments with w = lam2).  With rho = 1 and the sites of a Gaussian
+likelihood (lam2 = beta, lam1 = beta y) the update is collapsed.fit_q_'s formula; for a log-concave likelihood (Bernoulli,
+Poisson) it is Newton's method on the bound.  P' is factored as fit_q_ factors I + beta A_tt: the Cholesky factor of the reversed
+matrix, reversed back, so that G is lower triangular and u_tril = L_tt G needs no second factorisation.  Since lam2 >= 0,
+P' >= I wherever P >= I.
+
+The data part of a q's bound is the sums[:, 0] of the pass made AT that q, so a candidate's value is known after the next pass.
+Backtracking: a candidate whose bound is not finite, or lower than the bound of the q it came from in ANY output, is discarded;
+rho is halved for that step and the candidate rebuilt from the same q, at most 8 times; if all fail the fit stops at the last
+accepted q.  Every column of the returned trace is therefore non-decreasing.  The fit also stops when the bound summed over the
+outputs rises by less than tol |bound|, or after n_iters accepted steps.
+
+CAVEAT (Student-t): the likelihood is not log-concave, d ell / d var can be positive (an outlier), and the clamp lam2 >= 0 then
+replaces the Newton step by a Gauss-Newton-like majorisation.  Its fixed point is the stationary point of the bound only when no
+point is clamped at convergence: check SiteFit.n_clamped == 0.
+
+Routes: 'fused' as above, for Mt = all inducing points <= ops.SITE_MAX_MT (the K block of all rows lives in LDS).  'composed': the
+same quantities per tile of N from the per-op kernels -- the gram op, ops.bgemm, ops.lik_nll_bwd with a unit seed -- and Phi from
+ops.gram_moments; taken above the limit, on request (route='composed', or VARGP_SITES_ROUTE=composed in the environment), and as
+the on-device yardstick of the fused kernel.  The per-op likelihood entries return their value summed over outputs and points, so
+the composed route evaluates ell itself, in fp64 elementwise torch, by the formulas of csrc/lik.h."""
+import math
+import os
+from collections import namedtuple
+
+import torch
+
+from . import ops
+from .collapsed import _mv, inv_softplus
+from .kernels import DeepRBFKernel, MaternKernel, RBFKernel
+from .likelihoods import GaussianLikelihood, MulticlassSoftmax
+from .ops import LOWER, UPPER
+
+SiteFit = namedtuple('SiteFit', 'bound n_iters n_rejected n_clamped route')
+SiteFit.__doc__ = """bound (n_iters + 1, C) float64 on the host: the variational bound per output at the initial q(u) and after
+every accepted step (nats; non-decreasing in every column); n_iters: accepted steps; n_rejected: discarded candidates;
+n_clamped: points (over all outputs) whose lam2 was clamped to 0 at the final q(u); route: 'fused' or 'composed'."""
+
+SITE_KINDS = ('bernoulli', 'poisson', 'studentt')
+MAX_HALVINGS = 8
+COMPOSED_TILE = 8192
+
+# the positive half of numpy.polynomial.hermite.hermgauss(20) and its weights / sqrt(pi) (csrc/lik.h: kGhX, kGhW)
+_GH_X = (0.24534070830090124, 0.73747372854539439, 1.2340762153953231, 1.7385377121165861, 2.2549740020892757,
+         2.7888060584281305, 3.3478545673832163, 3.9447640401156252, 4.6036824495507442, 5.3874808900112328)
+_GH_W = (0.26079306344955488, 0.16173933398399998, 0.061506372063976897, 0.013997837447101022, 0.00183010313108049,
+         0.00012882627996192928, 4.402121090230851e-06, 6.127490259982928e-08, 2.4820623623151755e-10, 1.2578006724379234e-13)
+
+
+def check_supported(gp, who='fit_q_newton_'):
+    """ValueError unless the site iteration applies to the model: a Bernoulli, Poisson or Student-t likelihood, ep_var_mean=True,
+    an RBF / Matern / deep-RBF kernel.  Needs no device."""
+    lik = gp.likelihood
+    if isinstance(lik, MulticlassSoftmax):
+        raise ValueError(f'{who}: MulticlassSoftmax couples the outputs of a point, so it has no independent Gaussian sites; '
+                         'use create_clf(likelihood="bernoulli") for a one-vs-rest classifier')
+    if isinstance(lik, GaussianLikelihood):
+        raise ValueError(f'{who}: for GaussianLikelihood the optimal q(u) has a closed form, use fit_q_')
+    if getattr(lik, 'kind', None) not in SITE_KINDS:
+        raise ValueError(f'{who}: supported likelihoods are BernoulliLikelihood, PoissonLikelihood and StudentTLikelihood, got '
+                         f'{type(lik).__name__}')
+    if gp.var_mean_mask != 1.0:
+        raise ValueError(f'{who}: supported for ep_var_mean=True models only (with ep_var_mean=False the mean of q(u_t) is not '
+                         'u_mean alone)')
+    if not isinstance(gp.kernel, RBFKernel):
+        raise ValueError(f'{who}: supported kernels are RBFKernel, MaternKernel and DeepRBFKernel, got {type(gp.kernel).__name__}')
+
+
+def check_damping(damping, who='fit_q_newton_'):
+    damping = float(damping)
+    if not 0.0 < damping <= 1.0:
+        raise ValueError(f'{who}: damping must be in (0, 1], got {damping!r}')
+    return damping
+
+
+def pick_route(route, Mt, who='fit_q_newton_'):
+    """route None: VARGP_SITES_ROUTE from the environment if set, else 'fused' up to ops.SITE_MAX_MT inducing points and
+    'composed' above.  An explicit 'fused' above the limit is a ValueError."""
+    route = route or os.environ.get('VARGP_SITES_ROUTE') or None
+    if route not in (None, 'fused', 'composed'):
+        raise ValueError(f"{who}: route must be 'fused' or 'composed', got {route!r}")
+    if route == 'fused' and Mt > ops.SITE_MAX_MT:
+        raise ValueError(f'{who}: the fused pass holds at most {ops.SITE_MAX_MT} inducing points (all tasks), got {Mt}')
+    return route or ('fused' if Mt <= ops.SITE_MAX_MT else 'composed')
+
+
+def site_target(kind, y, C, N):
+    """The targets as float32 (C, N) or (N,): Bernoulli int64 class indices (N,) become the one-vs-rest rows (y[n] == c)."""
+    if kind == 'bernoulli':
+        if y.dtype == torch.int64:
+            if tuple(y.shape) != (N,):
+                raise ValueError(f'fit_q_newton_: int64 class indices must have shape ({N},), got {tuple(y.shape)}')
+            return (y.unsqueeze(0) == torch.arange(C, device=y.device).unsqueeze(1)).to(torch.float32)
+        if not (y.dtype.is_floating_point or y.dtype == torch.bool):
+            raise TypeError(f'fit_q_newton_: int64 class indices or float / bool 0 / 1 targets, got {y.dtype}')
+    return ops.reg_target(y.to(torch.float32), C, N)[0]
+
+
+def ell_torch(kind, extra, mu, var, y):
+    """E_{f ~ N(mu, var)} log p(y | f) elementwise in fp64 torch, by the formulas of csrc/lik.h (the 20-node rule where there is no
+    closed form).  mu, var, y broadcastable (C, B); extra as ops.lik_nll_fwd takes it.  Any device."""
+    mu, var, y = mu.double(), var.double(), y.double()
+    if kind == 'poisson':
+        return y * mu - (mu + 0.5 * var).exp() - torch.lgamma(y + 1.0)
+    x = torch.tensor(_GH_X, dtype=torch.float64, device=mu.device)
+    w = torch.tensor(_GH_W, dtype=torch.float64, device=mu.device)
+    d = (2.0 * var).sqrt().unsqueeze(-1) * x
+    if kind == 'bernoulli':
+        s = (2.0 * y - 1.0).unsqueeze(-1)
+        logp = torch.special.log_ndtr if int(extra[0]) == 0 else torch.nn.functional.logsigmoid
+        return ((logp(s * (mu.unsqueeze(-1) + d)) + logp(s * (mu.unsqueeze(-1) - d))) * w).sum(-1)
+    log_scale, df, lognorm = extra[0].double(), float(extra[1]), float(extra[2])
+    inv = ((-2.0 * log_scale).exp() / df).view(-1, 1, 1)
+    r0 = (y - mu).unsqueeze(-1)
+    el = ((torch.log1p((r0 - d).square() * inv) + torch.log1p((r0 + d).square() * inv)) * w).sum(-1)
+    return (lognorm - log_scale).unsqueeze(-1) - 0.5 * (df + 1.0) * el
+
+
+def composed_site_moments(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0, tile=COMPOSED_TILE):
+    """ops.site_moments from the per-op kernels, a tile of N at a time (arguments and results alike; any Mt): the gram op,
+    ops.bgemm for alpha K and Q K, ops.lik_nll_bwd with a unit seed for the derivatives, ell_torch for the value; c and sums are
+    accumulated in fp64 over the tiles."""
+    ops.require_device(theta, Z, X, alpha, Q, y, w)
+    (G, Mt, D), N = Z.shape, X.shape[0]
+    th = theta.detach().view(1, -1).contiguous()
+    gram = (lambda Xt: ops.rbf_gram(th, Z, Xt, True)) if nu2 == 0 else (lambda Xt: ops.matern_gram(th, Z, Xt, True, 0.5 * nu2))
+    g2 = (2.0 * th[0, -1]).exp()
+    shared = y.dim() == 1
+    seed = torch.ones((), dtype=torch.float32, device=X.device)
+    lam2 = torch.empty(G, N, dtype=torch.float32, device=X.device)
+    c = torch.zeros(G, Mt, dtype=torch.float64, device=X.device)
+    sums = torch.zeros(G, 4, dtype=torch.float64, device=X.device)
+    gpar = torch.empty(G, dtype=torch.float32, device=X.device) if kind == 'studentt' else None
+    for n0 in range(0, N, tile):
+        n1 = min(n0 + tile, N)
+        K = gram(X[n0:n1].contiguous())[0]                                            # (G, Mt, B)
+        mu = ops.bgemm(alpha.unsqueeze(-2), K).squeeze(-2).contiguous()               # (G, B)
+        var = (g2 - (K * ops.bgemm(Q, K)).sum(-2)).clamp_min(0.0).contiguous()
+        yt = (y[n0:n1] if shared else y[:, n0:n1]).contiguous()
+        gmu, gvar = torch.empty_like(mu), torch.empty_like(var)
+        ops.lik_nll_bwd(kind, mu.unsqueeze(0), var.unsqueeze(0), ops.lik_target(kind, yt, G, n1 - n0), extra, seed,
+                        gmu.unsqueeze(0), gvar.unsqueeze(0), gpar)
+        wt = torch.ones_like(mu) if w is None else w[:, n0:n1]
+        on = wt != 0
+        zero = torch.zeros_like(mu)
+        dvar = -gvar                                                                  # (the seeded gradients are those of -ell)
+        l2 = torch.where(on & ~(dvar > 0), wt * (-2.0 * dvar), zero)
+        l1 = torch.where(on, wt * (-gmu) + l2 * mu, zero)
+        ell = torch.where(on, wt.double() * ell_torch(kind, extra, mu, var, yt), zero.double())
+        lam2[:, n0:n1] = l2
+        c += ops.bgemm(K, l1.unsqueeze(-1)).squeeze(-1).double()
+        sums += torch.stack([ell.sum(-1), l2.double().sum(-1), (on & (dvar > 0)).double().sum(-1), wt.double().sum(-1)], -1)
+    return lam2, c.float(), sums.float()
+
+
+class _Problem:
+    """What the iteration needs of the model and the data, gathered once: theta, the (featurised) inducing points of all tasks
+    and inputs, the whitening factors, the frozen tasks' whitened posterior, targets, weights and the likelihood's arguments."""
+
+    def __init__(self, gp, x, y, weights, route):
+        kern, lik = gp.kernel, gp.likelihood
+        self.C, self.M, self.N = gp.z.size(0), gp.M, x.size(0)
+        C, M, N = self.C, self.M, self.N
+        self.theta = kern.log_mean.detach().to(torch.float32).contiguous()
+        prev = [gp._prev(i) for i in range(len(gp.prev_params))]
+        z_all = torch.cat([p['z'] for p in prev] + [gp.z.detach()], dim=-2).contiguous()
+        self.Mt = z_all.size(-2)
+        self.n_lt = self.Mt - M
+        self.route = pick_route(route, self.Mt)
+        self.kind, self.extra = lik.kind, tuple(t.detach() if torch.is_tensor(t) else t for t in lik._extra())
+        self.y = site_target(self.kind, y.detach(), C, N)
+        self.w = None
+        if weights is not None:
+            wt, ldw = ops.reg_target(weights, C, N)
+            self.w = wt.expand(C, N).contiguous() if ldw == 0 else wt
+        deep = isinstance(kern, DeepRBFKernel)
+        self.zf, self.xf = (kern.features(z_all), kern.features(x)) if deep else (z_all, x.detach().contiguous())
+        self.nu2 = int(round(2 * kern.nu)) if isinstance(kern, MaternKernel) else 0
+        self.L, self.T = ops.chol_inv(kern.compute(self.theta.unsqueeze(0), z_all)[0])   # (C, Mt, Mt): as block_joint factorises
+        self.L_tt = self.L[:, self.n_lt:, self.n_lt:].contiguous()
+        self.T_tt = self.T[:, self.n_lt:, self.n_lt:].contiguous()
+        a_lt, self.Hb, o = [], torch.zeros(C, self.Mt, self.Mt, dtype=torch.float32, device=x.device), 0
+        for p in prev:
+            n = p['z'].size(-2)
+            T_ii = self.T[:, o:o + n, o:o + n].contiguous()
+            a_lt.append(ops.matmul(T_ii, p['u_mean'], triA=LOWER).squeeze(-1).double())
+            self.Hb[:, o:o + n, o:o + n] = ops.matmul(T_ii, p['u_tril'], triA=LOWER, triB=LOWER).tril()
+            o += n
+        self.a_lt = torch.cat(a_lt, dim=-1) if a_lt else torch.zeros(C, 0, dtype=torch.float64, device=x.device)
+        self.eye_t = torch.eye(self.Mt, dtype=torch.float32, device=x.device)
+        self.eye = torch.eye(M, dtype=torch.float64, device=x.device)
+
+    def sites(self, a_t, H_t):
+        """The two passes over the data at q(v_t) = N(a_t, H_t H_t^T): -> (sum_n w ell (C,) float64, I + A_tt, tc_t - A_{t,<} a_<,
+        clamped points (C,))."""
+        a = torch.cat([self.a_lt, a_t], dim=-1)
+        alpha = _mv(self.T.mT.double(), a).float().contiguous()
+        self.Hb[:, self.n_lt:, self.n_lt:] = H_t
+        S = self.eye_t - ops.bgemm(self.Hb, self.Hb.mT)
+        Q = ops.bgemm(ops.bgemm(self.T.mT, S), self.T)
+        Q = (0.5 * (Q + Q.mT)).contiguous()
+        pass_ = ops.site_moments if self.route == 'fused' else composed_site_moments
+        lam2, c, sums = pass_(self.theta, self.zf, self.xf, alpha, Q, self.y, self.w, self.kind, self.extra, self.nu2)
+        Phi = ops.gram_moments(self.theta, self.zf, self.xf, lam2, lam2, self.nu2)[0]
+        T, n_lt = self.T, self.n_lt
+        A = ops.matmul(ops.matmul(T, Phi, triA=LOWER), T.mT, triB=UPPER).double()
+        A = 0.5 * (A + A.mT)
+        tc = ops.matmul(T, c.unsqueeze(-1), triA=LOWER).squeeze(-1).double()
+        P_new = self.eye + A[:, n_lt:, n_lt:]
+        h_new = tc[:, n_lt:] - _mv(A[:, n_lt:, :n_lt], self.a_lt)
+        return sums[:, 0].double(), P_new, h_new, sums[:, 2]
+
+    def from_natural(self, P, h):
+        """Sigma_t = P^-1 = G G^T with G lower triangular (the Cholesky factor of the reversed P, reversed back, as fit_q_ factors
+        I + beta A_tt) -> (a_t = Sigma_t h, G float32, KL(q(v_t) || N(0, I)) (C,))."""
+        Lr, Tr = ops.chol_inv(P.flip(-2, -1).float().contiguous(), 0.0)
+        G = Tr.mT.flip(-2, -1).contiguous()
+        G64 = G.double().tril()
+        a_t = _mv(G64, _mv(G64.mT, h))
+        logdet_sigma = -2.0 * Lr.diagonal(dim1=-2, dim2=-1).double().log().sum(-1)
+        kl = 0.5 * (a_t.square().sum(-1) + G64.square().sum((-2, -1)) - self.M - logdet_sigma)
+        return a_t, G.tril(), kl
+
+
+def fit_q_newton_(gp, x, y, n_iters=20, damping=1.0, tol=1e-6, weights=None, route=None, start='current'):
+    """Fit q(u_t) of the VARGP model `gp` (Bernoulli, Poisson or Student-t likelihood) to the data x (N, D), y as loss() takes it
+    ((N,) or (C, N); Bernoulli: int64 class indices (N,) read one-vs-rest, or float / bool 0 / 1 targets), by the natural-gradient
+    site iteration of the module docstring, started at the model's current q(u_t); in place and under no_grad.  At most n_iters
+    accepted steps of length damping in (0, 1] (halved while a candidate lowers the bound), until the summed bound rises by less
+    than tol |bound|.  weights None, (N,) or (C, N), >= 0: per-point weights of the log-likelihood.  First-task models and models
+    with prev_params alike; hyper-parameters, inducing points and the likelihood's own parameters are read, not changed.
+    route: None (the fused pass up to ops.SITE_MAX_MT inducing points, the composed one above; VARGP_SITES_ROUTE overrides),
+    'fused' or 'composed'.  start: 'current' (the model's u_mean / u_tril_vec) or 'prior' (q(u_t) = p(u_t | u_<): a_t = 0, H_t = I;
+    the model's q(u_t) is then not read).  The default start of a VARGP model (u_tril = 1.31 I in the space of u) is a WIDE q in
+    function space; a Poisson likelihood, whose expected log-likelihood holds exp(mu + var / 2), can be far too steep there for
+    any damped step to be accepted -- start such a model at the prior.  -> SiteFit(bound (n_iters + 1, C) float64 on the host, n_iters, n_rejected, n_clamped, route)."""
+    check_supported(gp)
+    damping = check_damping(damping)
+    n_iters = int(n_iters)
+    if n_iters < 0:
+        raise ValueError(f'fit_q_newton_: n_iters must be >= 0, got {n_iters}')
+    if start not in ('current', 'prior'):
+        raise ValueError(f"fit_q_newton_: start must be 'current' or 'prior', got {start!r}")
+    ops.require_device(gp.z, x, y, weights)
+    with torch.no_grad():
+        pr = _Problem(gp, x, y, weights, route)
+        M = pr.M
+        if start == 'prior':
+            a_t = torch.zeros(pr.C, M, dtype=torch.float64, device=x.device)
+            H_t = torch.eye(M, dtype=torch.float32, device=x.device).expand(pr.C, M, M).contiguous()
+            P, h, kl = pr.eye.expand(pr.C, M, M), torch.zeros_like(a_t), torch.zeros(pr.C, dtype=torch.float64, device=x.device)
+        else:
+            # the model's q(u_t) in whitened coordinates and natural parameters: H_t^-1 = L_u^-1 L_tt
+            L_u = ops.vec2tril(gp.u_tril_vec.detach().float(), M)
+            a_t = ops.matmul(pr.T_tt, gp.u_mean.detach().float(), triA=LOWER).squeeze(-1).double()
+            H_t = ops.bgemm(pr.T_tt, L_u, triA=LOWER, triB=LOWER).tril()
+            T_u = ops.chol_inv(ops.bgemm(L_u, L_u.mT), 0.0)[1]
+            H_inv = ops.bgemm(T_u, pr.L_tt, triA=LOWER, triB=LOWER).tril()
+            P = ops.bgemm(H_inv.mT, H_inv).double()
+            P = 0.5 * (P + P.mT)
+            h = _mv(P, a_t)
+            H64 = H_t.double()
+            kl = 0.5 * (a_t.square().sum(-1) + H64.square().sum((-2, -1)) - M
+                        - 2.0 * H64.diagonal(dim1=-2, dim2=-1).log().sum(-1))
+
+        data, P_new, h_new, clamped = pr.sites(a_t, H_t)
+        bound = (data - kl).cpu()
+        if not bool(torch.isfinite(bound).all()):
+            raise FloatingPointError(f'fit_q_newton_: the bound is not finite at the initial q(u): {bound.tolist()}')
+        trace, n_rejected, changed = [bound], 0, start == 'prior'
+        while len(trace) - 1 < n_iters:
+            rho, accepted = damping, None
+            for _ in range(MAX_HALVINGS + 1):
+                P_c, h_c = (1.0 - rho) * P + rho * P_new, (1.0 - rho) * h + rho * h_new
+                a_c, G_c, kl_c = pr.from_natural(P_c, h_c)
+                data_c, P_next, h_next, clamped_c = pr.sites(a_c, G_c)
+                bound_c = (data_c - kl_c).cpu()
+                if bool(torch.isfinite(bound_c).all()) and bool((bound_c >= trace[-1]).all()):
+                    accepted = (P_c, h_c, a_c, G_c, P_next, h_next, clamped_c)
+                    break
+                n_rejected += 1
+                rho *= 0.5
+            if accepted is None:
+                break
+            P, h, a_t, H_t, P_new, h_new, clamped = accepted
+            trace.append(bound_c)
+            changed = True
+            if (trace[-1].sum() - trace[-2].sum()).item() < tol * abs(trace[-1].sum().item()):
+                break
+
+        if changed:
+            u_mean = _mv(pr.L_tt.double().tril(), a_t).unsqueeze(-1)
+            u_tril = ops.bgemm(pr.L_tt, H_t, triA=LOWER, triB=LOWER).tril()
+            vec = ops.mat2trilvec(u_tril)
+            idx = torch.arange(M, device=x.device)
+            diag = idx * (idx + 1) // 2 + idx
+            vec[:, diag] = inv_softplus(vec[:, diag].double()).float()
+            gp.u_mean.copy_(u_mean.to(gp.u_mean.dtype))
+            gp.u_tril_vec.copy_(vec.to(gp.u_tril_vec.dtype))
+        n_clamped = int(round(clamped.double().sum().item()))
+    return SiteFit(torch.stack(trace), len(trace) - 1, n_rejected, n_clamped, pr.route)

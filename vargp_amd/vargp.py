@@ -19,7 +19,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import collapsed, fused, gp_utils, init, noise, ops
+from . import collapsed, fused, gp_utils, init, noise, ops, sites
 from .gp_utils import vec2tril, mat2trilvec, cholesky, rev_cholesky, gp_cond, block_joint, linear_marginal_diag
 from .kernels import RBFKernel, DeepRBFKernel, MaternKernel, native_code
 from .likelihoods import (BernoulliLikelihood, GaussianLikelihood, MulticlassSoftmax, PoissonLikelihood, StudentTLikelihood,
@@ -65,7 +65,8 @@ def _hand_over_hyper_prior(prev_params):
 
 _Z_INITS = ('greedy', 'kmeans', 'random')                  # create_clf / create_reg (z_init=)
 _LENGTHSCALE_INITS = ('default', 'median')        # (lengthscale_init=)
-_Q_INITS = ('default', 'optimal', 'collapsed')                # create_reg (q_init=)
+_Q_INITS = ('default', 'optimal', 'collapsed', 'newton')      # create_reg (q_init=)
+_CLF_Q_INITS = ('default', 'newton')                          # create_clf (q_init=)
 
 
 def _check_init_names(who, z_init, lengthscale_init):
@@ -599,6 +600,19 @@ class VARGP(nn.Module):
         the minimiser of kl_u + nll as VARGP.loss reports them; kl_u itself is the KL term of the bound."""
         return collapsed.fit_q_(self, x, y, weights=weights, temper=temper)
 
+    def fit_q_newton_(self, x, y, n_iters=20, damping=1.0, tol=1e-6, weights=None, route=None, start='current'):
+        """fit_q_'s counterpart for the Bernoulli, Poisson and Student-t likelihoods (sites.fit_q_newton_, not in the reference):
+        full-batch natural-gradient (conjugate-computation) iterations on q(u) of this task at theta = kernel.log_mean, from the
+        current u_mean / u_tril_vec (start='prior': from q(u) = the prior, the robust start for Poisson), which are overwritten in
+        place under no_grad.  Each iteration replaces every likelihood term
+        by a Gaussian site and refits q(u) in closed form (Newton's method on the bound for the log-concave likelihoods): two
+        fused passes over x (N, D), K(z, x) never stored.  y as loss() takes it; weights None, (N,) or (C, N): per-point weights.
+        -> sites.SiteFit(bound (n_iters + 1, C) float64 on the host, non-decreasing; n_iters; n_rejected; n_clamped; route).
+        ValueError for MulticlassSoftmax (coupled outputs), GaussianLikelihood (use fit_q_), ep_var_mean=False and a damping
+        outside (0, 1].  Student-t: see the caveat in sites.py (n_clamped)."""
+        return sites.fit_q_newton_(self, x, y, n_iters=n_iters, damping=damping, tol=tol, weights=weights, route=route,
+                                   start=start)
+
     def collapsed_bound(self, x, y, weights=None, temper=1.0):
         """The bound fit_q_ returns -- the variational bound of x (N, D), y (N,) or (C, N) at the optimal q(u) of the current
         task -- as a (C,) float64 tensor on the autograd graph of z, kernel.log_mean and likelihood.obs_log_var
@@ -644,7 +658,7 @@ class VARGP(nn.Module):
     def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None,
                    ep_var_mean=True, map_est_hypers=False, dkl=False, kernel='rbf', native_kernel=False,
                    likelihood='softmax', link='probit', z_init='random', kmeans_iters=20, lengthscale_init='default',
-                   greedy_candidates=4096):
+                   greedy_candidates=4096, q_init='default', newton_iters=20):
         """Factory used by the experiment driver (vargp.py:200-243): inducing points at random data
         points per class, hyper-prior = previous task's hyper-posterior (popped from prev_params[-1],
         which is mutated like the reference does).  kernel: 'rbf' (the reference's), or 'matern12' / 'matern32' /
@@ -656,7 +670,16 @@ class VARGP(nn.Module):
         kmeans_iters Lloyd iterations on the current CUDA device) or 'greedy' (greedy conditional-variance selection among
         min(len(dataset), greedy_candidates) random data points per output under the model's own kernel, started from the
         previous tasks' inducing points when there are any: init.greedy_inducing; not with dkl).  lengthscale_init: 'default' (0.5, the reference's) or 'median'
-        (the median pair distance of the task's data, first task only; not with dkl, whose features are untrained)."""
+        (the median pair distance of the task's data, first task only; not with dkl, whose features are untrained).
+        q_init: 'default' (u_mean ~ N(0, 0.25), u_tril = the softplus identity, as the reference starts) or 'newton'
+        (likelihood='bernoulli' only): once the inducing points and the lengthscale stand, fit_q_newton_(n_iters=newton_iters,
+        start='prior')
+        on the whole data set on the current CUDA device; the model returns on the device the default route returns it on."""
+        if q_init not in _CLF_Q_INITS:
+            raise ValueError(f'create_clf: q_init must be one of {sorted(_CLF_Q_INITS)}, got {q_init!r}')
+        if q_init == 'newton' and likelihood != 'bernoulli':
+            raise ValueError(f"create_clf: q_init='newton' fits independent Gaussian sites, which likelihood={likelihood!r} does "
+                             "not have (its outputs are coupled); use likelihood='bernoulli'")
         lik = make_clf_likelihood(likelihood, n_f, link)
         _check_init_names('create_clf', z_init, lengthscale_init)
         if dkl and lengthscale_init == 'median':
@@ -704,13 +727,21 @@ class VARGP(nn.Module):
         _init_lengthscale(kern, dataset, lengthscale_init, first_task)
         if z_init == 'greedy':
             z = _greedy_inducing(x_all, cand, M, kern, prior_log_mean, prev_params)
-        return VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean,
-                     prev_params=prev_params)
+        gp = VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean,
+                   prev_params=prev_params)
+        if q_init == 'newton':
+            sites.check_supported(gp, 'create_clf(q_init="newton")')
+            home, dev = gp.z.device, torch.device('cuda', torch.cuda.current_device())
+            x = dataset[torch.arange(len(dataset))][0].to(device=dev, dtype=torch.float32)
+            y = torch.as_tensor(dataset.targets).to(device=dev, dtype=torch.int64)
+            gp.to(dev).fit_q_newton_(x, y, n_iters=newton_iters, start='prior')
+            gp.to(home)
+        return gp
 
     @staticmethod
     def create_reg(dataset, M=20, n_var_samples=3, likelihood='gaussian', df=4.0, prev_params=None, ep_var_mean=True,
                    map_est_hypers=False, kernel='rbf', native_kernel=False, z_init='random', kmeans_iters=20,
-                   lengthscale_init='default', greedy_candidates=4096, q_init='default', collapsed_steps=200):
+                   lengthscale_init='default', greedy_candidates=4096, q_init='default', collapsed_steps=200, newton_iters=20):
         """Regression / count factory, the counterpart of create_clf (not in the reference): dataset[i] -> (x, y), dataset.targets
         (N,) (one output) or (N, C); inducing points at M random data points per output; hyper-prior = the previous task's
         hyper-posterior (popped from prev_params[-1], which is mutated as in create_clf).  likelihood: 'gaussian'
@@ -722,13 +753,17 @@ class VARGP(nn.Module):
         device -- q(u) starts at its closed-form optimum and the trainer only has to move hyper-parameters and inducing points; the
         model returns on the device the default route returns it on.  'collapsed' (Gaussian likelihood, RBF / Matern kernel):
         fit_collapsed_(n_steps=collapsed_steps) instead -- inducing points, lengthscales and noise variance are first moved up
-        the collapsed bound (without the hyper-prior), then q(u) is fitted.
+        the collapsed bound (without the hyper-prior), then q(u) is fitted.  'newton' (likelihood 'poisson' or 'studentt'; the
+        Gaussian's own route is 'optimal'): fit_q_newton_(n_iters=newton_iters, start='prior') on the whole data set instead.
         None of likelihood, df, kernel and native_kernel is part of a checkpoint: give them again on reload.  A minibatch's
         targets go to loss() as (C, B) -- y.t() of a (B, C) batch -- or (B,)."""
         if q_init not in _Q_INITS:
             raise ValueError(f'create_reg: q_init must be one of {sorted(_Q_INITS)}, got {q_init!r}')
-        if q_init != 'default' and likelihood != 'gaussian':
+        if q_init in ('optimal', 'collapsed') and likelihood != 'gaussian':
             raise ValueError(f"create_reg: q_init={q_init!r} is the closed form of likelihood='gaussian', got {likelihood!r}")
+        if q_init == 'newton' and likelihood == 'gaussian':
+            raise ValueError("create_reg: q_init='newton' iterates Gaussian sites of a non-Gaussian likelihood ('poisson', "
+                             "'studentt'); likelihood='gaussian' has the closed form q_init='optimal'")
         if kernel not in _KERNEL_NU:
             raise ValueError(f'create_reg: kernel must be one of {sorted(_KERNEL_NU)}, got {kernel!r}')
         if native_kernel and kernel == 'rbf':
@@ -759,7 +794,8 @@ class VARGP(nn.Module):
             z = _greedy_inducing(x_all, cand, M, kern, prior_log_mean, prev_params)
         gp = VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean, prev_params=prev_params)
         if q_init != 'default':
-            check = collapsed.check_supported if q_init == 'optimal' else collapsed.check_differentiable
+            check = {'optimal': collapsed.check_supported, 'collapsed': collapsed.check_differentiable,
+                     'newton': sites.check_supported}[q_init]
             check(gp, f'create_reg(q_init="{q_init}")')
             home, dev = gp.z.device, torch.device('cuda', torch.cuda.current_device())
             x = dataset[torch.arange(len(dataset))][0]
@@ -767,6 +803,8 @@ class VARGP(nn.Module):
             x, y = x.to(device=dev, dtype=torch.float32), y.to(device=dev, dtype=torch.float32)
             if q_init == 'optimal':
                 gp.to(dev).fit_q_(x, y)
+            elif q_init == 'newton':
+                gp.to(dev).fit_q_newton_(x, y, n_iters=newton_iters, start='prior')
             else:
                 gp.to(dev).fit_collapsed_(x, y, n_steps=collapsed_steps)
             gp.to(home)
