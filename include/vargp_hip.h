@@ -324,6 +324,46 @@ int vargp_site_moments(const float* theta, const float* Z, const float* X, const
                        float* c, float* sums, int G, int Mt, int N, int D, int nu2, void* ws, size_t ws_bytes,
                        vargp_stream_t stream);
 
+/* The backward of the first sum of vargp_site_moments, value[g] = sum_n w ell = sums[g, 0], for theta, Z, alpha and Q (and the
+ * Student-t log_scale) in one fused pass over the data: the M-step of variational EM on the site bound (vargp_amd/sites.py:
+ * site_bound, fit_sites_).  X, y and w get no gradient.  Inputs as vargp_site_moments takes them, and gout [G], the upstream seed
+ * s_g of every output.  With Qs the symmetric part of Q[g], q_n = k_n^T Qs k_n, mu_n and var_n as above (evaluated by the same
+ * device functions as the forward: bitwise its values for a symmetric Q), (ell, dmu, dvar) the likelihood's value and TRUE signed
+ * derivatives (not lam2: dvar is not clamped at 0) and u_n = 1 if gamma^2 - q_n > 0, else 0 (the variance clamp passes no gradient):
+ *   gm_n = s_g w_n dmu_n,   gv_n = s_g w_n dvar_n u_n                                        gv [G, N] is WRITTEN
+ *   galpha[g] = sum_n gm_n k_n                                                                [G, Mt]
+ *   gQ[g]     = -sum_n gv_n k_n k_n^T  (symmetric) is NOT written: it is -Phi of vargp_gram_moments with w = gv
+ *   gK[:, n]  = gm_n alpha[g] - 2 gv_n Qs k_n,   V = gK o (-2 dk/dd2)  (as vargp_gram_moments_bwd defines it per kernel; 0 at a zero
+ *               distance for nu = 1/2); neither is ever stored
+ *   r = V 1, cn = V^T 1, P = V X, wl_d = exp(-2 theta_d)
+ *   gZ[g, i]  = -wl o (r_i z_i - P_i)                                                          [G, Mt, D]
+ *   gtheta[d] = wl_d sum_g [sum_i z_id (r_i z_id - 2 P_id) + sum_n cn_n x_nd^2]                 d < D
+ *   gtheta[D] = sum_g sum_n [2 gm_n mu_n + gv_n (2 gamma^2 - 4 q_n)]   (log gamma; COMPLETE here, nothing is left to the caller)
+ *   gls[g]    = s_g sum_n w_n d ell_n / d log_scale[g]   [G], Student-t only (what vargp_studentt_nll_bwd's gparam holds, sign
+ *               turned; gls may be NULL and is not written for the other kinds)
+ * A point of weight 0 is not evaluated and its column of K is masked: it adds exactly nothing to any output and gets gv = 0,
+ * whatever its row of X and its target hold (NaN included).
+ * A workgroup owns (g, a chunk of N, a group of at most 128 values of d; D <= 32: one group) and walks 64 columns at a time: all
+ * Mt rows of the 64 columns of K and of the weight -2 dk/dd2 live in LDS (Mt <= 256: 2 x 64 KB at the limit, VARGP_EINVAL above
+ * it); Qs K runs on the f32 MFMA with the accumulators of all Mt rows in registers, V overwrites the weight in place, and P += V X
+ * runs on the same MFMA.  Every group of d recomputes V.  The points are cut into vargp_site_bound_bwd_chunks(G, Mt, N, D) chunks --
+ * a function of the shapes alone: the forward's rule (at most 1024, at least 256 columns each, about 1024 workgroups over G x
+ * groups), capped so that the partials of r, galpha and P, chunks x G x ceil(Mt / 64) x 64 (D + 2) floats, stay below 64 MiB (one
+ * chunk is always allowed) -- each accumulated in fp32 (the per-point scalars of gtheta[D] and gls: fp64); a last launch adds the
+ * chunks in ascending order in fp64, forms gZ and gtheta there and rounds once.  No atomics: two calls on the same input are
+ * bitwise equal.  Nothing is read behind row N of X.
+ * Workspace: per-chunk partials only (the above, chunks x G x (D floats + 16 bytes), and padding), 8-byte aligned; it does not grow
+ * with N beyond the chunk count.  VARGP_EINVAL before any launch: a null pointer other than w (and log_scale / gls unless
+ * Student-t), a size < 1, Mt > 256, G > 65535, an unknown kind or nu2, ldy in (0, N), df <= 0 for Student-t, a short or misaligned
+ * workspace.  The two queries return 0 for a size < 1.
+ */
+size_t vargp_site_bound_bwd_workspace_bytes(int G, int Mt, int N, int D);
+int vargp_site_bound_bwd_chunks(int G, int Mt, int N, int D);
+int vargp_site_bound_bwd(const float* theta, const float* Z, const float* X, const float* alpha, const float* Q, const float* y,
+                         int64_t ldy, const float* w, int kind, const float* log_scale, float df, float lognorm, const float* gout,
+                         float* gZ, float* gtheta, float* galpha, float* gv, float* gls, int G, int Mt, int N, int D, int nu2,
+                         void* ws, size_t ws_bytes, vargp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * KL(N(mu_q, Lq Lq^T) || N(mu_p, Lp Lp^T)) from its triangular ingredients (reference:
  * torch.distributions kl_divergence(MVN, MVN) as called from var_gp/vargp.py:182-190):

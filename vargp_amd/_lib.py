@@ -116,6 +116,10 @@ _SIGNATURES = {
     'vargp_site_moments_chunks': (c_int, [c_int] * 4),
     'vargp_site_moments': (c_int, [_P] * 6 + [c_int64, _P, c_int, _P, c_float, c_float, _P, _P, _P] + [c_int] * 5
                            + [_P, c_size_t, _P]),
+    'vargp_site_bound_bwd_workspace_bytes': (c_size_t, [c_int] * 4),
+    'vargp_site_bound_bwd_chunks': (c_int, [c_int] * 4),
+    'vargp_site_bound_bwd': (c_int, [_P] * 6 + [c_int64, _P, c_int, _P, c_float, c_float] + [_P] * 6 + [c_int] * 5
+                             + [_P, c_size_t, _P]),
     'vargp_mvn_kl_fwd':(c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),
     'vargp_mvn_kl_bwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),
     'vargp_logdet_tril_fwd': (c_int, [_P, _P, c_int, c_int, _P]),

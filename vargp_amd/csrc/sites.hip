@@ -339,9 +339,566 @@ static int site_launch(const SiteArgs& a, const typename LIK::Args& la, int nu2,
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The backward of the pass's first sum, value_g = sum_n w_gn ell_gn, for theta, Z, alpha and (through gv) Q: the M-step of
+// variational EM on the site bound (sites.py: site_bound, fit_sites_).  With Qs = (Q + Q^T) / 2, q_n = k_n^T Qs k_n, the seed s_g
+// of output g and u_n = [gamma^2 - q_n > 0] (the variance clamp passes no gradient):
+//   gm_n = s_g w_n dmu_n,   gv_n = s_g w_n dvar_n u_n           (the TRUE signed dvar: not lam2)
+//   galpha_g = sum_n gm_n k_n;   gQ_g = -sum_n gv_n k_n k_n^T is the caller's (vargp_gram_moments with w = gv)
+//   gK[:, n] = gm_n alpha_g - 2 gv_n Qs k_n,   V = gK o (-2 dk/dd2)        (Mt x N, neither ever reaches global memory)
+//   r = V 1,  cn = V^T 1,  P = V X,  q_d = sum_n cn_n x_nd^2
+//   gZ_i = -wl o (r_i z_i - P_i),   gtheta_d = wl_d sum_g [sum_i z_id (r_i z_id - 2 P_id) + q_d]   (d < D)
+//   gtheta_D = sum_g sum_n [2 gm_n mu_n + gv_n (2 gamma^2 - 4 q_n)],   gls_g = s_g sum_n w_n d ell_n / d log_scale_g.
+// A workgroup owns (output g, chunk of N, group of 64 NP values of d) and walks its chunk 64 columns at a time.  Per step: the K
+// block of ALL Mt rows is built in LDS exactly as the forward builds it, and beside it a second block of the same shape with the
+// weight -2 dk/dd2; mu by the forward's sums; every 64 x 64 tile of Qs (staged as [k][row] in the area the K build staged its
+// operands in) times panel j of K on the MFMA, the accumulators of ALL panels of Qs K staying in registers (16 nt per lane), and
+// q_n reduced from them in the forward's order -- mu and var are bitwise the forward's for a symmetric Q.  One wave evaluates
+// LIK::element<true> for the 64 points and leaves gm and gv; V overwrites the weight block in place from the accumulators.
+// galpha, r and cn are plain sums over the blocks; P += V X on the same MFMA, the step's 64 rows of X staged 64 values of d at a
+// time (waves as 2 row halves x 2 halves of the 64 values, nt NP accumulator tiles per wave for the whole chunk); q rides on the
+// staged X.  D > 64 NP: the grid is split over groups of d and every group recomputes V (group 0 alone writes gv, galpha, r and
+// the per-point scalars).
+// A column behind the end of the chunk OR of weight 0 is masked everywhere: its K, weight and staged X entries are written as
+// zeros whatever X and the target hold there (NaN included), so it adds exactly nothing.  No atomics; a last launch adds the
+// chunks' partials in ascending chunk order in fp64, forms gZ and gtheta there and rounds once.  The chunking (site_bwd_plan)
+// depends on the shapes alone: the forward's rule over G x groups workgroups, capped so that the partials of P stay below
+// kSbBudget bytes.
+constexpr int kSbNPMax = 2;                     // tiles of 64 values of d per group (GEMM form; the direct form has D <= 32: one)
+constexpr size_t kSbBudget = 64u << 20;         // bytes of the per-chunk partials of r, galpha and P, at most (one chunk always fits)
+constexpr int kSbStage = kSiStage > kMoT * kMoLD ? kSiStage : kMoT * kMoLD;
+
+// floats of LDS for nt panels: the K and weight / V blocks, the shared staging area (operands of K | a tile of Qs | X of the
+// step), alpha, exp(-2 theta), norms, gm, gv, cn, the column mask, two reduction pads
+static constexpr size_t site_bwd_lds_floats(int nt) {
+  return (size_t)2 * kMoT * (nt * kMoT + 1) + kSbStage + nt * kMoT + kRbfDirectD + 2 * kMoT + 4 * kMoT + 4 * kMoT + 4 * kMoT;
+}
+static_assert(site_bwd_lds_floats(kSiMaxNt) * sizeof(float) <= 160 * 1024, "the K and V blocks of kSiMaxMt rows must fit the LDS");
+
+struct SiteBwdPlan {
+  int nt, nch, np, ngrp;     // panels, chunks, tiles of d per group, groups of d
+  int64_t len;               // columns per chunk (a multiple of kMoT)
+  double* ps;                // partials of (gtheta_D, gls) [G][nch][2]
+  float *pr, *pa, *pq, *pp;  // partials r [G][nch][nt * 64], galpha alike, q [G][nch][D], P [G][nch][nt * 64][D]
+  size_t bytes;
+};
+
+static SiteBwdPlan site_bwd_plan(void* ws, int G, int Mt, int N, int D) {
+  SiteBwdPlan o{};
+  o.nt = cdiv(Mt, kMoT);
+  o.np = D <= kRbfDirectD ? 1 : kSbNPMax;
+  o.ngrp = cdiv(D, 64 * o.np);
+  int64_t want = cdiv(kMoTargetWg, (int64_t)G * o.ngrp);
+  const int64_t most = cdiv(N, kMoMinChunk);
+  const int64_t per = (int64_t)G * o.nt * kMoT * (D + 2) * (int64_t)sizeof(float);
+  const int64_t fit = (int64_t)kSbBudget / per;
+  want = want < most ? want : most;
+  want = want < fit ? want : fit;
+  want = want < 1 ? 1 : (want > kMoMaxChunks ? kMoMaxChunks : want);
+  o.len = round_up(cdiv(N, want), kMoT);
+  o.nch = cdiv(N, o.len);
+  char* p = reinterpret_cast<char*>(ws);
+  auto take = [&](int64_t bytes) { char* q = p; p += round_up(bytes, 256); return q; };
+  const int64_t parts = (int64_t)G * o.nch, f = sizeof(float);
+  o.ps = reinterpret_cast<double*>(take(parts * 2 * (int64_t)sizeof(double)));
+  o.pr = reinterpret_cast<float*>(take(parts * o.nt * kMoT * f));
+  o.pa = reinterpret_cast<float*>(take(parts * o.nt * kMoT * f));
+  o.pq = reinterpret_cast<float*>(take(parts * D * f));
+  o.pp = reinterpret_cast<float*>(take(parts * o.nt * kMoT * D * f));
+  o.bytes = (size_t)(p - reinterpret_cast<char*>(ws));
+  return o;
+}
+
+struct SiteBwdArgs {
+  const float *theta, *Z, *X, *alpha, *Q, *w, *gout;
+  float *gZ, *gtheta, *galpha, *gv, *gls;
+  SiteBwdPlan p;
+  int G, Mt, N, D;
+};
+
+// -2 dk/dd2 of an epilogue: the RBF's is K itself, the Matern's matern_w
+template <class EPI> struct SiteBwdW;
+template <> struct SiteBwdW<EpiRbf> {
+  static __device__ __forceinline__ float w(float g2, float d2) { return EpiRbf::off(g2, d2); }
+};
+template <int NU2> struct SiteBwdW<EpiMatern<NU2>> {
+  static __device__ __forceinline__ float w(float g2, float d2) { return matern_w<NU2>(g2, d2); }
+};
+
+// grid (nch * ngrp, G): blockIdx.x = chunk * ngrp + group
+template <class LIK, class EPI, bool DIRECT, int NP>
+__global__ __launch_bounds__(256) void site_bwd_kernel(const SiteBwdArgs a, const typename LIK::Args la) {
+  using real = typename LIK::real;
+  constexpr int T = kMoT, LD = kMoLD, BK = kMoBK;
+  extern __shared__ __attribute__((aligned(16))) float sb_lds[];
+  const int Mt = a.Mt, D = a.D, nt = a.p.nt, MtP = nt * T, LDK = MtP + 1, ngrp = a.p.ngrp;
+  float* Ks = sb_lds;                  // the K block: [n][m], m over all nt panels
+  float* Vs = Ks + T * LDK;            // the weight block, then V: [n][m]
+  float* stage = Vs + T * LDK;         // DIRECT: Z_j, X rows; else the slabs of a_j, b: [k][r]
+  float* Ss = stage;                   // then a tile of Qs: [k = row of panel j][row of panel i]; then X of the step: [n][d]
+  float* al = stage + kSbStage;        // alpha, zeros behind Mt
+  float* wl = al + MtP;                // DIRECT: exp(-2 theta_d)
+  float* nrm = wl + kRbfDirectD;       // !DIRECT: |a_j|^2, |b|^2
+  float* gms = nrm + 2 * T;            // gm of the step's columns (0 where masked)
+  float* gvs = gms + T;                // gv
+  float* cn = gvs + T;                 // cn
+  float* cok = cn + T;                 // 1 for a live column, 0 for a masked one
+  float* cred = cok + T;               // [4][T]
+  float* qred = cred + 4 * T;          // [4][32]: the waves' shares of k^T Qs k
+
+  const int grp = blockIdx.x % ngrp, chunk = blockIdx.x / ngrp;
+  const int dg0 = grp * 64 * NP;
+  const int64_t g = blockIdx.y;
+  const int64_t cbeg = (int64_t)chunk * a.p.len;
+  const int64_t cend = cbeg + a.p.len < a.N ? cbeg + a.p.len : a.N;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32, l31 = lane & 31, h = lane >> 5;
+  const int pr = (wave & 1) * 32, pd = (wave >> 1) * 32;
+  const float g2 = expf(2.f * a.theta[D]);
+  const float sg = a.gout[g];
+  const float* __restrict__ Zg = a.Z + g * (int64_t)Mt * D;
+  const float* __restrict__ X = a.X;
+  const float* __restrict__ Qg = a.Q + g * (int64_t)Mt * Mt;
+  const float* __restrict__ wg = a.w ? a.w + g * (int64_t)a.N : nullptr;
+  const int Dl = D | 1;
+  const typename LIK::Cls cls = LIK::cls(la, (int)g);
+
+  si_f32x16 pacc[NP][kSiMaxNt];
+#pragma unroll
+  for (int t = 0; t < NP; ++t)
+#pragma unroll
+    for (int p = 0; p < kSiMaxNt; ++p)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) pacc[t][p][r] = 0.f;
+  float qacc[NP], aacc[kSiMaxNt], racc[kSiMaxNt];
+#pragma unroll
+  for (int t = 0; t < NP; ++t) qacc[t] = 0.f;
+#pragma unroll
+  for (int p = 0; p < kSiMaxNt; ++p) aacc[p] = racc[p] = 0.f;
+  double s_th = 0.0, s_ls = 0.0;
+
+  for (int e = tid; e < MtP; e += 256) al[e] = e < Mt ? a.alpha[g * Mt + e] : 0.f;
+  if constexpr (DIRECT) {
+    if (tid < D) wl[tid] = expf(-2.f * a.theta[tid]);
+  }
+
+  for (int64_t n0 = cbeg; n0 < cend; n0 += T) {
+    if (tid < T) {
+      const int64_t n = n0 + tid;
+      cok[tid] = (n < cend && (!wg || wg[n] != 0.f)) ? 1.f : 0.f;
+    }
+    __syncthreads();
+    // ---- the K block and its weight: rows behind Mt and masked columns are zeros
+    if constexpr (DIRECT) {
+      float* Xs = stage + T * kMoDl;
+      for (int e = tid; e < T * D; e += 256) {
+        const int r = e / D, d = e - r * D;
+        Xs[r * Dl + d] = cok[r] != 0.f ? X[(n0 + r) * D + d] : 0.f;
+      }
+    }
+    for (int tj = 0; tj < nt; ++tj) {
+      const int j0 = tj * T;
+      if constexpr (DIRECT) {
+        const float* Xs = stage + T * kMoDl;
+        for (int e = tid; e < T * D; e += 256) {
+          const int r = e / D, d = e - r * D;
+          stage[r * Dl + d] = j0 + r < Mt ? Zg[(int64_t)(j0 + r) * D + d] : 0.f;
+        }
+        __syncthreads();
+        const float* zr = stage + lane * Dl;
+        const float* xr = Xs + 16 * wave * Dl;
+        float d2[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) d2[q] = 0.f;
+        for (int d = 0; d < D; ++d) {
+          const float zv = zr[d], wv = wl[d];
+#pragma unroll
+          for (int q = 0; q < 16; ++q) { const float v = zv - xr[q * Dl + d]; d2[q] = fmaf(wv * v, v, d2[q]); }
+        }
+        const bool rok = j0 + lane < Mt;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const bool ok = rok && cok[16 * wave + q] != 0.f;
+          Ks[(16 * wave + q) * LDK + j0 + lane] = ok ? EPI::off(g2, d2[q]) : 0.f;
+          Vs[(16 * wave + q) * LDK + j0 + lane] = ok ? SiteBwdW<EPI>::w(g2, d2[q]) : 0.f;
+        }
+      } else {
+        float* Aj = stage;
+        float* Bs = stage + BK * LD;
+        si_f32x16 dj;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dj[r] = 0.f;
+        float nr = 0.f;
+        const int k = tid & 31;
+        for (int k0 = 0; k0 < D; k0 += BK) {
+          const bool kok = k0 + k < D;
+          const float sq = kok ? expf(-a.theta[k0 + k]) : 0.f;           // 1 / lengthscale
+#pragma unroll
+          for (int r = tid >> 5; r < T; r += 8) {
+            Aj[k * LD + r] = (kok && j0 + r < Mt) ? sq * Zg[(int64_t)(j0 + r) * D + k0 + k] : 0.f;
+            Bs[k * LD + r] = (kok && cok[r] != 0.f) ? sq * X[(n0 + r) * D + k0 + k] : 0.f;
+          }
+          __syncthreads();
+#pragma unroll
+          for (int kk = 0; kk < BK; kk += 2)
+            dj = __builtin_amdgcn_mfma_f32_32x32x2f32(Aj[(kk + h) * LD + wr + l31], Bs[(kk + h) * LD + wc + l31], dj, 0, 0, 0);
+          if (wave < 2) {
+            const float* src = stage + wave * BK * LD + lane;
+#pragma unroll
+            for (int kk = 0; kk < BK; ++kk) { const float v = src[kk * LD]; nr = fmaf(v, v, nr); }
+          }
+          __syncthreads();
+        }
+        if (wave < 2) nrm[wave * T + lane] = nr;
+        __syncthreads();
+        const int col = wc + l31;
+        const bool cl = cok[col] != 0.f;
+        const float nb = nrm[T + col];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = wr + (r & 3) + 8 * (r >> 2) + 4 * h;
+          const bool ok = cl && j0 + row < Mt;
+          const float d2 = nrm[row] + nb - 2.f * dj[r];
+          Ks[col * LDK + j0 + row] = ok ? EPI::off(g2, d2) : 0.f;
+          Vs[col * LDK + j0 + row] = ok ? SiteBwdW<EPI>::w(g2, d2) : 0.f;
+        }
+      }
+      __syncthreads();
+    }
+
+    // ---- mu_n = alpha . k_n: the forward's sums
+    {
+      const float* kr = Ks + lane * LDK;
+      float s = 0.f;
+      for (int m = wave * (MtP >> 2); m < (wave + 1) * (MtP >> 2); ++m) s = fmaf(kr[m], al[m], s);
+      cred[wave * T + lane] = s;
+    }
+
+    // ---- Qs K: the accumulators of every panel stay in registers; k_n^T Qs k_n from them in the forward's order
+    si_f32x16 qk[kSiMaxNt];
+    float qv = 0.f;
+#pragma unroll
+    for (int ti = 0; ti < kSiMaxNt; ++ti) {
+      if (ti < nt) {
+        const int i0 = ti * T;
+        si_f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int tj = 0; tj < nt; ++tj) {
+          const int j0 = tj * T;
+          for (int e = tid; e < T * T; e += 256) {
+            const int k = e >> 6, r = e & 63;
+            Ss[k * LD + r] = (i0 + r < Mt && j0 + k < Mt)
+                                 ? 0.5f * (Qg[(int64_t)(j0 + k) * Mt + i0 + r] + Qg[(int64_t)(i0 + r) * Mt + j0 + k])
+                                 : 0.f;
+          }
+          __syncthreads();
+#pragma unroll
+          for (int kk = 0; kk < T; kk += 2)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Ss[(kk + h) * LD + wr + l31], Ks[(wc + l31) * LDK + j0 + kk + h], acc, 0, 0, 0);
+          __syncthreads();
+        }
+        const float* kc = Ks + (wc + l31) * LDK + i0 + wr + 4 * h;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) qv = fmaf(acc[r], kc[(r & 3) + 8 * (r >> 2)], qv);
+        qk[ti] = acc;
+      }
+    }
+    qv += __shfl_xor(qv, 32, 64);
+    if (h == 0) qred[wave * 32 + l31] = qv;
+    __syncthreads();
+
+    // ---- the likelihood of the step's points: one wave, a point per lane
+    if (tid < T) {
+      const int64_t n = n0 + tid;
+      const float mu = (cred[tid] + cred[T + tid]) + (cred[2 * T + tid] + cred[3 * T + tid]);
+      const float quad = qred[(tid >> 5) * 32 + (tid & 31)] + qred[((tid >> 5) + 2) * 32 + (tid & 31)];
+      const float var = fmaxf(g2 - quad, 0.f);
+      float gm = 0.f, gv = 0.f;
+      if (cok[tid] != 0.f) {
+        const float wv = wg ? wg[n] : 1.f;
+        real dmu = 0, dvar = 0, dpar = 0;
+        LIK::template element<true>(cls, (real)mu, (real)var, LIK::template target<real>(la, (int)g, (size_t)n), dmu, dvar, dpar);
+        gm = sg * (wv * (float)dmu);
+        gv = g2 - quad > 0.f ? sg * (wv * (float)dvar) : 0.f;
+        if (grp == 0) {
+          s_th += 2.0 * (double)gm * (double)mu + (double)gv * (2.0 * (double)g2 - 4.0 * (double)quad);
+          s_ls += (double)sg * (double)wv * (double)dpar;
+        }
+      }
+      if (grp == 0 && n < cend) a.gv[g * (int64_t)a.N + n] = gv;
+      gms[tid] = gm;
+      gvs[tid] = gv;
+    }
+    __syncthreads();
+
+    // ---- V = (gm alpha - 2 gv Qs K) o weight, in place; a masked column has weight 0
+    {
+      const int col = wc + l31;
+      const float gmc = gms[col], gvc = -2.f * gvs[col];
+#pragma unroll
+      for (int p = 0; p < kSiMaxNt; ++p) {
+        if (p < nt) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int row = p * T + wr + (r & 3) + 8 * (r >> 2) + 4 * h;
+            Vs[col * LDK + row] *= fmaf(gvc, qk[p][r], gmc * al[row]);
+          }
+        }
+      }
+    }
+    __syncthreads();
+
+    // ---- galpha += K gm, r += V 1 (lanes = rows of a panel, every wave 16 of the columns); cn = V^T 1
+#pragma unroll
+    for (int p = 0; p < kSiMaxNt; ++p) {
+      if (p < nt) {
+        float s = 0.f, t = 0.f;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          s = fmaf(Ks[(16 * wave + q) * LDK + p * T + lane], gms[16 * wave + q], s);
+          t += Vs[(16 * wave + q) * LDK + p * T + lane];
+        }
+        aacc[p] += s;
+        racc[p] += t;
+      }
+    }
+    {
+      const int n = tid >> 2, qd = tid & 3;       // four threads per column, a quarter of the rows each
+      const float* vr = Vs + n * LDK;
+      float t = 0.f;
+      for (int m = qd * (MtP >> 2); m < (qd + 1) * (MtP >> 2); ++m) t += vr[m];
+      cred[qd * T + n] = t;
+    }
+    __syncthreads();
+    if (tid < T) cn[tid] = (cred[tid] + cred[T + tid]) + (cred[2 * T + tid] + cred[3 * T + tid]);
+
+    // ---- P += V X, 64 values of d at a time; waves as (row half, half of the 64 values)
+#pragma unroll
+    for (int t = 0; t < NP; ++t) {
+      const int c0 = dg0 + t * 64;
+      if (c0 < D) {
+        for (int e = tid; e < T * T; e += 256) {
+          const int n = e >> 6, c = e & 63;
+          Ss[n * LD + c] = (cok[n] != 0.f && c0 + c < D) ? X[(n0 + n) * D + c0 + c] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int p = 0; p < kSiMaxNt; ++p) {
+          if (p < nt) {
+#pragma unroll
+            for (int kk = 0; kk < T; kk += 2)
+              pacc[t][p] = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[(kk + h) * LDK + p * T + pr + l31], Ss[(kk + h) * LD + pd + l31],
+                                                                pacc[t][p], 0, 0, 0);
+          }
+        }
+        {
+          float s = 0.f;
+#pragma unroll
+          for (int q = 0; q < 16; ++q) { const float xv = Ss[(16 * wave + q) * LD + lane]; s = fmaf(cn[16 * wave + q] * xv, xv, s); }
+          qacc[t] += s;
+        }
+        __syncthreads();
+      }
+    }
+    __syncthreads();
+  }
+
+  const int64_t part = g * a.p.nch + chunk;
+#pragma unroll
+  for (int t = 0; t < NP; ++t) {
+    const int d = dg0 + t * 64 + pd + l31;
+    if (d < D) {
+#pragma unroll
+      for (int p = 0; p < kSiMaxNt; ++p) {
+        if (p < nt) {
+          float* out = a.p.pp + (part * MtP + p * T) * (int64_t)D;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) out[(int64_t)(pr + (r & 3) + 8 * (r >> 2) + 4 * h) * D + d] = pacc[t][p][r];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < NP; ++t) {
+    __syncthreads();
+    cred[wave * T + lane] = qacc[t];
+    __syncthreads();
+    const int d = dg0 + t * 64 + tid;
+    if (tid < T && d < D) a.p.pq[part * D + d] = (cred[tid] + cred[T + tid]) + (cred[2 * T + tid] + cred[3 * T + tid]);
+  }
+  if (grp != 0) return;
+#pragma unroll
+  for (int p = 0; p < kSiMaxNt; ++p) {
+    if (p < nt) {
+      __syncthreads();
+      cred[wave * T + lane] = aacc[p];
+      qred[wave * T + lane] = racc[p];
+      __syncthreads();
+      if (tid < T) {
+        a.p.pa[(part * nt + p) * T + tid] = (cred[tid] + cred[T + tid]) + (cred[2 * T + tid] + cred[3 * T + tid]);
+        a.p.pr[(part * nt + p) * T + tid] = (qred[tid] + qred[T + tid]) + (qred[2 * T + tid] + qred[3 * T + tid]);
+      }
+    }
+  }
+  if (wave == 0) {
+    s_th = wave_sum(s_th);
+    s_ls = wave_sum(s_ls);
+    if (lane == 0) { a.p.ps[part * 2] = s_th; a.p.ps[part * 2 + 1] = s_ls; }
+  }
+}
+
+// The chunks' partials in ascending chunk order in fp64, then the outputs.  grid (cdiv(G * Mt * D, 256) + D + cdiv(G * Mt, 256) +
+// 1): 256 entries of gZ | one value of d of gtheta (every thread a strided share of the (g, row) pairs and of the partials of q,
+// then a fixed tree) | 256 entries of galpha | gtheta_D (the same tree) and gls
+__global__ __launch_bounds__(256) void site_bwd_reduce_kernel(const SiteBwdArgs a) {
+  constexpr int T = kMoT;
+  __shared__ double red[256];
+  const int Mt = a.Mt, D = a.D, MtP = a.p.nt * T, nch = a.p.nch, tid = threadIdx.x;
+  const int64_t total = (int64_t)a.G * Mt * D, rows = (int64_t)a.G * Mt;
+  const int64_t nz = (total + 255) / 256, na = (rows + 255) / 256;
+  const int64_t b = blockIdx.x;
+  auto rp = [&](int64_t g, int m, int d, double& r, double& P) {
+    const int64_t at = g * nch * MtP + m;
+    r = 0.0; P = 0.0;
+    for (int q = 0; q < nch; ++q) { r += (double)a.p.pr[at + (int64_t)q * MtP]; P += (double)a.p.pp[(at + (int64_t)q * MtP) * D + d]; }
+  };
+  auto tree = [&](double s) {
+    red[tid] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (tid < o) red[tid] += red[tid + o];
+      __syncthreads();
+    }
+    return red[0];
+  };
+  if (b < nz) {
+    const int64_t e = b * 256 + tid;
+    if (e >= total) return;
+    const int d = (int)(e % D);
+    const int64_t gm = e / D;
+    double r, P;
+    rp(gm / Mt, (int)(gm % Mt), d, r, P);
+    a.gZ[e] = (float)(-exp(-2.0 * (double)a.theta[d]) * (r * (double)a.Z[e] - P));
+  } else if (b < nz + D) {
+    const int d = (int)(b - nz);
+    double s = 0.0;
+    for (int64_t gm = tid; gm < rows; gm += 256) {
+      double r, P;
+      rp(gm / Mt, (int)(gm % Mt), d, r, P);
+      const double z = (double)a.Z[gm * D + d];
+      s += z * (r * z - 2.0 * P);
+    }
+    for (int64_t e = tid; e < (int64_t)a.G * nch; e += 256) s += (double)a.p.pq[e * D + d];
+    s = tree(s);
+    if (tid == 0) a.gtheta[d] = (float)(exp(-2.0 * (double)a.theta[d]) * s);
+  } else if (b < nz + D + na) {
+    const int64_t gm = (b - nz - D) * 256 + tid;
+    if (gm >= rows) return;
+    const float* p = a.p.pa + (gm / Mt) * nch * MtP + gm % Mt;
+    double s = 0.0;
+    for (int q = 0; q < nch; ++q) s += (double)p[(int64_t)q * MtP];
+    a.galpha[gm] = (float)s;
+  } else {
+    double s = 0.0;
+    for (int64_t e = tid; e < (int64_t)a.G * nch; e += 256) s += a.p.ps[2 * e];
+    s = tree(s);
+    if (tid == 0) a.gtheta[D] = (float)s;
+    if (a.gls) {
+      for (int64_t g = tid; g < a.G; g += 256) {
+        double t = 0.0;
+        for (int q = 0; q < nch; ++q) t += a.p.ps[2 * (g * nch + q) + 1];
+        a.gls[g] = (float)t;
+      }
+    }
+  }
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize is per device and per kernel: one mask per instantiation
+template <class LIK, class EPI, bool DIRECT, int NP>
+static int site_bwd_launch_form(const SiteBwdArgs& a, const typename LIK::Args& la, hipStream_t st) {
+  static std::atomic<unsigned> attr_mask[2] = {};
+  const size_t lds = site_bwd_lds_floats(kSiMaxNt) * sizeof(float);
+  int dev = 0;
+  VARGP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "site_bound_bwd: hipGetDevice failed");
+  if (!((attr_mask[dev >> 5].load(std::memory_order_acquire) >> (dev & 31)) & 1u)) {
+    VARGP_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(site_bwd_kernel<LIK, EPI, DIRECT, NP>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
+                  "site_bound_bwd: cannot reserve %zu bytes of LDS", lds);
+    attr_mask[dev >> 5].fetch_or(1u << (dev & 31), std::memory_order_release);
+  }
+  hipLaunchKernelGGL((site_bwd_kernel<LIK, EPI, DIRECT, NP>), dim3(a.p.nch * a.p.ngrp, a.G), dim3(256),
+                     site_bwd_lds_floats(a.p.nt) * sizeof(float), st, a, la);
+  return VARGP_OK;
+}
+
+template <class LIK, class EPI>
+static int site_bwd_launch_epi(const SiteBwdArgs& a, const typename LIK::Args& la, hipStream_t st) {
+  return a.D <= kRbfDirectD ? site_bwd_launch_form<LIK, EPI, true, 1>(a, la, st)
+                            : site_bwd_launch_form<LIK, EPI, false, kSbNPMax>(a, la, st);
+}
+
+template <class LIK>
+static int site_bwd_launch(const SiteBwdArgs& a, const typename LIK::Args& la, int nu2, hipStream_t st) {
+  switch (nu2) {
+    case 0: return site_bwd_launch_epi<LIK, EpiRbf>(a, la, st);
+    case 1: return site_bwd_launch_epi<LIK, EpiMatern<1>>(a, la, st);
+    case 3: return site_bwd_launch_epi<LIK, EpiMatern<3>>(a, la, st);
+    default: return site_bwd_launch_epi<LIK, EpiMatern<5>>(a, la, st);
+  }
+}
+
 }  // namespace vargp
 
 using namespace vargp;
+
+extern "C" int vargp_site_bound_bwd_chunks(int G, int Mt, int N, int D) {
+  if (G <= 0 || Mt <= 0 || N <= 0 || D <= 0) return 0;
+  return site_bwd_plan(nullptr, G, Mt, N, D).nch;
+}
+
+extern "C" size_t vargp_site_bound_bwd_workspace_bytes(int G, int Mt, int N, int D) {
+  if (G <= 0 || Mt <= 0 || N <= 0 || D <= 0) return 0;
+  return site_bwd_plan(nullptr, G, Mt, N, D).bytes + 256;
+}
+
+extern "C" int vargp_site_bound_bwd(const float* theta, const float* Z, const float* X, const float* alpha, const float* Q,
+                                    const float* y, int64_t ldy, const float* w, int kind, const float* log_scale, float df,
+                                    float lognorm, const float* gout, float* gZ, float* gtheta, float* galpha, float* gv, float* gls,
+                                    int G, int Mt, int N, int D, int nu2, void* ws, size_t ws_bytes, vargp_stream_t stream) {
+  VARGP_REQUIRE(theta && Z && X && alpha && Q && y && gout && gZ && gtheta && galpha && gv && ws, "site_bound_bwd: null pointer");
+  VARGP_REQUIRE(G > 0 && Mt > 0 && N > 0 && D > 0, "site_bound_bwd: bad dims");
+  VARGP_REQUIRE(kind >= VARGP_SITE_BERNOULLI_PROBIT && kind <= VARGP_SITE_STUDENTT,
+                "site_bound_bwd: kind = %d (0: Bernoulli probit, 1: Bernoulli logit, 2: Poisson, 3: Student-t)", kind);
+  VARGP_REQUIRE(nu2 == 0 || nu2 == 1 || nu2 == 3 || nu2 == 5, "site_bound_bwd: nu2 = %d (0: RBF; 1, 3, 5: Matern)", nu2);
+  VARGP_REQUIRE(G <= 65535, "site_bound_bwd: G = %d (at most 65535)", G);
+  VARGP_REQUIRE(Mt <= kSiMaxMt, "site_bound_bwd: Mt = %d (at most %d: the K block of all rows lives in LDS)", Mt, kSiMaxMt);
+  VARGP_REQUIRE(ldy == 0 || ldy >= N, "site_bound_bwd: ldy must be 0 or >= N");
+  VARGP_REQUIRE(kind != VARGP_SITE_STUDENTT || (log_scale && gls && df > 0.f),
+                "site_bound_bwd: Student-t needs log_scale, gls and df > 0");
+  VARGP_REQUIRE(reinterpret_cast<uintptr_t>(ws) % sizeof(double) == 0, "site_bound_bwd: ws must be 8-byte aligned");
+  VARGP_REQUIRE(ws_bytes >= vargp_site_bound_bwd_workspace_bytes(G, Mt, N, D), "site_bound_bwd: workspace too small");
+  SiteBwdArgs a{};
+  a.theta = theta; a.Z = Z; a.X = X; a.alpha = alpha; a.Q = Q; a.w = w; a.gout = gout;
+  a.gZ = gZ; a.gtheta = gtheta; a.galpha = galpha; a.gv = gv; a.gls = kind == VARGP_SITE_STUDENTT ? gls : nullptr;
+  a.p = site_bwd_plan(ws, G, Mt, N, D);
+  a.G = G; a.Mt = Mt; a.N = N; a.D = D;
+  const int64_t nred = cdiv((int64_t)G * Mt * D, 256) + D + cdiv((int64_t)G * Mt, 256) + 1;
+  VARGP_REQUIRE((int64_t)a.p.nch * a.p.ngrp < (1ll << 31) && nred < (1ll << 31),
+                "site_bound_bwd: G = %d, Mt = %d, D = %d need too many workgroups", G, Mt, D);
+  hipStream_t st = as_stream(stream);
+  ProfScope whole("site_bound_bwd", st);
+  int rc;
+  switch (kind) {
+    case VARGP_SITE_BERNOULLI_PROBIT: rc = site_bwd_launch<Bernoulli<LinkProbit>>(a, {y, ldy, nullptr}, nu2, st); break;
+    case VARGP_SITE_BERNOULLI_LOGIT: rc = site_bwd_launch<Bernoulli<LinkLogit>>(a, {y, ldy, nullptr}, nu2, st); break;
+    case VARGP_SITE_POISSON: rc = site_bwd_launch<Poisson>(a, {{y, ldy}}, nu2, st); break;
+    default: rc = site_bwd_launch<StudentT>(a, {{y, ldy}, log_scale, df, lognorm}, nu2, st); break;
+  }
+  if (rc != VARGP_OK) return rc;
+  hipLaunchKernelGGL(site_bwd_reduce_kernel, dim3((unsigned)nred), dim3(256), 0, st, a);
+  return check_launch("site_bound_bwd");
+}
 
 extern "C" int vargp_site_moments_chunks(int G, int Mt, int N, int D) {
   if (G <= 0 || Mt <= 0 || N <= 0 || D <= 0) return 0;

@@ -795,6 +795,78 @@ def site_moments(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0):
     return lam2, c, sums
 
 
+def site_bound_bwd_chunks(G, Mt, N, D):
+    """The number of chunks ops.site_bound_bwd cuts N points into for this shape; the shapes alone decide it."""
+    return int(lib().vargp_site_bound_bwd_chunks(int(G), int(Mt), int(N), int(D)))
+
+
+def site_bound_bwd(theta, Z, X, alpha, Q, y, w, kind, extra, gout, nu2=0):
+    """The fused backward of site_moments' sums[:, 0] (csrc/sites.hip, vargp_site_bound_bwd); operands as site_moments takes them
+    and gout (G,), the seed of every output.  -> (gZ (G, Mt, D), gtheta (D + 1,), complete; galpha (G, Mt); gv (G, N) = seed x w x
+    the TRUE d ell / d var, 0 where the variance is clamped: gQ = -gram_moments(w=gv).Phi; gls (G,) for Student-t, else None).
+    K(Z, X) and its gradient are never stored; bitwise reproducible; a point of weight 0 adds exactly nothing."""
+    require_device(theta, Z, X, alpha, Q, y, w, gout)
+    code, log_scale, df, lognorm = site_kind(kind, extra)
+    det = lambda t: t.detach().contiguous()
+    theta, Z, X, alpha, Q, gout = det(theta).view(-1), det(Z), det(X), det(alpha), det(Q), det(gout)
+    assert Z.dim() == 3 and X.dim() == 2 and Z.shape[-1] == X.shape[1] and theta.numel() == X.shape[1] + 1, (theta.shape, Z.shape, X.shape)
+    (G, Mt, D), N = Z.shape, X.shape[0]
+    assert tuple(alpha.shape) == (G, Mt) and tuple(Q.shape) == (G, Mt, Mt) and tuple(gout.shape) == (G,), (alpha.shape, Q.shape, gout.shape)
+    yt, ldy = reg_target(y, G, N)
+    if w is not None:
+        w = det(w)
+        assert tuple(w.shape) == (G, N) and w.dtype == torch.float32, (w.shape, w.dtype)
+    gls = None
+    if log_scale is not None:
+        log_scale = det(log_scale)
+        assert tuple(log_scale.shape) == (G,) and log_scale.dtype == torch.float32, (log_scale.shape, log_scale.dtype)
+        gls = torch.empty(G, dtype=torch.float32, device=X.device)
+    assert all(t.dtype == torch.float32 for t in (theta, Z, X, alpha, Q, gout)), (theta.dtype, Z.dtype, X.dtype, alpha.dtype, Q.dtype)
+    gZ = torch.empty_like(Z)
+    gtheta = torch.empty(D + 1, dtype=torch.float32, device=X.device)
+    galpha = torch.empty(G, Mt, dtype=torch.float32, device=X.device)
+    gv = torch.empty(G, N, dtype=torch.float32, device=X.device)
+    ws = scratch(lib().vargp_site_bound_bwd_workspace_bytes(G, Mt, N, D), X.device)
+    check(lib().vargp_site_bound_bwd(ptr(theta), ptr(Z), ptr(X), ptr(alpha), ptr(Q), ptr(yt), ldy, ptr(w), code, ptr(log_scale), df,
+                                     lognorm, ptr(gout), ptr(gZ), ptr(gtheta), ptr(galpha), ptr(gv), ptr(gls), G, Mt, N, D,
+                                     int(nu2), ptr(ws), ws.numel() * 4, stream_ptr()), 'vargp_site_bound_bwd')
+    return gZ, gtheta, galpha, gv, gls
+
+
+class _SiteBound(Function):
+    @staticmethod
+    def forward(ctx, theta, Z, X, alpha, Q, y, w, log_scale, kind, extra, nu2):
+        det = lambda t: None if t is None else t.detach().contiguous()
+        extra = tuple(extra) if log_scale is None else (det(log_scale),) + tuple(extra[1:])
+        value = site_moments(theta, Z, X, alpha, Q, y, w, kind, extra, nu2)[2][:, 0].contiguous()
+        ctx.save_for_backward(det(theta).view(-1), det(Z), det(X), det(alpha), det(Q), det(y), det(w), det(log_scale))
+        ctx.kind, ctx.extra, ctx.nu2, ctx.theta_shape = kind, extra, int(nu2), theta.shape
+        return value
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        theta, Z, X, alpha, Q, y, w, log_scale = ctx.saved_tensors
+        gout = gout.to(torch.float32).contiguous()
+        gZ, gtheta, galpha, gv, gls = site_bound_bwd(theta, Z, X, alpha, Q, y, w, ctx.kind, ctx.extra, gout, ctx.nu2)
+        gQ = -gram_moments(theta, Z, X, gv, gv, ctx.nu2)[0]
+        return gtheta.view(ctx.theta_shape), gZ, None, galpha, gQ, None, None, gls, None, None, None
+
+
+def site_bound_diff(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0):
+    """value (G,) = sum_n w_n E_{q(f_n)} log p(y_n | f_n) = site_moments(...)[2][:, 0] (the same forward call, bitwise) on the
+    autograd graph of theta (D+1,), Z (G, Mt, D), alpha (G, Mt), Q (G, Mt, Mt) (through its symmetric part; the variance clamp
+    passes no gradient) and, for Student-t, extra[0] = log_scale (G,).  The backward is one fused pass (site_bound_bwd) and one
+    gram_moments call for gQ; K(Z, X) is never stored in either.  No gradients are produced for X, y and w: a ValueError if one
+    of them requires grad."""
+    for name, t in (('X', X), ('y', y), ('w', w)):
+        if t is not None and t.requires_grad:
+            raise ValueError(f'site_bound_diff: {name} requires grad, but gradients are produced for theta, Z, alpha, Q and the '
+                             'Student-t log_scale only')
+    log_scale = extra[0] if kind == 'studentt' else None
+    return _SiteBound.apply(theta, Z, X, alpha, Q, y, w, log_scale, kind, tuple(extra), nu2)
+
+
 class _LogdetTril(Function):
     @staticmethod
     def forward(ctx, L):

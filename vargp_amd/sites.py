@@ -124,7 +124,8 @@ def ell_torch(kind, extra, mu, var, y):
         return y * mu - (mu + 0.5 * var).exp() - torch.lgamma(y + 1.0)
     x = torch.tensor(_GH_X, dtype=torch.float64, device=mu.device)
     w = torch.tensor(_GH_W, dtype=torch.float64, device=mu.device)
-    d = (2.0 * var).sqrt().unsqueeze(-1) * x
+    pos = var > 0                                                 # (sqrt has no derivative at a variance clamped to 0: that of 1, times 0)
+    d = torch.where(pos, (2.0 * torch.where(pos, var, torch.ones_like(var))).sqrt(), torch.zeros_like(var)).unsqueeze(-1) * x
     if kind == 'bernoulli':
         s = (2.0 * y - 1.0).unsqueeze(-1)
         logp = torch.special.log_ndtr if int(extra[0]) == 0 else torch.nn.functional.logsigmoid
@@ -242,6 +243,51 @@ class _Problem:
         return a_t, G.tril(), kl
 
 
+def _write_q(gp, L_tt, a_t, H_t):
+    """u_mean = L_tt a_t and u_tril = L_tt H_t into gp.u_mean / gp.u_tril_vec (the diagonal through the inverse softplus of
+    vec2tril).  Under no_grad."""
+    M = gp.M
+    u_mean = _mv(L_tt.double().tril(), a_t).unsqueeze(-1)
+    u_tril = ops.bgemm(L_tt, H_t, triA=LOWER, triB=LOWER).tril()
+    vec = ops.mat2trilvec(u_tril)
+    idx = torch.arange(M, device=vec.device)
+    diag = idx * (idx + 1) // 2 + idx
+    vec[:, diag] = inv_softplus(vec[:, diag].double()).float()
+    gp.u_mean.copy_(u_mean.to(gp.u_mean.dtype))
+    gp.u_tril_vec.copy_(vec.to(gp.u_tril_vec.dtype))
+
+
+def _new_block_factors(gp):
+    """(L_tt, T_tt) (C, M, M): the new task's diagonal blocks of the whitening factors at the CURRENT parameters, detached."""
+    with torch.no_grad():
+        kern = gp.kernel
+        theta = kern.log_mean.detach().to(torch.float32).contiguous()
+        z_all = torch.cat([gp._prev(i)['z'] for i in range(len(gp.prev_params))] + [gp.z.detach()], dim=-2).contiguous()
+        n_lt = z_all.size(-2) - gp.M
+        L, T = ops.chol_inv(kern.compute(theta.unsqueeze(0), z_all)[0])
+        return L[:, n_lt:, n_lt:].contiguous(), T[:, n_lt:, n_lt:].contiguous()
+
+
+def whitened_q(gp):
+    """The model's current q(u_t) in whitened coordinates at the current parameters: -> (a_t = T_tt u_mean (C, M) float64,
+    H_t = T_tt L_u (C, M, M) float32, lower triangular), detached."""
+    ops.require_device(gp.z)
+    with torch.no_grad():
+        _, T_tt = _new_block_factors(gp)
+        L_u = ops.vec2tril(gp.u_tril_vec.detach().float(), gp.M)
+        a_t = ops.matmul(T_tt, gp.u_mean.detach().float(), triA=LOWER).squeeze(-1).double()
+        return a_t, ops.bgemm(T_tt, L_u, triA=LOWER, triB=LOWER).tril()
+
+
+def set_whitened_q_(gp, a_t, H_t):
+    """Write q(v_t) = N(a_t, H_t H_t^T) as u_mean = L_tt a_t, u_tril = L_tt H_t at the CURRENT parameters into u_mean /
+    u_tril_vec: what keeps q fixed in whitened coordinates after inducing points or hyper-parameters have moved."""
+    ops.require_device(gp.z, a_t, H_t)
+    with torch.no_grad():
+        L_tt, _ = _new_block_factors(gp)
+        _write_q(gp, L_tt, a_t.double(), H_t.float().contiguous())
+
+
 def fit_q_newton_(gp, x, y, n_iters=20, damping=1.0, tol=1e-6, weights=None, route=None, start='current'):
     """Fit q(u_t) of the VARGP model `gp` (Bernoulli, Poisson or Student-t likelihood) to the data x (N, D), y as loss() takes it
     ((N,) or (C, N); Bernoulli: int64 class indices (N,) read one-vs-rest, or float / bool 0 / 1 targets), by the natural-gradient
@@ -309,13 +355,216 @@ def fit_q_newton_(gp, x, y, n_iters=20, damping=1.0, tol=1e-6, weights=None, rou
                 break
 
         if changed:
-            u_mean = _mv(pr.L_tt.double().tril(), a_t).unsqueeze(-1)
-            u_tril = ops.bgemm(pr.L_tt, H_t, triA=LOWER, triB=LOWER).tril()
-            vec = ops.mat2trilvec(u_tril)
-            idx = torch.arange(M, device=x.device)
-            diag = idx * (idx + 1) // 2 + idx
-            vec[:, diag] = inv_softplus(vec[:, diag].double()).float()
-            gp.u_mean.copy_(u_mean.to(gp.u_mean.dtype))
-            gp.u_tril_vec.copy_(vec.to(gp.u_tril_vec.dtype))
+            _write_q(gp, pr.L_tt, a_t, H_t)
         n_clamped = int(round(clamped.double().sum().item()))
     return SiteFit(torch.stack(trace), len(trace) - 1, n_rejected, n_clamped, pr.route)
+
+
+# -- the site bound on the autograd graph: variational EM ----------------------------------------------------------------------------
+# With q(v_t) = N(a_t, H_t H_t^T) held FIXED in whitened coordinates, the bound of the module docstring is a function of the
+# inducing points, theta = kernel.log_mean and the likelihood's own parameter through alpha = T^T a, Q = T^T (I - H H^T) T and
+# k_n alone (the KL term is a constant), and d bound / d (alpha, Q, K) are sums over the points:
+#     gm_n = s w_n d ell_n / d mu,   gv_n = s w_n d ell_n / d var [gamma^2 - k_n^T Q k_n > 0]      (the TRUE signed d ell / d var)
+#     galpha = sum_n gm_n k_n,   gQ = -sum_n gv_n k_n k_n^T,   gK[:, n] = gm_n alpha - 2 gv_n Q k_n
+# ops.site_bound_diff is that function with ONE fused backward pass (csrc/sites.hip: vargp_site_bound_bwd; gQ by ops.gram_moments
+# with w = gv); the frozen tasks' a_i = T_ii m_i, H_i = T_ii Lu_i and T itself are differentiated by the per-op nodes
+# (ops.chol_inv, ops.matmul), as collapsed._whitened_bound does it.  fit_sites_ alternates fit_q_newton_ (E-step) with a few Yogi
+# steps on the bound (M-step); by the envelope theorem the partial gradient at the fixed whitened q IS the gradient of the
+# re-converged bound at a converged E-step (tests/test_site_bound_host.py).
+EMFit = namedtuple('EMFit', 'bound n_rounds n_newton stopped')
+EMFit.__doc__ = """bound (n_rounds + 1, C) float64 on the host: the bound per output after every E-step (its sum over the outputs
+is non-decreasing); n_rounds: completed rounds (M-step + E-step); n_newton: accepted Newton steps over all E-steps; stopped:
+'rounds' (all rounds done) or 'm_step' (an M-step lowered the bound and was undone)."""
+
+
+def check_differentiable(gp, who):
+    """check_supported, and exactly RBFKernel or MaternKernel: the bound's gradient for a DeepRBFKernel needs the gradient of the
+    site pass for its inputs X (the feature map), which the fused backward does not produce."""
+    if isinstance(gp.kernel, DeepRBFKernel):
+        raise ValueError(f'{who}: DeepRBFKernel is not supported (the feature map needs the gradient of the site pass for its '
+                         'inputs X, which the fused backward does not produce); fit_q_newton_ supports it')
+    check_supported(gp, who)
+    if type(gp.kernel) not in (RBFKernel, MaternKernel):
+        raise ValueError(f'{who}: supported kernels are exactly RBFKernel and MaternKernel, got {type(gp.kernel).__name__}')
+
+
+def _tile_value(theta, Z, alpha, Q, log_scale, Xt, yt, wt, kind, extra, nu2):
+    """sum_n w_n ell_n (G,) float64 of one tile of points from the differentiable per-op nodes: the gram op, ops.matmul, and
+    ell_torch in fp64."""
+    th = theta.view(1, -1)
+    K = (ops.rbf_gram(th, Z, Xt, True) if nu2 == 0 else ops.matern_gram(th, Z, Xt, True, 0.5 * nu2))[0]      # (G, Mt, B)
+    mu = ops.matmul(alpha.unsqueeze(-2), K).squeeze(-2)
+    var = ((2.0 * theta[-1]).exp() - (K * ops.matmul(0.5 * (Q + Q.mT), K)).sum(-2)).clamp_min(0.0)
+    ex = extra if log_scale is None else (log_scale,) + tuple(extra[1:])
+    ell = ell_torch(kind, ex, mu, var, yt)
+    if wt is None:
+        return ell.sum(-1)
+    return torch.where(wt != 0, wt.double() * ell, torch.zeros_like(ell)).sum(-1)
+
+
+class _ComposedSiteBound(torch.autograd.Function):
+    """ops.site_bound_diff for any Mt, a tile of N at a time: the forward adds the tiles' values in fp64 under no_grad; the
+    backward revisits the same tiles, rebuilds each tile's graph from the per-op nodes and accumulates the gradients in fp64 --
+    memory O(Mt x tile)."""
+    @staticmethod
+    def forward(ctx, theta, Z, alpha, Q, log_scale, X, y, w, kind, extra, nu2, tile):
+        ctx.save_for_backward(theta, Z, alpha, Q, log_scale, X, y, w)
+        ctx.cfg = (kind, extra, nu2, tile)
+        value = torch.zeros(Z.size(0), dtype=torch.float64, device=X.device)
+        for Xt, yt, wt in _tiles(X, y, w, tile):
+            value += _tile_value(theta, Z, alpha, Q, log_scale, Xt, yt, wt, kind, extra, nu2)
+        return value
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        theta, Z, alpha, Q, log_scale, X, y, w = ctx.saved_tensors
+        kind, extra, nu2, tile = ctx.cfg
+        leaves = [t.detach().clone().requires_grad_(True) for t in (theta, Z, alpha, Q) + (() if log_scale is None else (log_scale,))]
+        acc = [torch.zeros(t.shape, dtype=torch.float64, device=t.device) for t in leaves]
+        with torch.enable_grad():
+            for Xt, yt, wt in _tiles(X, y, w, tile):
+                val = _tile_value(*leaves[:4], leaves[4] if log_scale is not None else None, Xt, yt, wt, kind, extra, nu2)
+                for a, g in zip(acc, torch.autograd.grad((val * gout.double()).sum(), leaves)):
+                    a += g.double()
+        out = [a.to(t.dtype) for a, t in zip(acc, leaves)]
+        return (*out[:4], out[4] if log_scale is not None else None, None, None, None, None, None, None, None)
+
+
+def _tiles(X, y, w, tile):
+    for n0 in range(0, X.size(0), tile):
+        n1 = min(n0 + tile, X.size(0))
+        yield (X[n0:n1].contiguous(), (y[n0:n1] if y.dim() == 1 else y[:, n0:n1]).contiguous(),
+               None if w is None else w[:, n0:n1].contiguous())
+
+
+def composed_site_bound(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0, tile=COMPOSED_TILE):
+    """ops.site_bound_diff from the per-op kernels (arguments alike, any Mt; value (G,) float64): the route above
+    ops.SITE_MAX_MT inducing points and the on-device yardstick of the fused backward."""
+    ops.require_device(theta, Z, X, alpha, Q, y, w)
+    for name, t in (('X', X), ('y', y), ('w', w)):
+        if t is not None and t.requires_grad:
+            raise ValueError(f'composed_site_bound: {name} requires grad, but gradients are produced for theta, Z, alpha, Q and '
+                             'the Student-t log_scale only')
+    log_scale = extra[0] if kind == 'studentt' else None
+    return _ComposedSiteBound.apply(theta, Z, alpha, Q, log_scale, X, y, w, kind, tuple(extra), int(nu2), int(tile))
+
+
+def site_bound(gp, x, y, weights=None, q=None, route=None):
+    """The variational bound of the data x (N, D), y (as fit_q_newton_ takes it) per output, (C,) float64: data term -
+    KL(q(v_t) || N(0, I)), ON THE AUTOGRAD GRAPH of gp.z, gp.kernel.log_mean and, for Student-t, gp.likelihood.log_scale.
+    q = (a_t (C, M), H_t (C, M, M) lower) is q(u_t) in whitened coordinates and a CONSTANT; None: whitened_q(gp), the model's own,
+    with which the value is fit_q_newton_(n_iters=0).bound[0].  The frozen tasks' inducing points and q(u) are constants; their
+    whitened moments depend on theta through the whitening and are differentiated.  x, y and weights get no gradient.  One fused
+    pass over the data forward and one backward plus one ops.gram_moments call; K(z, x) is never stored (route 'fused', up to
+    ops.SITE_MAX_MT inducing points over all tasks; 'composed' above it or on request: per-op kernels, a tile of N at a time).
+    Bernoulli, Poisson or Student-t likelihood, ep_var_mean=True, exactly RBFKernel or MaternKernel; a DeepRBFKernel is refused
+    (ValueError).  The hyper-prior (kl_hypers) is NOT part of the bound."""
+    check_differentiable(gp, 'site_bound')
+    ops.require_device(gp.z, x, y, weights)
+    kern, lik = gp.kernel, gp.likelihood
+    C, M, N = gp.z.size(0), gp.M, x.size(0)
+    theta = kern.log_mean.to(torch.float32).contiguous()
+    prev = [gp._prev(i) for i in range(len(gp.prev_params))]
+    z_all = torch.cat([p['z'] for p in prev] + [gp.z], dim=-2).contiguous()
+    Mt = z_all.size(-2)
+    n_lt = Mt - M
+    route = pick_route(route, Mt, 'site_bound')
+    a_t, H_t = whitened_q(gp) if q is None else (q[0].detach().double(), q[1].detach().float())
+    own = lik.ext_param()
+    extra = (() if own is None else (own.to(torch.float32),)) + tuple(lik._consts())
+    yt = site_target(lik.kind, y.detach(), C, N)
+    w = None
+    if weights is not None:
+        wt, ldw = ops.reg_target(weights.detach(), C, N)
+        w = wt.expand(C, N).contiguous() if ldw == 0 else wt
+    nu2 = int(round(2 * kern.nu)) if isinstance(kern, MaternKernel) else 0
+
+    L, T = ops.chol_inv(kern.compute(theta.unsqueeze(0), z_all)[0])                  # (C, Mt, Mt): as block_joint factorises
+    a, Hb, o = [], torch.zeros(C, Mt, Mt, dtype=torch.float32, device=x.device), 0
+    for p in prev:
+        n = p['z'].size(-2)
+        T_ii = T[:, o:o + n, o:o + n].contiguous()
+        a.append(ops.matmul(T_ii, p['u_mean'], triA=LOWER).squeeze(-1).double())
+        Hb[:, o:o + n, o:o + n] = ops.matmul(T_ii, p['u_tril'], triA=LOWER, triB=LOWER).tril()
+        o += n
+    Hb[:, n_lt:, n_lt:] = H_t
+    alpha = _mv(T.mT.double(), torch.cat(a + [a_t], dim=-1)).float().contiguous()
+    S = torch.eye(Mt, dtype=torch.float32, device=x.device) - ops.matmul(Hb, Hb.mT)
+    Q = ops.matmul(ops.matmul(T.mT, S), T)
+    Q = (0.5 * (Q + Q.mT)).contiguous()
+    pass_ = ops.site_bound_diff if route == 'fused' else composed_site_bound
+    data = pass_(theta, z_all, x.detach().contiguous(), alpha, Q, yt, w, lik.kind, extra, nu2)
+    H64 = H_t.double()
+    kl = 0.5 * (a_t.square().sum(-1) + H64.square().sum((-2, -1)) - M - 2.0 * H64.diagonal(dim1=-2, dim2=-1).log().sum(-1))
+    return data.double() - kl
+
+
+def fit_sites_(gp, x, y, n_rounds=5, m_steps=20, lr=1e-2, params=None, newton_iters=20, damping=1.0, tol=1e-6, weights=None,
+               route=None, start='current'):
+    """Variational EM on the site bound, full batch and in place.  Every round: E-step fit_q_newton_(n_iters=newton_iters,
+    damping, tol; the first from `start`, the later ones from the current q); M-step m_steps steps of the project's Yogi
+    (optim.py, step lr) on -sum_c site_bound over the chosen subset `params` of {'z': gp.z, 'kernel': gp.kernel.log_mean, 'lik':
+    the likelihood's own parameter (Student-t log_scale)} with q held at the E-step's whitened (a_t, H_t), then
+    set_whitened_q_.  A last E-step ends the fit.  params None: ('z', 'kernel'), and 'lik' where the likelihood has a
+    parameter; 'lik' on a likelihood without one is a ValueError.  An M-step after which the summed bound is lower than before
+    it is undone (parameters and q restored), stopped = 'm_step', and the loop ends: the summed trace never falls.  The
+    objective is the bound alone: the hyper-prior (kl_hypers) is NOT in it, so this is maximum likelihood (type II) for the
+    hyper-parameters, not the MAP / variational treatment of VARGP.loss.  -> EMFit(bound (n_rounds + 1, C) float64 on the
+    host, n_rounds, n_newton, stopped)."""
+    from .optim import Yogi
+    check_differentiable(gp, 'fit_sites_')
+    own = gp.likelihood.ext_param()
+    named = dict(z=gp.z, kernel=gp.kernel.log_mean, lik=own)
+    if params is None:
+        params = ('z', 'kernel') + (('lik',) if own is not None else ())
+    params = tuple(params)
+    if not params or any(p not in named for p in params):
+        raise ValueError(f'fit_sites_: params must be a non-empty subset of {sorted(named)}, got {params!r}')
+    if 'lik' in params and own is None:
+        raise ValueError(f"fit_sites_: params names 'lik', but {type(gp.likelihood).__name__} has no parameter")
+    damping = check_damping(damping, 'fit_sites_')
+    n_rounds, m_steps = int(n_rounds), int(m_steps)
+    if n_rounds < 0 or m_steps < 0:
+        raise ValueError(f'fit_sites_: n_rounds and m_steps must be >= 0, got {n_rounds}, {m_steps}')
+    ops.require_device(gp.z, x, y, weights)
+    chosen = [named[p] for p in dict.fromkeys(params)]
+    e_step = lambda st: fit_q_newton_(gp, x, y, n_iters=newton_iters, damping=damping, tol=tol, weights=weights, route=route, start=st)
+    fit = e_step(start)
+    trace, n_newton, stopped, done = [fit.bound[-1]], fit.n_iters, 'rounds', 0
+    for _ in range(n_rounds):
+        q = whitened_q(gp)
+        keep = [t.detach().clone() for t in chosen + [gp.u_mean, gp.u_tril_vec]]
+
+        def undo():
+            with torch.no_grad():
+                for t, k in zip(chosen + [gp.u_mean, gp.u_tril_vec], keep):
+                    t.copy_(k)
+
+        opt = Yogi(chosen, lr=lr)
+        before = None
+        for _ in range(m_steps):
+            bound = site_bound(gp, x, y, weights=weights, q=q, route=route)
+            before = bound.detach().sum() if before is None else before
+            for p, g in zip(chosen, torch.autograd.grad(-bound.sum(), chosen)):
+                p.grad = g.to(p.dtype)
+            opt.step()
+        for p in chosen:
+            p.grad = None
+        if m_steps:
+            with torch.no_grad():
+                after = site_bound(gp, x, y, weights=weights, q=q, route=route).sum()
+            if not bool(after >= before):
+                undo()
+                stopped = 'm_step'
+                break
+            set_whitened_q_(gp, *q)
+        fit = e_step('current')
+        if not bool(fit.bound[-1].sum() >= trace[-1].sum()):       # (rounding between the M-step's bound and the E-step's own)
+            undo()
+            stopped = 'm_step'
+            break
+        trace.append(fit.bound[-1])
+        n_newton += fit.n_iters
+        done += 1
+    return EMFit(torch.stack(trace), done, n_newton, stopped)

@@ -65,8 +65,8 @@ def _hand_over_hyper_prior(prev_params):
 
 _Z_INITS = ('greedy', 'kmeans', 'random')                  # create_clf / create_reg (z_init=)
 _LENGTHSCALE_INITS = ('default', 'median')        # (lengthscale_init=)
-_Q_INITS = ('default', 'optimal', 'collapsed', 'newton')      # create_reg (q_init=)
-_CLF_Q_INITS = ('default', 'newton')                          # create_clf (q_init=)
+_Q_INITS = ('default', 'optimal', 'collapsed', 'newton', 'em')      # create_reg (q_init=)
+_CLF_Q_INITS = ('default', 'newton', 'em')                          # create_clf (q_init=)
 
 
 def _check_init_names(who, z_init, lengthscale_init):
@@ -613,6 +613,27 @@ class VARGP(nn.Module):
         return sites.fit_q_newton_(self, x, y, n_iters=n_iters, damping=damping, tol=tol, weights=weights, route=route,
                                    start=start)
 
+    def site_bound(self, x, y, weights=None, q=None, route=None):
+        """The variational bound of x (N, D), y (as fit_q_newton_ takes it) per output for a Bernoulli, Poisson or Student-t model
+        (sites.site_bound, not in the reference): (C,) float64 on the autograd graph of z, kernel.log_mean and the Student-t
+        log_scale, with q(u_t) held FIXED in whitened coordinates -- q = (a_t, H_t) as sites.whitened_q returns it, None: the
+        model's own q, where the value is fit_q_newton_(n_iters=0).bound[0].  One fused pass over the data forward and one
+        backward (csrc/sites.hip: vargp_site_bound_bwd) plus one moment pass; K(z, x) is never stored.  The frozen tasks are
+        constants; x, y and weights get no gradient.  ep_var_mean=True, exactly RBFKernel or MaternKernel (a DeepRBFKernel is
+        refused: ValueError).  The hyper-prior is not part of the bound."""
+        return sites.site_bound(self, x, y, weights=weights, q=q, route=route)
+
+    def fit_sites_(self, x, y, n_rounds=5, m_steps=20, lr=1e-2, params=None, newton_iters=20, damping=1.0, tol=1e-6,
+                   weights=None, route=None, start='current'):
+        """Variational EM for the Bernoulli, Poisson and Student-t likelihoods (sites.fit_sites_): n_rounds of fit_q_newton_
+        (E-step) and m_steps Yogi steps up sum_c site_bound over the chosen subset of {'z', 'kernel' (kernel.log_mean), 'lik'
+        (the Student-t log_scale)} with q held fixed in whitened coordinates (M-step), then a last E-step.  An M-step that lowers
+        the bound is undone and ends the fit.  The objective is the bound alone, WITHOUT the hyper-prior (kl_hypers): type-II
+        maximum likelihood, not what VARGP.loss optimises.  -> sites.EMFit(bound (n_rounds + 1, C) float64 on the host, its
+        sum over outputs non-decreasing; n_rounds; n_newton; stopped)."""
+        return sites.fit_sites_(self, x, y, n_rounds=n_rounds, m_steps=m_steps, lr=lr, params=params, newton_iters=newton_iters,
+                                damping=damping, tol=tol, weights=weights, route=route, start=start)
+
     def collapsed_bound(self, x, y, weights=None, temper=1.0):
         """The bound fit_q_ returns -- the variational bound of x (N, D), y (N,) or (C, N) at the optimal q(u) of the current
         task -- as a (C,) float64 tensor on the autograd graph of z, kernel.log_mean and likelihood.obs_log_var
@@ -658,7 +679,7 @@ class VARGP(nn.Module):
     def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None,
                    ep_var_mean=True, map_est_hypers=False, dkl=False, kernel='rbf', native_kernel=False,
                    likelihood='softmax', link='probit', z_init='random', kmeans_iters=20, lengthscale_init='default',
-                   greedy_candidates=4096, q_init='default', newton_iters=20):
+                   greedy_candidates=4096, q_init='default', newton_iters=20, em_rounds=5, em_steps=20):
         """Factory used by the experiment driver (vargp.py:200-243): inducing points at random data
         points per class, hyper-prior = previous task's hyper-posterior (popped from prev_params[-1],
         which is mutated like the reference does).  kernel: 'rbf' (the reference's), or 'matern12' / 'matern32' /
@@ -674,11 +695,14 @@ class VARGP(nn.Module):
         q_init: 'default' (u_mean ~ N(0, 0.25), u_tril = the softplus identity, as the reference starts) or 'newton'
         (likelihood='bernoulli' only): once the inducing points and the lengthscale stand, fit_q_newton_(n_iters=newton_iters,
         start='prior')
-        on the whole data set on the current CUDA device; the model returns on the device the default route returns it on."""
+        on the whole data set on the current CUDA device; the model returns on the device the default route returns it on.
+        'em' (likelihood='bernoulli', RBF / Matern kernel): fit_sites_(n_rounds=em_rounds, m_steps=em_steps,
+        newton_iters=newton_iters, start='prior') instead -- variational EM that also moves the inducing points and
+        kernel.log_mean up the bound (without the hyper-prior)."""
         if q_init not in _CLF_Q_INITS:
             raise ValueError(f'create_clf: q_init must be one of {sorted(_CLF_Q_INITS)}, got {q_init!r}')
-        if q_init == 'newton' and likelihood != 'bernoulli':
-            raise ValueError(f"create_clf: q_init='newton' fits independent Gaussian sites, which likelihood={likelihood!r} does "
+        if q_init in ('newton', 'em') and likelihood != 'bernoulli':
+            raise ValueError(f"create_clf: q_init={q_init!r} fits independent Gaussian sites, which likelihood={likelihood!r} does "
                              "not have (its outputs are coupled); use likelihood='bernoulli'")
         lik = make_clf_likelihood(likelihood, n_f, link)
         _check_init_names('create_clf', z_init, lengthscale_init)
@@ -729,19 +753,23 @@ class VARGP(nn.Module):
             z = _greedy_inducing(x_all, cand, M, kern, prior_log_mean, prev_params)
         gp = VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean,
                    prev_params=prev_params)
-        if q_init == 'newton':
-            sites.check_supported(gp, 'create_clf(q_init="newton")')
+        if q_init in ('newton', 'em'):
+            (sites.check_supported if q_init == 'newton' else sites.check_differentiable)(gp, f'create_clf(q_init="{q_init}")')
             home, dev = gp.z.device, torch.device('cuda', torch.cuda.current_device())
             x = dataset[torch.arange(len(dataset))][0].to(device=dev, dtype=torch.float32)
             y = torch.as_tensor(dataset.targets).to(device=dev, dtype=torch.int64)
-            gp.to(dev).fit_q_newton_(x, y, n_iters=newton_iters, start='prior')
+            if q_init == 'newton':
+                gp.to(dev).fit_q_newton_(x, y, n_iters=newton_iters, start='prior')
+            else:
+                gp.to(dev).fit_sites_(x, y, n_rounds=em_rounds, m_steps=em_steps, newton_iters=newton_iters, start='prior')
             gp.to(home)
         return gp
 
     @staticmethod
     def create_reg(dataset, M=20, n_var_samples=3, likelihood='gaussian', df=4.0, prev_params=None, ep_var_mean=True,
                    map_est_hypers=False, kernel='rbf', native_kernel=False, z_init='random', kmeans_iters=20,
-                   lengthscale_init='default', greedy_candidates=4096, q_init='default', collapsed_steps=200, newton_iters=20):
+                   lengthscale_init='default', greedy_candidates=4096, q_init='default', collapsed_steps=200, newton_iters=20,
+                   em_rounds=5, em_steps=20):
         """Regression / count factory, the counterpart of create_clf (not in the reference): dataset[i] -> (x, y), dataset.targets
         (N,) (one output) or (N, C); inducing points at M random data points per output; hyper-prior = the previous task's
         hyper-posterior (popped from prev_params[-1], which is mutated as in create_clf).  likelihood: 'gaussian'
@@ -755,14 +783,17 @@ class VARGP(nn.Module):
         fit_collapsed_(n_steps=collapsed_steps) instead -- inducing points, lengthscales and noise variance are first moved up
         the collapsed bound (without the hyper-prior), then q(u) is fitted.  'newton' (likelihood 'poisson' or 'studentt'; the
         Gaussian's own route is 'optimal'): fit_q_newton_(n_iters=newton_iters, start='prior') on the whole data set instead.
+        'em' (likelihood 'poisson' or 'studentt', RBF / Matern kernel): fit_sites_(n_rounds=em_rounds, m_steps=em_steps,
+        newton_iters=newton_iters, start='prior') -- variational EM that also moves inducing points, kernel.log_mean and the
+        Student-t log_scale up the bound (without the hyper-prior); the prior start for the reason 'newton' uses it.
         None of likelihood, df, kernel and native_kernel is part of a checkpoint: give them again on reload.  A minibatch's
         targets go to loss() as (C, B) -- y.t() of a (B, C) batch -- or (B,)."""
         if q_init not in _Q_INITS:
             raise ValueError(f'create_reg: q_init must be one of {sorted(_Q_INITS)}, got {q_init!r}')
         if q_init in ('optimal', 'collapsed') and likelihood != 'gaussian':
             raise ValueError(f"create_reg: q_init={q_init!r} is the closed form of likelihood='gaussian', got {likelihood!r}")
-        if q_init == 'newton' and likelihood == 'gaussian':
-            raise ValueError("create_reg: q_init='newton' iterates Gaussian sites of a non-Gaussian likelihood ('poisson', "
+        if q_init in ('newton', 'em') and likelihood == 'gaussian':
+            raise ValueError(f"create_reg: q_init={q_init!r} iterates Gaussian sites of a non-Gaussian likelihood ('poisson', "
                              "'studentt'); likelihood='gaussian' has the closed form q_init='optimal'")
         if kernel not in _KERNEL_NU:
             raise ValueError(f'create_reg: kernel must be one of {sorted(_KERNEL_NU)}, got {kernel!r}')
@@ -795,7 +826,7 @@ class VARGP(nn.Module):
         gp = VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean, prev_params=prev_params)
         if q_init != 'default':
             check = {'optimal': collapsed.check_supported, 'collapsed': collapsed.check_differentiable,
-                     'newton': sites.check_supported}[q_init]
+                     'newton': sites.check_supported, 'em': sites.check_differentiable}[q_init]
             check(gp, f'create_reg(q_init="{q_init}")')
             home, dev = gp.z.device, torch.device('cuda', torch.cuda.current_device())
             x = dataset[torch.arange(len(dataset))][0]
@@ -805,6 +836,8 @@ class VARGP(nn.Module):
                 gp.to(dev).fit_q_(x, y)
             elif q_init == 'newton':
                 gp.to(dev).fit_q_newton_(x, y, n_iters=newton_iters, start='prior')
+            elif q_init == 'em':
+                gp.to(dev).fit_sites_(x, y, n_rounds=em_rounds, m_steps=em_steps, newton_iters=newton_iters, start='prior')
             else:
                 gp.to(dev).fit_collapsed_(x, y, n_steps=collapsed_steps)
             gp.to(home)
