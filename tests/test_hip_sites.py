@@ -49,6 +49,7 @@ SITE_CASES = [
     (130, 65, 40, 0, 'probit', False, None),
     (65, 63, 1, 5, 'poisson', True, None),
     (64, 513, 33, 1, 'logit', False, 'rand'),
+    (200, 65, 33, 3, 'probit', True, 'rand'),       # four row panels, the last with 8 live rows; D % 32 == 1; a one-column tail
 ]
 
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <atomic>
 #include <functional>
 #include "../../include/vargp_hip.h"
 
@@ -100,6 +101,23 @@ int check_launch(const char* what);
   } while (0)
 
 static inline hipStream_t as_stream(vargp_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+// Let KERNEL be launched with up to `bytes` of dynamic LDS.  hipFuncAttributeMaxDynamicSharedMemorySize is per device and per
+// kernel: one mask of the devices already served per instantiation.  what: the entry's name, for the error text; dev_out: the
+// current device, for a caller that wants it.
+template <auto KERNEL>
+static int reserve_dynamic_lds(size_t bytes, const char* what, int* dev_out = nullptr) {
+  static std::atomic<unsigned> attr_mask[2] = {};
+  int dev = 0;
+  VARGP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "%s: hipGetDevice failed", what);
+  if (!((attr_mask[dev >> 5].load(std::memory_order_acquire) >> (dev & 31)) & 1u)) {
+    VARGP_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)bytes) == hipSuccess,
+                  "%s: cannot reserve %zu bytes of LDS", what, bytes);
+    attr_mask[dev >> 5].fetch_or(1u << (dev & 31), std::memory_order_release);
+  }
+  if (dev_out) *dev_out = dev;
+  return VARGP_OK;
+}
 static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 

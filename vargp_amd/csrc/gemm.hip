@@ -1551,16 +1551,8 @@ int launch_bwdmat_gemm(const BwdMatArgs& a, int first, int nmat, const GemmParam
     const BwdMatArgs ac = a;
     prof_remember(tag, [=](hipStream_t s) { launch_bwdmat_gemm(ac, first, nmat, pc, nbatch, s, "replay", nullptr); });
   }
-  // hipFuncAttributeMaxDynamicSharedMemorySize is per device
-  static std::atomic<unsigned> attr_mask[2] = {};
   int dev = 0;
-  VARGP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "bwdmat_gemm: hipGetDevice failed");
-  if (!((attr_mask[dev >> 5].load(std::memory_order_acquire) >> (dev & 31)) & 1u)) {
-    VARGP_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(t0_bwdmat_gemm_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBwdMatLdsBytes) == hipSuccess,
-                  "bwdmat_gemm: cannot reserve %zu bytes of LDS", kBwdMatLdsBytes);
-    attr_mask[dev >> 5].fetch_or(1u << (dev & 31), std::memory_order_release);
-  }
+  if (int rc = reserve_dynamic_lds<t0_bwdmat_gemm_kernel>(kBwdMatLdsBytes, "bwdmat_gemm", &dev)) return rc;
   ProfScope prof(tag, st);
   GemmParams q = p;
   q.splitk = 1; q.nofast = 0; q.group_m = 0; q.xcd_remap = 1;

@@ -17,15 +17,15 @@
 // entry (i, j), j <= i, to both triangles: Phi is bitwise symmetric and two calls on the same input are bitwise equal.
 // The chunking depends on the shapes alone (mom_plan): at most kMoMaxChunks chunks of at least kMoMinChunk columns, as many as
 // give the launch about kMoTargetWg workgroups.
-#include "moments_plan.h"      // kMoT and the other tiling / chunking constants (shared with sites.hip)
+#include "dataset_pass.h"      // the tiling constants, the chunking rule and the other pieces shared with sites.hip
 
 namespace vargp {
 
 typedef float mo_f32x16 __attribute__((ext_vector_type(16)));
 
 struct MomPlan {
-  int nt, ntri, nch;         // tiles per side, lower-triangle tiles, chunks
-  int64_t len;               // columns per chunk (a multiple of kMoT)
+  int nt, ntri;              // tiles per side, lower-triangle tiles
+  Chunks ch;                 // ch.nch chunks of ch.len columns
   float *pphi, *pc, *ps;     // partials [G][nch][ntri][64 * 64], [G][nch][nt * 64], [G][nch][2]
   size_t bytes;
 };
@@ -34,17 +34,12 @@ static MomPlan mom_plan(void* ws, int G, int Mt, int N) {
   MomPlan o{};
   o.nt = cdiv(Mt, kMoT);
   o.ntri = o.nt * (o.nt + 1) / 2;
-  int64_t want = cdiv(kMoTargetWg, (int64_t)G * o.ntri);
-  const int64_t most = cdiv(N, kMoMinChunk);
-  want = want < most ? want : most;
-  want = want < 1 ? 1 : (want > kMoMaxChunks ? kMoMaxChunks : want);
-  o.len = round_up(cdiv(N, want), kMoT);
-  o.nch = cdiv(N, o.len);
+  o.ch = chunk_rule(N, (int64_t)G * o.ntri);
   float* p = reinterpret_cast<float*>(ws);
   auto take = [&](int64_t n) { float* q = p; p += round_up(n, 64); return q; };
-  o.pphi = take((int64_t)G * o.nch * o.ntri * kMoT * kMoT);
-  o.pc = take((int64_t)G * o.nch * o.nt * kMoT);
-  o.ps = take((int64_t)G * o.nch * 2);
+  o.pphi = take((int64_t)G * o.ch.nch * o.ntri * kMoT * kMoT);
+  o.pc = take((int64_t)G * o.ch.nch * o.nt * kMoT);
+  o.ps = take((int64_t)G * o.ch.nch * 2);
   o.bytes = (size_t)((char*)p - (char*)ws);
   return o;
 }
@@ -73,7 +68,7 @@ __global__ __launch_bounds__(256) void moments_kernel(const MomArgs a) {
   __shared__ float wl[kRbfDirectD];                              // DIRECT: exp(-2 theta_d)
   __shared__ float wn[T], wyn[T];                                // w_n and w_n y_n of the step's columns (0 behind the end)
   __shared__ float nrm[3][T];                                    // !DIRECT: |a_i|^2, |a_j|^2, |b|^2
-  __shared__ float cred[4][T];
+  __shared__ float cred[4 * T];
 
   const int Mt = a.Mt, D = a.D, ntri = a.p.ntri;
   const int chunk = blockIdx.x / ntri, t = blockIdx.x - chunk * ntri;
@@ -82,8 +77,8 @@ __global__ __launch_bounds__(256) void moments_kernel(const MomArgs a) {
   const bool two = ti != tj;
   const int i0 = ti * T, j0 = tj * T;
   const int64_t g = blockIdx.y;
-  const int64_t cbeg = (int64_t)chunk * a.p.len;
-  const int64_t cend = cbeg + a.p.len < a.N ? cbeg + a.p.len : a.N;
+  const int64_t cbeg = (int64_t)chunk * a.p.ch.len;
+  const int64_t cend = cbeg + a.p.ch.len < a.N ? cbeg + a.p.ch.len : a.N;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32, l31 = lane & 31, h = lane >> 5;
   const float g2 = expf(2.f * a.theta[D]);
@@ -204,14 +199,14 @@ __global__ __launch_bounds__(256) void moments_kernel(const MomArgs a) {
     __syncthreads();
   }
 
-  const int64_t part = g * a.p.nch + chunk;
+  const int64_t part = g * a.p.ch.nch + chunk;
   float* out = a.p.pphi + (part * ntri + t) * (T * T);
 #pragma unroll
   for (int r = 0; r < 16; ++r) out[(wr + (r & 3) + 8 * (r >> 2) + 4 * h) * T + wc + l31] = acc[r];
   if (tj == 0) {
-    cred[wave][lane] = cacc;
+    cred[wave * T + lane] = cacc;
     __syncthreads();
-    if (tid < T) a.p.pc[part * a.p.nt * T + i0 + tid] = (cred[0][tid] + cred[1][tid]) + (cred[2][tid] + cred[3][tid]);
+    if (tid < T) a.p.pc[part * a.p.nt * T + i0 + tid] = wave4_sum(cred, tid);
   }
   if (t == 0 && wave == 0) {
     sw = wave_sum(sw);
@@ -224,7 +219,7 @@ __global__ __launch_bounds__(256) void moments_kernel(const MomArgs a) {
 // entries of c | the two sums
 __global__ __launch_bounds__(256) void moments_reduce_kernel(const MomArgs a) {
   constexpr int T = kMoT;
-  const int Mt = a.Mt, ntri = a.p.ntri, nch = a.p.nch;
+  const int Mt = a.Mt, ntri = a.p.ntri, nch = a.p.ch.nch;
   const int64_t g = blockIdx.y;
   const int b = blockIdx.x, tid = threadIdx.x;
   if (b < ntri * 16) {
@@ -256,7 +251,7 @@ __global__ __launch_bounds__(256) void moments_reduce_kernel(const MomArgs a) {
 
 template <class EPI>
 static void moments_launch(const MomArgs& a, hipStream_t st) {
-  const dim3 grid(a.p.ntri * a.p.nch, a.G), blk(256);
+  const dim3 grid(a.p.ntri * a.p.ch.nch, a.G), blk(256);
   if (a.D <= kRbfDirectD) hipLaunchKernelGGL((moments_kernel<EPI, true>), grid, blk, 0, st, a);
   else hipLaunchKernelGGL((moments_kernel<EPI, false>), grid, blk, 0, st, a);
 }
@@ -283,8 +278,8 @@ constexpr int kMoBwdNPMax = 7;                  // accumulator tiles of P per wa
 constexpr size_t kMoBwdBudget = 64u << 20;      // bytes of the per-chunk partials of r and P, at most (one chunk always fits)
 
 struct MomBwdPlan {
-  int nt, nch, np, ngrp;     // panels, chunks, P tiles per wave, groups of d
-  int64_t len;               // columns per chunk (a multiple of kMoT)
+  int nt, np, ngrp;          // panels, P tiles per wave, groups of d
+  Chunks ch;                 // ch.nch chunks of ch.len columns
   float *S, *pr, *pp, *pq;   // S [G][Mt][Mt]; partials r [G][nch][nt][64], P [G][nch][nt][64][D], q [G][nch][nt][D]
   size_t bytes;
 };
@@ -294,21 +289,14 @@ static MomBwdPlan mom_bwd_plan(void* ws, int G, int Mt, int N, int D) {
   o.nt = cdiv(Mt, kMoT);
   o.np = D <= 64 ? 1 : (D <= 128 ? 2 : kMoBwdNPMax);
   o.ngrp = cdiv(D, 64 * o.np);
-  int64_t want = cdiv(kMoTargetWg, (int64_t)G * o.nt * o.ngrp);
-  const int64_t most = cdiv(N, kMoMinChunk);
   const int64_t per = (int64_t)G * o.nt * kMoT * (D + 1) * (int64_t)sizeof(float);
-  const int64_t fit = (int64_t)kMoBwdBudget / per;
-  want = want < most ? want : most;
-  want = want < fit ? want : fit;
-  want = want < 1 ? 1 : (want > kMoMaxChunks ? kMoMaxChunks : want);
-  o.len = round_up(cdiv(N, want), kMoT);
-  o.nch = cdiv(N, o.len);
+  o.ch = chunk_rule(N, (int64_t)G * o.nt * o.ngrp, (int64_t)kMoBwdBudget / per);
   float* p = reinterpret_cast<float*>(ws);
   auto take = [&](int64_t n) { float* q = p; p += round_up(n, 64); return q; };
   o.S = take((int64_t)G * Mt * Mt);
-  o.pr = take((int64_t)G * o.nch * o.nt * kMoT);
-  o.pp = take((int64_t)G * o.nch * o.nt * kMoT * D);
-  o.pq = take((int64_t)G * o.nch * o.nt * D);
+  o.pr = take((int64_t)G * o.ch.nch * o.nt * kMoT);
+  o.pp = take((int64_t)G * o.ch.nch * o.nt * kMoT * D);
+  o.pq = take((int64_t)G * o.ch.nch * o.nt * D);
   o.bytes = (size_t)((char*)p - (char*)ws);
   return o;
 }
@@ -318,15 +306,6 @@ struct MomBwdArgs {
   float *gZ, *gtheta;
   MomBwdPlan p;
   int G, Mt, N, D;
-};
-
-// -2 dk/dd2 of an epilogue: the RBF's is K itself, the Matern's matern_w
-template <class EPI> struct MomBwdW;
-template <> struct MomBwdW<EpiRbf> {
-  static __device__ __forceinline__ float w(float g2, float d2) { return EpiRbf::off(g2, d2); }
-};
-template <int NU2> struct MomBwdW<EpiMatern<NU2>> {
-  static __device__ __forceinline__ float w(float g2, float d2) { return matern_w<NU2>(g2, d2); }
 };
 
 // S = gPhi + gPhi^T.  grid (cdiv(Mt * Mt, 256), G)
@@ -349,15 +328,15 @@ __global__ __launch_bounds__(256) void moments_bwd_kernel(const MomBwdArgs a) {
   __shared__ float wl[kRbfDirectD];
   __shared__ float wn[T], wyn[T], gci[T], cn[T];
   __shared__ float nrm[2][T];                                    // !DIRECT: |a_j|^2, |b|^2
-  __shared__ float cred[4][T];
+  __shared__ float cred[4 * T];
 
   const int Mt = a.Mt, D = a.D, nt = a.p.nt, ngrp = a.p.ngrp;
   const int grp = blockIdx.x % ngrp, pc = blockIdx.x / ngrp;
   const int chunk = pc / nt, ti = pc - chunk * nt;
   const int i0 = ti * T, dg0 = grp * 64 * NP;
   const int64_t g = blockIdx.y;
-  const int64_t cbeg = (int64_t)chunk * a.p.len;
-  const int64_t cend = cbeg + a.p.len < a.N ? cbeg + a.p.len : a.N;
+  const int64_t cbeg = (int64_t)chunk * a.p.ch.len;
+  const int64_t cend = cbeg + a.p.ch.len < a.N ? cbeg + a.p.ch.len : a.N;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32, l31 = lane & 31, h = lane >> 5;
   const float g2 = expf(2.f * a.theta[D]);
@@ -431,7 +410,7 @@ __global__ __launch_bounds__(256) void moments_bwd_kernel(const MomBwdArgs a) {
         for (int q = 0; q < 16; ++q) {
           const bool ok = n0 + 16 * wave + q < cend;
           Ks[(16 * wave + q) * LD + lane] = ok ? EPI::off(g2, d2[q]) : 0.f;
-          if (own) Vs[(16 * wave + q) * LD + lane] = ok ? MomBwdW<EPI>::w(g2, d2[q]) : 0.f;
+          if (own) Vs[(16 * wave + q) * LD + lane] = ok ? EpiDk<EPI>::w(g2, d2[q]) : 0.f;
         }
       } else {
         float* Aj = stage;
@@ -470,14 +449,12 @@ __global__ __launch_bounds__(256) void moments_bwd_kernel(const MomBwdArgs a) {
           const int row = wr + (r & 3) + 8 * (r >> 2) + 4 * h;
           const float d2 = nrm[0][row] + nb - 2.f * dj[r];
           Ks[col * LD + row] = cok ? EPI::off(g2, d2) : 0.f;
-          if (own) Vs[col * LD + row] = cok ? MomBwdW<EPI>::w(g2, d2) : 0.f;
+          if (own) Vs[col * LD + row] = cok ? EpiDk<EPI>::w(g2, d2) : 0.f;
         }
       }
       __syncthreads();
       // gK_i += S_ij K_j: A = S_ij [row][k], B = K_j [k][n]
-#pragma unroll
-      for (int kk = 0; kk < T; kk += 2)
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Ss[(kk + h) * LD + wr + l31], Ks[(wc + l31) * LD + kk + h], acc, 0, 0, 0);
+      acc = sk_tile(acc, Ss, Ks, LD, wr + l31, wc + l31, h);
       __syncthreads();
     }
 
@@ -502,10 +479,10 @@ __global__ __launch_bounds__(256) void moments_bwd_kernel(const MomBwdArgs a) {
       float t = 0.f;
 #pragma unroll
       for (int q = 0; q < 16; ++q) t += Vs[n * LD + 16 * qd + q];
-      cred[qd][n] = t;
+      cred[qd * T + n] = t;
     }
     __syncthreads();
-    if (tid < T) cn[tid] = (cred[0][tid] + cred[1][tid]) + (cred[2][tid] + cred[3][tid]);
+    if (tid < T) cn[tid] = wave4_sum(cred, tid);
 
     // P_i += V_i X, 64 values of d at a time; waves as (row half, half of the 64 values)
     const int pr = (wave & 1) * 32, pd = (wave >> 1) * 32;
@@ -533,7 +510,7 @@ __global__ __launch_bounds__(256) void moments_bwd_kernel(const MomBwdArgs a) {
     __syncthreads();
   }
 
-  const int64_t part = (g * a.p.nch + chunk) * nt + ti;
+  const int64_t part = (g * a.p.ch.nch + chunk) * nt + ti;
   {
     const int pr = (wave & 1) * 32, pd = (wave >> 1) * 32;
     float* out = a.p.pp + part * T * D;
@@ -549,16 +526,16 @@ __global__ __launch_bounds__(256) void moments_bwd_kernel(const MomBwdArgs a) {
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
     __syncthreads();
-    cred[wave][lane] = qacc[p];
+    cred[wave * T + lane] = qacc[p];
     __syncthreads();
     const int d = dg0 + p * 64 + tid;
-    if (tid < T && d < D) a.p.pq[part * D + d] = (cred[0][tid] + cred[1][tid]) + (cred[2][tid] + cred[3][tid]);
+    if (tid < T && d < D) a.p.pq[part * D + d] = wave4_sum(cred, tid);
   }
   if (grp == 0) {
     __syncthreads();
-    cred[wave][lane] = racc;
+    cred[wave * T + lane] = racc;
     __syncthreads();
-    if (tid < T) a.p.pr[part * T + tid] = (cred[0][tid] + cred[1][tid]) + (cred[2][tid] + cred[3][tid]);
+    if (tid < T) a.p.pr[part * T + tid] = wave4_sum(cred, tid);
   }
 }
 
@@ -567,46 +544,21 @@ __global__ __launch_bounds__(256) void moments_bwd_kernel(const MomBwdArgs a) {
 __global__ __launch_bounds__(256) void moments_bwd_reduce_kernel(const MomBwdArgs a) {
   constexpr int T = kMoT;
   __shared__ double red[256];
-  const int Mt = a.Mt, D = a.D, nt = a.p.nt, nch = a.p.nch, tid = threadIdx.x;
+  const int Mt = a.Mt, D = a.D, nt = a.p.nt, nch = a.p.ch.nch, tid = threadIdx.x;
   const int64_t total = (int64_t)a.G * Mt * D;
   const int nz = (int)((total + 255) / 256);
-  auto rp = [&](int64_t g, int m, int d, double& r, double& P) {
-    const int64_t at = (g * nch * nt + m / T) * T + m % T, step = (int64_t)nt * T;
-    r = 0.0; P = 0.0;
-    for (int q = 0; q < nch; ++q) { r += (double)a.p.pr[at + q * step]; P += (double)a.p.pp[(at + q * step) * D + d]; }
-  };
+  const BwdPartials b{a.p.pr, a.p.pp, a.p.pq, nch, nt * T, nt};
   if ((int)blockIdx.x < nz) {
     const int64_t e = (int64_t)blockIdx.x * 256 + tid;
-    if (e >= total) return;
-    const int d = (int)(e % D);
-    const int64_t gm = e / D;
-    const int m = (int)(gm % Mt);
-    double r, P;
-    rp(gm / Mt, m, d, r, P);
-    a.gZ[e] = (float)(-exp(-2.0 * (double)a.theta[d]) * (r * (double)a.Z[e] - P));
+    if (e < total) gz_entry(b, a.theta, a.Z, a.gZ, e, Mt, D);
     return;
   }
-  const int d = blockIdx.x - nz;
-  double s = 0.0;
-  for (int64_t gm = tid; gm < (int64_t)a.G * Mt; gm += 256) {
-    double r, P;
-    rp(gm / Mt, (int)(gm % Mt), d, r, P);
-    const double z = (double)a.Z[gm * D + d];
-    s += z * (r * z - 2.0 * P);
-  }
-  for (int64_t e = tid; e < (int64_t)a.G * nch * nt; e += 256) s += (double)a.p.pq[e * D + d];
-  red[tid] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) a.gtheta[d] = (float)(exp(-2.0 * (double)a.theta[d]) * red[0]);
+  gtheta_d_block(b, a.theta, a.Z, a.gtheta, red, blockIdx.x - nz, a.G, Mt, D);
 }
 
 template <class EPI>
 static void moments_bwd_launch(const MomBwdArgs& a, hipStream_t st) {
-  const dim3 grid(a.p.nch * a.p.nt * a.p.ngrp, a.G), blk(256);
+  const dim3 grid(a.p.ch.nch * a.p.nt * a.p.ngrp, a.G), blk(256);
   if (a.D <= kRbfDirectD) hipLaunchKernelGGL((moments_bwd_kernel<EPI, true, 1>), grid, blk, 0, st, a);
   else if (a.p.np == 1) hipLaunchKernelGGL((moments_bwd_kernel<EPI, false, 1>), grid, blk, 0, st, a);
   else if (a.p.np == 2) hipLaunchKernelGGL((moments_bwd_kernel<EPI, false, 2>), grid, blk, 0, st, a);
@@ -619,7 +571,7 @@ using namespace vargp;
 
 extern "C" int vargp_gram_moments_bwd_chunks(int G, int Mt, int N, int D) {
   if (G <= 0 || Mt <= 0 || N <= 0 || D <= 0) return 0;
-  return mom_bwd_plan(nullptr, G, Mt, N, D).nch;
+  return mom_bwd_plan(nullptr, G, Mt, N, D).ch.nch;
 }
 
 extern "C" size_t vargp_gram_moments_bwd_workspace_bytes(int G, int Mt, int N, int D) {
@@ -639,24 +591,19 @@ extern "C" int vargp_gram_moments_bwd(const float* theta, const float* Z, const 
   a.theta = theta; a.Z = Z; a.X = X; a.w = w; a.y = y; a.gPhi = gPhi; a.gc = gc; a.gZ = gZ; a.gtheta = gtheta;
   a.p = mom_bwd_plan(ws, G, Mt, N, D);
   a.G = G; a.Mt = Mt; a.N = N; a.D = D;
-  VARGP_REQUIRE((int64_t)a.p.nch * a.p.nt * a.p.ngrp < (1ll << 31) && (int64_t)G * Mt * D / 256 + D < (1ll << 31) - 1,
+  VARGP_REQUIRE((int64_t)a.p.ch.nch * a.p.nt * a.p.ngrp < (1ll << 31) && (int64_t)G * Mt * D / 256 + D < (1ll << 31) - 1,
                 "gram_moments_bwd: Mt = %d, D = %d need too many workgroups", Mt, D);
   hipStream_t st = as_stream(stream);
   ProfScope whole("gram_moments_bwd", st);
   hipLaunchKernelGGL(moments_bwd_sym_kernel, dim3(cdiv((int64_t)Mt * Mt, 256), G), dim3(256), 0, st, a);
-  switch (nu2) {
-    case 0: moments_bwd_launch<EpiRbf>(a, st); break;
-    case 1: moments_bwd_launch<EpiMatern<1>>(a, st); break;
-    case 3: moments_bwd_launch<EpiMatern<3>>(a, st); break;
-    default: moments_bwd_launch<EpiMatern<5>>(a, st); break;
-  }
+  with_epi(nu2, [&](auto epi) { moments_bwd_launch<decltype(epi)>(a, st); });
   hipLaunchKernelGGL(moments_bwd_reduce_kernel, dim3(cdiv((int64_t)G * Mt * D, 256) + D), dim3(256), 0, st, a);
   return check_launch("gram_moments_bwd");
 }
 
 extern "C" int vargp_gram_moments_chunks(int G, int Mt, int N, int D) {
   if (G <= 0 || Mt <= 0 || N <= 0 || D <= 0) return 0;
-  return mom_plan(nullptr, G, Mt, N).nch;
+  return mom_plan(nullptr, G, Mt, N).ch.nch;
 }
 
 extern "C" size_t vargp_gram_moments_workspace_bytes(int G, int Mt, int N, int D) {
@@ -676,15 +623,10 @@ extern "C" int vargp_gram_moments(const float* theta, const float* Z, const floa
   a.theta = theta; a.Z = Z; a.X = X; a.w = w; a.y = y; a.Phi = Phi; a.c = c; a.sums = sums;
   a.p = mom_plan(ws, G, Mt, N);
   a.G = G; a.Mt = Mt; a.N = N; a.D = D;
-  VARGP_REQUIRE((int64_t)a.p.ntri * a.p.nch < (1ll << 31), "gram_moments: Mt = %d needs too many tiles", Mt);
+  VARGP_REQUIRE((int64_t)a.p.ntri * a.p.ch.nch < (1ll << 31), "gram_moments: Mt = %d needs too many tiles", Mt);
   hipStream_t st = as_stream(stream);
   ProfScope whole("gram_moments", st);
-  switch (nu2) {
-    case 0: moments_launch<EpiRbf>(a, st); break;
-    case 1: moments_launch<EpiMatern<1>>(a, st); break;
-    case 3: moments_launch<EpiMatern<3>>(a, st); break;
-    default: moments_launch<EpiMatern<5>>(a, st); break;
-  }
+  with_epi(nu2, [&](auto epi) { moments_launch<decltype(epi)>(a, st); });
   hipLaunchKernelGGL(moments_reduce_kernel, dim3(a.p.ntri * 16 + cdiv(Mt, 256) + 1, G), dim3(256), 0, st, a);
   return check_launch("gram_moments");
 }

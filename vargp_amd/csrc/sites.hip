@@ -12,16 +12,14 @@
 // which is coalesced and the same quadratic form) is multiplied with panel j of K by 32 v_mfma_f32_32x32x2_f32 per wave (four waves
 // as 2 x 2), and the accumulators of (Q K)_i are reduced against panel i of K over the rows.  One wave then evaluates the
 // likelihood for the 64 points, and all four add lam1 K to the accumulators of c, which stay in registers for the whole chunk.
-// The block needs Mt <= kSiMaxMt (moments_plan.h): 64 (Mt + 1) floats of the at most 160 KB of LDS; above it there is no fused
+// The block needs Mt <= kSiMaxMt (dataset_pass.h): 64 (Mt + 1) floats of the at most 160 KB of LDS; above it there is no fused
 // pass (sites.py composes the same quantities from the per-op kernels).
 // A point of weight 0 is never evaluated: it adds exactly nothing whatever its row of X and its target hold (K is finite for
 // finite inputs; the likelihood's derivatives need not be).  Columns behind the end of the chunk are masked as in moments.hip.
 // No atomics.  A second launch adds the chunks' partials in ascending chunk order in fp64 and rounds once: two calls on the same
 // input are bitwise equal.  The chunking depends on the shapes alone (site_plan).
-#include <atomic>
-
+#include "dataset_pass.h"
 #include "lik.h"
-#include "moments_plan.h"
 
 namespace vargp {
 
@@ -39,8 +37,8 @@ static constexpr size_t site_lds_floats(int nt) {
 static_assert(site_lds_floats(kSiMaxNt) * sizeof(float) <= 160 * 1024, "the K block of kSiMaxMt rows must fit the LDS");
 
 struct SitePlan {
-  int nt, nch;               // 64-row panels, chunks
-  int64_t len;               // columns per chunk (a multiple of kMoT)
+  int nt;                    // 64-row panels
+  Chunks ch;                 // ch.nch chunks of ch.len columns
   double* ps;                // partials of sums [G][nch][4]
   float* pc;                 // partials of c [G][nch][nt * 64]
   size_t bytes;
@@ -49,17 +47,12 @@ struct SitePlan {
 static SitePlan site_plan(void* ws, int G, int Mt, int N) {
   SitePlan o{};
   o.nt = cdiv(Mt, kMoT);
-  int64_t want = cdiv(kMoTargetWg, G);
-  const int64_t most = cdiv(N, kMoMinChunk);
-  want = want < most ? want : most;
-  want = want < 1 ? 1 : (want > kMoMaxChunks ? kMoMaxChunks : want);
-  o.len = round_up(cdiv(N, want), kMoT);
-  o.nch = cdiv(N, o.len);
+  o.ch = chunk_rule(N, G);
   char* p = reinterpret_cast<char*>(ws);
   o.ps = reinterpret_cast<double*>(p);
-  p += round_up((int64_t)G * o.nch * 4 * (int64_t)sizeof(double), 256);
+  p += round_up((int64_t)G * o.ch.nch * 4 * (int64_t)sizeof(double), 256);
   o.pc = reinterpret_cast<float*>(p);
-  p += round_up((int64_t)G * o.nch * o.nt * kMoT * (int64_t)sizeof(float), 256);
+  p += round_up((int64_t)G * o.ch.nch * o.nt * kMoT * (int64_t)sizeof(float), 256);
   o.bytes = (size_t)(p - reinterpret_cast<char*>(ws));
   return o;
 }
@@ -91,8 +84,8 @@ __global__ __launch_bounds__(256) void site_kernel(const SiteArgs a, const typen
 
   const int chunk = blockIdx.x;
   const int64_t g = blockIdx.y;
-  const int64_t cbeg = (int64_t)chunk * a.p.len;
-  const int64_t cend = cbeg + a.p.len < a.N ? cbeg + a.p.len : a.N;
+  const int64_t cbeg = (int64_t)chunk * a.p.ch.len;
+  const int64_t cend = cbeg + a.p.ch.len < a.N ? cbeg + a.p.ch.len : a.N;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32, l31 = lane & 31, h = lane >> 5;
   const float g2 = expf(2.f * a.theta[D]);
@@ -209,9 +202,7 @@ __global__ __launch_bounds__(256) void site_kernel(const SiteArgs a, const typen
           Ss[k * LD + r] = (i0 + r < Mt && j0 + k < Mt) ? Qg[(int64_t)(j0 + k) * Mt + i0 + r] : 0.f;
         }
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < T; kk += 2)
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Ss[(kk + h) * LD + wr + l31], Ks[(wc + l31) * LDK + j0 + kk + h], acc, 0, 0, 0);
+        acc = sk_tile(acc, Ss, Ks + j0, LDK, wr + l31, wc + l31, h);
         __syncthreads();
       }
       const float* kc = Ks + (wc + l31) * LDK + i0 + wr + 4 * h;
@@ -225,7 +216,7 @@ __global__ __launch_bounds__(256) void site_kernel(const SiteArgs a, const typen
     // ---- the likelihood of the step's points: one wave, a point per lane
     if (tid < T) {
       const int64_t n = n0 + tid;
-      const float mu = (cred[tid] + cred[T + tid]) + (cred[2 * T + tid] + cred[3 * T + tid]);
+      const float mu = wave4_sum(cred, tid);
       const float quad = qred[(tid >> 5) * 32 + (tid & 31)] + qred[((tid >> 5) + 2) * 32 + (tid & 31)];
       const float var = fmaxf(g2 - quad, 0.f);
       float l1 = 0.f;
@@ -263,14 +254,14 @@ __global__ __launch_bounds__(256) void site_kernel(const SiteArgs a, const typen
     __syncthreads();
   }
 
-  const int64_t part = g * a.p.nch + chunk;
+  const int64_t part = g * a.p.ch.nch + chunk;
 #pragma unroll
   for (int p = 0; p < kSiMaxNt; ++p) {
     if (p < nt) {
       __syncthreads();
       cred[wave * T + lane] = cacc[p];
       __syncthreads();
-      if (tid < T) a.p.pc[(part * nt + p) * T + tid] = (cred[tid] + cred[T + tid]) + (cred[2 * T + tid] + cred[3 * T + tid]);
+      if (tid < T) a.p.pc[(part * nt + p) * T + tid] = wave4_sum(cred, tid);
     }
   }
   if (wave == 0) {
@@ -288,7 +279,7 @@ __global__ __launch_bounds__(256) void site_kernel(const SiteArgs a, const typen
 // The chunks' partials in ascending chunk order, in fp64.  grid (cdiv(Mt, 256) + 1, G): 256 entries of c | the four sums
 __global__ __launch_bounds__(256) void site_reduce_kernel(const SiteArgs a) {
   constexpr int T = kMoT;
-  const int Mt = a.Mt, nch = a.p.nch, nt = a.p.nt;
+  const int Mt = a.Mt, nch = a.p.ch.nch, nt = a.p.nt;
   const int64_t g = blockIdx.y;
   const int b = blockIdx.x, tid = threadIdx.x;
   if (b < (Mt + 255) / 256) {
@@ -306,37 +297,20 @@ __global__ __launch_bounds__(256) void site_reduce_kernel(const SiteArgs a) {
   }
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is per device and per kernel: one mask per instantiation
 template <class LIK, class EPI, bool DIRECT>
 static int site_launch_form(const SiteArgs& a, const typename LIK::Args& la, hipStream_t st) {
-  static std::atomic<unsigned> attr_mask[2] = {};
-  const size_t lds = site_lds_floats(kSiMaxNt) * sizeof(float);
-  int dev = 0;
-  VARGP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "site_moments: hipGetDevice failed");
-  if (!((attr_mask[dev >> 5].load(std::memory_order_acquire) >> (dev & 31)) & 1u)) {
-    VARGP_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(site_kernel<LIK, EPI, DIRECT>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
-                  "site_moments: cannot reserve %zu bytes of LDS", lds);
-    attr_mask[dev >> 5].fetch_or(1u << (dev & 31), std::memory_order_release);
-  }
-  hipLaunchKernelGGL((site_kernel<LIK, EPI, DIRECT>), dim3(a.p.nch, a.G), dim3(256), site_lds_floats(a.p.nt) * sizeof(float), st, a,
-                     la);
+  constexpr auto kernel = site_kernel<LIK, EPI, DIRECT>;
+  if (int rc = reserve_dynamic_lds<kernel>(site_lds_floats(kSiMaxNt) * sizeof(float), "site_moments")) return rc;
+  hipLaunchKernelGGL(kernel, dim3(a.p.ch.nch, a.G), dim3(256), site_lds_floats(a.p.nt) * sizeof(float), st, a, la);
   return VARGP_OK;
-}
-
-template <class LIK, class EPI>
-static int site_launch_epi(const SiteArgs& a, const typename LIK::Args& la, hipStream_t st) {
-  return a.D <= kRbfDirectD ? site_launch_form<LIK, EPI, true>(a, la, st) : site_launch_form<LIK, EPI, false>(a, la, st);
 }
 
 template <class LIK>
 static int site_launch(const SiteArgs& a, const typename LIK::Args& la, int nu2, hipStream_t st) {
-  switch (nu2) {
-    case 0: return site_launch_epi<LIK, EpiRbf>(a, la, st);
-    case 1: return site_launch_epi<LIK, EpiMatern<1>>(a, la, st);
-    case 3: return site_launch_epi<LIK, EpiMatern<3>>(a, la, st);
-    default: return site_launch_epi<LIK, EpiMatern<5>>(a, la, st);
-  }
+  return with_epi(nu2, [&](auto epi) {
+    using EPI = decltype(epi);
+    return a.D <= kRbfDirectD ? site_launch_form<LIK, EPI, true>(a, la, st) : site_launch_form<LIK, EPI, false>(a, la, st);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -376,8 +350,8 @@ static constexpr size_t site_bwd_lds_floats(int nt) {
 static_assert(site_bwd_lds_floats(kSiMaxNt) * sizeof(float) <= 160 * 1024, "the K and V blocks of kSiMaxMt rows must fit the LDS");
 
 struct SiteBwdPlan {
-  int nt, nch, np, ngrp;     // panels, chunks, tiles of d per group, groups of d
-  int64_t len;               // columns per chunk (a multiple of kMoT)
+  int nt, np, ngrp;          // panels, tiles of d per group, groups of d
+  Chunks ch;                 // ch.nch chunks of ch.len columns
   double* ps;                // partials of (gtheta_D, gls) [G][nch][2]
   float *pr, *pa, *pq, *pp;  // partials r [G][nch][nt * 64], galpha alike, q [G][nch][D], P [G][nch][nt * 64][D]
   size_t bytes;
@@ -388,18 +362,11 @@ static SiteBwdPlan site_bwd_plan(void* ws, int G, int Mt, int N, int D) {
   o.nt = cdiv(Mt, kMoT);
   o.np = D <= kRbfDirectD ? 1 : kSbNPMax;
   o.ngrp = cdiv(D, 64 * o.np);
-  int64_t want = cdiv(kMoTargetWg, (int64_t)G * o.ngrp);
-  const int64_t most = cdiv(N, kMoMinChunk);
   const int64_t per = (int64_t)G * o.nt * kMoT * (D + 2) * (int64_t)sizeof(float);
-  const int64_t fit = (int64_t)kSbBudget / per;
-  want = want < most ? want : most;
-  want = want < fit ? want : fit;
-  want = want < 1 ? 1 : (want > kMoMaxChunks ? kMoMaxChunks : want);
-  o.len = round_up(cdiv(N, want), kMoT);
-  o.nch = cdiv(N, o.len);
+  o.ch = chunk_rule(N, (int64_t)G * o.ngrp, (int64_t)kSbBudget / per);
   char* p = reinterpret_cast<char*>(ws);
   auto take = [&](int64_t bytes) { char* q = p; p += round_up(bytes, 256); return q; };
-  const int64_t parts = (int64_t)G * o.nch, f = sizeof(float);
+  const int64_t parts = (int64_t)G * o.ch.nch, f = sizeof(float);
   o.ps = reinterpret_cast<double*>(take(parts * 2 * (int64_t)sizeof(double)));
   o.pr = reinterpret_cast<float*>(take(parts * o.nt * kMoT * f));
   o.pa = reinterpret_cast<float*>(take(parts * o.nt * kMoT * f));
@@ -414,15 +381,6 @@ struct SiteBwdArgs {
   float *gZ, *gtheta, *galpha, *gv, *gls;
   SiteBwdPlan p;
   int G, Mt, N, D;
-};
-
-// -2 dk/dd2 of an epilogue: the RBF's is K itself, the Matern's matern_w
-template <class EPI> struct SiteBwdW;
-template <> struct SiteBwdW<EpiRbf> {
-  static __device__ __forceinline__ float w(float g2, float d2) { return EpiRbf::off(g2, d2); }
-};
-template <int NU2> struct SiteBwdW<EpiMatern<NU2>> {
-  static __device__ __forceinline__ float w(float g2, float d2) { return matern_w<NU2>(g2, d2); }
 };
 
 // grid (nch * ngrp, G): blockIdx.x = chunk * ngrp + group
@@ -449,8 +407,8 @@ __global__ __launch_bounds__(256) void site_bwd_kernel(const SiteBwdArgs a, cons
   const int grp = blockIdx.x % ngrp, chunk = blockIdx.x / ngrp;
   const int dg0 = grp * 64 * NP;
   const int64_t g = blockIdx.y;
-  const int64_t cbeg = (int64_t)chunk * a.p.len;
-  const int64_t cend = cbeg + a.p.len < a.N ? cbeg + a.p.len : a.N;
+  const int64_t cbeg = (int64_t)chunk * a.p.ch.len;
+  const int64_t cend = cbeg + a.p.ch.len < a.N ? cbeg + a.p.ch.len : a.N;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32, l31 = lane & 31, h = lane >> 5;
   const int pr = (wave & 1) * 32, pd = (wave >> 1) * 32;
@@ -520,7 +478,7 @@ __global__ __launch_bounds__(256) void site_bwd_kernel(const SiteBwdArgs a, cons
         for (int q = 0; q < 16; ++q) {
           const bool ok = rok && cok[16 * wave + q] != 0.f;
           Ks[(16 * wave + q) * LDK + j0 + lane] = ok ? EPI::off(g2, d2[q]) : 0.f;
-          Vs[(16 * wave + q) * LDK + j0 + lane] = ok ? SiteBwdW<EPI>::w(g2, d2[q]) : 0.f;
+          Vs[(16 * wave + q) * LDK + j0 + lane] = ok ? EpiDk<EPI>::w(g2, d2[q]) : 0.f;
         }
       } else {
         float* Aj = stage;
@@ -560,7 +518,7 @@ __global__ __launch_bounds__(256) void site_bwd_kernel(const SiteBwdArgs a, cons
           const bool ok = cl && j0 + row < Mt;
           const float d2 = nrm[row] + nb - 2.f * dj[r];
           Ks[col * LDK + j0 + row] = ok ? EPI::off(g2, d2) : 0.f;
-          Vs[col * LDK + j0 + row] = ok ? SiteBwdW<EPI>::w(g2, d2) : 0.f;
+          Vs[col * LDK + j0 + row] = ok ? EpiDk<EPI>::w(g2, d2) : 0.f;
         }
       }
       __syncthreads();
@@ -593,6 +551,7 @@ __global__ __launch_bounds__(256) void site_bwd_kernel(const SiteBwdArgs a, cons
                                  : 0.f;
           }
           __syncthreads();
+          // (sk_tile's loop, written out: through the shared piece this kernel measured 0.7 % slower at D = 784)
 #pragma unroll
           for (int kk = 0; kk < T; kk += 2)
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Ss[(kk + h) * LD + wr + l31], Ks[(wc + l31) * LDK + j0 + kk + h], acc, 0, 0, 0);
@@ -611,7 +570,7 @@ __global__ __launch_bounds__(256) void site_bwd_kernel(const SiteBwdArgs a, cons
     // ---- the likelihood of the step's points: one wave, a point per lane
     if (tid < T) {
       const int64_t n = n0 + tid;
-      const float mu = (cred[tid] + cred[T + tid]) + (cred[2 * T + tid] + cred[3 * T + tid]);
+      const float mu = wave4_sum(cred, tid);
       const float quad = qred[(tid >> 5) * 32 + (tid & 31)] + qred[((tid >> 5) + 2) * 32 + (tid & 31)];
       const float var = fmaxf(g2 - quad, 0.f);
       float gm = 0.f, gv = 0.f;
@@ -671,7 +630,7 @@ __global__ __launch_bounds__(256) void site_bwd_kernel(const SiteBwdArgs a, cons
       cred[qd * T + n] = t;
     }
     __syncthreads();
-    if (tid < T) cn[tid] = (cred[tid] + cred[T + tid]) + (cred[2 * T + tid] + cred[3 * T + tid]);
+    if (tid < T) cn[tid] = wave4_sum(cred, tid);
 
     // ---- P += V X, 64 values of d at a time; waves as (row half, half of the 64 values)
 #pragma unroll
@@ -704,7 +663,7 @@ __global__ __launch_bounds__(256) void site_bwd_kernel(const SiteBwdArgs a, cons
     __syncthreads();
   }
 
-  const int64_t part = g * a.p.nch + chunk;
+  const int64_t part = g * a.p.ch.nch + chunk;
 #pragma unroll
   for (int t = 0; t < NP; ++t) {
     const int d = dg0 + t * 64 + pd + l31;
@@ -725,7 +684,7 @@ __global__ __launch_bounds__(256) void site_bwd_kernel(const SiteBwdArgs a, cons
     cred[wave * T + lane] = qacc[t];
     __syncthreads();
     const int d = dg0 + t * 64 + tid;
-    if (tid < T && d < D) a.p.pq[part * D + d] = (cred[tid] + cred[T + tid]) + (cred[2 * T + tid] + cred[3 * T + tid]);
+    if (tid < T && d < D) a.p.pq[part * D + d] = wave4_sum(cred, tid);
   }
   if (grp != 0) return;
 #pragma unroll
@@ -736,8 +695,8 @@ __global__ __launch_bounds__(256) void site_bwd_kernel(const SiteBwdArgs a, cons
       qred[wave * T + lane] = racc[p];
       __syncthreads();
       if (tid < T) {
-        a.p.pa[(part * nt + p) * T + tid] = (cred[tid] + cred[T + tid]) + (cred[2 * T + tid] + cred[3 * T + tid]);
-        a.p.pr[(part * nt + p) * T + tid] = (qred[tid] + qred[T + tid]) + (qred[2 * T + tid] + qred[3 * T + tid]);
+        a.p.pa[(part * nt + p) * T + tid] = wave4_sum(cred, tid);
+        a.p.pr[(part * nt + p) * T + tid] = wave4_sum(qred, tid);
       }
     }
   }
@@ -754,44 +713,16 @@ __global__ __launch_bounds__(256) void site_bwd_kernel(const SiteBwdArgs a, cons
 __global__ __launch_bounds__(256) void site_bwd_reduce_kernel(const SiteBwdArgs a) {
   constexpr int T = kMoT;
   __shared__ double red[256];
-  const int Mt = a.Mt, D = a.D, MtP = a.p.nt * T, nch = a.p.nch, tid = threadIdx.x;
+  const int Mt = a.Mt, D = a.D, MtP = a.p.nt * T, nch = a.p.ch.nch, tid = threadIdx.x;
   const int64_t total = (int64_t)a.G * Mt * D, rows = (int64_t)a.G * Mt;
   const int64_t nz = (total + 255) / 256, na = (rows + 255) / 256;
   const int64_t b = blockIdx.x;
-  auto rp = [&](int64_t g, int m, int d, double& r, double& P) {
-    const int64_t at = g * nch * MtP + m;
-    r = 0.0; P = 0.0;
-    for (int q = 0; q < nch; ++q) { r += (double)a.p.pr[at + (int64_t)q * MtP]; P += (double)a.p.pp[(at + (int64_t)q * MtP) * D + d]; }
-  };
-  auto tree = [&](double s) {
-    red[tid] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if (tid < o) red[tid] += red[tid + o];
-      __syncthreads();
-    }
-    return red[0];
-  };
+  const BwdPartials part{a.p.pr, a.p.pp, a.p.pq, nch, MtP, 1};
   if (b < nz) {
     const int64_t e = b * 256 + tid;
-    if (e >= total) return;
-    const int d = (int)(e % D);
-    const int64_t gm = e / D;
-    double r, P;
-    rp(gm / Mt, (int)(gm % Mt), d, r, P);
-    a.gZ[e] = (float)(-exp(-2.0 * (double)a.theta[d]) * (r * (double)a.Z[e] - P));
+    if (e < total) gz_entry(part, a.theta, a.Z, a.gZ, e, Mt, D);
   } else if (b < nz + D) {
-    const int d = (int)(b - nz);
-    double s = 0.0;
-    for (int64_t gm = tid; gm < rows; gm += 256) {
-      double r, P;
-      rp(gm / Mt, (int)(gm % Mt), d, r, P);
-      const double z = (double)a.Z[gm * D + d];
-      s += z * (r * z - 2.0 * P);
-    }
-    for (int64_t e = tid; e < (int64_t)a.G * nch; e += 256) s += (double)a.p.pq[e * D + d];
-    s = tree(s);
-    if (tid == 0) a.gtheta[d] = (float)(exp(-2.0 * (double)a.theta[d]) * s);
+    gtheta_d_block(part, a.theta, a.Z, a.gtheta, red, (int)(b - nz), a.G, Mt, D);
   } else if (b < nz + D + na) {
     const int64_t gm = (b - nz - D) * 256 + tid;
     if (gm >= rows) return;
@@ -802,7 +733,7 @@ __global__ __launch_bounds__(256) void site_bwd_reduce_kernel(const SiteBwdArgs 
   } else {
     double s = 0.0;
     for (int64_t e = tid; e < (int64_t)a.G * nch; e += 256) s += a.p.ps[2 * e];
-    s = tree(s);
+    s = block_tree_sum(red, s);
     if (tid == 0) a.gtheta[D] = (float)s;
     if (a.gls) {
       for (int64_t g = tid; g < a.G; g += 256) {
@@ -814,38 +745,50 @@ __global__ __launch_bounds__(256) void site_bwd_reduce_kernel(const SiteBwdArgs 
   }
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is per device and per kernel: one mask per instantiation
 template <class LIK, class EPI, bool DIRECT, int NP>
 static int site_bwd_launch_form(const SiteBwdArgs& a, const typename LIK::Args& la, hipStream_t st) {
-  static std::atomic<unsigned> attr_mask[2] = {};
-  const size_t lds = site_bwd_lds_floats(kSiMaxNt) * sizeof(float);
-  int dev = 0;
-  VARGP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "site_bound_bwd: hipGetDevice failed");
-  if (!((attr_mask[dev >> 5].load(std::memory_order_acquire) >> (dev & 31)) & 1u)) {
-    VARGP_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(site_bwd_kernel<LIK, EPI, DIRECT, NP>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
-                  "site_bound_bwd: cannot reserve %zu bytes of LDS", lds);
-    attr_mask[dev >> 5].fetch_or(1u << (dev & 31), std::memory_order_release);
-  }
-  hipLaunchKernelGGL((site_bwd_kernel<LIK, EPI, DIRECT, NP>), dim3(a.p.nch * a.p.ngrp, a.G), dim3(256),
-                     site_bwd_lds_floats(a.p.nt) * sizeof(float), st, a, la);
+  constexpr auto kernel = site_bwd_kernel<LIK, EPI, DIRECT, NP>;
+  if (int rc = reserve_dynamic_lds<kernel>(site_bwd_lds_floats(kSiMaxNt) * sizeof(float), "site_bound_bwd")) return rc;
+  hipLaunchKernelGGL(kernel, dim3(a.p.ch.nch * a.p.ngrp, a.G), dim3(256), site_bwd_lds_floats(a.p.nt) * sizeof(float), st, a, la);
   return VARGP_OK;
-}
-
-template <class LIK, class EPI>
-static int site_bwd_launch_epi(const SiteBwdArgs& a, const typename LIK::Args& la, hipStream_t st) {
-  return a.D <= kRbfDirectD ? site_bwd_launch_form<LIK, EPI, true, 1>(a, la, st)
-                            : site_bwd_launch_form<LIK, EPI, false, kSbNPMax>(a, la, st);
 }
 
 template <class LIK>
 static int site_bwd_launch(const SiteBwdArgs& a, const typename LIK::Args& la, int nu2, hipStream_t st) {
-  switch (nu2) {
-    case 0: return site_bwd_launch_epi<LIK, EpiRbf>(a, la, st);
-    case 1: return site_bwd_launch_epi<LIK, EpiMatern<1>>(a, la, st);
-    case 3: return site_bwd_launch_epi<LIK, EpiMatern<3>>(a, la, st);
-    default: return site_bwd_launch_epi<LIK, EpiMatern<5>>(a, la, st);
+  return with_epi(nu2, [&](auto epi) {
+    using EPI = decltype(epi);
+    return a.D <= kRbfDirectD ? site_bwd_launch_form<LIK, EPI, true, 1>(a, la, st)
+                              : site_bwd_launch_form<LIK, EPI, false, kSbNPMax>(a, la, st);
+  });
+}
+
+// f(LIK{}, its Args) for the likelihood a (checked) kind names
+template <class F>
+static int with_site_lik(int kind, const float* y, int64_t ldy, const float* log_scale, float df, float lognorm, F f) {
+  switch (kind) {
+    case VARGP_SITE_BERNOULLI_PROBIT: return f(Bernoulli<LinkProbit>{}, Bernoulli<LinkProbit>::Args{y, ldy, nullptr});
+    case VARGP_SITE_BERNOULLI_LOGIT: return f(Bernoulli<LinkLogit>{}, Bernoulli<LinkLogit>::Args{y, ldy, nullptr});
+    case VARGP_SITE_POISSON: return f(Poisson{}, Poisson::Args{{y, ldy}});
+    default: return f(StudentT{}, StudentT::Args{{y, ldy}, log_scale, df, lognorm});
   }
+}
+
+// The argument checks of both entries, in one order.  ptrs: all of the entry's required pointers are there; st_ok / st_needs: what
+// the entry asks of a Student-t call
+static int site_check_args(const char* name, bool ptrs, int64_t ldy, int kind, bool st_ok, const char* st_needs, int G, int Mt, int N,
+                           int D, int nu2, const void* ws, size_t ws_bytes, size_t ws_need) {
+  VARGP_REQUIRE(ptrs, "%s: null pointer", name);
+  VARGP_REQUIRE(G > 0 && Mt > 0 && N > 0 && D > 0, "%s: bad dims", name);
+  VARGP_REQUIRE(kind >= VARGP_SITE_BERNOULLI_PROBIT && kind <= VARGP_SITE_STUDENTT,
+                "%s: kind = %d (0: Bernoulli probit, 1: Bernoulli logit, 2: Poisson, 3: Student-t)", name, kind);
+  VARGP_REQUIRE(nu2 == 0 || nu2 == 1 || nu2 == 3 || nu2 == 5, "%s: nu2 = %d (0: RBF; 1, 3, 5: Matern)", name, nu2);
+  VARGP_REQUIRE(G <= 65535, "%s: G = %d (at most 65535)", name, G);
+  VARGP_REQUIRE(Mt <= kSiMaxMt, "%s: Mt = %d (at most %d: the K block of all rows lives in LDS)", name, Mt, kSiMaxMt);
+  VARGP_REQUIRE(ldy == 0 || ldy >= N, "%s: ldy must be 0 or >= N", name);
+  VARGP_REQUIRE(kind != VARGP_SITE_STUDENTT || st_ok, "%s: Student-t needs %s", name, st_needs);
+  VARGP_REQUIRE(reinterpret_cast<uintptr_t>(ws) % sizeof(double) == 0, "%s: ws must be 8-byte aligned", name);
+  VARGP_REQUIRE(ws_bytes >= ws_need, "%s: workspace too small", name);
+  return VARGP_OK;
 }
 
 }  // namespace vargp
@@ -854,7 +797,7 @@ using namespace vargp;
 
 extern "C" int vargp_site_bound_bwd_chunks(int G, int Mt, int N, int D) {
   if (G <= 0 || Mt <= 0 || N <= 0 || D <= 0) return 0;
-  return site_bwd_plan(nullptr, G, Mt, N, D).nch;
+  return site_bwd_plan(nullptr, G, Mt, N, D).ch.nch;
 }
 
 extern "C" size_t vargp_site_bound_bwd_workspace_bytes(int G, int Mt, int N, int D) {
@@ -866,35 +809,22 @@ extern "C" int vargp_site_bound_bwd(const float* theta, const float* Z, const fl
                                     const float* y, int64_t ldy, const float* w, int kind, const float* log_scale, float df,
                                     float lognorm, const float* gout, float* gZ, float* gtheta, float* galpha, float* gv, float* gls,
                                     int G, int Mt, int N, int D, int nu2, void* ws, size_t ws_bytes, vargp_stream_t stream) {
-  VARGP_REQUIRE(theta && Z && X && alpha && Q && y && gout && gZ && gtheta && galpha && gv && ws, "site_bound_bwd: null pointer");
-  VARGP_REQUIRE(G > 0 && Mt > 0 && N > 0 && D > 0, "site_bound_bwd: bad dims");
-  VARGP_REQUIRE(kind >= VARGP_SITE_BERNOULLI_PROBIT && kind <= VARGP_SITE_STUDENTT,
-                "site_bound_bwd: kind = %d (0: Bernoulli probit, 1: Bernoulli logit, 2: Poisson, 3: Student-t)", kind);
-  VARGP_REQUIRE(nu2 == 0 || nu2 == 1 || nu2 == 3 || nu2 == 5, "site_bound_bwd: nu2 = %d (0: RBF; 1, 3, 5: Matern)", nu2);
-  VARGP_REQUIRE(G <= 65535, "site_bound_bwd: G = %d (at most 65535)", G);
-  VARGP_REQUIRE(Mt <= kSiMaxMt, "site_bound_bwd: Mt = %d (at most %d: the K block of all rows lives in LDS)", Mt, kSiMaxMt);
-  VARGP_REQUIRE(ldy == 0 || ldy >= N, "site_bound_bwd: ldy must be 0 or >= N");
-  VARGP_REQUIRE(kind != VARGP_SITE_STUDENTT || (log_scale && gls && df > 0.f),
-                "site_bound_bwd: Student-t needs log_scale, gls and df > 0");
-  VARGP_REQUIRE(reinterpret_cast<uintptr_t>(ws) % sizeof(double) == 0, "site_bound_bwd: ws must be 8-byte aligned");
-  VARGP_REQUIRE(ws_bytes >= vargp_site_bound_bwd_workspace_bytes(G, Mt, N, D), "site_bound_bwd: workspace too small");
+  if (int rc = site_check_args("site_bound_bwd", theta && Z && X && alpha && Q && y && gout && gZ && gtheta && galpha && gv && ws, ldy,
+                               kind, log_scale && gls && df > 0.f, "log_scale, gls and df > 0", G, Mt, N, D, nu2, ws, ws_bytes,
+                               vargp_site_bound_bwd_workspace_bytes(G, Mt, N, D)))
+    return rc;
   SiteBwdArgs a{};
   a.theta = theta; a.Z = Z; a.X = X; a.alpha = alpha; a.Q = Q; a.w = w; a.gout = gout;
   a.gZ = gZ; a.gtheta = gtheta; a.galpha = galpha; a.gv = gv; a.gls = kind == VARGP_SITE_STUDENTT ? gls : nullptr;
   a.p = site_bwd_plan(ws, G, Mt, N, D);
   a.G = G; a.Mt = Mt; a.N = N; a.D = D;
   const int64_t nred = cdiv((int64_t)G * Mt * D, 256) + D + cdiv((int64_t)G * Mt, 256) + 1;
-  VARGP_REQUIRE((int64_t)a.p.nch * a.p.ngrp < (1ll << 31) && nred < (1ll << 31),
+  VARGP_REQUIRE((int64_t)a.p.ch.nch * a.p.ngrp < (1ll << 31) && nred < (1ll << 31),
                 "site_bound_bwd: G = %d, Mt = %d, D = %d need too many workgroups", G, Mt, D);
   hipStream_t st = as_stream(stream);
   ProfScope whole("site_bound_bwd", st);
-  int rc;
-  switch (kind) {
-    case VARGP_SITE_BERNOULLI_PROBIT: rc = site_bwd_launch<Bernoulli<LinkProbit>>(a, {y, ldy, nullptr}, nu2, st); break;
-    case VARGP_SITE_BERNOULLI_LOGIT: rc = site_bwd_launch<Bernoulli<LinkLogit>>(a, {y, ldy, nullptr}, nu2, st); break;
-    case VARGP_SITE_POISSON: rc = site_bwd_launch<Poisson>(a, {{y, ldy}}, nu2, st); break;
-    default: rc = site_bwd_launch<StudentT>(a, {{y, ldy}, log_scale, df, lognorm}, nu2, st); break;
-  }
+  const int rc = with_site_lik(kind, y, ldy, log_scale, df, lognorm,
+                               [&](auto lik, const auto& la) { return site_bwd_launch<decltype(lik)>(a, la, nu2, st); });
   if (rc != VARGP_OK) return rc;
   hipLaunchKernelGGL(site_bwd_reduce_kernel, dim3((unsigned)nred), dim3(256), 0, st, a);
   return check_launch("site_bound_bwd");
@@ -902,7 +832,7 @@ extern "C" int vargp_site_bound_bwd(const float* theta, const float* Z, const fl
 
 extern "C" int vargp_site_moments_chunks(int G, int Mt, int N, int D) {
   if (G <= 0 || Mt <= 0 || N <= 0 || D <= 0) return 0;
-  return site_plan(nullptr, G, Mt, N).nch;
+  return site_plan(nullptr, G, Mt, N).ch.nch;
 }
 
 extern "C" size_t vargp_site_moments_workspace_bytes(int G, int Mt, int N, int D) {
@@ -914,30 +844,18 @@ extern "C" int vargp_site_moments(const float* theta, const float* Z, const floa
                                   const float* y, int64_t ldy, const float* w, int kind, const float* log_scale, float df,
                                   float lognorm, float* lam2, float* c, float* sums, int G, int Mt, int N, int D, int nu2, void* ws,
                                   size_t ws_bytes, vargp_stream_t stream) {
-  VARGP_REQUIRE(theta && Z && X && alpha && Q && y && lam2 && c && sums && ws, "site_moments: null pointer");
-  VARGP_REQUIRE(G > 0 && Mt > 0 && N > 0 && D > 0, "site_moments: bad dims");
-  VARGP_REQUIRE(kind >= VARGP_SITE_BERNOULLI_PROBIT && kind <= VARGP_SITE_STUDENTT,
-                "site_moments: kind = %d (0: Bernoulli probit, 1: Bernoulli logit, 2: Poisson, 3: Student-t)", kind);
-  VARGP_REQUIRE(nu2 == 0 || nu2 == 1 || nu2 == 3 || nu2 == 5, "site_moments: nu2 = %d (0: RBF; 1, 3, 5: Matern)", nu2);
-  VARGP_REQUIRE(G <= 65535, "site_moments: G = %d (at most 65535)", G);
-  VARGP_REQUIRE(Mt <= kSiMaxMt, "site_moments: Mt = %d (at most %d: the K block of all rows lives in LDS)", Mt, kSiMaxMt);
-  VARGP_REQUIRE(ldy == 0 || ldy >= N, "site_moments: ldy must be 0 or >= N");
-  VARGP_REQUIRE(kind != VARGP_SITE_STUDENTT || (log_scale && df > 0.f), "site_moments: Student-t needs log_scale and df > 0");
-  VARGP_REQUIRE(reinterpret_cast<uintptr_t>(ws) % sizeof(double) == 0, "site_moments: ws must be 8-byte aligned");
-  VARGP_REQUIRE(ws_bytes >= vargp_site_moments_workspace_bytes(G, Mt, N, D), "site_moments: workspace too small");
+  if (int rc = site_check_args("site_moments", theta && Z && X && alpha && Q && y && lam2 && c && sums && ws, ldy, kind,
+                               log_scale && df > 0.f, "log_scale and df > 0", G, Mt, N, D, nu2, ws, ws_bytes,
+                               vargp_site_moments_workspace_bytes(G, Mt, N, D)))
+    return rc;
   SiteArgs a{};
   a.theta = theta; a.Z = Z; a.X = X; a.alpha = alpha; a.Q = Q; a.w = w; a.lam2 = lam2; a.c = c; a.sums = sums;
   a.p = site_plan(ws, G, Mt, N);
   a.G = G; a.Mt = Mt; a.N = N; a.D = D;
   hipStream_t st = as_stream(stream);
   ProfScope whole("site_moments", st);
-  int rc;
-  switch (kind) {
-    case VARGP_SITE_BERNOULLI_PROBIT: rc = site_launch<Bernoulli<LinkProbit>>(a, {y, ldy, nullptr}, nu2, st); break;
-    case VARGP_SITE_BERNOULLI_LOGIT: rc = site_launch<Bernoulli<LinkLogit>>(a, {y, ldy, nullptr}, nu2, st); break;
-    case VARGP_SITE_POISSON: rc = site_launch<Poisson>(a, {{y, ldy}}, nu2, st); break;
-    default: rc = site_launch<StudentT>(a, {{y, ldy}, log_scale, df, lognorm}, nu2, st); break;
-  }
+  const int rc = with_site_lik(kind, y, ldy, log_scale, df, lognorm,
+                               [&](auto lik, const auto& la) { return site_launch<decltype(lik)>(a, la, nu2, st); });
   if (rc != VARGP_OK) return rc;
   hipLaunchKernelGGL(site_reduce_kernel, dim3(cdiv(Mt, 256) + 1, G), dim3(256), 0, st, a);
   return check_launch("site_moments");

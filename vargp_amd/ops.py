@@ -741,7 +741,7 @@ def gram_moments_diff(theta, Z, X, w, y, nu2=0):
 
 
 # Gaussian sites of a non-Gaussian likelihood over a data set (csrc/sites.hip -- not in the reference).  No autograd.
-SITE_MAX_MT = 256                # kSiMaxMt (csrc/moments_plan.h): the fused pass holds all Mt rows of a K block in LDS
+SITE_MAX_MT = 256                # kSiMaxMt (csrc/dataset_pass.h): the fused pass holds all Mt rows of a K block in LDS
 _SITE_KINDS = {('bernoulli', 0): 0, ('bernoulli', 1): 1, ('poisson', None): 2, ('studentt', None): 3}
 
 
@@ -755,6 +755,26 @@ def site_kind(kind, extra):
     if kind == 'studentt':
         return _SITE_KINDS[(kind, None)], extra[0], float(extra[1]), float(extra[2])
     raise ValueError(f"site_moments: kind must be 'bernoulli', 'poisson' or 'studentt', got {kind!r}")
+
+
+def _site_operands(theta, Z, X, alpha, Q, y, w, kind, extra):
+    """The operands of the two site entries, detached, contiguous and checked -> (theta, Z, X, alpha, Q, yt, ldy, w, code,
+    log_scale, df, lognorm, (G, Mt, N, D))."""
+    code, log_scale, df, lognorm = site_kind(kind, extra)
+    det = lambda t: t.detach().contiguous()
+    theta, Z, X, alpha, Q = det(theta).view(-1), det(Z), det(X), det(alpha), det(Q)
+    assert Z.dim() == 3 and X.dim() == 2 and Z.shape[-1] == X.shape[1] and theta.numel() == X.shape[1] + 1, (theta.shape, Z.shape, X.shape)
+    (G, Mt, D), N = Z.shape, X.shape[0]
+    assert tuple(alpha.shape) == (G, Mt) and tuple(Q.shape) == (G, Mt, Mt), (alpha.shape, Q.shape, G, Mt)
+    yt, ldy = reg_target(y, G, N)
+    if w is not None:
+        w = det(w)
+        assert tuple(w.shape) == (G, N) and w.dtype == torch.float32, (w.shape, w.dtype)
+    if log_scale is not None:
+        log_scale = det(log_scale)
+        assert tuple(log_scale.shape) == (G,) and log_scale.dtype == torch.float32, (log_scale.shape, log_scale.dtype)
+    assert all(t.dtype == torch.float32 for t in (theta, Z, X, alpha, Q)), (theta.dtype, Z.dtype, X.dtype, alpha.dtype, Q.dtype)
+    return theta, Z, X, alpha, Q, yt, ldy, w, code, log_scale, df, lognorm, (G, Mt, N, D)
 
 
 def site_moments_chunks(G, Mt, N, D):
@@ -771,20 +791,7 @@ def site_moments(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0):
     sum lam2, clamped points, sum w)).  K(Z, X) is never stored and the scratch does not grow with N beyond the chunk count;
     bitwise reproducible; a point of weight 0 adds exactly nothing."""
     require_device(theta, Z, X, alpha, Q, y, w)
-    code, log_scale, df, lognorm = site_kind(kind, extra)
-    det = lambda t: t.detach().contiguous()
-    theta, Z, X, alpha, Q = det(theta).view(-1), det(Z), det(X), det(alpha), det(Q)
-    assert Z.dim() == 3 and X.dim() == 2 and Z.shape[-1] == X.shape[1] and theta.numel() == X.shape[1] + 1, (theta.shape, Z.shape, X.shape)
-    (G, Mt, D), N = Z.shape, X.shape[0]
-    assert tuple(alpha.shape) == (G, Mt) and tuple(Q.shape) == (G, Mt, Mt), (alpha.shape, Q.shape, G, Mt)
-    yt, ldy = reg_target(y, G, N)
-    if w is not None:
-        w = det(w)
-        assert tuple(w.shape) == (G, N) and w.dtype == torch.float32, (w.shape, w.dtype)
-    if log_scale is not None:
-        log_scale = det(log_scale)
-        assert tuple(log_scale.shape) == (G,) and log_scale.dtype == torch.float32, (log_scale.shape, log_scale.dtype)
-    assert all(t.dtype == torch.float32 for t in (theta, Z, X, alpha, Q)), (theta.dtype, Z.dtype, X.dtype, alpha.dtype, Q.dtype)
+    theta, Z, X, alpha, Q, yt, ldy, w, code, log_scale, df, lognorm, (G, Mt, N, D) = _site_operands(theta, Z, X, alpha, Q, y, w, kind, extra)
     lam2 = torch.empty(G, N, dtype=torch.float32, device=X.device)
     c = torch.empty(G, Mt, dtype=torch.float32, device=X.device)
     sums = torch.empty(G, 4, dtype=torch.float32, device=X.device)
@@ -806,22 +813,10 @@ def site_bound_bwd(theta, Z, X, alpha, Q, y, w, kind, extra, gout, nu2=0):
     the TRUE d ell / d var, 0 where the variance is clamped: gQ = -gram_moments(w=gv).Phi; gls (G,) for Student-t, else None).
     K(Z, X) and its gradient are never stored; bitwise reproducible; a point of weight 0 adds exactly nothing."""
     require_device(theta, Z, X, alpha, Q, y, w, gout)
-    code, log_scale, df, lognorm = site_kind(kind, extra)
-    det = lambda t: t.detach().contiguous()
-    theta, Z, X, alpha, Q, gout = det(theta).view(-1), det(Z), det(X), det(alpha), det(Q), det(gout)
-    assert Z.dim() == 3 and X.dim() == 2 and Z.shape[-1] == X.shape[1] and theta.numel() == X.shape[1] + 1, (theta.shape, Z.shape, X.shape)
-    (G, Mt, D), N = Z.shape, X.shape[0]
-    assert tuple(alpha.shape) == (G, Mt) and tuple(Q.shape) == (G, Mt, Mt) and tuple(gout.shape) == (G,), (alpha.shape, Q.shape, gout.shape)
-    yt, ldy = reg_target(y, G, N)
-    if w is not None:
-        w = det(w)
-        assert tuple(w.shape) == (G, N) and w.dtype == torch.float32, (w.shape, w.dtype)
-    gls = None
-    if log_scale is not None:
-        log_scale = det(log_scale)
-        assert tuple(log_scale.shape) == (G,) and log_scale.dtype == torch.float32, (log_scale.shape, log_scale.dtype)
-        gls = torch.empty(G, dtype=torch.float32, device=X.device)
-    assert all(t.dtype == torch.float32 for t in (theta, Z, X, alpha, Q, gout)), (theta.dtype, Z.dtype, X.dtype, alpha.dtype, Q.dtype)
+    theta, Z, X, alpha, Q, yt, ldy, w, code, log_scale, df, lognorm, (G, Mt, N, D) = _site_operands(theta, Z, X, alpha, Q, y, w, kind, extra)
+    gout = gout.detach().contiguous()
+    assert tuple(gout.shape) == (G,) and gout.dtype == torch.float32, (gout.shape, gout.dtype)
+    gls = None if log_scale is None else torch.empty(G, dtype=torch.float32, device=X.device)
     gZ = torch.empty_like(Z)
     gtheta = torch.empty(D + 1, dtype=torch.float32, device=X.device)
     galpha = torch.empty(G, Mt, dtype=torch.float32, device=X.device)
