@@ -53,7 +53,8 @@ def train(task_id, train_set, val_set, test_set, ep_var_mean=True, map_est_hyper
           eval_interval=10, patience=20, prev_params=None, logger=None, device=None, graph=False, seed=None,
           retrain=False, eval_shared_hypers=False, dataloader=False, kernel='rbf', native_kernel=False,
           likelihood='softmax', link='probit', lpd=False, z_init='random', kmeans_iters=20, lengthscale_init='default',
-          uncertainty=False, greedy_candidates=4096, q_init='default', newton_iters=20, em_rounds=5, em_steps=20):
+          uncertainty=False, greedy_candidates=4096, q_init='default', newton_iters=20, em_rounds=5, em_steps=20,
+          site_samples=32):
     if retrain:      # the variant of experiments/vargp_retrain.py:14-19 (earlier tasks' inducing parameters re-optimised)
         from vargp_amd.vargp_retrain import VARGPRetrain
         assert kernel == 'rbf', '--retrain builds its model with the RBF kernel'
@@ -68,7 +69,7 @@ def train(task_id, train_set, val_set, test_set, ep_var_mean=True, map_est_hyper
                               native_kernel=native_kernel, likelihood=likelihood, link=link, z_init=z_init,
                               kmeans_iters=kmeans_iters, lengthscale_init=lengthscale_init,
                               greedy_candidates=greedy_candidates, q_init=q_init, newton_iters=newton_iters, em_rounds=em_rounds,
-                              em_steps=em_steps).to(device)
+                              em_steps=em_steps, site_samples=site_samples).to(device)
     stopper = EarlyStopper(patience=patience)
     N = len(train_set)
     # the program's counter-based noise generator is keyed by the run's seed (the reference draws from the torch global
@@ -205,7 +206,7 @@ def toy(args):
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed, retrain=args.retrain,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
                    lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init, q_init=args.q_init,
-                   newton_iters=args.newton_iters, em_rounds=args.em_rounds, em_steps=args.em_steps,
+                   newton_iters=args.newton_iters, em_rounds=args.em_rounds, em_steps=args.em_steps, site_samples=args.site_samples,
                    uncertainty=args.uncertainty, greedy_candidates=args.greedy_candidates)
         prev_params.append(sd)
     logger.close()
@@ -234,7 +235,7 @@ def split_mnist(args):
                    eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
                    lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init, q_init=args.q_init,
-                   newton_iters=args.newton_iters, em_rounds=args.em_rounds, em_steps=args.em_steps,
+                   newton_iters=args.newton_iters, em_rounds=args.em_rounds, em_steps=args.em_steps, site_samples=args.site_samples,
                    uncertainty=args.uncertainty, greedy_candidates=args.greedy_candidates)
         prev_params.append(sd)
     logger.close()
@@ -266,7 +267,7 @@ def permuted_mnist(args):
                    device=device, eval_interval=args.eval_interval, graph=args.graph, seed=args.seed,
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
                    lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init, q_init=args.q_init,
-                   newton_iters=args.newton_iters, em_rounds=args.em_rounds, em_steps=args.em_steps,
+                   newton_iters=args.newton_iters, em_rounds=args.em_rounds, em_steps=args.em_steps, site_samples=args.site_samples,
                    uncertainty=args.uncertainty, greedy_candidates=args.greedy_candidates)
         prev_params.append(sd)
     logger.close()
@@ -311,11 +312,12 @@ def parse_args(argv=None):
         sp.add_argument('--lengthscale_init', choices=('default', 'median'), default='default',
                         help="lengthscales of the first task: 0.5 (the reference's), or the median distance between pairs of "
                              'its points (not with --dkl)')
-        sp.add_argument('--q_init', choices=('default', 'newton', 'em'), default='default',
+        sp.add_argument('--q_init', choices=('default', 'newton', 'em', 'newton_softmax'), default='default',
                         help="q(u) of each task: the reference's start, fit_q_newton_ on the task's whole training set, or "
                              'fit_sites_ (variational EM: inducing points and kernel hyper-parameters move too) '
-                             '(--likelihood bernoulli only)')
+                             '(--likelihood bernoulli only), or fit_q_softmax_ (--likelihood softmax only)')
         sp.add_argument('--newton_iters', type=int, default=20, help='iterations of --q_init newton / of an E-step of em (at most)')
+        sp.add_argument('--site_samples', type=int, default=32, help='draws per point of --q_init newton_softmax')
         sp.add_argument('--em_rounds', type=int, default=5, help='rounds of --q_init em')
         sp.add_argument('--em_steps', type=int, default=20, help='Yogi steps per M-step of --q_init em')
         sp.add_argument('--seed', type=int, default=None)

@@ -365,6 +365,48 @@ int vargp_site_bound_bwd(const float* theta, const float* Z, const float* X, con
                          void* ws, size_t ws_bytes, vargp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The three data passes of one natural-gradient iteration on q(u) of a SOFTMAX model (vargp_amd/sites.py: fit_q_softmax_).  Not
+ * in the reference.  q factorises over the classes, so there is one Gaussian site per (class, point); the classes of a point are
+ * coupled only in how the site parameters are computed.  Every entry checks its arguments on the host before any launch
+ * (VARGP_EINVAL, vargp_last_error), works on the caller's stream and uses no atomics: partials are added in ascending chunk order
+ * in fp64 and two calls on the same input are bitwise equal.
+ *
+ * vargp_site_marginals: mu[g, n] = alpha[g] . k_n, var[g, n] = max(gamma^2 - k_n^T Q[g] k_n, 0), both [G, N], with the operands,
+ * the kernel, the chunking and the limit Mt <= 256 of vargp_site_moments -- it IS that entry's kernel, stopped after the
+ * marginals: no likelihood, no c, no partials, no workspace and no second launch.  K(Z, X) is never stored.  VARGP_EINVAL: a
+ * null pointer, a size < 1, Mt > 256, G > 65535, an unknown nu2.
+ *
+ * vargp_softmax_sites: mu, var [C, N] (fp32; var >= 0), y [N] int64 class indices, w [N] or NULL = 1, F draws per point.  With
+ * f = mu + sqrt(var) eps and p = softmax(f) (per draw: logits shifted by their maximum, one exp per class):
+ *   ell_n = mu[y_n, n] - mean_f logsumexp(f),   Ep_c = mean_f p_c,   Ev_c = mean_f p_c (1 - p_c)
+ *   lam2[c, n] = w_n Ev_c  (>= 0: nothing is clamped),   lam1[c, n] = w_n ([y_n = c] - Ep_c) + lam2[c, n] mu[c, n]     [C, N]
+ *   sums = (sum_n w_n ell_n, sum_cn lam2, the number of points with w != 0, sum_n w_n)                              [4]
+ * eps [F, C, N], or NULL: the draws are generated inside the kernel from `seed` -- Philox4x32-10 + Box-Muller as the ELBO
+ * programs', noise stream 2, step 0; the draws of (point n, sample f) are the groups (n F + f) ceil(C / 4) + j, element l of group
+ * j belonging to class 4 j + l -- and the [F, C, N] tensor need not exist.  vargp_softmax_site_noise writes exactly those draws
+ * to eps [F, C, N]; the two ways are bitwise equal.  A point of weight 0 is never evaluated: lam1 = lam2 = 0 and it adds exactly
+ * nothing, whatever its mu, var and y hold.  A label outside [0, C) makes sums[0] NaN.  2 <= C <= 128: lanes run over points, the
+ * class accumulators live in registers up to C = 16 and in LDS above (VARGP_EINVAL beyond 128).  The points are cut into at most
+ * 1024 chunks by N alone.  Workspace: 32 bytes per chunk and padding, 8-byte aligned.  VARGP_EINVAL: a null pointer other than
+ * w and eps, N or F < 1, F > 65535, C outside [2, 128], a short or misaligned workspace.
+ *
+ * vargp_gram_moments_v: vargp_gram_moments with a weight vector of its own for c: Phi[g] = sum_n w[g, n] k_n k_n^T as there, but
+ * c[g] = sum_n v[g, n] k_n and sums[g] = (sum_n w, sum_n v).  The same kernel, chunking and workspace
+ * (vargp_gram_moments_workspace_bytes); with v = w o y (rounded to fp32) Phi and c are bitwise vargp_gram_moments'.  The softmax
+ * sites need it because lam1 / lam2 is not representable: lam2 underflows to 0 exactly at the confidently misclassified points,
+ * where lam1 ~ 1 matters most.  VARGP_EINVAL as vargp_gram_moments.
+ */
+int vargp_site_marginals(const float* theta, const float* Z, const float* X, const float* alpha, const float* Q, float* mu,
+                         float* var, int G, int Mt, int N, int D, int nu2, vargp_stream_t stream);
+size_t vargp_softmax_sites_workspace_bytes(int C, int N);
+int vargp_softmax_sites(const float* mu, const float* var, const int64_t* y, const float* w, const float* eps, uint64_t seed,
+                        float* lam1, float* lam2, float* sums, int C, int N, int F, void* ws, size_t ws_bytes,
+                        vargp_stream_t stream);
+int vargp_softmax_site_noise(uint64_t seed, float* eps, int F, int C, int N, vargp_stream_t stream);
+int vargp_gram_moments_v(const float* theta, const float* Z, const float* X, const float* w, const float* v, float* Phi, float* c,
+                         float* sums, int G, int Mt, int N, int D, int nu2, void* ws, size_t ws_bytes, vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * KL(N(mu_q, Lq Lq^T) || N(mu_p, Lp Lp^T)) from its triangular ingredients (reference:
  * torch.distributions kl_divergence(MVN, MVN) as called from var_gp/vargp.py:182-190):
  *   kl = logdet_p - logdet_q + 0.5 * (|G|_F^2 + |d|^2 - M),  G = Lp^-1 Lq [nb, M, M],

@@ -17,6 +17,8 @@
 // entry (i, j), j <= i, to both triangles: Phi is bitwise symmetric and two calls on the same input are bitwise equal.
 // The chunking depends on the shapes alone (mom_plan): at most kMoMaxChunks chunks of at least kMoMinChunk columns, as many as
 // give the launch about kMoTargetWg workgroups.
+// vargp_gram_moments_v is the same kernel with VW = true: c = sum_n v_n k_n with a weight vector v of its own in place of w y
+// (a.y holds v), sums = (sum w, sum v).  The softmax sites need it: lam1 / lam2 is not representable where lam2 underflows.
 #include "dataset_pass.h"      // the tiling constants, the chunking rule and the other pieces shared with sites.hip
 
 namespace vargp {
@@ -60,7 +62,7 @@ __device__ __forceinline__ void mo_tile(int t, int& ti, int& tj) {
 }
 
 // grid (ntri * nch, G): blockIdx.x = chunk * ntri + tile
-template <class EPI, bool DIRECT>
+template <class EPI, bool DIRECT, bool VW>
 __global__ __launch_bounds__(256) void moments_kernel(const MomArgs a) {
   constexpr int T = kMoT, LD = kMoLD, BK = kMoBK;
   __shared__ float Ks[2][T * LD];                                // the K panels of the tile's rows and columns: [n][m]
@@ -108,9 +110,15 @@ __global__ __launch_bounds__(256) void moments_kernel(const MomArgs a) {
       float wv = 0.f, yv = 0.f;
       if (n < cend) { wv = wg ? wg[n] : 1.f; yv = yg[n]; }
       wn[tid] = wv;
-      wyn[tid] = wv * yv;
-      sw += wv;
-      syy = fmaf(wv * yv, yv, syy);
+      if constexpr (VW) {
+        wyn[tid] = yv;
+        sw += wv;
+        syy += yv;
+      } else {
+        wyn[tid] = wv * yv;
+        sw += wv;
+        syy = fmaf(wv * yv, yv, syy);
+      }
     }
     if constexpr (DIRECT) {
       float* Xs = stage + 2 * T * kMoDl;
@@ -249,11 +257,11 @@ __global__ __launch_bounds__(256) void moments_reduce_kernel(const MomArgs a) {
   }
 }
 
-template <class EPI>
+template <class EPI, bool VW>
 static void moments_launch(const MomArgs& a, hipStream_t st) {
   const dim3 grid(a.p.ntri * a.p.ch.nch, a.G), blk(256);
-  if (a.D <= kRbfDirectD) hipLaunchKernelGGL((moments_kernel<EPI, true>), grid, blk, 0, st, a);
-  else hipLaunchKernelGGL((moments_kernel<EPI, false>), grid, blk, 0, st, a);
+  if (a.D <= kRbfDirectD) hipLaunchKernelGGL((moments_kernel<EPI, true, VW>), grid, blk, 0, st, a);
+  else hipLaunchKernelGGL((moments_kernel<EPI, false, VW>), grid, blk, 0, st, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -611,22 +619,36 @@ extern "C" size_t vargp_gram_moments_workspace_bytes(int G, int Mt, int N, int D
   return mom_plan(nullptr, G, Mt, N).bytes + 256;
 }
 
-extern "C" int vargp_gram_moments(const float* theta, const float* Z, const float* X, const float* w, const float* y, float* Phi,
-                                  float* c, float* sums, int G, int Mt, int N, int D, int nu2, void* ws, size_t ws_bytes,
-                                  vargp_stream_t stream) {
-  VARGP_REQUIRE(theta && Z && X && y && Phi && c && sums && ws, "gram_moments: null pointer");
-  VARGP_REQUIRE(G > 0 && Mt > 0 && N > 0 && D > 0, "gram_moments: bad dims");
-  VARGP_REQUIRE(nu2 == 0 || nu2 == 1 || nu2 == 3 || nu2 == 5, "gram_moments: nu2 = %d (0: RBF; 1, 3, 5: Matern)", nu2);
-  VARGP_REQUIRE(G <= 65535, "gram_moments: G = %d (at most 65535)", G);
-  VARGP_REQUIRE(ws_bytes >= vargp_gram_moments_workspace_bytes(G, Mt, N, D), "gram_moments: workspace too small");
+// both forward entries: y is the targets (VW = false) or the weight vector v of c (VW = true)
+template <bool VW>
+static int moments_entry(const char* name, const float* theta, const float* Z, const float* X, const float* w, const float* y,
+                         float* Phi, float* c, float* sums, int G, int Mt, int N, int D, int nu2, void* ws, size_t ws_bytes,
+                         vargp_stream_t stream) {
+  VARGP_REQUIRE(theta && Z && X && y && Phi && c && sums && ws, "%s: null pointer", name);
+  VARGP_REQUIRE(G > 0 && Mt > 0 && N > 0 && D > 0, "%s: bad dims", name);
+  VARGP_REQUIRE(nu2 == 0 || nu2 == 1 || nu2 == 3 || nu2 == 5, "%s: nu2 = %d (0: RBF; 1, 3, 5: Matern)", name, nu2);
+  VARGP_REQUIRE(G <= 65535, "%s: G = %d (at most 65535)", name, G);
+  VARGP_REQUIRE(ws_bytes >= vargp_gram_moments_workspace_bytes(G, Mt, N, D), "%s: workspace too small", name);
   MomArgs a{};
   a.theta = theta; a.Z = Z; a.X = X; a.w = w; a.y = y; a.Phi = Phi; a.c = c; a.sums = sums;
   a.p = mom_plan(ws, G, Mt, N);
   a.G = G; a.Mt = Mt; a.N = N; a.D = D;
-  VARGP_REQUIRE((int64_t)a.p.ntri * a.p.ch.nch < (1ll << 31), "gram_moments: Mt = %d needs too many tiles", Mt);
+  VARGP_REQUIRE((int64_t)a.p.ntri * a.p.ch.nch < (1ll << 31), "%s: Mt = %d needs too many tiles", name, Mt);
   hipStream_t st = as_stream(stream);
-  ProfScope whole("gram_moments", st);
-  with_epi(nu2, [&](auto epi) { moments_launch<decltype(epi)>(a, st); });
+  ProfScope whole(name, st);
+  with_epi(nu2, [&](auto epi) { moments_launch<decltype(epi), VW>(a, st); });
   hipLaunchKernelGGL(moments_reduce_kernel, dim3(a.p.ntri * 16 + cdiv(Mt, 256) + 1, G), dim3(256), 0, st, a);
-  return check_launch("gram_moments");
+  return check_launch(name);
+}
+
+extern "C" int vargp_gram_moments(const float* theta, const float* Z, const float* X, const float* w, const float* y, float* Phi,
+                                  float* c, float* sums, int G, int Mt, int N, int D, int nu2, void* ws, size_t ws_bytes,
+                                  vargp_stream_t stream) {
+  return moments_entry<false>("gram_moments", theta, Z, X, w, y, Phi, c, sums, G, Mt, N, D, nu2, ws, ws_bytes, stream);
+}
+
+extern "C" int vargp_gram_moments_v(const float* theta, const float* Z, const float* X, const float* w, const float* v, float* Phi,
+                                    float* c, float* sums, int G, int Mt, int N, int D, int nu2, void* ws, size_t ws_bytes,
+                                    vargp_stream_t stream) {
+  return moments_entry<true>("gram_moments_v", theta, Z, X, w, v, Phi, c, sums, G, Mt, N, D, nu2, ws, ws_bytes, stream);
 }

@@ -18,6 +18,9 @@
 // finite inputs; the likelihood's derivatives need not be).  Columns behind the end of the chunk are masked as in moments.hip.
 // No atomics.  A second launch adds the chunks' partials in ascending chunk order in fp64 and rounds once: two calls on the same
 // input are bitwise equal.  The chunking depends on the shapes alone (site_plan).
+// The same kernel with LIK = SiteMarginals is vargp_site_marginals: the frame up to mu_n and var_n, which it writes out [G][N]; no
+// likelihood wave, no accumulators of c, no partials and no reduce launch (the coupled softmax sites of softmax_sites.hip need the
+// marginals of ALL outputs of a point at once).
 #include "dataset_pass.h"
 #include "lik.h"
 
@@ -57,6 +60,16 @@ static SitePlan site_plan(void* ws, int G, int Mt, int N) {
   return o;
 }
 
+// Not a likelihood: site_kernel stops after the marginals and writes them
+struct SiteMarginals {
+  using real = float;
+  struct Args { float *mu, *var; };
+  struct Cls {};
+  static __device__ __forceinline__ Cls cls(const Args&, int) { return {}; }
+};
+template <class LIK> constexpr bool kSiteMarginals = false;
+template <> constexpr bool kSiteMarginals<SiteMarginals> = true;
+
 struct SiteArgs {
   const float *theta, *Z, *X, *alpha, *Q, *w;
   float *lam2, *c, *sums;
@@ -69,6 +82,7 @@ template <class LIK, class EPI, bool DIRECT>
 __global__ __launch_bounds__(256) void site_kernel(const SiteArgs a, const typename LIK::Args la) {
   using real = typename LIK::real;
   constexpr int T = kMoT, LD = kMoLD, BK = kMoBK;
+  constexpr bool MARG = kSiteMarginals<LIK>;
   extern __shared__ __attribute__((aligned(16))) float si_lds[];
   const int Mt = a.Mt, D = a.D, nt = a.p.nt, MtP = nt * T, LDK = MtP + 1;
   float* Ks = si_lds;                  // the K block: [n][m], m over all nt panels
@@ -220,7 +234,12 @@ __global__ __launch_bounds__(256) void site_kernel(const SiteArgs a, const typen
       const float quad = qred[(tid >> 5) * 32 + (tid & 31)] + qred[((tid >> 5) + 2) * 32 + (tid & 31)];
       const float var = fmaxf(g2 - quad, 0.f);
       float l1 = 0.f;
-      if (n < cend) {
+      if constexpr (MARG) {
+        if (n < cend) {
+          la.mu[g * (int64_t)a.N + n] = mu;
+          la.var[g * (int64_t)a.N + n] = var;
+        }
+      } else if (n < cend) {
         const float wv = wg ? wg[n] : 1.f;
         float l2 = 0.f;
         if (wv != 0.f) {
@@ -240,6 +259,7 @@ __global__ __launch_bounds__(256) void site_kernel(const SiteArgs a, const typen
       l1s[tid] = l1;
     }
     __syncthreads();
+    if constexpr (MARG) continue;
 
     // ---- c += K lam1: lanes = rows of a panel, every wave 16 of the columns
 #pragma unroll
@@ -253,6 +273,7 @@ __global__ __launch_bounds__(256) void site_kernel(const SiteArgs a, const typen
     }
     __syncthreads();
   }
+  if constexpr (MARG) return;
 
   const int64_t part = g * a.p.ch.nch + chunk;
 #pragma unroll
@@ -300,7 +321,8 @@ __global__ __launch_bounds__(256) void site_reduce_kernel(const SiteArgs a) {
 template <class LIK, class EPI, bool DIRECT>
 static int site_launch_form(const SiteArgs& a, const typename LIK::Args& la, hipStream_t st) {
   constexpr auto kernel = site_kernel<LIK, EPI, DIRECT>;
-  if (int rc = reserve_dynamic_lds<kernel>(site_lds_floats(kSiMaxNt) * sizeof(float), "site_moments")) return rc;
+  if (int rc = reserve_dynamic_lds<kernel>(site_lds_floats(kSiMaxNt) * sizeof(float), kSiteMarginals<LIK> ? "site_marginals" : "site_moments"))
+    return rc;
   hipLaunchKernelGGL(kernel, dim3(a.p.ch.nch, a.G), dim3(256), site_lds_floats(a.p.nt) * sizeof(float), st, a, la);
   return VARGP_OK;
 }
@@ -859,4 +881,21 @@ extern "C" int vargp_site_moments(const float* theta, const float* Z, const floa
   if (rc != VARGP_OK) return rc;
   hipLaunchKernelGGL(site_reduce_kernel, dim3(cdiv(Mt, 256) + 1, G), dim3(256), 0, st, a);
   return check_launch("site_moments");
+}
+
+extern "C" int vargp_site_marginals(const float* theta, const float* Z, const float* X, const float* alpha, const float* Q, float* mu,
+                                    float* var, int G, int Mt, int N, int D, int nu2, vargp_stream_t stream) {
+  VARGP_REQUIRE(theta && Z && X && alpha && Q && mu && var, "site_marginals: null pointer");
+  VARGP_REQUIRE(G > 0 && Mt > 0 && N > 0 && D > 0, "site_marginals: bad dims");
+  VARGP_REQUIRE(nu2 == 0 || nu2 == 1 || nu2 == 3 || nu2 == 5, "site_marginals: nu2 = %d (0: RBF; 1, 3, 5: Matern)", nu2);
+  VARGP_REQUIRE(G <= 65535, "site_marginals: G = %d (at most 65535)", G);
+  VARGP_REQUIRE(Mt <= kSiMaxMt, "site_marginals: Mt = %d (at most %d: the K block of all rows lives in LDS)", Mt, kSiMaxMt);
+  SiteArgs a{};
+  a.theta = theta; a.Z = Z; a.X = X; a.alpha = alpha; a.Q = Q;
+  a.p = site_plan(nullptr, G, Mt, N);          // the chunking alone: the marginals leave no partials
+  a.G = G; a.Mt = Mt; a.N = N; a.D = D;
+  hipStream_t st = as_stream(stream);
+  ProfScope whole("site_marginals", st);
+  if (int rc = site_launch<SiteMarginals>(a, SiteMarginals::Args{mu, var}, nu2, st)) return rc;
+  return check_launch("site_marginals");
 }

@@ -802,6 +802,96 @@ def site_moments(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0):
     return lam2, c, sums
 
 
+# The data passes of the softmax site iteration (csrc/sites.hip, csrc/softmax_sites.hip, csrc/moments.hip -- not in the
+# reference).  No autograd.
+SOFTMAX_SITE_MAX_C = 128         # kSmMaxC (csrc/softmax_sites.hip)
+
+
+def site_marginals(theta, Z, X, alpha, Q, nu2=0):
+    """The marginals of q(f) at every point: theta, Z (G, Mt, D), Mt <= SITE_MAX_MT, X (N, D), alpha (G, Mt) and a symmetric Q (G,
+    Mt, Mt) as site_moments takes them -> (mu (G, N) = alpha . k_n, var (G, N) = max(gamma^2 - k_n^T Q k_n, 0)).  site_moments'
+    kernel stopped after the marginals (vargp_site_marginals): K(Z, X) is never stored, no workspace, bitwise reproducible."""
+    require_device(theta, Z, X, alpha, Q)
+    det = lambda t: t.detach().contiguous()
+    theta, Z, X, alpha, Q = det(theta).view(-1), det(Z), det(X), det(alpha), det(Q)
+    assert Z.dim() == 3 and X.dim() == 2 and Z.shape[-1] == X.shape[1] and theta.numel() == X.shape[1] + 1, (theta.shape, Z.shape, X.shape)
+    (G, Mt, D), N = Z.shape, X.shape[0]
+    assert tuple(alpha.shape) == (G, Mt) and tuple(Q.shape) == (G, Mt, Mt), (alpha.shape, Q.shape, G, Mt)
+    assert all(t.dtype == torch.float32 for t in (theta, Z, X, alpha, Q)), (theta.dtype, Z.dtype, X.dtype, alpha.dtype, Q.dtype)
+    mu = torch.empty(G, N, dtype=torch.float32, device=X.device)
+    var = torch.empty(G, N, dtype=torch.float32, device=X.device)
+    check(lib().vargp_site_marginals(ptr(theta), ptr(Z), ptr(X), ptr(alpha), ptr(Q), ptr(mu), ptr(var), G, Mt, N, D, int(nu2),
+                                     stream_ptr()), 'vargp_site_marginals')
+    return mu, var
+
+
+def _seed64(seed):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def softmax_site_noise(seed, n_f, C, N, device=None):
+    """The standard-normal draws (n_f, C, N) that softmax_sites(eps=None, seed=seed) generates inside its kernel
+    (vargp_softmax_site_noise): Philox group (n n_f + f) ceil(C / 4) + j of noise stream 2, element l of group j for class 4 j + l."""
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != 'cuda':
+        raise _lib.VargpHipError('vargp_amd ops need a ROCm device (cuda:N); there is no CPU path in the product')
+    eps = torch.empty(int(n_f), int(C), int(N), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        check(lib().vargp_softmax_site_noise(_seed64(seed), ptr(eps), int(n_f), int(C), int(N), stream_ptr()),
+              'vargp_softmax_site_noise')
+    return eps
+
+
+def softmax_sites(mu, var, y, w, n_f, seed=0, eps=None):
+    """The Gaussian sites of the softmax likelihood at the marginals mu, var (C, N) fp32 of q(f): y (N,) int64 class indices, w
+    (N,) or None = 1, n_f Monte-Carlo draws per point -- eps (n_f, C, N) if given, else generated in the kernel from `seed` (the
+    draws softmax_site_noise(seed, n_f, C, N) returns; bitwise the same result).  With p = softmax(mu + sqrt(var) eps):
+    -> (lam1 (C, N) = w ([y = c] - E p_c) + lam2 mu, lam2 (C, N) = w E p_c (1 - p_c) >= 0, sums (4,) = (sum_n w ell, sum lam2,
+    #{w != 0}, sum w)), ell_n = mu[y_n, n] - E logsumexp(f).  2 <= C <= SOFTMAX_SITE_MAX_C; a point of weight 0 is not evaluated
+    and adds exactly nothing; bitwise reproducible."""
+    require_device(mu, var, y, w, eps)
+    det = lambda t: t.detach().contiguous()
+    mu, var, y = det(mu), det(var), det(y)
+    assert mu.dim() == 2 and mu.shape == var.shape and mu.dtype == var.dtype == torch.float32, (mu.shape, var.shape, mu.dtype, var.dtype)
+    C, N = mu.shape
+    F = int(n_f)
+    assert tuple(y.shape) == (N,) and y.dtype == torch.int64, (y.shape, y.dtype)
+    if w is not None:
+        w = det(w)
+        assert tuple(w.shape) == (N,) and w.dtype == torch.float32, (w.shape, w.dtype)
+    if eps is not None:
+        eps = det(eps)
+        assert tuple(eps.shape) == (F, C, N) and eps.dtype == torch.float32, (eps.shape, eps.dtype, (F, C, N))
+    lam1, lam2 = torch.empty_like(mu), torch.empty_like(mu)
+    sums = torch.empty(4, dtype=torch.float32, device=mu.device)
+    ws = scratch(lib().vargp_softmax_sites_workspace_bytes(C, N), mu.device)
+    check(lib().vargp_softmax_sites(ptr(mu), ptr(var), ptr(y), ptr(w), ptr(eps), _seed64(seed), ptr(lam1), ptr(lam2), ptr(sums),
+                                    C, N, F, ptr(ws), ws.numel() * 4, stream_ptr()), 'vargp_softmax_sites')
+    return lam1, lam2, sums
+
+
+def gram_moments_v(theta, Z, X, w, v, nu2=0):
+    """gram_moments with a weight vector of its own for c: w (G, N) or None = 1 and v (G, N) -> (Phi (G, Mt, Mt) = sum_n w_n k_n
+    k_n^T, c (G, Mt) = sum_n v_n k_n, sums (G, 2) = (sum w, sum v)).  The same kernel, chunking and scratch; with v = w * y, Phi
+    and c are bitwise gram_moments'."""
+    require_device(theta, Z, X, w, v)
+    theta, Z, X, v = theta.detach().contiguous().view(-1), Z.detach().contiguous(), X.detach().contiguous(), v.detach().contiguous()
+    assert Z.dim() == 3 and X.dim() == 2 and Z.shape[-1] == X.shape[1] and theta.numel() == X.shape[1] + 1, (theta.shape, Z.shape, X.shape)
+    (G, Mt, D), N = Z.shape, X.shape[0]
+    assert tuple(v.shape) == (G, N), (v.shape, G, N)
+    if w is not None:
+        w = w.detach().contiguous()
+        assert tuple(w.shape) == (G, N) and w.dtype == torch.float32, (w.shape, w.dtype)
+    assert all(t.dtype == torch.float32 for t in (theta, Z, X, v)), (theta.dtype, Z.dtype, X.dtype, v.dtype)
+    Phi = torch.empty(G, Mt, Mt, dtype=torch.float32, device=X.device)
+    c = torch.empty(G, Mt, dtype=torch.float32, device=X.device)
+    sums = torch.empty(G, 2, dtype=torch.float32, device=X.device)
+    ws = scratch(lib().vargp_gram_moments_workspace_bytes(G, Mt, N, D), X.device)
+    check(lib().vargp_gram_moments_v(ptr(theta), ptr(Z), ptr(X), ptr(w), ptr(v), ptr(Phi), ptr(c), ptr(sums), G, Mt, N, D, int(nu2),
+                                     ptr(ws), ws.numel() * 4, stream_ptr()), 'vargp_gram_moments_v')
+    return Phi, c, sums
+
+
 def site_bound_bwd_chunks(G, Mt, N, D):
     """The number of chunks ops.site_bound_bwd cuts N points into for this shape; the shapes alone decide it."""
     return int(lib().vargp_site_bound_bwd_chunks(int(G), int(Mt), int(N), int(D)))

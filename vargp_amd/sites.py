@@ -73,7 +73,8 @@ def check_supported(gp, who='fit_q_newton_'):
     lik = gp.likelihood
     if isinstance(lik, MulticlassSoftmax):
         raise ValueError(f'{who}: MulticlassSoftmax couples the outputs of a point, so it has no independent Gaussian sites; '
-                         'use create_clf(likelihood="bernoulli") for a one-vs-rest classifier')
+                         'its own fit is fit_q_softmax_ (create_clf(q_init="newton_softmax")), or use '
+                         'create_clf(likelihood="bernoulli") for a one-vs-rest classifier')
     if isinstance(lik, GaussianLikelihood):
         raise ValueError(f'{who}: for GaussianLikelihood the optimal q(u) has a closed form, use fit_q_')
     if getattr(lik, 'kind', None) not in SITE_KINDS:
@@ -178,8 +179,10 @@ class _Problem:
     """What the iteration needs of the model and the data, gathered once: theta, the (featurised) inducing points of all tasks
     and inputs, the whitening factors, the frozen tasks' whitened posterior, targets, weights and the likelihood's arguments."""
 
+    who = 'fit_q_newton_'
+
     def __init__(self, gp, x, y, weights, route):
-        kern, lik = gp.kernel, gp.likelihood
+        kern = gp.kernel
         self.C, self.M, self.N = gp.z.size(0), gp.M, x.size(0)
         C, M, N = self.C, self.M, self.N
         self.theta = kern.log_mean.detach().to(torch.float32).contiguous()
@@ -187,13 +190,8 @@ class _Problem:
         z_all = torch.cat([p['z'] for p in prev] + [gp.z.detach()], dim=-2).contiguous()
         self.Mt = z_all.size(-2)
         self.n_lt = self.Mt - M
-        self.route = pick_route(route, self.Mt)
-        self.kind, self.extra = lik.kind, tuple(t.detach() if torch.is_tensor(t) else t for t in lik._extra())
-        self.y = site_target(self.kind, y.detach(), C, N)
-        self.w = None
-        if weights is not None:
-            wt, ldw = ops.reg_target(weights, C, N)
-            self.w = wt.expand(C, N).contiguous() if ldw == 0 else wt
+        self.route = pick_route(route, self.Mt, self.who)
+        self._targets(gp.likelihood, y, weights)
         deep = isinstance(kern, DeepRBFKernel)
         self.zf, self.xf = (kern.features(z_all), kern.features(x)) if deep else (z_all, x.detach().contiguous())
         self.nu2 = int(round(2 * kern.nu)) if isinstance(kern, MaternKernel) else 0
@@ -211,25 +209,45 @@ class _Problem:
         self.eye_t = torch.eye(self.Mt, dtype=torch.float32, device=x.device)
         self.eye = torch.eye(M, dtype=torch.float64, device=x.device)
 
+    def _targets(self, lik, y, weights):
+        """The likelihood's arguments, the targets and the weights as the data passes take them."""
+        C, N = self.C, self.N
+        self.kind, self.extra = lik.kind, tuple(t.detach() if torch.is_tensor(t) else t for t in lik._extra())
+        self.y = site_target(self.kind, y.detach(), C, N)
+        self.w = None
+        if weights is not None:
+            wt, ldw = ops.reg_target(weights, C, N)
+            self.w = wt.expand(C, N).contiguous() if ldw == 0 else wt
+
+    def _passes(self, alpha, Q):
+        """The passes over the data at q(f_n) = N(alpha . k_n, gamma^2 - k_n^T Q k_n): -> (Phi (C, Mt, Mt), c (C, Mt), the data
+        term of the bound float64, clamped points)."""
+        pass_ = ops.site_moments if self.route == 'fused' else composed_site_moments
+        lam2, c, sums = pass_(self.theta, self.zf, self.xf, alpha, Q, self.y, self.w, self.kind, self.extra, self.nu2)
+        Phi = ops.gram_moments(self.theta, self.zf, self.xf, lam2, lam2, self.nu2)[0]
+        return Phi, c, sums[:, 0].double(), sums[:, 2]
+
+    def bound(self, data, kl):
+        """The bound as the trace holds it, from the data term and KL(q(v_t) || N(0, I)) (C,): one entry per output."""
+        return data - kl
+
     def sites(self, a_t, H_t):
-        """The two passes over the data at q(v_t) = N(a_t, H_t H_t^T): -> (sum_n w ell (C,) float64, I + A_tt, tc_t - A_{t,<} a_<,
-        clamped points (C,))."""
+        """The passes over the data at q(v_t) = N(a_t, H_t H_t^T): -> (the data term of the bound, float64, I + A_tt,
+        tc_t - A_{t,<} a_<, clamped points)."""
         a = torch.cat([self.a_lt, a_t], dim=-1)
         alpha = _mv(self.T.mT.double(), a).float().contiguous()
         self.Hb[:, self.n_lt:, self.n_lt:] = H_t
         S = self.eye_t - ops.bgemm(self.Hb, self.Hb.mT)
         Q = ops.bgemm(ops.bgemm(self.T.mT, S), self.T)
         Q = (0.5 * (Q + Q.mT)).contiguous()
-        pass_ = ops.site_moments if self.route == 'fused' else composed_site_moments
-        lam2, c, sums = pass_(self.theta, self.zf, self.xf, alpha, Q, self.y, self.w, self.kind, self.extra, self.nu2)
-        Phi = ops.gram_moments(self.theta, self.zf, self.xf, lam2, lam2, self.nu2)[0]
+        Phi, c, data, clamped = self._passes(alpha, Q)
         T, n_lt = self.T, self.n_lt
         A = ops.matmul(ops.matmul(T, Phi, triA=LOWER), T.mT, triB=UPPER).double()
         A = 0.5 * (A + A.mT)
         tc = ops.matmul(T, c.unsqueeze(-1), triA=LOWER).squeeze(-1).double()
         P_new = self.eye + A[:, n_lt:, n_lt:]
         h_new = tc[:, n_lt:] - _mv(A[:, n_lt:, :n_lt], self.a_lt)
-        return sums[:, 0].double(), P_new, h_new, sums[:, 2]
+        return data, P_new, h_new, clamped
 
     def from_natural(self, P, h):
         """Sigma_t = P^-1 = G G^T with G lower triangular (the Cholesky factor of the reversed P, reversed back, as fit_q_ factors
@@ -301,63 +319,202 @@ def fit_q_newton_(gp, x, y, n_iters=20, damping=1.0, tol=1e-6, weights=None, rou
     function space; a Poisson likelihood, whose expected log-likelihood holds exp(mu + var / 2), can be far too steep there for
     any damped step to be accepted -- start such a model at the prior.  -> SiteFit(bound (n_iters + 1, C) float64 on the host, n_iters, n_rejected, n_clamped, route)."""
     check_supported(gp)
-    damping = check_damping(damping)
-    n_iters = int(n_iters)
-    if n_iters < 0:
-        raise ValueError(f'fit_q_newton_: n_iters must be >= 0, got {n_iters}')
-    if start not in ('current', 'prior'):
-        raise ValueError(f"fit_q_newton_: start must be 'current' or 'prior', got {start!r}")
+    damping, n_iters = _check_loop_args('fit_q_newton_', damping, n_iters, start)
     ops.require_device(gp.z, x, y, weights)
     with torch.no_grad():
-        pr = _Problem(gp, x, y, weights, route)
-        M = pr.M
-        if start == 'prior':
-            a_t = torch.zeros(pr.C, M, dtype=torch.float64, device=x.device)
-            H_t = torch.eye(M, dtype=torch.float32, device=x.device).expand(pr.C, M, M).contiguous()
-            P, h, kl = pr.eye.expand(pr.C, M, M), torch.zeros_like(a_t), torch.zeros(pr.C, dtype=torch.float64, device=x.device)
-        else:
-            # the model's q(u_t) in whitened coordinates and natural parameters: H_t^-1 = L_u^-1 L_tt
-            L_u = ops.vec2tril(gp.u_tril_vec.detach().float(), M)
-            a_t = ops.matmul(pr.T_tt, gp.u_mean.detach().float(), triA=LOWER).squeeze(-1).double()
-            H_t = ops.bgemm(pr.T_tt, L_u, triA=LOWER, triB=LOWER).tril()
-            T_u = ops.chol_inv(ops.bgemm(L_u, L_u.mT), 0.0)[1]
-            H_inv = ops.bgemm(T_u, pr.L_tt, triA=LOWER, triB=LOWER).tril()
-            P = ops.bgemm(H_inv.mT, H_inv).double()
-            P = 0.5 * (P + P.mT)
-            h = _mv(P, a_t)
-            H64 = H_t.double()
-            kl = 0.5 * (a_t.square().sum(-1) + H64.square().sum((-2, -1)) - M
-                        - 2.0 * H64.diagonal(dim1=-2, dim2=-1).log().sum(-1))
+        return _fit(gp, _Problem(gp, x, y, weights, route), n_iters, damping, tol, start)
 
-        data, P_new, h_new, clamped = pr.sites(a_t, H_t)
-        bound = (data - kl).cpu()
-        if not bool(torch.isfinite(bound).all()):
-            raise FloatingPointError(f'fit_q_newton_: the bound is not finite at the initial q(u): {bound.tolist()}')
-        trace, n_rejected, changed = [bound], 0, start == 'prior'
-        while len(trace) - 1 < n_iters:
-            rho, accepted = damping, None
-            for _ in range(MAX_HALVINGS + 1):
-                P_c, h_c = (1.0 - rho) * P + rho * P_new, (1.0 - rho) * h + rho * h_new
-                a_c, G_c, kl_c = pr.from_natural(P_c, h_c)
-                data_c, P_next, h_next, clamped_c = pr.sites(a_c, G_c)
-                bound_c = (data_c - kl_c).cpu()
-                if bool(torch.isfinite(bound_c).all()) and bool((bound_c >= trace[-1]).all()):
-                    accepted = (P_c, h_c, a_c, G_c, P_next, h_next, clamped_c)
-                    break
-                n_rejected += 1
-                rho *= 0.5
-            if accepted is None:
-                break
-            P, h, a_t, H_t, P_new, h_new, clamped = accepted
-            trace.append(bound_c)
-            changed = True
-            if (trace[-1].sum() - trace[-2].sum()).item() < tol * abs(trace[-1].sum().item()):
-                break
 
-        if changed:
-            _write_q(gp, pr.L_tt, a_t, H_t)
-        n_clamped = int(round(clamped.double().sum().item()))
+def _check_loop_args(who, damping, n_iters, start):
+    damping = check_damping(damping, who)
+    n_iters = int(n_iters)
+    if n_iters < 0:
+        raise ValueError(f'{who}: n_iters must be >= 0, got {n_iters}')
+    if start not in ('current', 'prior'):
+        raise ValueError(f"{who}: start must be 'current' or 'prior', got {start!r}")
+    return damping, n_iters
+
+
+def _fit(gp, pr, n_iters, damping, tol, start):
+    """The iteration of the module docstring on the problem `pr` (its passes over the data, its form of the bound), from `start`
+    with backtracking; writes the last accepted q(u_t) into gp.  Under no_grad.  -> SiteFit"""
+    M, dev = pr.M, pr.theta.device
+    if start == 'prior':
+        a_t = torch.zeros(pr.C, M, dtype=torch.float64, device=dev)
+        H_t = torch.eye(M, dtype=torch.float32, device=dev).expand(pr.C, M, M).contiguous()
+        P, h, kl = pr.eye.expand(pr.C, M, M), torch.zeros_like(a_t), torch.zeros(pr.C, dtype=torch.float64, device=dev)
+    else:
+        # the model's q(u_t) in whitened coordinates and natural parameters: H_t^-1 = L_u^-1 L_tt
+        L_u = ops.vec2tril(gp.u_tril_vec.detach().float(), M)
+        a_t = ops.matmul(pr.T_tt, gp.u_mean.detach().float(), triA=LOWER).squeeze(-1).double()
+        H_t = ops.bgemm(pr.T_tt, L_u, triA=LOWER, triB=LOWER).tril()
+        T_u = ops.chol_inv(ops.bgemm(L_u, L_u.mT), 0.0)[1]
+        H_inv = ops.bgemm(T_u, pr.L_tt, triA=LOWER, triB=LOWER).tril()
+        P = ops.bgemm(H_inv.mT, H_inv).double()
+        P = 0.5 * (P + P.mT)
+        h = _mv(P, a_t)
+        H64 = H_t.double()
+        kl = 0.5 * (a_t.square().sum(-1) + H64.square().sum((-2, -1)) - M
+                    - 2.0 * H64.diagonal(dim1=-2, dim2=-1).log().sum(-1))
+
+    data, P_new, h_new, clamped = pr.sites(a_t, H_t)
+    bound = pr.bound(data, kl).cpu()
+    if not bool(torch.isfinite(bound).all()):
+        raise FloatingPointError(f'{pr.who}: the bound is not finite at the initial q(u): {bound.tolist()}')
+    trace, n_rejected, changed = [bound], 0, start == 'prior'
+    while len(trace) - 1 < n_iters:
+        rho, accepted = damping, None
+        for _ in range(MAX_HALVINGS + 1):
+            P_c, h_c = (1.0 - rho) * P + rho * P_new, (1.0 - rho) * h + rho * h_new
+            a_c, G_c, kl_c = pr.from_natural(P_c, h_c)
+            data_c, P_next, h_next, clamped_c = pr.sites(a_c, G_c)
+            bound_c = pr.bound(data_c, kl_c).cpu()
+            if bool(torch.isfinite(bound_c).all()) and bool((bound_c >= trace[-1]).all()):
+                accepted = (P_c, h_c, a_c, G_c, P_next, h_next, clamped_c)
+                break
+            n_rejected += 1
+            rho *= 0.5
+        if accepted is None:
+            break
+        P, h, a_t, H_t, P_new, h_new, clamped = accepted
+        trace.append(bound_c)
+        changed = True
+        if (trace[-1].sum() - trace[-2].sum()).item() < tol * abs(trace[-1].sum().item()):
+            break
+
+    if changed:
+        _write_q(gp, pr.L_tt, a_t, H_t)
+    n_clamped = int(round(clamped.double().sum().item()))
     return SiteFit(torch.stack(trace), len(trace) - 1, n_rejected, n_clamped, pr.route)
+
+
+# -- the softmax: coupled outputs, one Gaussian site per (class, point) all the same --------------------------------------------------
+# q factorises over the classes, so conjugate-computation VI still gives one Gaussian site per (class, point); the coupling is
+# only in how the site parameters are COMPUTED: all C marginals of a point enter one expectation over p = softmax(f_n),
+# f_n ~ N(mu_n, diag(var_n)):
+#     ell_n = E log p_{y_n} = mu_{y_n, n} - E logsumexp(f_n)
+#     d ell / d mu_c = [y_n = c] - E p_c (Bonnet),   d ell / d var_c = -1/2 E[p_c (1 - p_c)] <= 0 (Price): nothing is ever clamped
+#     lam2_cn = w_n E[p_c (1 - p_c)],   lam1_cn = w_n ([y_n = c] - E p_c) + lam2_cn mu_cn
+# Everything after that is the iteration of the module docstring, per class.  The expectations are Monte-Carlo means over n_f draws
+# per point, as the softmax nll takes them, with noise FIXED for the whole fit (common random numbers: a counter-based stream keyed
+# by `seed`, generated inside the kernel), so the bound is a deterministic function of q.  The data term is joint over the
+# classes: a candidate is accepted on the SUMMED bound, and the trace has one column.
+# One iteration is three launches-with-reduce over the data: ops.site_marginals (site_moments' kernel stopped after mu and var),
+# ops.softmax_sites, ops.gram_moments_v(w=lam2, v=lam1) -- v a weight vector of its own because lam1 / lam2 is not representable:
+# lam2 underflows to 0 exactly at the confidently MISCLASSIFIED points, where lam1 ~ 1 matters most.
+# CAVEAT: lam1 and lam2 are unbiased Bonnet / Price estimates of the derivatives of the exact ell; they are NOT the exact
+# derivatives of its n_f-sample estimate (whose derivative for var_c holds eps / sqrt(var) terms).  Near the optimum a full step
+# can therefore lower the ESTIMATED bound, by about 1e-5 relative; the fit then ends by rejection (all halvings fail) rather than
+# by tol, at the last accepted q.
+def check_softmax_supported(gp, who='fit_q_softmax_'):
+    """ValueError unless the softmax site iteration applies to the model: MulticlassSoftmax, ep_var_mean=True, an RBF / Matern /
+    deep-RBF kernel.  Needs no device."""
+    if not isinstance(gp.likelihood, MulticlassSoftmax):
+        raise ValueError(f'{who}: supported for MulticlassSoftmax only, got {type(gp.likelihood).__name__}; the likelihoods with '
+                         'independent outputs have fit_q_newton_ (q_init="newton"), GaussianLikelihood has fit_q_')
+    if gp.var_mean_mask != 1.0:
+        raise ValueError(f'{who}: supported for ep_var_mean=True models only (with ep_var_mean=False the mean of q(u_t) is not '
+                         'u_mean alone)')
+    if not isinstance(gp.kernel, RBFKernel):
+        raise ValueError(f'{who}: supported kernels are RBFKernel, MaternKernel and DeepRBFKernel, got {type(gp.kernel).__name__}')
+    if gp.z.size(0) > ops.SOFTMAX_SITE_MAX_C:
+        raise ValueError(f'{who}: at most {ops.SOFTMAX_SITE_MAX_C} classes, got {gp.z.size(0)}')
+
+
+def composed_softmax_marginals(theta, Z, X, alpha, Q, nu2=0, tile=COMPOSED_TILE):
+    """ops.site_marginals from the per-op kernels, a tile of N at a time (arguments and results alike; any Mt): the gram op and
+    ops.bgemm for alpha K and Q K."""
+    ops.require_device(theta, Z, X, alpha, Q)
+    (G, Mt, D), N = Z.shape, X.shape[0]
+    th = theta.detach().view(1, -1).contiguous()
+    gram = (lambda Xt: ops.rbf_gram(th, Z, Xt, True)) if nu2 == 0 else (lambda Xt: ops.matern_gram(th, Z, Xt, True, 0.5 * nu2))
+    g2 = (2.0 * th[0, -1]).exp()
+    mu = torch.empty(G, N, dtype=torch.float32, device=X.device)
+    var = torch.empty(G, N, dtype=torch.float32, device=X.device)
+    for n0 in range(0, N, tile):
+        n1 = min(n0 + tile, N)
+        K = gram(X[n0:n1].contiguous())[0]                                            # (G, Mt, B)
+        mu[:, n0:n1] = ops.bgemm(alpha.unsqueeze(-2), K).squeeze(-2)
+        var[:, n0:n1] = (g2 - (K * ops.bgemm(Q, K)).sum(-2)).clamp_min(0.0)
+    return mu, var
+
+
+def composed_softmax_sites(mu, var, y, w, eps):
+    """ops.softmax_sites in plain fp32 elementwise torch on the device, with explicit eps (n_f, C, N) (arguments and results
+    alike; the sums in fp64): the on-device yardstick of the kernel."""
+    ops.require_device(mu, var, y, w, eps)
+    C, N = mu.shape
+    f = mu + var.sqrt() * eps                                                         # (F, C, N)
+    m = f.max(-2, keepdim=True).values
+    e = (f - m).exp()
+    s = e.sum(-2, keepdim=True)
+    p = e / s
+    lse = (m + s.log()).squeeze(-2).mean(0)                                           # (N,)
+    Ep, Ev = p.mean(0), (p * (1.0 - p)).mean(0)
+    wt = torch.ones(N, dtype=torch.float32, device=mu.device) if w is None else w
+    on = wt != 0
+    hot = (y.unsqueeze(0) == torch.arange(C, device=y.device).unsqueeze(1)).to(torch.float32)
+    zero = torch.zeros_like(mu)
+    lam2 = torch.where(on, wt * Ev, zero)
+    lam1 = torch.where(on, wt * (hot - Ep) + lam2 * mu, zero)
+    ell = torch.where(on, wt.double() * ((mu * hot).sum(0) - lse).double(), torch.zeros(N, dtype=torch.float64, device=mu.device))
+    sums = torch.stack([ell.sum(), lam2.double().sum(), on.double().sum(), wt.double().sum()])
+    return lam1, lam2, sums.float()
+
+
+class _SoftmaxProblem(_Problem):
+    """_Problem with the softmax's three passes and its joint data term."""
+    who = 'fit_q_softmax_'
+
+    def __init__(self, gp, x, y, weights, route, n_f, seed):
+        self.n_f, self.seed = n_f, seed
+        super().__init__(gp, x, y, weights, route)
+
+    def _targets(self, lik, y, weights):
+        N = self.N
+        y = y.detach()
+        if y.dtype != torch.int64 or tuple(y.shape) != (N,):
+            raise ValueError(f'fit_q_softmax_: y must be int64 class indices of shape ({N},), got {y.dtype} {tuple(y.shape)}')
+        self.y = y.contiguous()
+        self.w = None if weights is None else weights.detach().to(torch.float32).contiguous()
+
+    def _passes(self, alpha, Q):
+        marginals = ops.site_marginals if self.route == 'fused' else composed_softmax_marginals
+        mu, var = marginals(self.theta, self.zf, self.xf, alpha, Q, self.nu2)
+        lam1, lam2, sums = ops.softmax_sites(mu, var, self.y, self.w, self.n_f, self.seed)
+        Phi, c, _ = ops.gram_moments_v(self.theta, self.zf, self.xf, lam2, lam1, self.nu2)
+        return Phi, c, sums[:1].double(), torch.zeros((), device=mu.device)
+
+    def bound(self, data, kl):
+        return data - kl.sum(-1, keepdim=True)
+
+
+def fit_q_softmax_(gp, x, y, n_iters=20, damping=1.0, tol=1e-6, weights=None, route=None, start='current', n_f=32, seed=0):
+    """fit_q_newton_ for the model the project exists for: fit q(u_t) of a MulticlassSoftmax VARGP model to the data x (N, D), y
+    (N,) int64 class indices, by the natural-gradient site iteration of the module docstring with the softmax sites of the comment
+    above; in place and under no_grad.  The expectations over the softmax are means over n_f draws per point whose noise is fixed
+    by `seed` for the whole fit, so the bound is a deterministic function of q and the trace never falls.  At most n_iters accepted
+    steps of length damping in (0, 1] (halved while a candidate lowers the SUMMED bound -- the data term is joint over the
+    classes), until it rises by less than tol |bound|.  weights None or (N,), >= 0.  First-task models and models with
+    prev_params; RBF, Matern and deep-RBF kernels; ep_var_mean=True.  route: None ('fused' up to ops.SITE_MAX_MT inducing points
+    over all tasks, 'composed' above; VARGP_SITES_ROUTE overrides), 'fused' or 'composed' (the marginals from the gram op and
+    ops.bgemm a tile of N at a time; the other two passes have no limit).  start: 'current' or 'prior', as fit_q_newton_.
+    CAVEAT: lam1 and lam2 are unbiased Bonnet / Price estimates, not the exact derivatives of the n_f-sample estimate of the
+    expected log-likelihood: near the optimum a full step can lower the estimated bound by about 1e-5 relative, and the fit then
+    ends by rejection rather than by tol, at the last accepted q.
+    -> SiteFit(bound (n_iters + 1, 1) float64 on the host: the summed bound, non-decreasing; n_iters; n_rejected; n_clamped = 0
+    always (d ell / d var <= 0); route)."""
+    check_softmax_supported(gp)
+    damping, n_iters = _check_loop_args('fit_q_softmax_', damping, n_iters, start)
+    n_f = int(n_f)
+    if not 1 <= n_f <= 65535:
+        raise ValueError(f'fit_q_softmax_: n_f must be in [1, 65535], got {n_f}')
+    if weights is not None and tuple(weights.shape) != (x.size(0),):
+        raise ValueError(f'fit_q_softmax_: weights must have shape ({x.size(0)},): one weight per point (the classes of a point '
+                         f'share one likelihood term), got {tuple(weights.shape)}')
+    ops.require_device(gp.z, x, y, weights)
+    with torch.no_grad():
+        return _fit(gp, _SoftmaxProblem(gp, x, y, weights, route, n_f, int(seed)), n_iters, damping, tol, start)
 
 
 # -- the site bound on the autograd graph: variational EM ----------------------------------------------------------------------------

@@ -66,7 +66,7 @@ def _hand_over_hyper_prior(prev_params):
 _Z_INITS = ('greedy', 'kmeans', 'random')                  # create_clf / create_reg (z_init=)
 _LENGTHSCALE_INITS = ('default', 'median')        # (lengthscale_init=)
 _Q_INITS = ('default', 'optimal', 'collapsed', 'newton', 'em')      # create_reg (q_init=)
-_CLF_Q_INITS = ('default', 'newton', 'em')                          # create_clf (q_init=)
+_CLF_Q_INITS = ('default', 'newton', 'em', 'newton_softmax')        # create_clf (q_init=)
 
 
 def _check_init_names(who, z_init, lengthscale_init):
@@ -613,6 +613,18 @@ class VARGP(nn.Module):
         return sites.fit_q_newton_(self, x, y, n_iters=n_iters, damping=damping, tol=tol, weights=weights, route=route,
                                    start=start)
 
+    def fit_q_softmax_(self, x, y, n_iters=20, damping=1.0, tol=1e-6, weights=None, route=None, start='current', n_f=32, seed=0):
+        """fit_q_newton_'s counterpart for MulticlassSoftmax (sites.fit_q_softmax_, not in the reference): the same full-batch
+        natural-gradient iterations on q(u) of this task, with one Gaussian site per (class, point) whose parameters come from
+        ONE expectation over the softmax of all C marginals of the point -- a mean over n_f draws per point, their noise fixed by
+        `seed` for the whole fit.  Three fused passes over x (N, D) per iteration, K(z, x) never stored.  y (N,) int64 class
+        indices; weights None or (N,).  A candidate is accepted on the bound summed over the classes.
+        -> sites.SiteFit(bound (n_iters + 1, 1) float64 on the host, non-decreasing; n_iters; n_rejected; n_clamped = 0; route).
+        ValueError for any other likelihood, ep_var_mean=False, (C, N) weights and a bad damping, start or n_f.  Near the optimum
+        the fit usually ends by a rejected step rather than by tol: see the caveat in sites.py."""
+        return sites.fit_q_softmax_(self, x, y, n_iters=n_iters, damping=damping, tol=tol, weights=weights, route=route,
+                                    start=start, n_f=n_f, seed=seed)
+
     def site_bound(self, x, y, weights=None, q=None, route=None):
         """The variational bound of x (N, D), y (as fit_q_newton_ takes it) per output for a Bernoulli, Poisson or Student-t model
         (sites.site_bound, not in the reference): (C,) float64 on the autograd graph of z, kernel.log_mean and the Student-t
@@ -679,7 +691,7 @@ class VARGP(nn.Module):
     def create_clf(dataset, M=20, n_f=10, n_var_samples=3, prev_params=None,
                    ep_var_mean=True, map_est_hypers=False, dkl=False, kernel='rbf', native_kernel=False,
                    likelihood='softmax', link='probit', z_init='random', kmeans_iters=20, lengthscale_init='default',
-                   greedy_candidates=4096, q_init='default', newton_iters=20, em_rounds=5, em_steps=20):
+                   greedy_candidates=4096, q_init='default', newton_iters=20, em_rounds=5, em_steps=20, site_samples=32):
         """Factory used by the experiment driver (vargp.py:200-243): inducing points at random data
         points per class, hyper-prior = previous task's hyper-posterior (popped from prev_params[-1],
         which is mutated like the reference does).  kernel: 'rbf' (the reference's), or 'matern12' / 'matern32' /
@@ -698,9 +710,14 @@ class VARGP(nn.Module):
         on the whole data set on the current CUDA device; the model returns on the device the default route returns it on.
         'em' (likelihood='bernoulli', RBF / Matern kernel): fit_sites_(n_rounds=em_rounds, m_steps=em_steps,
         newton_iters=newton_iters, start='prior') instead -- variational EM that also moves the inducing points and
-        kernel.log_mean up the bound (without the hyper-prior)."""
+        kernel.log_mean up the bound (without the hyper-prior).  'newton_softmax' (likelihood='softmax' only):
+        fit_q_softmax_(n_iters=newton_iters, start='prior', n_f=site_samples) -- the same fit for the reference's own
+        likelihood, with site_samples draws per point behind every expectation over the softmax."""
         if q_init not in _CLF_Q_INITS:
             raise ValueError(f'create_clf: q_init must be one of {sorted(_CLF_Q_INITS)}, got {q_init!r}')
+        if q_init == 'newton_softmax' and likelihood != 'softmax':
+            raise ValueError(f"create_clf: q_init='newton_softmax' fits the coupled sites of likelihood='softmax', got "
+                             f"{likelihood!r}; the likelihoods with independent outputs have q_init='newton'")
         if q_init in ('newton', 'em') and likelihood != 'bernoulli':
             raise ValueError(f"create_clf: q_init={q_init!r} fits independent Gaussian sites, which likelihood={likelihood!r} does "
                              "not have (its outputs are coupled); use likelihood='bernoulli'")
@@ -762,6 +779,13 @@ class VARGP(nn.Module):
                 gp.to(dev).fit_q_newton_(x, y, n_iters=newton_iters, start='prior')
             else:
                 gp.to(dev).fit_sites_(x, y, n_rounds=em_rounds, m_steps=em_steps, newton_iters=newton_iters, start='prior')
+            gp.to(home)
+        elif q_init == 'newton_softmax':
+            sites.check_softmax_supported(gp, 'create_clf(q_init="newton_softmax")')
+            home, dev = gp.z.device, torch.device('cuda', torch.cuda.current_device())
+            x = dataset[torch.arange(len(dataset))][0].to(device=dev, dtype=torch.float32)
+            y = torch.as_tensor(dataset.targets).to(device=dev, dtype=torch.int64)
+            gp.to(dev).fit_q_softmax_(x, y, n_iters=newton_iters, start='prior', n_f=site_samples)
             gp.to(home)
         return gp
 
