@@ -4,12 +4,12 @@ u_tril_vec and returns the bound's value at the optimum; for a Gaussian likeliho
 `collapsed_bound` is the same value on the autograd graph of z, kernel.log_mean and obs_log_var, and `fit_collapsed_` climbs it
 (SGPR: no q(u) parameter; VARGP.collapsed_bound, VARGP.fit_collapsed_, create_reg(q_init='collapsed')).
 
-Everything happens at ONE hyper vector, theta = kernel.log_mean, in the whitened coordinates of gp_utils.block_joint: with
-K' = K(z_<=t) + eps I = L L^T, T = L^-1 and v = T u, the posterior is q(v) = N(a, H H^T) with block-diagonal H, the blocks of the
-frozen tasks i < t being a_i = T_ii m_i, H_i = T_ii Lu_i.  The data enter through two weighted moments of the cross-kernel,
-Phi = sum_n w_n k_n k_n^T and c = sum_n w_n y_n k_n, k_n = k(z_<=t, x_n) (ops.gram_moments, csrc/moments.hip: K(z, X) is never
-stored), and sw = sum_n w_n, syy = sum_n w_n y_n^2.  With A = T Phi T^T, tc = T c, beta = temper / sigma^2 per output, `<` the
-earlier tasks and `t` the new block:
+Everything happens at ONE hyper vector, theta = kernel.log_mean, in the whitened coordinates of whitened.py's docstring (K' = L L^T,
+T = L^-1, v = T u, q(v) = N(a, H H^T) with the frozen tasks' blocks a_i, H_i; A, tc, the reversed Cholesky and the writer are
+defined there).  The data enter through two weighted moments of the cross-kernel, Phi = sum_n w_n k_n k_n^T and
+c = sum_n w_n y_n k_n, k_n = k(z_<=t, x_n) (ops.gram_moments, csrc/moments.hip: K(z, X) is never stored), and sw = sum_n w_n,
+syy = sum_n w_n y_n^2.  With A = T Phi T^T, tc = T c, beta = temper / sigma^2 per output, `<` the earlier tasks and `t` the new
+block:
 
     b_t     = tc_t - A_{t,<} a_<
     Sigma_t = (I + beta A_tt)^-1           a_t = beta Sigma_t b_t
@@ -21,8 +21,8 @@ earlier tasks and `t` the new block:
 `bound` = E_q log N(y | f, 1 / beta) - KL(q(v_t) || N(0, I)) at its maximum over (a_t, H_t): the standard variational bound of the
 new task's data (tests/test_collapsed.py restates all of this in fp64, checks that the bound's gradient vanishes there and that the
 closed form equals the evaluated bound).  Sigma_t has its eigenvalues in (0, 1] whatever the conditioning of K'.  u_tril comes
-without a second factorisation: I + beta A_tt = U U^T with U UPPER triangular (the Cholesky factor of the matrix with rows and
-columns reversed, reversed back), so Sigma_t = G G^T with G = U^-T lower triangular and u_tril = L_tt G.
+without a second factorisation: I + beta A_tt = U U^T with U upper triangular (whitened.reversed_chol), so Sigma_t = G G^T with
+G = U^-T lower triangular and u_tril = L_tt G.
 
 CAVEAT: GaussianLikelihood.loss is the reference's -log N(y | mu, var + sigma^2) (its mean over outputs), not -E_q log p(y | f).
 fit_q_ maximises the standard bound above, so the q(u) it writes is NOT exactly the minimiser of kl_u + nll as VARGP.loss
@@ -33,98 +33,68 @@ from collections import namedtuple
 import torch
 
 from . import ops
-from .kernels import DeepRBFKernel, MaternKernel, RBFKernel
 from .likelihoods import GaussianLikelihood
-from .ops import LOWER, UPPER
+from .optim import ascend_, choose_params
+from .whitened import Frame, check_model, mv, reversed_chol, rows, whiten_moments, write_q_
+from .whitened import inv_softplus  # noqa: F401  (public here too: the inverse of the diagonal map of u_tril_vec that fit_q_ writes)
 
 CollapsedFit = namedtuple('CollapsedFit', 'bound n_chunks')
 CollapsedFit.__doc__ = """bound (C,) float64: per output, the variational bound of the fitted data at the optimal q(u) (nats);
 n_chunks: the number of chunks the moment kernel cut the N points into (ops.gram_moments_chunks)."""
 
 
+def _check_likelihood(lik, who):
+    if not isinstance(lik, GaussianLikelihood):
+        raise ValueError(f'{who}: the closed-form q(u) exists for GaussianLikelihood only (create_reg(likelihood="gaussian")), '
+                         f'got {type(lik).__name__}')
+
+
 def check_supported(gp, who='fit_q_'):
     """ValueError unless the closed form applies to the model: GaussianLikelihood, ep_var_mean=True, an RBF / Matern / deep-RBF
     kernel.  Needs no device."""
-    if not isinstance(gp.likelihood, GaussianLikelihood):
-        raise ValueError(f'{who}: the closed-form q(u) exists for GaussianLikelihood only (create_reg(likelihood="gaussian")), '
-                         f'got {type(gp.likelihood).__name__}')
-    if gp.var_mean_mask != 1.0:
-        raise ValueError(f'{who}: supported for ep_var_mean=True models only (with ep_var_mean=False the mean of q(u_t) is not '
-                         'u_mean alone)')
-    if not isinstance(gp.kernel, RBFKernel):
-        raise ValueError(f'{who}: supported kernels are RBFKernel, MaternKernel and DeepRBFKernel, got {type(gp.kernel).__name__}')
-
-
-def _mv(A, v):
-    """A v over the last dims, elementwise (fp64 on the device without a BLAS call): A (.., m, n), v (.., n) -> (.., m)."""
-    return (A * v.unsqueeze(-2)).sum(-1)
-
-
-def inv_softplus(d):
-    """v with softplus(v) = d > 0 (the diagonal of vec2tril), in the dtype of d."""
-    return torch.where(d > 20.0, d, torch.log(torch.expm1(d.clamp_max(20.0))))
+    check_model(gp, who, _check_likelihood)
 
 
 def _whitened_bound(gp, x, y, weights, temper):
     """The module docstring's formulas, once, for fit_q_ and collapsed_bound alike: every step is a differentiable op (or fp64
     elementwise torch), so under no_grad this is the plain computation and otherwise the bound sits on the autograd graph of gp.z,
     kernel.log_mean and obs_log_var.  -> (bound (C,) float64, n_chunks, what fit_q_ needs for q(u_t): beta, L_tt, G, G64, gb)."""
-    kern = gp.kernel
-    C, M, N = gp.z.size(0), gp.M, x.size(0)
-    theta = kern.log_mean.to(torch.float32).contiguous()
-    prev = [gp._prev(i) for i in range(len(gp.prev_params))]
-    z_all = torch.cat([p['z'] for p in prev] + [gp.z], dim=-2).contiguous()
-    Mt = z_all.size(-2)
-    n_lt = Mt - M
-    yt, ldy = ops.reg_target(y, C, N)
-    yt = yt.expand(C, N).contiguous() if ldy == 0 else yt
-    wt = None
-    if weights is not None:
-        wt, ldw = ops.reg_target(weights, C, N)
-        wt = wt.expand(C, N).contiguous() if ldw == 0 else wt
-    deep = isinstance(kern, DeepRBFKernel)
-    zf, xf = (kern.features(z_all), kern.features(x)) if deep else (z_all, x)
-    nu2 = int(round(2 * kern.nu)) if isinstance(kern, MaternKernel) else 0
+    fr = Frame(gp)
+    C, M, N, n_lt = fr.C, fr.M, x.size(0), fr.n_lt
+    wt = None if weights is None else rows(weights, C, N)
+    zf, xf = fr.operands(x)
 
-    # the only pass over the data (and, in the backward, the only other one)
-    Phi, c, sums = ops.gram_moments_diff(theta, zf, xf, wt, yt, nu2)
-    n_chunks = ops.gram_moments_chunks(C, Mt, N, zf.size(-1))
+    # the only pass over the data (and, in the backward, the only other one); BEFORE the factorisation (whitened.py: ORDER)
+    Phi, c, sums = ops.gram_moments_diff(fr.theta, zf, xf, wt, rows(y, C, N), fr.nu2)
+    n_chunks = ops.gram_moments_chunks(C, fr.Mt, N, zf.size(-1))
 
-    L, T = ops.chol_inv(kern.compute(theta.unsqueeze(0), z_all)[0])                  # (C, Mt, Mt): as block_joint factorises
-    A = ops.matmul(ops.matmul(T, Phi, triA=LOWER), T.mT, triB=UPPER).double()
-    A = 0.5 * (A + A.mT)
-    tc = ops.matmul(T, c.unsqueeze(-1), triA=LOWER).squeeze(-1).double()
+    A, tc = whiten_moments(fr.T, Phi, c)
     sw, syy = sums[:, 0].double(), sums[:, 1].double()
     beta = float(temper) * (-gp.likelihood.obs_log_var.double()).exp()               # (C,)
-    g2 = (2.0 * theta[-1].double()).exp()
+    g2 = (2.0 * fr.theta[-1].double()).exp()
 
     # the frozen tasks: a_< and sum_i tr(H_i^T A_ii H_i)
-    a_lt, trHAH, o = [], torch.zeros(C, dtype=torch.float64, device=x.device), 0
-    for p in prev:
-        n = p['z'].size(-2)
-        T_ii = T[:, o:o + n, o:o + n].contiguous()
-        a_lt.append(ops.matmul(T_ii, p['u_mean'], triA=LOWER).squeeze(-1).double())
-        H = ops.matmul(T_ii, p['u_tril'], triA=LOWER, triB=LOWER).double().tril()
+    a_lt, H_lt = fr.frozen
+    trHAH, o = torch.zeros(C, dtype=torch.float64, device=x.device), 0
+    for H in H_lt:
+        n, H = H.size(-1), H.double()
         A_ii = A[:, o:o + n, o:o + n]
         trHAH = trHAH + ((A_ii.unsqueeze(-1) * H.unsqueeze(-3)).sum(-2) * H).sum((-2, -1))
         o += n
-    a_lt = torch.cat(a_lt, dim=-1) if a_lt else tc.new_zeros(C, 0)
     A_ll, A_tl, A_tt = A[:, :n_lt, :n_lt], A[:, n_lt:, :n_lt], A[:, n_lt:, n_lt:]
-    b_t = tc[:, n_lt:] - _mv(A_tl, a_lt)
+    b_t = tc[:, n_lt:] - mv(A_tl, a_lt)
 
-    # I + beta A_tt = U U^T, U upper: the Cholesky factor of the reversed matrix, reversed back; G = U^-T is lower
-    Bm = torch.eye(M, dtype=torch.float64, device=x.device) + beta.view(C, 1, 1) * A_tt
-    Lr, Tr = ops.chol_inv(Bm.flip(-2, -1).float().contiguous(), 0.0)
-    G = Tr.mT.flip(-2, -1).contiguous()                                               # Sigma_t = G G^T
+    # Sigma_t = (I + beta A_tt)^-1 = G G^T
+    Lr, G = reversed_chol(torch.eye(M, dtype=torch.float64, device=x.device) + beta.view(C, 1, 1) * A_tt)
     G64 = G.double().tril()
-    gb = _mv(G64.mT, b_t)
+    gb = mv(G64.mT, b_t)
     quad = gb.square().sum(-1)                                                        # b_t^T Sigma_t b_t
     logdet = 2.0 * Lr.diagonal(dim1=-2, dim2=-1).double().log().sum(-1)
 
-    fixed = syy - 2.0 * (a_lt * tc[:, :n_lt]).sum(-1) + (a_lt * _mv(A_ll, a_lt)).sum(-1) + g2 * sw \
+    fixed = syy - 2.0 * (a_lt * tc[:, :n_lt]).sum(-1) + (a_lt * mv(A_ll, a_lt)).sum(-1) + g2 * sw \
         - A.diagonal(dim1=-2, dim2=-1).sum(-1) + trHAH
     bound = -0.5 * sw * (2.0 * math.pi / beta).log() - 0.5 * beta * fixed + 0.5 * beta.square() * quad - 0.5 * logdet
-    return bound, n_chunks, (beta, L[:, n_lt:, n_lt:].contiguous(), G, G64, gb)
+    return bound, n_chunks, (beta, fr.L_tt, G, G64, gb)
 
 
 def fit_q_(gp, x, y, weights=None, temper=1.0):
@@ -136,30 +106,16 @@ def fit_q_(gp, x, y, weights=None, temper=1.0):
     check_supported(gp)
     ops.require_device(gp.z, x, y, weights)
     with torch.no_grad():
-        M = gp.M
         bound, n_chunks, (beta, L_tt, G, G64, gb) = _whitened_bound(gp, x, y, weights, temper)
-        a_t = beta.unsqueeze(-1) * _mv(G64, gb)
-        u_mean = _mv(L_tt.double().tril(), a_t).unsqueeze(-1)
-        u_tril = ops.bgemm(L_tt, G, triA=LOWER, triB=LOWER).tril()
-        vec = ops.mat2trilvec(u_tril)
-        idx = torch.arange(M, device=x.device)
-        diag = idx * (idx + 1) // 2 + idx
-        vec[:, diag] = inv_softplus(vec[:, diag].double()).float()
-
-        gp.u_mean.copy_(u_mean.to(gp.u_mean.dtype))
-        gp.u_tril_vec.copy_(vec.to(gp.u_tril_vec.dtype))
+        write_q_(gp, L_tt, beta.unsqueeze(-1) * mv(G64, gb), G)
     return CollapsedFit(bound, n_chunks)
 
 
 def check_differentiable(gp, who):
     """check_supported, and exactly RBFKernel or MaternKernel: the bound's gradient for a DeepRBFKernel needs the gradient of the
     moments for X (the feature map), which ops.gram_moments_diff does not produce."""
-    if isinstance(gp.kernel, DeepRBFKernel):
-        raise ValueError(f'{who}: DeepRBFKernel is not supported (the feature map needs the gradient of the moments for their '
-                         'inputs X, which the fused backward does not produce); fit_q_ supports it')
-    check_supported(gp, who)
-    if type(gp.kernel) not in (RBFKernel, MaternKernel):
-        raise ValueError(f'{who}: supported kernels are exactly RBFKernel and MaternKernel, got {type(gp.kernel).__name__}')
+    check_model(gp, who, _check_likelihood, deep='the feature map needs the gradient of the moments for their inputs X, which '
+                                                 'the fused backward does not produce); fit_q_ supports it')
 
 
 def collapsed_bound(gp, x, y, weights=None, temper=1.0):
@@ -181,27 +137,12 @@ def fit_collapsed_(gp, x, y, n_steps=200, lr=1e-2, weights=None, temper=1.0, par
     is maximum likelihood (type II) for the hyper-parameters, not the MAP / variational treatment of VARGP.loss.
     -> the bound per step, float64 (n_steps + 1, C) on the host: row k is the bound BEFORE step k + 1, the last row the bound
     fit_q_ reports at the final parameters.  One device synchronisation, at the end."""
-    from .optim import Yogi
     check_differentiable(gp, 'fit_collapsed_')
-    named = dict(z=gp.z, kernel=gp.kernel.log_mean, noise=gp.likelihood.obs_log_var)
-    unknown = [p for p in params if p not in named]
-    if unknown or not params:
-        raise ValueError(f'fit_collapsed_: params must be a non-empty subset of {sorted(named)}, got {tuple(params)!r}')
+    chosen = choose_params('fit_collapsed_', dict(z=gp.z, kernel=gp.kernel.log_mean, noise=gp.likelihood.obs_log_var), params)
     n_steps = int(n_steps)
     if n_steps < 0:
         raise ValueError(f'fit_collapsed_: n_steps must be >= 0, got {n_steps}')
     ops.require_device(gp.z, x, y, weights)
-    chosen = [named[p] for p in dict.fromkeys(params)]
-    opt = Yogi(chosen, lr=lr)
-    trace = []
-    for _ in range(n_steps):
-        bound = collapsed_bound(gp, x, y, weights=weights, temper=temper)
-        grads = torch.autograd.grad(-bound.sum(), chosen)
-        for p, g in zip(chosen, grads):
-            p.grad = g.to(p.dtype)
-        opt.step()
-        trace.append(bound.detach())
-    for p in chosen:
-        p.grad = None
+    trace = ascend_(lambda: collapsed_bound(gp, x, y, weights=weights, temper=temper), chosen, n_steps, lr)
     trace.append(fit_q_(gp, x, y, weights=weights, temper=temper).bound)
     return torch.stack(trace).cpu()

@@ -659,6 +659,37 @@ def greedy_select(theta, X, cand=None, LT0=None, d0=None, M=None, nu2=0, eps=JIT
 
 # Weighted moments of the cross-kernel over a data set (csrc/moments.hip -- not in the reference).  No autograd.
 
+def _data_operands(theta, Z, X, alpha=None, Q=None):
+    """The operands every data-set pass shares -- theta (D+1,), Z (G, Mt, D), X (N, D) and, for the site passes, alpha (G, Mt) and
+    Q (G, Mt, Mt) -- detached, contiguous and checked -> (theta, Z, X, alpha, Q, (G, Mt, N, D))."""
+    det = lambda t: None if t is None else t.detach().contiguous()
+    theta, Z, X, alpha, Q = det(theta).view(-1), det(Z), det(X), det(alpha), det(Q)
+    assert Z.dim() == 3 and X.dim() == 2 and Z.shape[-1] == X.shape[1] and theta.numel() == X.shape[1] + 1, (theta.shape, Z.shape, X.shape)
+    (G, Mt, D), N = Z.shape, X.shape[0]
+    if alpha is not None:
+        assert tuple(alpha.shape) == (G, Mt) and tuple(Q.shape) == (G, Mt, Mt), (alpha.shape, Q.shape, G, Mt)
+    assert all(t is None or t.dtype == torch.float32 for t in (theta, Z, X, alpha, Q)), [t.dtype for t in (theta, Z, X)]
+    return theta, Z, X, alpha, Q, (G, Mt, N, D)
+
+
+def _gram_moments(entry, theta, Z, X, w, y, nu2=0):
+    """gram_moments (entry vargp_gram_moments) and gram_moments_v (vargp_gram_moments_v): y is the latter's v."""
+    require_device(theta, Z, X, w, y)
+    theta, Z, X, _, _, (G, Mt, N, D) = _data_operands(theta, Z, X)
+    y = y.detach().contiguous()
+    assert tuple(y.shape) == (G, N) and y.dtype == torch.float32, (y.shape, y.dtype, G, N)
+    if w is not None:
+        w = w.detach().contiguous()
+        assert tuple(w.shape) == (G, N) and w.dtype == torch.float32, (w.shape, w.dtype)
+    Phi = torch.empty(G, Mt, Mt, dtype=torch.float32, device=X.device)
+    c = torch.empty(G, Mt, dtype=torch.float32, device=X.device)
+    sums = torch.empty(G, 2, dtype=torch.float32, device=X.device)
+    ws = scratch(lib().vargp_gram_moments_workspace_bytes(G, Mt, N, D), X.device)
+    check(getattr(lib(), entry)(ptr(theta), ptr(Z), ptr(X), ptr(w), ptr(y), ptr(Phi), ptr(c), ptr(sums), G, Mt, N, D, int(nu2),
+                                ptr(ws), ws.numel() * 4, stream_ptr()), entry)
+    return Phi, c, sums
+
+
 def gram_moments_chunks(G, Mt, N, D):
     """The number of chunks ops.gram_moments cuts N points into for this shape (= partials per output tile); the shapes alone
     decide it."""
@@ -670,22 +701,7 @@ def gram_moments(theta, Z, X, w, y, nu2=0):
     k_n = k(Z_g, x_n): -> (Phi (G, Mt, Mt) = sum_n w_n k_n k_n^T, exactly symmetric; c (G, Mt) = sum_n w_n y_n k_n; sums (G, 2) =
     (sum_n w_n, sum_n w_n y_n^2)).  nu2: 0 = RBF, 1 | 3 | 5 = Matern.  K(Z, X) is never stored and the scratch does not grow with
     N; fp32 within a chunk of points, fp64 across chunks; bitwise reproducible."""
-    require_device(theta, Z, X, w, y)
-    theta, Z, X, y = theta.detach().contiguous().view(-1), Z.detach().contiguous(), X.detach().contiguous(), y.detach().contiguous()
-    assert Z.dim() == 3 and X.dim() == 2 and Z.shape[-1] == X.shape[1] and theta.numel() == X.shape[1] + 1, (theta.shape, Z.shape, X.shape)
-    (G, Mt, D), N = Z.shape, X.shape[0]
-    assert tuple(y.shape) == (G, N), (y.shape, G, N)
-    if w is not None:
-        w = w.detach().contiguous()
-        assert tuple(w.shape) == (G, N) and w.dtype == torch.float32, (w.shape, w.dtype)
-    assert all(t.dtype == torch.float32 for t in (theta, Z, X, y)), (theta.dtype, Z.dtype, X.dtype, y.dtype)
-    Phi = torch.empty(G, Mt, Mt, dtype=torch.float32, device=X.device)
-    c = torch.empty(G, Mt, dtype=torch.float32, device=X.device)
-    sums = torch.empty(G, 2, dtype=torch.float32, device=X.device)
-    ws = scratch(lib().vargp_gram_moments_workspace_bytes(G, Mt, N, D), X.device)
-    check(lib().vargp_gram_moments(ptr(theta), ptr(Z), ptr(X), ptr(w), ptr(y), ptr(Phi), ptr(c), ptr(sums), G, Mt, N, D, int(nu2),
-                                   ptr(ws), ws.numel() * 4, stream_ptr()), 'vargp_gram_moments')
-    return Phi, c, sums
+    return _gram_moments('vargp_gram_moments', theta, Z, X, w, y, nu2)
 
 
 def gram_moments_bwd_chunks(G, Mt, N, D):
@@ -729,19 +745,25 @@ class _GramMoments(Function):
         return gtheta.view(ctx.theta_shape), gZ, None, None, None, None
 
 
+def refuse_grad(who, produced, **data):
+    """ValueError if one of the named data tensors requires grad: `who` produces gradients for `produced` only."""
+    for name, t in data.items():
+        if t is not None and t.requires_grad:
+            raise ValueError(f'{who}: {name} requires grad, but gradients are produced for {produced} only')
+
+
 def gram_moments_diff(theta, Z, X, w, y, nu2=0):
     """ops.gram_moments on the autograd graph of theta (D+1,) and Z (G, Mt, D): the same forward call and outputs (Phi, c, sums),
     with a fused backward that never stores K(Z, X) either (gram_moments_bwd).  gPhi may be any matrix (it is not assumed
     symmetric).  No gradients are produced for X, w and y: a ValueError if one of them requires grad.  sums depends on w and y
     alone and is not differentiable."""
-    for name, t in (('X', X), ('w', w), ('y', y)):
-        if t is not None and t.requires_grad:
-            raise ValueError(f'gram_moments_diff: {name} requires grad, but gradients are produced for theta and Z only')
+    refuse_grad('gram_moments_diff', 'theta and Z', X=X, w=w, y=y)
     return _GramMoments.apply(theta, Z, X, w, y, nu2)
 
 
 # Gaussian sites of a non-Gaussian likelihood over a data set (csrc/sites.hip -- not in the reference).  No autograd.
 SITE_MAX_MT = 256                # kSiMaxMt (csrc/dataset_pass.h): the fused pass holds all Mt rows of a K block in LDS
+SITE_BOUND_GRADS = 'theta, Z, alpha, Q and the Student-t log_scale'      # what the site bound's two routes differentiate
 _SITE_KINDS = {('bernoulli', 0): 0, ('bernoulli', 1): 1, ('poisson', None): 2, ('studentt', None): 3}
 
 
@@ -761,19 +783,14 @@ def _site_operands(theta, Z, X, alpha, Q, y, w, kind, extra):
     """The operands of the two site entries, detached, contiguous and checked -> (theta, Z, X, alpha, Q, yt, ldy, w, code,
     log_scale, df, lognorm, (G, Mt, N, D))."""
     code, log_scale, df, lognorm = site_kind(kind, extra)
-    det = lambda t: t.detach().contiguous()
-    theta, Z, X, alpha, Q = det(theta).view(-1), det(Z), det(X), det(alpha), det(Q)
-    assert Z.dim() == 3 and X.dim() == 2 and Z.shape[-1] == X.shape[1] and theta.numel() == X.shape[1] + 1, (theta.shape, Z.shape, X.shape)
-    (G, Mt, D), N = Z.shape, X.shape[0]
-    assert tuple(alpha.shape) == (G, Mt) and tuple(Q.shape) == (G, Mt, Mt), (alpha.shape, Q.shape, G, Mt)
+    theta, Z, X, alpha, Q, (G, Mt, N, D) = _data_operands(theta, Z, X, alpha, Q)
     yt, ldy = reg_target(y, G, N)
     if w is not None:
-        w = det(w)
+        w = w.detach().contiguous()
         assert tuple(w.shape) == (G, N) and w.dtype == torch.float32, (w.shape, w.dtype)
     if log_scale is not None:
-        log_scale = det(log_scale)
+        log_scale = log_scale.detach().contiguous()
         assert tuple(log_scale.shape) == (G,) and log_scale.dtype == torch.float32, (log_scale.shape, log_scale.dtype)
-    assert all(t.dtype == torch.float32 for t in (theta, Z, X, alpha, Q)), (theta.dtype, Z.dtype, X.dtype, alpha.dtype, Q.dtype)
     return theta, Z, X, alpha, Q, yt, ldy, w, code, log_scale, df, lognorm, (G, Mt, N, D)
 
 
@@ -812,12 +829,7 @@ def site_marginals(theta, Z, X, alpha, Q, nu2=0):
     Mt, Mt) as site_moments takes them -> (mu (G, N) = alpha . k_n, var (G, N) = max(gamma^2 - k_n^T Q k_n, 0)).  site_moments'
     kernel stopped after the marginals (vargp_site_marginals): K(Z, X) is never stored, no workspace, bitwise reproducible."""
     require_device(theta, Z, X, alpha, Q)
-    det = lambda t: t.detach().contiguous()
-    theta, Z, X, alpha, Q = det(theta).view(-1), det(Z), det(X), det(alpha), det(Q)
-    assert Z.dim() == 3 and X.dim() == 2 and Z.shape[-1] == X.shape[1] and theta.numel() == X.shape[1] + 1, (theta.shape, Z.shape, X.shape)
-    (G, Mt, D), N = Z.shape, X.shape[0]
-    assert tuple(alpha.shape) == (G, Mt) and tuple(Q.shape) == (G, Mt, Mt), (alpha.shape, Q.shape, G, Mt)
-    assert all(t.dtype == torch.float32 for t in (theta, Z, X, alpha, Q)), (theta.dtype, Z.dtype, X.dtype, alpha.dtype, Q.dtype)
+    theta, Z, X, alpha, Q, (G, Mt, N, D) = _data_operands(theta, Z, X, alpha, Q)
     mu = torch.empty(G, N, dtype=torch.float32, device=X.device)
     var = torch.empty(G, N, dtype=torch.float32, device=X.device)
     check(lib().vargp_site_marginals(ptr(theta), ptr(Z), ptr(X), ptr(alpha), ptr(Q), ptr(mu), ptr(var), G, Mt, N, D, int(nu2),
@@ -874,22 +886,7 @@ def gram_moments_v(theta, Z, X, w, v, nu2=0):
     """gram_moments with a weight vector of its own for c: w (G, N) or None = 1 and v (G, N) -> (Phi (G, Mt, Mt) = sum_n w_n k_n
     k_n^T, c (G, Mt) = sum_n v_n k_n, sums (G, 2) = (sum w, sum v)).  The same kernel, chunking and scratch; with v = w * y, Phi
     and c are bitwise gram_moments'."""
-    require_device(theta, Z, X, w, v)
-    theta, Z, X, v = theta.detach().contiguous().view(-1), Z.detach().contiguous(), X.detach().contiguous(), v.detach().contiguous()
-    assert Z.dim() == 3 and X.dim() == 2 and Z.shape[-1] == X.shape[1] and theta.numel() == X.shape[1] + 1, (theta.shape, Z.shape, X.shape)
-    (G, Mt, D), N = Z.shape, X.shape[0]
-    assert tuple(v.shape) == (G, N), (v.shape, G, N)
-    if w is not None:
-        w = w.detach().contiguous()
-        assert tuple(w.shape) == (G, N) and w.dtype == torch.float32, (w.shape, w.dtype)
-    assert all(t.dtype == torch.float32 for t in (theta, Z, X, v)), (theta.dtype, Z.dtype, X.dtype, v.dtype)
-    Phi = torch.empty(G, Mt, Mt, dtype=torch.float32, device=X.device)
-    c = torch.empty(G, Mt, dtype=torch.float32, device=X.device)
-    sums = torch.empty(G, 2, dtype=torch.float32, device=X.device)
-    ws = scratch(lib().vargp_gram_moments_workspace_bytes(G, Mt, N, D), X.device)
-    check(lib().vargp_gram_moments_v(ptr(theta), ptr(Z), ptr(X), ptr(w), ptr(v), ptr(Phi), ptr(c), ptr(sums), G, Mt, N, D, int(nu2),
-                                     ptr(ws), ws.numel() * 4, stream_ptr()), 'vargp_gram_moments_v')
-    return Phi, c, sums
+    return _gram_moments('vargp_gram_moments_v', theta, Z, X, w, v, nu2)
 
 
 def site_bound_bwd_chunks(G, Mt, N, D):
@@ -944,10 +941,7 @@ def site_bound_diff(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0):
     passes no gradient) and, for Student-t, extra[0] = log_scale (G,).  The backward is one fused pass (site_bound_bwd) and one
     gram_moments call for gQ; K(Z, X) is never stored in either.  No gradients are produced for X, y and w: a ValueError if one
     of them requires grad."""
-    for name, t in (('X', X), ('y', y), ('w', w)):
-        if t is not None and t.requires_grad:
-            raise ValueError(f'site_bound_diff: {name} requires grad, but gradients are produced for theta, Z, alpha, Q and the '
-                             'Student-t log_scale only')
+    refuse_grad('site_bound_diff', SITE_BOUND_GRADS, X=X, y=y, w=w)
     log_scale = extra[0] if kind == 'studentt' else None
     return _SiteBound.apply(theta, Z, X, alpha, Q, y, w, log_scale, kind, tuple(extra), nu2)
 

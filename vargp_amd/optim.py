@@ -126,3 +126,27 @@ class Yogi(torch.optim.Optimizer):
                                                   group['lr'], b1, b2, group['eps'], ptr(group['step']), 0,
                                                   stream_ptr()),
                       'vargp_yogi_step_multi')
+
+
+def choose_params(who, named, params):
+    """The tensors of the non-empty subset `params` of the names of `named`, each once, in the order given; ValueError else."""
+    params = tuple(params)
+    if not params or any(p not in named for p in params):
+        raise ValueError(f'{who}: params must be a non-empty subset of {sorted(named)}, got {params!r}')
+    return [named[p] for p in dict.fromkeys(params)]
+
+
+def ascend_(bound_fn, chosen, n_steps, lr):
+    """n_steps steps of the project's Yogi (optim.py) up sum_c bound_fn() over the tensors `chosen`; their grads are cleared
+    afterwards.  -> [the (C,) bound BEFORE each step, detached]; no synchronisation."""
+    opt = Yogi(chosen, lr=lr)
+    trace = []
+    for _ in range(n_steps):
+        bound = bound_fn()
+        for p, g in zip(chosen, torch.autograd.grad(-bound.sum(), chosen)):
+            p.grad = g.to(p.dtype)
+        opt.step()
+        trace.append(bound.detach())
+    for p in chosen:
+        p.grad = None
+    return trace

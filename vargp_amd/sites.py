@@ -3,12 +3,11 @@ Student-t -- by conjugate-computation variational inference (Khan & Lin 2017); n
 by minibatch gradient steps.  `fit_q_newton_` (VARGP.fit_q_newton_, create_clf / create_reg(q_init='newton')) is the counterpart
 of collapsed.fit_q_: a stand-alone, full-batch call under no_grad that overwrites u_mean and u_tril_vec.
 
-Everything happens at ONE hyper vector, theta = kernel.log_mean, in the whitened coordinates of collapsed.py's docstring:
-K' = K(z_<=t) + eps I = L L^T, T = L^-1, v = T u, q(v) = N(a, H H^T) with a = (a_<, a_t) and block-diagonal H, the blocks of the
-frozen tasks being a_i = T_ii m_i, H_i = T_ii Lu_i.  The new block starts at the model's current q(u_t): a_t = T_tt u_mean,
-H_t = T_tt L_u, and is carried in natural parameters P = Sigma_t^-1, h = P a_t.  One iteration, with k_n = k(z_<=t, x_n):
+Everything happens at ONE hyper vector, theta = kernel.log_mean, in the whitened coordinates of whitened.py's docstring (T, the
+frozen tasks' blocks, alpha and Q, A and tc, the KL term and the reader / writer of q(u_t) are defined there).  The new block
+starts at the model's current q(u_t): a_t = T_tt u_mean, H_t = T_tt L_u, and is carried in natural parameters P = Sigma_t^-1,
+h = P a_t.  One iteration, with k_n = k(z_<=t, x_n) and q(f_n) = N(alpha . k_n, gamma^2 - k_n^T Q k_n):
 
-    alpha = T^T a,   Q = T^T (I - H H^T) T                          (so that q(f_n) = N(alpha . k_n, gamma^2 - k_n^T Q k_n))
     mu_n = alpha . k_n,   var_n = max(gamma^2 - k_n^T Q k_n, 0)
     (ell, dmu, dvar) = E_{N(mu_n, var_n)} log p(y_n | f) and its derivatives for (mu_n, var_n)      (csrc/lik.h)
     lam2_n = w_n max(-2 dvar, 0),   lam1_n = w_n dmu + lam2_n mu_n                                  (the Gaussian site of point n)
@@ -46,10 +45,10 @@ from collections import namedtuple
 import torch
 
 from . import ops
-from .collapsed import _mv, inv_softplus
-from .kernels import DeepRBFKernel, MaternKernel, RBFKernel
 from .likelihoods import GaussianLikelihood, MulticlassSoftmax
-from .ops import LOWER, UPPER
+from .ops import LOWER
+from .optim import ascend_, choose_params
+from .whitened import Frame, alpha_Q, check_model, kl_standard, mv, read_q, reversed_chol, rows, whiten_moments, write_q_
 
 SiteFit = namedtuple('SiteFit', 'bound n_iters n_rejected n_clamped route')
 SiteFit.__doc__ = """bound (n_iters + 1, C) float64 on the host: the variational bound per output at the initial q(u) and after
@@ -67,10 +66,7 @@ _GH_W = (0.26079306344955488, 0.16173933398399998, 0.061506372063976897, 0.01399
          0.00012882627996192928, 4.402121090230851e-06, 6.127490259982928e-08, 2.4820623623151755e-10, 1.2578006724379234e-13)
 
 
-def check_supported(gp, who='fit_q_newton_'):
-    """ValueError unless the site iteration applies to the model: a Bernoulli, Poisson or Student-t likelihood, ep_var_mean=True,
-    an RBF / Matern / deep-RBF kernel.  Needs no device."""
-    lik = gp.likelihood
+def _check_likelihood(lik, who):
     if isinstance(lik, MulticlassSoftmax):
         raise ValueError(f'{who}: MulticlassSoftmax couples the outputs of a point, so it has no independent Gaussian sites; '
                          'its own fit is fit_q_softmax_ (create_clf(q_init="newton_softmax")), or use '
@@ -80,11 +76,12 @@ def check_supported(gp, who='fit_q_newton_'):
     if getattr(lik, 'kind', None) not in SITE_KINDS:
         raise ValueError(f'{who}: supported likelihoods are BernoulliLikelihood, PoissonLikelihood and StudentTLikelihood, got '
                          f'{type(lik).__name__}')
-    if gp.var_mean_mask != 1.0:
-        raise ValueError(f'{who}: supported for ep_var_mean=True models only (with ep_var_mean=False the mean of q(u_t) is not '
-                         'u_mean alone)')
-    if not isinstance(gp.kernel, RBFKernel):
-        raise ValueError(f'{who}: supported kernels are RBFKernel, MaternKernel and DeepRBFKernel, got {type(gp.kernel).__name__}')
+
+
+def check_supported(gp, who='fit_q_newton_'):
+    """ValueError unless the site iteration applies to the model: a Bernoulli, Poisson or Student-t likelihood, ep_var_mean=True,
+    an RBF / Matern / deep-RBF kernel.  Needs no device."""
+    check_model(gp, who, _check_likelihood)
 
 
 def check_damping(damping, who='fit_q_newton_'):
@@ -138,31 +135,45 @@ def ell_torch(kind, extra, mu, var, y):
     return (lognorm - log_scale).unsqueeze(-1) - 0.5 * (df + 1.0) * el
 
 
+def _gram_tile(th, Z, Xt, nu2):
+    """K (G, Mt, B) = k(Z, Xt) of one tile of points from the gram op; th (1, D+1)."""
+    return (ops.rbf_gram(th, Z, Xt, True) if nu2 == 0 else ops.matern_gram(th, Z, Xt, True, 0.5 * nu2))[0]
+
+
+def _tile_marginals(K, alpha, Q, g2):
+    """A tile's K (G, Mt, B) -> (mu = alpha K, var = max(gamma^2 - k Q k, 0)) (G, B), contiguous; Q symmetric, g2 = gamma^2."""
+    mu = ops.matmul(alpha.unsqueeze(-2), K).squeeze(-2).contiguous()
+    return mu, (g2 - (K * ops.matmul(Q, K)).sum(-2)).clamp_min(0.0).contiguous()
+
+
+def _tiles(X, tile, y=None, w=None):
+    """The tiles of N points: (n0, n1, X[n0:n1], the tile's columns of y (N,) or (G, N) and of w (G, N), or None), contiguous."""
+    for n0 in range(0, X.size(0), tile):
+        n1 = min(n0 + tile, X.size(0))
+        yield (n0, n1, X[n0:n1].contiguous(), None if y is None else (y[n0:n1] if y.dim() == 1 else y[:, n0:n1]).contiguous(),
+               None if w is None else w[:, n0:n1].contiguous())
+
+
 def composed_site_moments(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0, tile=COMPOSED_TILE):
     """ops.site_moments from the per-op kernels, a tile of N at a time (arguments and results alike; any Mt): the gram op,
-    ops.bgemm for alpha K and Q K, ops.lik_nll_bwd with a unit seed for the derivatives, ell_torch for the value; c and sums are
+    ops.matmul for alpha K and Q K, ops.lik_nll_bwd with a unit seed for the derivatives, ell_torch for the value; c and sums are
     accumulated in fp64 over the tiles."""
     ops.require_device(theta, Z, X, alpha, Q, y, w)
     (G, Mt, D), N = Z.shape, X.shape[0]
     th = theta.detach().view(1, -1).contiguous()
-    gram = (lambda Xt: ops.rbf_gram(th, Z, Xt, True)) if nu2 == 0 else (lambda Xt: ops.matern_gram(th, Z, Xt, True, 0.5 * nu2))
     g2 = (2.0 * th[0, -1]).exp()
-    shared = y.dim() == 1
     seed = torch.ones((), dtype=torch.float32, device=X.device)
     lam2 = torch.empty(G, N, dtype=torch.float32, device=X.device)
     c = torch.zeros(G, Mt, dtype=torch.float64, device=X.device)
     sums = torch.zeros(G, 4, dtype=torch.float64, device=X.device)
     gpar = torch.empty(G, dtype=torch.float32, device=X.device) if kind == 'studentt' else None
-    for n0 in range(0, N, tile):
-        n1 = min(n0 + tile, N)
-        K = gram(X[n0:n1].contiguous())[0]                                            # (G, Mt, B)
-        mu = ops.bgemm(alpha.unsqueeze(-2), K).squeeze(-2).contiguous()               # (G, B)
-        var = (g2 - (K * ops.bgemm(Q, K)).sum(-2)).clamp_min(0.0).contiguous()
-        yt = (y[n0:n1] if shared else y[:, n0:n1]).contiguous()
+    for n0, n1, Xt, yt, wt in _tiles(X, tile, y, w):
+        K = _gram_tile(th, Z, Xt, nu2)
+        mu, var = _tile_marginals(K, alpha, Q, g2)
         gmu, gvar = torch.empty_like(mu), torch.empty_like(var)
         ops.lik_nll_bwd(kind, mu.unsqueeze(0), var.unsqueeze(0), ops.lik_target(kind, yt, G, n1 - n0), extra, seed,
                         gmu.unsqueeze(0), gvar.unsqueeze(0), gpar)
-        wt = torch.ones_like(mu) if w is None else w[:, n0:n1]
+        wt = torch.ones_like(mu) if wt is None else wt
         on = wt != 0
         zero = torch.zeros_like(mu)
         dvar = -gvar                                                                  # (the seeded gradients are those of -ell)
@@ -182,49 +193,26 @@ class _Problem:
     who = 'fit_q_newton_'
 
     def __init__(self, gp, x, y, weights, route):
-        kern = gp.kernel
-        self.C, self.M, self.N = gp.z.size(0), gp.M, x.size(0)
-        C, M, N = self.C, self.M, self.N
-        self.theta = kern.log_mean.detach().to(torch.float32).contiguous()
-        prev = [gp._prev(i) for i in range(len(gp.prev_params))]
-        z_all = torch.cat([p['z'] for p in prev] + [gp.z.detach()], dim=-2).contiguous()
-        self.Mt = z_all.size(-2)
-        self.n_lt = self.Mt - M
-        self.route = pick_route(route, self.Mt, self.who)
+        self.fr = fr = Frame(gp)
+        self.C, self.M, self.N = fr.C, fr.M, x.size(0)
+        self.route = pick_route(route, fr.Mt, self.who)
         self._targets(gp.likelihood, y, weights)
-        deep = isinstance(kern, DeepRBFKernel)
-        self.zf, self.xf = (kern.features(z_all), kern.features(x)) if deep else (z_all, x.detach().contiguous())
-        self.nu2 = int(round(2 * kern.nu)) if isinstance(kern, MaternKernel) else 0
-        self.L, self.T = ops.chol_inv(kern.compute(self.theta.unsqueeze(0), z_all)[0])   # (C, Mt, Mt): as block_joint factorises
-        self.L_tt = self.L[:, self.n_lt:, self.n_lt:].contiguous()
-        self.T_tt = self.T[:, self.n_lt:, self.n_lt:].contiguous()
-        a_lt, self.Hb, o = [], torch.zeros(C, self.Mt, self.Mt, dtype=torch.float32, device=x.device), 0
-        for p in prev:
-            n = p['z'].size(-2)
-            T_ii = self.T[:, o:o + n, o:o + n].contiguous()
-            a_lt.append(ops.matmul(T_ii, p['u_mean'], triA=LOWER).squeeze(-1).double())
-            self.Hb[:, o:o + n, o:o + n] = ops.matmul(T_ii, p['u_tril'], triA=LOWER, triB=LOWER).tril()
-            o += n
-        self.a_lt = torch.cat(a_lt, dim=-1) if a_lt else torch.zeros(C, 0, dtype=torch.float64, device=x.device)
-        self.eye_t = torch.eye(self.Mt, dtype=torch.float32, device=x.device)
-        self.eye = torch.eye(M, dtype=torch.float64, device=x.device)
+        self.zf, self.xf = fr.operands(x.detach().contiguous())
+        self.eye = torch.eye(fr.M, dtype=torch.float64, device=x.device)
 
     def _targets(self, lik, y, weights):
         """The likelihood's arguments, the targets and the weights as the data passes take them."""
         C, N = self.C, self.N
         self.kind, self.extra = lik.kind, tuple(t.detach() if torch.is_tensor(t) else t for t in lik._extra())
         self.y = site_target(self.kind, y.detach(), C, N)
-        self.w = None
-        if weights is not None:
-            wt, ldw = ops.reg_target(weights, C, N)
-            self.w = wt.expand(C, N).contiguous() if ldw == 0 else wt
+        self.w = None if weights is None else rows(weights, C, N)
 
     def _passes(self, alpha, Q):
         """The passes over the data at q(f_n) = N(alpha . k_n, gamma^2 - k_n^T Q k_n): -> (Phi (C, Mt, Mt), c (C, Mt), the data
         term of the bound float64, clamped points)."""
         pass_ = ops.site_moments if self.route == 'fused' else composed_site_moments
-        lam2, c, sums = pass_(self.theta, self.zf, self.xf, alpha, Q, self.y, self.w, self.kind, self.extra, self.nu2)
-        Phi = ops.gram_moments(self.theta, self.zf, self.xf, lam2, lam2, self.nu2)[0]
+        lam2, c, sums = pass_(self.fr.theta, self.zf, self.xf, alpha, Q, self.y, self.w, self.kind, self.extra, self.fr.nu2)
+        Phi = ops.gram_moments(self.fr.theta, self.zf, self.xf, lam2, lam2, self.fr.nu2)[0]
         return Phi, c, sums[:, 0].double(), sums[:, 2]
 
     def bound(self, data, kl):
@@ -234,56 +222,22 @@ class _Problem:
     def sites(self, a_t, H_t):
         """The passes over the data at q(v_t) = N(a_t, H_t H_t^T): -> (the data term of the bound, float64, I + A_tt,
         tc_t - A_{t,<} a_<, clamped points)."""
-        a = torch.cat([self.a_lt, a_t], dim=-1)
-        alpha = _mv(self.T.mT.double(), a).float().contiguous()
-        self.Hb[:, self.n_lt:, self.n_lt:] = H_t
-        S = self.eye_t - ops.bgemm(self.Hb, self.Hb.mT)
-        Q = ops.bgemm(ops.bgemm(self.T.mT, S), self.T)
-        Q = (0.5 * (Q + Q.mT)).contiguous()
-        Phi, c, data, clamped = self._passes(alpha, Q)
-        T, n_lt = self.T, self.n_lt
-        A = ops.matmul(ops.matmul(T, Phi, triA=LOWER), T.mT, triB=UPPER).double()
-        A = 0.5 * (A + A.mT)
-        tc = ops.matmul(T, c.unsqueeze(-1), triA=LOWER).squeeze(-1).double()
+        fr, n_lt = self.fr, self.fr.n_lt
+        Phi, c, data, clamped = self._passes(*alpha_Q(fr, a_t, H_t))
+        A, tc = whiten_moments(fr.T, Phi, c)
         P_new = self.eye + A[:, n_lt:, n_lt:]
-        h_new = tc[:, n_lt:] - _mv(A[:, n_lt:, :n_lt], self.a_lt)
+        h_new = tc[:, n_lt:] - mv(A[:, n_lt:, :n_lt], fr.frozen[0])
         return data, P_new, h_new, clamped
 
     def from_natural(self, P, h):
         """Sigma_t = P^-1 = G G^T with G lower triangular (the Cholesky factor of the reversed P, reversed back, as fit_q_ factors
         I + beta A_tt) -> (a_t = Sigma_t h, G float32, KL(q(v_t) || N(0, I)) (C,))."""
-        Lr, Tr = ops.chol_inv(P.flip(-2, -1).float().contiguous(), 0.0)
-        G = Tr.mT.flip(-2, -1).contiguous()
+        Lr, G = reversed_chol(P)
         G64 = G.double().tril()
-        a_t = _mv(G64, _mv(G64.mT, h))
+        a_t = mv(G64, mv(G64.mT, h))
         logdet_sigma = -2.0 * Lr.diagonal(dim1=-2, dim2=-1).double().log().sum(-1)
         kl = 0.5 * (a_t.square().sum(-1) + G64.square().sum((-2, -1)) - self.M - logdet_sigma)
         return a_t, G.tril(), kl
-
-
-def _write_q(gp, L_tt, a_t, H_t):
-    """u_mean = L_tt a_t and u_tril = L_tt H_t into gp.u_mean / gp.u_tril_vec (the diagonal through the inverse softplus of
-    vec2tril).  Under no_grad."""
-    M = gp.M
-    u_mean = _mv(L_tt.double().tril(), a_t).unsqueeze(-1)
-    u_tril = ops.bgemm(L_tt, H_t, triA=LOWER, triB=LOWER).tril()
-    vec = ops.mat2trilvec(u_tril)
-    idx = torch.arange(M, device=vec.device)
-    diag = idx * (idx + 1) // 2 + idx
-    vec[:, diag] = inv_softplus(vec[:, diag].double()).float()
-    gp.u_mean.copy_(u_mean.to(gp.u_mean.dtype))
-    gp.u_tril_vec.copy_(vec.to(gp.u_tril_vec.dtype))
-
-
-def _new_block_factors(gp):
-    """(L_tt, T_tt) (C, M, M): the new task's diagonal blocks of the whitening factors at the CURRENT parameters, detached."""
-    with torch.no_grad():
-        kern = gp.kernel
-        theta = kern.log_mean.detach().to(torch.float32).contiguous()
-        z_all = torch.cat([gp._prev(i)['z'] for i in range(len(gp.prev_params))] + [gp.z.detach()], dim=-2).contiguous()
-        n_lt = z_all.size(-2) - gp.M
-        L, T = ops.chol_inv(kern.compute(theta.unsqueeze(0), z_all)[0])
-        return L[:, n_lt:, n_lt:].contiguous(), T[:, n_lt:, n_lt:].contiguous()
 
 
 def whitened_q(gp):
@@ -291,10 +245,7 @@ def whitened_q(gp):
     H_t = T_tt L_u (C, M, M) float32, lower triangular), detached."""
     ops.require_device(gp.z)
     with torch.no_grad():
-        _, T_tt = _new_block_factors(gp)
-        L_u = ops.vec2tril(gp.u_tril_vec.detach().float(), gp.M)
-        a_t = ops.matmul(T_tt, gp.u_mean.detach().float(), triA=LOWER).squeeze(-1).double()
-        return a_t, ops.bgemm(T_tt, L_u, triA=LOWER, triB=LOWER).tril()
+        return read_q(gp, Frame(gp).T_tt)[:2]
 
 
 def set_whitened_q_(gp, a_t, H_t):
@@ -302,8 +253,7 @@ def set_whitened_q_(gp, a_t, H_t):
     u_tril_vec: what keeps q fixed in whitened coordinates after inducing points or hyper-parameters have moved."""
     ops.require_device(gp.z, a_t, H_t)
     with torch.no_grad():
-        L_tt, _ = _new_block_factors(gp)
-        _write_q(gp, L_tt, a_t.double(), H_t.float().contiguous())
+        write_q_(gp, Frame(gp).L_tt, a_t.double(), H_t.float().contiguous())
 
 
 def fit_q_newton_(gp, x, y, n_iters=20, damping=1.0, tol=1e-6, weights=None, route=None, start='current'):
@@ -338,24 +288,20 @@ def _check_loop_args(who, damping, n_iters, start):
 def _fit(gp, pr, n_iters, damping, tol, start):
     """The iteration of the module docstring on the problem `pr` (its passes over the data, its form of the bound), from `start`
     with backtracking; writes the last accepted q(u_t) into gp.  Under no_grad.  -> SiteFit"""
-    M, dev = pr.M, pr.theta.device
+    M, dev = pr.M, pr.fr.theta.device
     if start == 'prior':
         a_t = torch.zeros(pr.C, M, dtype=torch.float64, device=dev)
         H_t = torch.eye(M, dtype=torch.float32, device=dev).expand(pr.C, M, M).contiguous()
         P, h, kl = pr.eye.expand(pr.C, M, M), torch.zeros_like(a_t), torch.zeros(pr.C, dtype=torch.float64, device=dev)
     else:
         # the model's q(u_t) in whitened coordinates and natural parameters: H_t^-1 = L_u^-1 L_tt
-        L_u = ops.vec2tril(gp.u_tril_vec.detach().float(), M)
-        a_t = ops.matmul(pr.T_tt, gp.u_mean.detach().float(), triA=LOWER).squeeze(-1).double()
-        H_t = ops.bgemm(pr.T_tt, L_u, triA=LOWER, triB=LOWER).tril()
+        a_t, H_t, L_u = read_q(gp, pr.fr.T_tt)
         T_u = ops.chol_inv(ops.bgemm(L_u, L_u.mT), 0.0)[1]
-        H_inv = ops.bgemm(T_u, pr.L_tt, triA=LOWER, triB=LOWER).tril()
+        H_inv = ops.bgemm(T_u, pr.fr.L_tt, triA=LOWER, triB=LOWER).tril()
         P = ops.bgemm(H_inv.mT, H_inv).double()
         P = 0.5 * (P + P.mT)
-        h = _mv(P, a_t)
-        H64 = H_t.double()
-        kl = 0.5 * (a_t.square().sum(-1) + H64.square().sum((-2, -1)) - M
-                    - 2.0 * H64.diagonal(dim1=-2, dim2=-1).log().sum(-1))
+        h = mv(P, a_t)
+        kl = kl_standard(a_t, H_t)
 
     data, P_new, h_new, clamped = pr.sites(a_t, H_t)
     bound = pr.bound(data, kl).cpu()
@@ -383,7 +329,7 @@ def _fit(gp, pr, n_iters, damping, tol, start):
             break
 
     if changed:
-        _write_q(gp, pr.L_tt, a_t, H_t)
+        write_q_(gp, pr.fr.L_tt, a_t, H_t)
     n_clamped = int(round(clamped.double().sum().item()))
     return SiteFit(torch.stack(trace), len(trace) - 1, n_rejected, n_clamped, pr.route)
 
@@ -406,36 +352,31 @@ def _fit(gp, pr, n_iters, damping, tol, start):
 # derivatives of its n_f-sample estimate (whose derivative for var_c holds eps / sqrt(var) terms).  Near the optimum a full step
 # can therefore lower the ESTIMATED bound, by about 1e-5 relative; the fit then ends by rejection (all halvings fail) rather than
 # by tol, at the last accepted q.
+def _check_softmax_likelihood(lik, who):
+    if not isinstance(lik, MulticlassSoftmax):
+        raise ValueError(f'{who}: supported for MulticlassSoftmax only, got {type(lik).__name__}; the likelihoods with '
+                         'independent outputs have fit_q_newton_ (q_init="newton"), GaussianLikelihood has fit_q_')
+
+
 def check_softmax_supported(gp, who='fit_q_softmax_'):
     """ValueError unless the softmax site iteration applies to the model: MulticlassSoftmax, ep_var_mean=True, an RBF / Matern /
     deep-RBF kernel.  Needs no device."""
-    if not isinstance(gp.likelihood, MulticlassSoftmax):
-        raise ValueError(f'{who}: supported for MulticlassSoftmax only, got {type(gp.likelihood).__name__}; the likelihoods with '
-                         'independent outputs have fit_q_newton_ (q_init="newton"), GaussianLikelihood has fit_q_')
-    if gp.var_mean_mask != 1.0:
-        raise ValueError(f'{who}: supported for ep_var_mean=True models only (with ep_var_mean=False the mean of q(u_t) is not '
-                         'u_mean alone)')
-    if not isinstance(gp.kernel, RBFKernel):
-        raise ValueError(f'{who}: supported kernels are RBFKernel, MaternKernel and DeepRBFKernel, got {type(gp.kernel).__name__}')
+    check_model(gp, who, _check_softmax_likelihood)
     if gp.z.size(0) > ops.SOFTMAX_SITE_MAX_C:
         raise ValueError(f'{who}: at most {ops.SOFTMAX_SITE_MAX_C} classes, got {gp.z.size(0)}')
 
 
 def composed_softmax_marginals(theta, Z, X, alpha, Q, nu2=0, tile=COMPOSED_TILE):
     """ops.site_marginals from the per-op kernels, a tile of N at a time (arguments and results alike; any Mt): the gram op and
-    ops.bgemm for alpha K and Q K."""
+    ops.matmul for alpha K and Q K."""
     ops.require_device(theta, Z, X, alpha, Q)
     (G, Mt, D), N = Z.shape, X.shape[0]
     th = theta.detach().view(1, -1).contiguous()
-    gram = (lambda Xt: ops.rbf_gram(th, Z, Xt, True)) if nu2 == 0 else (lambda Xt: ops.matern_gram(th, Z, Xt, True, 0.5 * nu2))
     g2 = (2.0 * th[0, -1]).exp()
     mu = torch.empty(G, N, dtype=torch.float32, device=X.device)
     var = torch.empty(G, N, dtype=torch.float32, device=X.device)
-    for n0 in range(0, N, tile):
-        n1 = min(n0 + tile, N)
-        K = gram(X[n0:n1].contiguous())[0]                                            # (G, Mt, B)
-        mu[:, n0:n1] = ops.bgemm(alpha.unsqueeze(-2), K).squeeze(-2)
-        var[:, n0:n1] = (g2 - (K * ops.bgemm(Q, K)).sum(-2)).clamp_min(0.0)
+    for n0, n1, Xt, _, _ in _tiles(X, tile):
+        mu[:, n0:n1], var[:, n0:n1] = _tile_marginals(_gram_tile(th, Z, Xt, nu2), alpha, Q, g2)
     return mu, var
 
 
@@ -480,9 +421,9 @@ class _SoftmaxProblem(_Problem):
 
     def _passes(self, alpha, Q):
         marginals = ops.site_marginals if self.route == 'fused' else composed_softmax_marginals
-        mu, var = marginals(self.theta, self.zf, self.xf, alpha, Q, self.nu2)
+        mu, var = marginals(self.fr.theta, self.zf, self.xf, alpha, Q, self.fr.nu2)
         lam1, lam2, sums = ops.softmax_sites(mu, var, self.y, self.w, self.n_f, self.seed)
-        Phi, c, _ = ops.gram_moments_v(self.theta, self.zf, self.xf, lam2, lam1, self.nu2)
+        Phi, c, _ = ops.gram_moments_v(self.fr.theta, self.zf, self.xf, lam2, lam1, self.fr.nu2)
         return Phi, c, sums[:1].double(), torch.zeros((), device=mu.device)
 
     def bound(self, data, kl):
@@ -525,7 +466,7 @@ def fit_q_softmax_(gp, x, y, n_iters=20, damping=1.0, tol=1e-6, weights=None, ro
 #     galpha = sum_n gm_n k_n,   gQ = -sum_n gv_n k_n k_n^T,   gK[:, n] = gm_n alpha - 2 gv_n Q k_n
 # ops.site_bound_diff is that function with ONE fused backward pass (csrc/sites.hip: vargp_site_bound_bwd; gQ by ops.gram_moments
 # with w = gv); the frozen tasks' a_i = T_ii m_i, H_i = T_ii Lu_i and T itself are differentiated by the per-op nodes
-# (ops.chol_inv, ops.matmul), as collapsed._whitened_bound does it.  fit_sites_ alternates fit_q_newton_ (E-step) with a few Yogi
+# (ops.chol_inv, ops.matmul): whitened.py.  fit_sites_ alternates fit_q_newton_ (E-step) with a few Yogi
 # steps on the bound (M-step); by the envelope theorem the partial gradient at the fixed whitened q IS the gradient of the
 # re-converged bound at a converged E-step (tests/test_site_bound_host.py).
 EMFit = namedtuple('EMFit', 'bound n_rounds n_newton stopped')
@@ -537,21 +478,14 @@ is non-decreasing); n_rounds: completed rounds (M-step + E-step); n_newton: acce
 def check_differentiable(gp, who):
     """check_supported, and exactly RBFKernel or MaternKernel: the bound's gradient for a DeepRBFKernel needs the gradient of the
     site pass for its inputs X (the feature map), which the fused backward does not produce."""
-    if isinstance(gp.kernel, DeepRBFKernel):
-        raise ValueError(f'{who}: DeepRBFKernel is not supported (the feature map needs the gradient of the site pass for its '
-                         'inputs X, which the fused backward does not produce); fit_q_newton_ supports it')
-    check_supported(gp, who)
-    if type(gp.kernel) not in (RBFKernel, MaternKernel):
-        raise ValueError(f'{who}: supported kernels are exactly RBFKernel and MaternKernel, got {type(gp.kernel).__name__}')
+    check_model(gp, who, _check_likelihood, deep='the feature map needs the gradient of the site pass for its inputs X, which the '
+                                                 'fused backward does not produce); fit_q_newton_ supports it')
 
 
 def _tile_value(theta, Z, alpha, Q, log_scale, Xt, yt, wt, kind, extra, nu2):
     """sum_n w_n ell_n (G,) float64 of one tile of points from the differentiable per-op nodes: the gram op, ops.matmul, and
     ell_torch in fp64."""
-    th = theta.view(1, -1)
-    K = (ops.rbf_gram(th, Z, Xt, True) if nu2 == 0 else ops.matern_gram(th, Z, Xt, True, 0.5 * nu2))[0]      # (G, Mt, B)
-    mu = ops.matmul(alpha.unsqueeze(-2), K).squeeze(-2)
-    var = ((2.0 * theta[-1]).exp() - (K * ops.matmul(0.5 * (Q + Q.mT), K)).sum(-2)).clamp_min(0.0)
+    mu, var = _tile_marginals(_gram_tile(theta.view(1, -1), Z, Xt, nu2), alpha, 0.5 * (Q + Q.mT), (2.0 * theta[-1]).exp())
     ex = extra if log_scale is None else (log_scale,) + tuple(extra[1:])
     ell = ell_torch(kind, ex, mu, var, yt)
     if wt is None:
@@ -568,7 +502,7 @@ class _ComposedSiteBound(torch.autograd.Function):
         ctx.save_for_backward(theta, Z, alpha, Q, log_scale, X, y, w)
         ctx.cfg = (kind, extra, nu2, tile)
         value = torch.zeros(Z.size(0), dtype=torch.float64, device=X.device)
-        for Xt, yt, wt in _tiles(X, y, w, tile):
+        for _, _, Xt, yt, wt in _tiles(X, tile, y, w):
             value += _tile_value(theta, Z, alpha, Q, log_scale, Xt, yt, wt, kind, extra, nu2)
         return value
 
@@ -580,7 +514,7 @@ class _ComposedSiteBound(torch.autograd.Function):
         leaves = [t.detach().clone().requires_grad_(True) for t in (theta, Z, alpha, Q) + (() if log_scale is None else (log_scale,))]
         acc = [torch.zeros(t.shape, dtype=torch.float64, device=t.device) for t in leaves]
         with torch.enable_grad():
-            for Xt, yt, wt in _tiles(X, y, w, tile):
+            for _, _, Xt, yt, wt in _tiles(X, tile, y, w):
                 val = _tile_value(*leaves[:4], leaves[4] if log_scale is not None else None, Xt, yt, wt, kind, extra, nu2)
                 for a, g in zip(acc, torch.autograd.grad((val * gout.double()).sum(), leaves)):
                     a += g.double()
@@ -588,21 +522,11 @@ class _ComposedSiteBound(torch.autograd.Function):
         return (*out[:4], out[4] if log_scale is not None else None, None, None, None, None, None, None, None)
 
 
-def _tiles(X, y, w, tile):
-    for n0 in range(0, X.size(0), tile):
-        n1 = min(n0 + tile, X.size(0))
-        yield (X[n0:n1].contiguous(), (y[n0:n1] if y.dim() == 1 else y[:, n0:n1]).contiguous(),
-               None if w is None else w[:, n0:n1].contiguous())
-
-
 def composed_site_bound(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0, tile=COMPOSED_TILE):
     """ops.site_bound_diff from the per-op kernels (arguments alike, any Mt; value (G,) float64): the route above
     ops.SITE_MAX_MT inducing points and the on-device yardstick of the fused backward."""
     ops.require_device(theta, Z, X, alpha, Q, y, w)
-    for name, t in (('X', X), ('y', y), ('w', w)):
-        if t is not None and t.requires_grad:
-            raise ValueError(f'composed_site_bound: {name} requires grad, but gradients are produced for theta, Z, alpha, Q and '
-                             'the Student-t log_scale only')
+    ops.refuse_grad('composed_site_bound', ops.SITE_BOUND_GRADS, X=X, y=y, w=w)
     log_scale = extra[0] if kind == 'studentt' else None
     return _ComposedSiteBound.apply(theta, Z, alpha, Q, log_scale, X, y, w, kind, tuple(extra), int(nu2), int(tile))
 
@@ -619,42 +543,16 @@ def site_bound(gp, x, y, weights=None, q=None, route=None):
     (ValueError).  The hyper-prior (kl_hypers) is NOT part of the bound."""
     check_differentiable(gp, 'site_bound')
     ops.require_device(gp.z, x, y, weights)
-    kern, lik = gp.kernel, gp.likelihood
-    C, M, N = gp.z.size(0), gp.M, x.size(0)
-    theta = kern.log_mean.to(torch.float32).contiguous()
-    prev = [gp._prev(i) for i in range(len(gp.prev_params))]
-    z_all = torch.cat([p['z'] for p in prev] + [gp.z], dim=-2).contiguous()
-    Mt = z_all.size(-2)
-    n_lt = Mt - M
-    route = pick_route(route, Mt, 'site_bound')
+    lik, fr = gp.likelihood, Frame(gp)
+    route = pick_route(route, fr.Mt, 'site_bound')
     a_t, H_t = whitened_q(gp) if q is None else (q[0].detach().double(), q[1].detach().float())
     own = lik.ext_param()
     extra = (() if own is None else (own.to(torch.float32),)) + tuple(lik._consts())
-    yt = site_target(lik.kind, y.detach(), C, N)
-    w = None
-    if weights is not None:
-        wt, ldw = ops.reg_target(weights.detach(), C, N)
-        w = wt.expand(C, N).contiguous() if ldw == 0 else wt
-    nu2 = int(round(2 * kern.nu)) if isinstance(kern, MaternKernel) else 0
-
-    L, T = ops.chol_inv(kern.compute(theta.unsqueeze(0), z_all)[0])                  # (C, Mt, Mt): as block_joint factorises
-    a, Hb, o = [], torch.zeros(C, Mt, Mt, dtype=torch.float32, device=x.device), 0
-    for p in prev:
-        n = p['z'].size(-2)
-        T_ii = T[:, o:o + n, o:o + n].contiguous()
-        a.append(ops.matmul(T_ii, p['u_mean'], triA=LOWER).squeeze(-1).double())
-        Hb[:, o:o + n, o:o + n] = ops.matmul(T_ii, p['u_tril'], triA=LOWER, triB=LOWER).tril()
-        o += n
-    Hb[:, n_lt:, n_lt:] = H_t
-    alpha = _mv(T.mT.double(), torch.cat(a + [a_t], dim=-1)).float().contiguous()
-    S = torch.eye(Mt, dtype=torch.float32, device=x.device) - ops.matmul(Hb, Hb.mT)
-    Q = ops.matmul(ops.matmul(T.mT, S), T)
-    Q = (0.5 * (Q + Q.mT)).contiguous()
+    yt = site_target(lik.kind, y.detach(), fr.C, x.size(0))
+    w = None if weights is None else rows(weights, fr.C, x.size(0))
     pass_ = ops.site_bound_diff if route == 'fused' else composed_site_bound
-    data = pass_(theta, z_all, x.detach().contiguous(), alpha, Q, yt, w, lik.kind, extra, nu2)
-    H64 = H_t.double()
-    kl = 0.5 * (a_t.square().sum(-1) + H64.square().sum((-2, -1)) - M - 2.0 * H64.diagonal(dim1=-2, dim2=-1).log().sum(-1))
-    return data.double() - kl
+    data = pass_(fr.theta, fr.z_all, x.detach().contiguous(), *alpha_Q(fr, a_t, H_t), yt, w, lik.kind, extra, fr.nu2)
+    return data.double() - kl_standard(a_t, H_t)
 
 
 def fit_sites_(gp, x, y, n_rounds=5, m_steps=20, lr=1e-2, params=None, newton_iters=20, damping=1.0, tol=1e-6, weights=None,
@@ -669,15 +567,12 @@ def fit_sites_(gp, x, y, n_rounds=5, m_steps=20, lr=1e-2, params=None, newton_it
     objective is the bound alone: the hyper-prior (kl_hypers) is NOT in it, so this is maximum likelihood (type II) for the
     hyper-parameters, not the MAP / variational treatment of VARGP.loss.  -> EMFit(bound (n_rounds + 1, C) float64 on the
     host, n_rounds, n_newton, stopped)."""
-    from .optim import Yogi
     check_differentiable(gp, 'fit_sites_')
     own = gp.likelihood.ext_param()
     named = dict(z=gp.z, kernel=gp.kernel.log_mean, lik=own)
     if params is None:
         params = ('z', 'kernel') + (('lik',) if own is not None else ())
-    params = tuple(params)
-    if not params or any(p not in named for p in params):
-        raise ValueError(f'fit_sites_: params must be a non-empty subset of {sorted(named)}, got {params!r}')
+    chosen = choose_params('fit_sites_', named, params)
     if 'lik' in params and own is None:
         raise ValueError(f"fit_sites_: params names 'lik', but {type(gp.likelihood).__name__} has no parameter")
     damping = check_damping(damping, 'fit_sites_')
@@ -685,7 +580,6 @@ def fit_sites_(gp, x, y, n_rounds=5, m_steps=20, lr=1e-2, params=None, newton_it
     if n_rounds < 0 or m_steps < 0:
         raise ValueError(f'fit_sites_: n_rounds and m_steps must be >= 0, got {n_rounds}, {m_steps}')
     ops.require_device(gp.z, x, y, weights)
-    chosen = [named[p] for p in dict.fromkeys(params)]
     e_step = lambda st: fit_q_newton_(gp, x, y, n_iters=newton_iters, damping=damping, tol=tol, weights=weights, route=route, start=st)
     fit = e_step(start)
     trace, n_newton, stopped, done = [fit.bound[-1]], fit.n_iters, 'rounds', 0
@@ -698,20 +592,11 @@ def fit_sites_(gp, x, y, n_rounds=5, m_steps=20, lr=1e-2, params=None, newton_it
                 for t, k in zip(chosen + [gp.u_mean, gp.u_tril_vec], keep):
                     t.copy_(k)
 
-        opt = Yogi(chosen, lr=lr)
-        before = None
-        for _ in range(m_steps):
-            bound = site_bound(gp, x, y, weights=weights, q=q, route=route)
-            before = bound.detach().sum() if before is None else before
-            for p, g in zip(chosen, torch.autograd.grad(-bound.sum(), chosen)):
-                p.grad = g.to(p.dtype)
-            opt.step()
-        for p in chosen:
-            p.grad = None
+        before = ascend_(lambda: site_bound(gp, x, y, weights=weights, q=q, route=route), chosen, m_steps, lr)
         if m_steps:
             with torch.no_grad():
                 after = site_bound(gp, x, y, weights=weights, q=q, route=route).sum()
-            if not bool(after >= before):
+            if not bool(after >= before[0].sum()):
                 undo()
                 stopped = 'm_step'
                 break
