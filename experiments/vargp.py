@@ -312,14 +312,15 @@ def parse_args(argv=None):
         sp.add_argument('--lengthscale_init', choices=('default', 'median'), default='default',
                         help="lengthscales of the first task: 0.5 (the reference's), or the median distance between pairs of "
                              'its points (not with --dkl)')
-        sp.add_argument('--q_init', choices=('default', 'newton', 'em', 'newton_softmax'), default='default',
+        sp.add_argument('--q_init', choices=('default', 'newton', 'em', 'newton_softmax', 'em_softmax'), default='default',
                         help="q(u) of each task: the reference's start, fit_q_newton_ on the task's whole training set, or "
                              'fit_sites_ (variational EM: inducing points and kernel hyper-parameters move too) '
-                             '(--likelihood bernoulli only), or fit_q_softmax_ (--likelihood softmax only)')
+                             '(--likelihood bernoulli only), or fit_q_softmax_ / fit_softmax_sites_ (its variational EM) '
+                             '(--likelihood softmax only)')
         sp.add_argument('--newton_iters', type=int, default=20, help='iterations of --q_init newton / of an E-step of em (at most)')
-        sp.add_argument('--site_samples', type=int, default=32, help='draws per point of --q_init newton_softmax')
-        sp.add_argument('--em_rounds', type=int, default=5, help='rounds of --q_init em')
-        sp.add_argument('--em_steps', type=int, default=20, help='Yogi steps per M-step of --q_init em')
+        sp.add_argument('--site_samples', type=int, default=32, help='draws per point of --q_init newton_softmax / em_softmax')
+        sp.add_argument('--em_rounds', type=int, default=5, help='rounds of --q_init em / em_softmax')
+        sp.add_argument('--em_steps', type=int, default=20, help='Yogi steps per M-step of --q_init em / em_softmax')
         sp.add_argument('--seed', type=int, default=None)
         sp.add_argument('--eval_interval', type=int, default=10)
         sp.add_argument('--log_dir', default=os.path.join('runs', f'{name}-{int(time.time())}'))

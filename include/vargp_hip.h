@@ -407,6 +407,44 @@ int vargp_gram_moments_v(const float* theta, const float* Z, const float* X, con
                          float* sums, int G, int Mt, int N, int D, int nu2, void* ws, size_t ws_bytes, vargp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The backward of the softmax site bound (vargp_amd/sites.py: softmax_site_bound, fit_softmax_sites_; ops.softmax_site_bound_diff).
+ * Not in the reference.  The value is vargp_softmax_sites' sums[0] at the marginals of vargp_site_marginals; its gradient is these
+ * two entries and one vargp_gram_moments call.  Both check their arguments on the host before any launch (VARGP_EINVAL,
+ * vargp_last_error), work on the caller's stream and use no atomics: two calls on the same input are bitwise equal.
+ *
+ * vargp_softmax_site_grads: the EXACT derivatives of the F-sample estimate sum_n w_n [mu[y_n, n] - mean_f logsumexp(f)] for the
+ * marginals, seeded by s = gout[0] (a DEVICE pointer: the caller needs no host sync), with f, p, eps as vargp_softmax_sites has them:
+ *   gmu[c, n]  = s w_n ([y_n = c] - mean_f p_c)                                                                       [C, N]
+ *   gvar[c, n] = -s w_n / (2 sqrt(var[c, n])) mean_f (p_c eps_c)   where var[c, n] > 0, else exactly 0                [C, N]
+ * the pathwise derivative for var, NOT the Price estimate -1/2 E p (1 - p) behind lam2: only this one is the derivative of the
+ * sampled value (its slope is unbounded as var -> 0+; at var = 0 the convention is 0).  Layout, limits (2 <= C <= 128, F <= 65535),
+ * the noise stream, the draw indexing and the chunking are vargp_softmax_sites'; every p comes from the same device functions;
+ * eps NULL and the tensor vargp_softmax_site_noise writes give bitwise equal results.  Two accumulators per class (sum p_c, sum
+ * p_c eps_c), in registers up to C = 16 and in LDS above (with the draw's logits and noise: 4 C x 64 floats).  Nothing is reduced
+ * over the points: no workspace and no second launch.  A point of weight 0 is never evaluated and writes exact zeros, whatever
+ * its mu, var and y hold.  VARGP_EINVAL: a null pointer other than w and eps, N or F < 1, F > 65535, C outside [2, 128].
+ *
+ * vargp_site_transport_bwd: vargp_site_bound_bwd with GIVEN per-point seeds gm, gv [G, N] (d value / d mu_n, d value / d var_n,
+ * weights and upstream seed included) in place of a likelihood: no targets, no weights, no parameter, no gls.  With u_n =
+ * [gamma^2 - q_n > 0] recomputed here, gv_out = gv o u [G, N] (gQ[g] = -Phi of vargp_gram_moments with w = gv_out), and gZ, gtheta
+ * (complete, D + 1 entries) and galpha are that entry's formulas with gm_n = gm[g, n], gv_n = gv_out[g, n].  It IS that entry's
+ * kernel with a policy that loads the two derivatives of a point from memory, and everything else is inherited: Mt <= 256 with the
+ * K block and the weight block in LDS; Qs K and V X on the f32 MFMA; groups of at most 128 values of d; the chunk rule
+ * (vargp_site_transport_bwd_chunks is vargp_site_bound_bwd_chunks) and a workspace of per-chunk partials that does not grow with N
+ * beyond the chunk count; fp32 within a chunk, fp64 across chunks in ascending order by the reduce launch; no atomics, bitwise
+ * reproducible; nothing is read behind row N of X.  A point whose gm and gv are both 0 is masked like a point of weight 0: it
+ * adds exactly nothing, whatever its row of X holds (NaN included).  VARGP_EINVAL: a null pointer, a size < 1, Mt > 256,
+ * G > 65535, an unknown nu2, a short or misaligned workspace.  The two queries return 0 for a size < 1.
+ */
+int vargp_softmax_site_grads(const float* mu, const float* var, const int64_t* y, const float* w, const float* eps, uint64_t seed,
+                             const float* gout, float* gmu, float* gvar, int C, int N, int F, vargp_stream_t stream);
+size_t vargp_site_transport_bwd_workspace_bytes(int G, int Mt, int N, int D);
+int vargp_site_transport_bwd_chunks(int G, int Mt, int N, int D);
+int vargp_site_transport_bwd(const float* theta, const float* Z, const float* X, const float* alpha, const float* Q, const float* gm,
+                             const float* gv, float* gZ, float* gtheta, float* galpha, float* gv_out, int G, int Mt, int N, int D,
+                             int nu2, void* ws, size_t ws_bytes, vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * KL(N(mu_q, Lq Lq^T) || N(mu_p, Lp Lp^T)) from its triangular ingredients (reference:
  * torch.distributions kl_divergence(MVN, MVN) as called from var_gp/vargp.py:182-190):
  *   kl = logdet_p - logdet_q + 0.5 * (|G|_F^2 + |d|^2 - M),  G = Lp^-1 Lq [nb, M, M],

@@ -125,6 +125,10 @@ _SIGNATURES = {
     'vargp_softmax_sites': (c_int, [_P] * 5 + [ctypes.c_uint64, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
     'vargp_softmax_site_noise': (c_int, [ctypes.c_uint64, _P, c_int, c_int, c_int, _P]),
     'vargp_gram_moments_v': (c_int, [_P] * 8 + [c_int] * 5 + [_P, c_size_t, _P]),
+    'vargp_softmax_site_grads': (c_int, [_P] * 5 + [ctypes.c_uint64, _P, _P, _P, c_int, c_int, c_int, _P]),
+    'vargp_site_transport_bwd_workspace_bytes': (c_size_t, [c_int] * 4),
+    'vargp_site_transport_bwd_chunks': (c_int, [c_int] * 4),
+    'vargp_site_transport_bwd': (c_int, [_P] * 11 + [c_int] * 5 + [_P, c_size_t, _P]),
     'vargp_mvn_kl_fwd':(c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),
     'vargp_mvn_kl_bwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),
     'vargp_logdet_tril_fwd': (c_int, [_P, _P, c_int, c_int, _P]),

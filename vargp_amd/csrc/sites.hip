@@ -70,6 +70,32 @@ struct SiteMarginals {
 template <class LIK> constexpr bool kSiteMarginals = false;
 template <> constexpr bool kSiteMarginals<SiteMarginals> = true;
 
+// Not a likelihood either: site_bwd_kernel with GIVEN per-point seeds (vargp_site_transport_bwd).  Its "element" loads (dmu, dvar)
+// = (gm, gv) [G][N] of a point from memory; there are no targets, weights or parameters, and a point whose two seeds are both 0 is
+// masked like a point of weight 0
+struct SiteTransport {
+  using real = float;
+  struct Args { const float *gm, *gv; int64_t N; };
+  struct Seeds { float gm, gv; };
+  struct Cls {};
+  static __device__ __forceinline__ Cls cls(const Args&, int) { return {}; }
+  template <class T>
+  static __device__ __forceinline__ Seeds target(const Args& a, int g, size_t n) {
+    return {a.gm[g * a.N + (int64_t)n], a.gv[g * a.N + (int64_t)n]};
+  }
+  template <bool GRAD>
+  static __device__ __forceinline__ float element(const Cls&, float, float, Seeds s, float& dmu, float& dvar, float&) {
+    dmu = s.gm;
+    dvar = s.gv;
+    return 0.f;
+  }
+  static __device__ __forceinline__ bool live(const Args& a, int g, int64_t n) {
+    return a.gm[g * a.N + n] != 0.f || a.gv[g * a.N + n] != 0.f;
+  }
+};
+template <class LIK> constexpr bool kSiteTransport = false;
+template <> constexpr bool kSiteTransport<SiteTransport> = true;
+
 struct SiteArgs {
   const float *theta, *Z, *X, *alpha, *Q, *w;
   float *lam2, *c, *sums;
@@ -360,6 +386,9 @@ static int site_launch(const SiteArgs& a, const typename LIK::Args& la, int nu2,
 // chunks' partials in ascending chunk order in fp64, forms gZ and gtheta there and rounds once.  The chunking (site_bwd_plan)
 // depends on the shapes alone: the forward's rule over G x groups workgroups, capped so that the partials of P stay below
 // kSbBudget bytes.
+// The same kernel with LIK = SiteTransport is vargp_site_transport_bwd: (gm, gv) [G][N] are GIVEN (the softmax's, from
+// softmax_sites.hip: vargp_softmax_site_grads) and carried back to Z, theta, alpha and, through gv_out = gv u, Q.  No likelihood is
+// evaluated; u_n is recomputed here; a column whose gm and gv are both 0 is masked like one of weight 0.
 constexpr int kSbNPMax = 2;                     // tiles of 64 values of d per group (GEMM form; the direct form has D <= 32: one)
 constexpr size_t kSbBudget = 64u << 20;         // bytes of the per-chunk partials of r, galpha and P, at most (one chunk always fits)
 constexpr int kSbStage = kSiStage > kMoT * kMoLD ? kSiStage : kMoT * kMoLD;
@@ -410,6 +439,7 @@ template <class LIK, class EPI, bool DIRECT, int NP>
 __global__ __launch_bounds__(256) void site_bwd_kernel(const SiteBwdArgs a, const typename LIK::Args la) {
   using real = typename LIK::real;
   constexpr int T = kMoT, LD = kMoLD, BK = kMoBK;
+  constexpr bool TRANS = kSiteTransport<LIK>;      // the seeds are given: no weights, no upstream seed (they carry both)
   extern __shared__ __attribute__((aligned(16))) float sb_lds[];
   const int Mt = a.Mt, D = a.D, nt = a.p.nt, MtP = nt * T, LDK = MtP + 1, ngrp = a.p.ngrp;
   float* Ks = sb_lds;                  // the K block: [n][m], m over all nt panels
@@ -435,7 +465,8 @@ __global__ __launch_bounds__(256) void site_bwd_kernel(const SiteBwdArgs a, cons
   const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32, l31 = lane & 31, h = lane >> 5;
   const int pr = (wave & 1) * 32, pd = (wave >> 1) * 32;
   const float g2 = expf(2.f * a.theta[D]);
-  const float sg = a.gout[g];
+  float sg = 1.f;
+  if constexpr (!TRANS) sg = a.gout[g];
   const float* __restrict__ Zg = a.Z + g * (int64_t)Mt * D;
   const float* __restrict__ X = a.X;
   const float* __restrict__ Qg = a.Q + g * (int64_t)Mt * Mt;
@@ -465,7 +496,9 @@ __global__ __launch_bounds__(256) void site_bwd_kernel(const SiteBwdArgs a, cons
   for (int64_t n0 = cbeg; n0 < cend; n0 += T) {
     if (tid < T) {
       const int64_t n = n0 + tid;
-      cok[tid] = (n < cend && (!wg || wg[n] != 0.f)) ? 1.f : 0.f;
+      bool live = n < cend && (!wg || wg[n] != 0.f);
+      if constexpr (TRANS) live = live && LIK::live(la, (int)g, n);
+      cok[tid] = live ? 1.f : 0.f;
     }
     __syncthreads();
     // ---- the K block and its weight: rows behind Mt and masked columns are zeros
@@ -770,7 +803,9 @@ __global__ __launch_bounds__(256) void site_bwd_reduce_kernel(const SiteBwdArgs 
 template <class LIK, class EPI, bool DIRECT, int NP>
 static int site_bwd_launch_form(const SiteBwdArgs& a, const typename LIK::Args& la, hipStream_t st) {
   constexpr auto kernel = site_bwd_kernel<LIK, EPI, DIRECT, NP>;
-  if (int rc = reserve_dynamic_lds<kernel>(site_bwd_lds_floats(kSiMaxNt) * sizeof(float), "site_bound_bwd")) return rc;
+  if (int rc = reserve_dynamic_lds<kernel>(site_bwd_lds_floats(kSiMaxNt) * sizeof(float),
+                                           kSiteTransport<LIK> ? "site_transport_bwd" : "site_bound_bwd"))
+    return rc;
   hipLaunchKernelGGL(kernel, dim3(a.p.ch.nch * a.p.ngrp, a.G), dim3(256), site_bwd_lds_floats(a.p.nt) * sizeof(float), st, a, la);
   return VARGP_OK;
 }
@@ -850,6 +885,35 @@ extern "C" int vargp_site_bound_bwd(const float* theta, const float* Z, const fl
   if (rc != VARGP_OK) return rc;
   hipLaunchKernelGGL(site_bwd_reduce_kernel, dim3((unsigned)nred), dim3(256), 0, st, a);
   return check_launch("site_bound_bwd");
+}
+
+extern "C" int vargp_site_transport_bwd_chunks(int G, int Mt, int N, int D) { return vargp_site_bound_bwd_chunks(G, Mt, N, D); }
+
+extern "C" size_t vargp_site_transport_bwd_workspace_bytes(int G, int Mt, int N, int D) {
+  return vargp_site_bound_bwd_workspace_bytes(G, Mt, N, D);
+}
+
+extern "C" int vargp_site_transport_bwd(const float* theta, const float* Z, const float* X, const float* alpha, const float* Q,
+                                        const float* gm, const float* gv, float* gZ, float* gtheta, float* galpha, float* gv_out,
+                                        int G, int Mt, int N, int D, int nu2, void* ws, size_t ws_bytes, vargp_stream_t stream) {
+  // (no targets and no likelihood: the checks of the sibling entry with a shared row of targets and a kind without parameters)
+  if (int rc = site_check_args("site_transport_bwd", theta && Z && X && alpha && Q && gm && gv && gZ && gtheta && galpha && gv_out && ws,
+                               0, VARGP_SITE_BERNOULLI_PROBIT, true, "", G, Mt, N, D, nu2, ws, ws_bytes,
+                               vargp_site_transport_bwd_workspace_bytes(G, Mt, N, D)))
+    return rc;
+  SiteBwdArgs a{};
+  a.theta = theta; a.Z = Z; a.X = X; a.alpha = alpha; a.Q = Q;
+  a.gZ = gZ; a.gtheta = gtheta; a.galpha = galpha; a.gv = gv_out;
+  a.p = site_bwd_plan(ws, G, Mt, N, D);
+  a.G = G; a.Mt = Mt; a.N = N; a.D = D;
+  const int64_t nred = cdiv((int64_t)G * Mt * D, 256) + D + cdiv((int64_t)G * Mt, 256) + 1;
+  VARGP_REQUIRE((int64_t)a.p.ch.nch * a.p.ngrp < (1ll << 31) && nred < (1ll << 31),
+                "site_transport_bwd: G = %d, Mt = %d, D = %d need too many workgroups", G, Mt, D);
+  hipStream_t st = as_stream(stream);
+  ProfScope whole("site_transport_bwd", st);
+  if (int rc = site_bwd_launch<SiteTransport>(a, SiteTransport::Args{gm, gv, (int64_t)N}, nu2, st)) return rc;
+  hipLaunchKernelGGL(site_bwd_reduce_kernel, dim3((unsigned)nred), dim3(256), 0, st, a);
+  return check_launch("site_transport_bwd");
 }
 
 extern "C" int vargp_site_moments_chunks(int G, int Mt, int N, int D) {

@@ -946,6 +946,94 @@ def site_bound_diff(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0):
     return _SiteBound.apply(theta, Z, X, alpha, Q, y, w, log_scale, kind, tuple(extra), nu2)
 
 
+# The softmax site bound on the autograd graph (csrc/softmax_sites.hip: vargp_softmax_site_grads; csrc/sites.hip:
+# vargp_site_transport_bwd -- not in the reference).
+SOFTMAX_BOUND_GRADS = 'theta, Z, alpha and Q'
+
+
+def softmax_site_grads(mu, var, y, w, n_f, gout, seed=0, eps=None):
+    """The exact derivatives of softmax_sites(...)[2][0] -- the n_f-sample estimate sum_n w_n (mu[y_n, n] - mean_f logsumexp(f)) --
+    for the marginals, operands as softmax_sites takes them and gout (1,) fp32 on the device, the upstream seed:
+    -> (gmu (C, N) = gout w ([y = c] - mean_f p_c), gvar (C, N) = -gout w mean_f (p_c eps_c) / (2 sqrt(var)), exactly 0 where var
+    == 0).  The pathwise derivative for var, not the Price estimate behind lam2.  The same draws as softmax_sites (eps or seed,
+    bitwise alike); a point of weight 0 is not evaluated and gets exact zeros; no workspace; bitwise reproducible."""
+    require_device(mu, var, y, w, eps, gout)
+    det = lambda t: t.detach().contiguous()
+    mu, var, y, gout = det(mu), det(var), det(y), det(gout).view(-1)
+    assert mu.dim() == 2 and mu.shape == var.shape and mu.dtype == var.dtype == torch.float32, (mu.shape, var.shape, mu.dtype, var.dtype)
+    C, N = mu.shape
+    F = int(n_f)
+    assert tuple(y.shape) == (N,) and y.dtype == torch.int64, (y.shape, y.dtype)
+    assert gout.numel() == 1 and gout.dtype == torch.float32, (gout.shape, gout.dtype)
+    if w is not None:
+        w = det(w)
+        assert tuple(w.shape) == (N,) and w.dtype == torch.float32, (w.shape, w.dtype)
+    if eps is not None:
+        eps = det(eps)
+        assert tuple(eps.shape) == (F, C, N) and eps.dtype == torch.float32, (eps.shape, eps.dtype, (F, C, N))
+    gmu, gvar = torch.empty_like(mu), torch.empty_like(mu)
+    check(lib().vargp_softmax_site_grads(ptr(mu), ptr(var), ptr(y), ptr(w), ptr(eps), _seed64(seed), ptr(gout), ptr(gmu), ptr(gvar),
+                                         C, N, F, stream_ptr()), 'vargp_softmax_site_grads')
+    return gmu, gvar
+
+
+def site_transport_bwd_chunks(G, Mt, N, D):
+    """The number of chunks ops.site_transport_bwd cuts N points into for this shape (site_bound_bwd's rule)."""
+    return int(lib().vargp_site_transport_bwd_chunks(int(G), int(Mt), int(N), int(D)))
+
+
+def site_transport_bwd(theta, Z, X, alpha, Q, gm, gv, nu2=0):
+    """site_bound_bwd with GIVEN per-point seeds in place of a likelihood (csrc/sites.hip, vargp_site_transport_bwd): theta, Z, X,
+    alpha, Q as site_marginals takes them; gm, gv (G, N) = d value / d mu, d value / d var of every point (weights and upstream
+    seed included).  -> (gZ (G, Mt, D); gtheta (D + 1,), complete; galpha (G, Mt); gv_out (G, N) = gv where gamma^2 - k^T Q k > 0,
+    else 0: gQ = -gram_moments(w=gv_out).Phi).  K(Z, X) and its gradient are never stored; bitwise reproducible; a point whose gm
+    and gv are both 0 adds exactly nothing whatever its row of X holds."""
+    require_device(theta, Z, X, alpha, Q, gm, gv)
+    theta, Z, X, alpha, Q, (G, Mt, N, D) = _data_operands(theta, Z, X, alpha, Q)
+    gm, gv = gm.detach().contiguous(), gv.detach().contiguous()
+    assert tuple(gm.shape) == tuple(gv.shape) == (G, N) and gm.dtype == gv.dtype == torch.float32, (gm.shape, gv.shape, gm.dtype)
+    gZ = torch.empty_like(Z)
+    gtheta = torch.empty(D + 1, dtype=torch.float32, device=X.device)
+    galpha = torch.empty(G, Mt, dtype=torch.float32, device=X.device)
+    gv_out = torch.empty(G, N, dtype=torch.float32, device=X.device)
+    ws = scratch(lib().vargp_site_transport_bwd_workspace_bytes(G, Mt, N, D), X.device)
+    check(lib().vargp_site_transport_bwd(ptr(theta), ptr(Z), ptr(X), ptr(alpha), ptr(Q), ptr(gm), ptr(gv), ptr(gZ), ptr(gtheta),
+                                         ptr(galpha), ptr(gv_out), G, Mt, N, D, int(nu2), ptr(ws), ws.numel() * 4, stream_ptr()),
+          'vargp_site_transport_bwd')
+    return gZ, gtheta, galpha, gv_out
+
+
+class _SoftmaxSiteBound(Function):
+    @staticmethod
+    def forward(ctx, theta, Z, X, alpha, Q, y, w, eps, n_f, seed, nu2):
+        det = lambda t: None if t is None else t.detach().contiguous()
+        mu, var = site_marginals(theta, Z, X, alpha, Q, nu2)
+        value = softmax_sites(mu, var, y, w, n_f, seed, eps)[2][:1].contiguous()
+        ctx.save_for_backward(det(theta).view(-1), det(Z), det(X), det(alpha), det(Q), det(y), det(w), det(eps), mu, var)
+        ctx.n_f, ctx.seed, ctx.nu2, ctx.theta_shape = int(n_f), seed, int(nu2), theta.shape
+        return value
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        theta, Z, X, alpha, Q, y, w, eps, mu, var = ctx.saved_tensors
+        gmu, gvar = softmax_site_grads(mu, var, y, w, ctx.n_f, gout.to(torch.float32).contiguous(), ctx.seed, eps)
+        gZ, gtheta, galpha, gv = site_transport_bwd(theta, Z, X, alpha, Q, gmu, gvar, ctx.nu2)
+        gQ = -gram_moments(theta, Z, X, gv, gv, ctx.nu2)[0]
+        return gtheta.view(ctx.theta_shape), gZ, None, galpha, gQ, None, None, None, None, None, None
+
+
+def softmax_site_bound_diff(theta, Z, X, alpha, Q, y, w, n_f, seed=0, eps=None, nu2=0):
+    """value (1,) = sum_n w_n (mu[y_n, n] - mean_f logsumexp(mu_n + sqrt(var_n) eps_nf)) at the marginals of q(f) -- site_marginals
+    followed by softmax_sites, its sums[0] bitwise -- on the autograd graph of theta (D+1,), Z (C, Mt, D), alpha (C, Mt) and Q (C,
+    Mt, Mt) (through its symmetric part; the variance clamp passes no gradient).  y (N,) int64, w (N,) or None, n_f draws per point
+    fixed by `seed` (or eps (n_f, C, N)).  mu and var (2 C N floats) are kept for the backward: softmax_site_grads (the exact
+    derivative of the sampled value), site_transport_bwd and one gram_moments call for gQ; K(Z, X) is never stored.  No
+    gradients are produced for X, y and w: a ValueError if one of them requires grad."""
+    refuse_grad('softmax_site_bound_diff', SOFTMAX_BOUND_GRADS, X=X, y=y, w=w)
+    return _SoftmaxSiteBound.apply(theta, Z, X, alpha, Q, y, w, eps, n_f, seed, nu2)
+
+
 class _LogdetTril(Function):
     @staticmethod
     def forward(ctx, L):

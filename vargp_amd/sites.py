@@ -575,12 +575,25 @@ def fit_sites_(gp, x, y, n_rounds=5, m_steps=20, lr=1e-2, params=None, newton_it
     chosen = choose_params('fit_sites_', named, params)
     if 'lik' in params and own is None:
         raise ValueError(f"fit_sites_: params names 'lik', but {type(gp.likelihood).__name__} has no parameter")
-    damping = check_damping(damping, 'fit_sites_')
-    n_rounds, m_steps = int(n_rounds), int(m_steps)
-    if n_rounds < 0 or m_steps < 0:
-        raise ValueError(f'fit_sites_: n_rounds and m_steps must be >= 0, got {n_rounds}, {m_steps}')
+    damping, n_rounds, m_steps = _check_em_args('fit_sites_', damping, n_rounds, m_steps)
     ops.require_device(gp.z, x, y, weights)
     e_step = lambda st: fit_q_newton_(gp, x, y, n_iters=newton_iters, damping=damping, tol=tol, weights=weights, route=route, start=st)
+    bound_at = lambda q: site_bound(gp, x, y, weights=weights, q=q, route=route)
+    return _em(gp, chosen, e_step, bound_at, start, n_rounds, m_steps, lr)
+
+
+def _check_em_args(who, damping, n_rounds, m_steps):
+    damping = check_damping(damping, who)
+    n_rounds, m_steps = int(n_rounds), int(m_steps)
+    if n_rounds < 0 or m_steps < 0:
+        raise ValueError(f'{who}: n_rounds and m_steps must be >= 0, got {n_rounds}, {m_steps}')
+    return damping, n_rounds, m_steps
+
+
+def _em(gp, chosen, e_step, bound_at, start, n_rounds, m_steps, lr):
+    """The round loop both EM fits share: e_step(start) -> a SiteFit (the first from `start`, the later ones from 'current');
+    bound_at(q) -> the bound on the autograd graph of `chosen` with q(v_t) held at the whitened q; the undo rule of fit_sites_'
+    docstring.  -> EMFit"""
     fit = e_step(start)
     trace, n_newton, stopped, done = [fit.bound[-1]], fit.n_iters, 'rounds', 0
     for _ in range(n_rounds):
@@ -592,10 +605,10 @@ def fit_sites_(gp, x, y, n_rounds=5, m_steps=20, lr=1e-2, params=None, newton_it
                 for t, k in zip(chosen + [gp.u_mean, gp.u_tril_vec], keep):
                     t.copy_(k)
 
-        before = ascend_(lambda: site_bound(gp, x, y, weights=weights, q=q, route=route), chosen, m_steps, lr)
+        before = ascend_(lambda: bound_at(q), chosen, m_steps, lr)
         if m_steps:
             with torch.no_grad():
-                after = site_bound(gp, x, y, weights=weights, q=q, route=route).sum()
+                after = bound_at(q).sum()
             if not bool(after >= before[0].sum()):
                 undo()
                 stopped = 'm_step'
@@ -610,3 +623,144 @@ def fit_sites_(gp, x, y, n_rounds=5, m_steps=20, lr=1e-2, params=None, newton_it
         n_newton += fit.n_iters
         done += 1
     return EMFit(torch.stack(trace), done, n_newton, stopped)
+
+
+# -- the softmax site bound on the autograd graph: variational EM for MulticlassSoftmax ---------------------------------------------
+# With q(v_t) fixed in whitened coordinates and the noise fixed by (n_f, seed), fit_q_softmax_'s bound
+#     value = sum_n w_n [mu_{y_n, n} - mean_f logsumexp(mu_n + sqrt(var_n) o eps_nf)] - sum_c KL(q(v_t, c) || N(0, I))
+# is a deterministic function of the inducing points and theta through alpha, Q and k_n.  Its gradient is the EXACT derivative of
+# that n_f-sample estimate (s the upstream seed):
+#     gm_cn = s w_n ([y_n = c] - mean_f p_c),   gv_cn = -s w_n / (2 sqrt(var_cn)) mean_f (p_c eps_c)  (var_cn > 0; else exactly 0)
+# -- the pathwise derivative for var, NOT the Price estimate -1/2 E p (1 - p) behind the E-step's lam2: the M-step ascends a
+# deterministic function whose values the undo rule compares, and only the exact derivative can be held against autograd.  (The
+# sampled objective has an unbounded slope as var -> 0+; nothing guards against it, and at var = 0 the derivative is 0 by the
+# convention of ell_torch.)  Everything behind (gm, gv) is the site bound's algebra with the seeds given: ops.site_transport_bwd
+# and gQ = -gram_moments(w = gv u).Phi.  Four launches-with-reduce forward and back: ops.site_marginals, ops.softmax_sites |
+# ops.softmax_site_grads, ops.site_transport_bwd, ops.gram_moments.
+# CAVEAT: the E-step's Bonnet / Price sites are not the stationarity condition of the SAMPLED bound, so at the E-step's q the
+# partial gradient for (z, theta) is the gradient of the re-converged bound only up to the Monte-Carlo error of the sites: the
+# envelope argument of fit_sites_ is approximate here, and it is the undo rule that guarantees a non-decreasing trace.
+def check_softmax_differentiable(gp, who):
+    """check_softmax_supported, and exactly RBFKernel or MaternKernel: a DeepRBFKernel is refused for check_differentiable's
+    reason.  Needs no device."""
+    check_model(gp, who, _check_softmax_likelihood, deep='the feature map needs the gradient of the site pass for its inputs X, which '
+                                                         'the fused backward does not produce); fit_q_softmax_ supports it')
+    check_softmax_supported(gp, who)
+
+
+def softmax_value_torch(mu, var, y, w, eps):
+    """sum_n w_n [mu_{y_n, n} - mean_f logsumexp(mu_n + sqrt(var_n) eps_nf)] () float64 in fp32 elementwise torch (summed in fp64),
+    differentiable in mu and var (C, B); eps (F, C, B).  sqrt has no derivative at a variance of 0: that of 1, times 0 (ell_torch's
+    convention).  Any device."""
+    pos = var > 0
+    sd = torch.where(pos, torch.where(pos, var, torch.ones_like(var)).sqrt(), torch.zeros_like(var))
+    lse = torch.logsumexp(mu + sd * eps, -2).mean(0)
+    hot = (y.unsqueeze(0) == torch.arange(mu.size(0), device=y.device).unsqueeze(1)).to(mu.dtype)
+    ell = ((mu * hot).sum(0) - lse).double()
+    if w is None:
+        return ell.sum()
+    return torch.where(w != 0, w.double() * ell, torch.zeros_like(ell)).sum()
+
+
+def _softmax_tile_value(theta, Z, alpha, Q, Xt, yt, wt, eps_t, nu2):
+    """sum_n w_n ell_n () float64 of one tile of points from the differentiable per-op nodes (the gram op, ops.matmul) and
+    softmax_value_torch on the tile's noise eps_t (F, C, B)."""
+    mu, var = _tile_marginals(_gram_tile(theta.view(1, -1), Z, Xt, nu2), alpha, 0.5 * (Q + Q.mT), (2.0 * theta[-1]).exp())
+    return softmax_value_torch(mu, var, yt, wt, eps_t)
+
+
+class _ComposedSoftmaxSiteBound(torch.autograd.Function):
+    """ops.softmax_site_bound_diff for any Mt, a tile of N at a time, in the shape of _ComposedSiteBound: values added in fp64
+    under no_grad; the backward rebuilds each tile's graph and accumulates the gradients in fp64."""
+    @staticmethod
+    def forward(ctx, theta, Z, alpha, Q, X, y, w, eps, nu2, tile):
+        ctx.save_for_backward(theta, Z, alpha, Q, X, y, w, eps)
+        ctx.cfg = (nu2, tile)
+        value = torch.zeros(1, dtype=torch.float64, device=X.device)
+        for n0, n1, Xt, yt, _ in _tiles(X, tile, y):
+            value += _softmax_tile_value(theta, Z, alpha, Q, Xt, yt, None if w is None else w[n0:n1], eps[:, :, n0:n1], nu2)
+        return value
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        theta, Z, alpha, Q, X, y, w, eps = ctx.saved_tensors
+        nu2, tile = ctx.cfg
+        leaves = [t.detach().clone().requires_grad_(True) for t in (theta, Z, alpha, Q)]
+        acc = [torch.zeros(t.shape, dtype=torch.float64, device=t.device) for t in leaves]
+        with torch.enable_grad():
+            for n0, n1, Xt, yt, _ in _tiles(X, tile, y):
+                val = _softmax_tile_value(*leaves, Xt, yt, None if w is None else w[n0:n1], eps[:, :, n0:n1], nu2)
+                for a, g in zip(acc, torch.autograd.grad((val * gout.double()).sum(), leaves)):
+                    a += g.double()
+        return (*[a.to(t.dtype) for a, t in zip(acc, leaves)], None, None, None, None, None, None)
+
+
+def composed_softmax_site_bound(theta, Z, X, alpha, Q, y, w, n_f, seed=0, eps=None, nu2=0, tile=COMPOSED_TILE):
+    """ops.softmax_site_bound_diff from the per-op kernels (arguments alike, any Mt; value (1,) float64) on an explicit noise
+    tensor (eps, or ops.softmax_site_noise(seed, n_f, C, N): n_f C N floats), sliced per tile: the route above ops.SITE_MAX_MT
+    inducing points and the on-device yardstick of the fused backward."""
+    ops.require_device(theta, Z, X, alpha, Q, y, w, eps)
+    ops.refuse_grad('composed_softmax_site_bound', ops.SOFTMAX_BOUND_GRADS, X=X, y=y, w=w)
+    if eps is None:
+        eps = ops.softmax_site_noise(seed, n_f, Z.size(0), X.size(0), device=X.device)
+    assert tuple(eps.shape) == (int(n_f), Z.size(0), X.size(0)), (eps.shape, n_f, Z.shape, X.shape)
+    return _ComposedSoftmaxSiteBound.apply(theta, Z, alpha, Q, X, y, w, eps, int(nu2), int(tile))
+
+
+def _check_softmax_data(who, x, y, weights, n_f):
+    n_f = int(n_f)
+    if not 1 <= n_f <= 65535:
+        raise ValueError(f'{who}: n_f must be in [1, 65535], got {n_f}')
+    if y.dtype != torch.int64 or tuple(y.shape) != (x.size(0),):
+        raise ValueError(f'{who}: y must be int64 class indices of shape ({x.size(0)},), got {y.dtype} {tuple(y.shape)}')
+    if weights is not None and tuple(weights.shape) != (x.size(0),):
+        raise ValueError(f'{who}: weights must have shape ({x.size(0)},): one weight per point, got {tuple(weights.shape)}')
+    return n_f
+
+
+def softmax_site_bound(gp, x, y, weights=None, q=None, route=None, n_f=32, seed=0):
+    """fit_q_softmax_'s bound of the data x (N, D), y (N,) int64 -- the n_f-sample estimate of the data term with the noise of
+    `seed`, minus sum_c KL(q(v_t, c) || N(0, I)) -- as a (1,) float64 ON THE AUTOGRAD GRAPH of gp.z and gp.kernel.log_mean.
+    q = (a_t (C, M), H_t (C, M, M) lower) is q(u_t) in whitened coordinates and a CONSTANT; None: whitened_q(gp), with which the
+    value is fit_q_softmax_(n_iters=0, n_f, seed).bound[0].  The frozen tasks are constants whose whitened moments are
+    differentiated through the whitening, as in site_bound.  The gradient is the exact derivative of the sampled value (the
+    comment above).  route 'fused' (up to ops.SITE_MAX_MT inducing points over all tasks; K(z, x) is never stored) or 'composed'
+    (above it or on request: per-op kernels, a tile of N at a time, on an explicit noise tensor of n_f C N floats).
+    MulticlassSoftmax, ep_var_mean=True, exactly RBFKernel or MaternKernel, at most ops.SOFTMAX_SITE_MAX_C classes.  The
+    hyper-prior (kl_hypers) is NOT part of the bound."""
+    check_softmax_differentiable(gp, 'softmax_site_bound')
+    n_f = _check_softmax_data('softmax_site_bound', x, y, weights, n_f)
+    ops.require_device(gp.z, x, y, weights)
+    fr = Frame(gp)
+    route = pick_route(route, fr.Mt, 'softmax_site_bound')
+    a_t, H_t = whitened_q(gp) if q is None else (q[0].detach().double(), q[1].detach().float())
+    w = None if weights is None else weights.detach().to(torch.float32).contiguous()
+    pass_ = ops.softmax_site_bound_diff if route == 'fused' else composed_softmax_site_bound
+    data = pass_(fr.theta, fr.z_all, x.detach().contiguous(), *alpha_Q(fr, a_t, H_t), y.detach().contiguous(), w, n_f, int(seed),
+                 None, fr.nu2)
+    return data.double() - kl_standard(a_t, H_t).sum(-1, keepdim=True)
+
+
+def fit_softmax_sites_(gp, x, y, n_rounds=5, m_steps=20, lr=1e-2, params=None, newton_iters=20, damping=1.0, tol=1e-6, weights=None,
+                       route=None, start='current', n_f=32, seed=0):
+    """fit_sites_ for MulticlassSoftmax: variational EM on the softmax site bound, full batch and in place.  E-step
+    fit_q_softmax_(n_iters=newton_iters, damping, tol, n_f, seed); M-step m_steps Yogi steps on -softmax_site_bound with the same
+    (n_f, seed) -- one deterministic function for the whole fit -- over the subset `params` of {'z': gp.z, 'kernel':
+    gp.kernel.log_mean} (None: both; the softmax has no parameter, 'lik' is a ValueError), with q held at the E-step's whitened
+    (a_t, H_t), then set_whitened_q_.  The undo rule and `stopped` are fit_sites_': the trace never falls.  The E-step's sites
+    are Bonnet / Price estimates, not the stationarity condition of the sampled bound, so the M-step's partial gradient is the
+    re-converged bound's only approximately; the undo rule is what guarantees monotonicity.  The hyper-prior is NOT in the
+    objective.  -> EMFit(bound (n_rounds + 1, 1) float64 on the host, n_rounds, n_newton, stopped)."""
+    check_softmax_differentiable(gp, 'fit_softmax_sites_')
+    params = ('z', 'kernel') if params is None else tuple(params)
+    if 'lik' in params:
+        raise ValueError("fit_softmax_sites_: params names 'lik', but MulticlassSoftmax has no parameter")
+    chosen = choose_params('fit_softmax_sites_', dict(z=gp.z, kernel=gp.kernel.log_mean), params)
+    damping, n_rounds, m_steps = _check_em_args('fit_softmax_sites_', damping, n_rounds, m_steps)
+    n_f = _check_softmax_data('fit_softmax_sites_', x, y, weights, n_f)
+    ops.require_device(gp.z, x, y, weights)
+    e_step = lambda st: fit_q_softmax_(gp, x, y, n_iters=newton_iters, damping=damping, tol=tol, weights=weights, route=route,
+                                       start=st, n_f=n_f, seed=seed)
+    bound_at = lambda q: softmax_site_bound(gp, x, y, weights=weights, q=q, route=route, n_f=n_f, seed=seed)
+    return _em(gp, chosen, e_step, bound_at, start, n_rounds, m_steps, lr)

@@ -66,7 +66,7 @@ def _hand_over_hyper_prior(prev_params):
 _Z_INITS = ('greedy', 'kmeans', 'random')                  # create_clf / create_reg (z_init=)
 _LENGTHSCALE_INITS = ('default', 'median')        # (lengthscale_init=)
 _Q_INITS = ('default', 'optimal', 'collapsed', 'newton', 'em')      # create_reg (q_init=)
-_CLF_Q_INITS = ('default', 'newton', 'em', 'newton_softmax')        # create_clf (q_init=)
+_CLF_Q_INITS = ('default', 'newton', 'em', 'newton_softmax', 'em_softmax')        # create_clf (q_init=)
 
 
 def _check_init_names(who, z_init, lengthscale_init):
@@ -646,6 +646,27 @@ class VARGP(nn.Module):
         return sites.fit_sites_(self, x, y, n_rounds=n_rounds, m_steps=m_steps, lr=lr, params=params, newton_iters=newton_iters,
                                 damping=damping, tol=tol, weights=weights, route=route, start=start)
 
+    def softmax_site_bound(self, x, y, weights=None, q=None, route=None, n_f=32, seed=0):
+        """site_bound's counterpart for MulticlassSoftmax (sites.softmax_site_bound, not in the reference): fit_q_softmax_'s bound
+        of x (N, D), y (N,) int64 -- the n_f-sample estimate with the noise of `seed`, summed over the classes -- as a (1,) float64
+        on the autograd graph of z and kernel.log_mean, with q(u_t) held FIXED in whitened coordinates (q = (a_t, H_t) as
+        sites.whitened_q returns it; None: the model's own q, where the value is fit_q_softmax_(n_iters=0, n_f, seed).bound[0]).
+        The gradient is the exact derivative of the sampled value.  Two fused passes over the data forward and three backward
+        (csrc/softmax_sites.hip: vargp_softmax_site_grads; csrc/sites.hip: vargp_site_transport_bwd; one moment pass); K(z, x) is
+        never stored.  ep_var_mean=True, exactly RBFKernel or MaternKernel.  The hyper-prior is not part of the bound."""
+        return sites.softmax_site_bound(self, x, y, weights=weights, q=q, route=route, n_f=n_f, seed=seed)
+
+    def fit_softmax_sites_(self, x, y, n_rounds=5, m_steps=20, lr=1e-2, params=None, newton_iters=20, damping=1.0, tol=1e-6,
+                           weights=None, route=None, start='current', n_f=32, seed=0):
+        """Variational EM for MulticlassSoftmax (sites.fit_softmax_sites_): n_rounds of fit_q_softmax_ (E-step) and m_steps Yogi
+        steps up softmax_site_bound over the chosen subset of {'z', 'kernel' (kernel.log_mean)} with q held fixed in whitened
+        coordinates (M-step), all on the noise of (n_f, seed), then a last E-step.  An M-step that lowers the bound is undone and
+        ends the fit.  The objective is the bound alone, WITHOUT the hyper-prior.  -> sites.EMFit(bound (n_rounds + 1, 1)
+        float64 on the host, non-decreasing; n_rounds; n_newton; stopped)."""
+        return sites.fit_softmax_sites_(self, x, y, n_rounds=n_rounds, m_steps=m_steps, lr=lr, params=params,
+                                        newton_iters=newton_iters, damping=damping, tol=tol, weights=weights, route=route,
+                                        start=start, n_f=n_f, seed=seed)
+
     def collapsed_bound(self, x, y, weights=None, temper=1.0):
         """The bound fit_q_ returns -- the variational bound of x (N, D), y (N,) or (C, N) at the optimal q(u) of the current
         task -- as a (C,) float64 tensor on the autograd graph of z, kernel.log_mean and likelihood.obs_log_var
@@ -712,12 +733,18 @@ class VARGP(nn.Module):
         newton_iters=newton_iters, start='prior') instead -- variational EM that also moves the inducing points and
         kernel.log_mean up the bound (without the hyper-prior).  'newton_softmax' (likelihood='softmax' only):
         fit_q_softmax_(n_iters=newton_iters, start='prior', n_f=site_samples) -- the same fit for the reference's own
-        likelihood, with site_samples draws per point behind every expectation over the softmax."""
+        likelihood, with site_samples draws per point behind every expectation over the softmax.  'em_softmax'
+        (likelihood='softmax' only, RBF / Matern kernel): fit_softmax_sites_(n_rounds=em_rounds, m_steps=em_steps,
+        newton_iters=newton_iters, start='prior', n_f=site_samples) instead -- variational EM that also moves the inducing points
+        and kernel.log_mean up the sampled bound (without the hyper-prior)."""
         if q_init not in _CLF_Q_INITS:
             raise ValueError(f'create_clf: q_init must be one of {sorted(_CLF_Q_INITS)}, got {q_init!r}')
         if q_init == 'newton_softmax' and likelihood != 'softmax':
             raise ValueError(f"create_clf: q_init='newton_softmax' fits the coupled sites of likelihood='softmax', got "
                              f"{likelihood!r}; the likelihoods with independent outputs have q_init='newton'")
+        if q_init == 'em_softmax' and likelihood != 'softmax':
+            raise ValueError(f"create_clf: q_init='em_softmax' is variational EM on the coupled sites of likelihood='softmax', got "
+                             f"{likelihood!r}; the likelihoods with independent outputs have q_init='em'")
         if q_init in ('newton', 'em') and likelihood != 'bernoulli':
             raise ValueError(f"create_clf: q_init={q_init!r} fits independent Gaussian sites, which likelihood={likelihood!r} does "
                              "not have (its outputs are coupled); use likelihood='bernoulli'")
@@ -780,12 +807,17 @@ class VARGP(nn.Module):
             else:
                 gp.to(dev).fit_sites_(x, y, n_rounds=em_rounds, m_steps=em_steps, newton_iters=newton_iters, start='prior')
             gp.to(home)
-        elif q_init == 'newton_softmax':
-            sites.check_softmax_supported(gp, 'create_clf(q_init="newton_softmax")')
+        elif q_init in ('newton_softmax', 'em_softmax'):
+            check = sites.check_softmax_supported if q_init == 'newton_softmax' else sites.check_softmax_differentiable
+            check(gp, f'create_clf(q_init="{q_init}")')
             home, dev = gp.z.device, torch.device('cuda', torch.cuda.current_device())
             x = dataset[torch.arange(len(dataset))][0].to(device=dev, dtype=torch.float32)
             y = torch.as_tensor(dataset.targets).to(device=dev, dtype=torch.int64)
-            gp.to(dev).fit_q_softmax_(x, y, n_iters=newton_iters, start='prior', n_f=site_samples)
+            if q_init == 'newton_softmax':
+                gp.to(dev).fit_q_softmax_(x, y, n_iters=newton_iters, start='prior', n_f=site_samples)
+            else:
+                gp.to(dev).fit_softmax_sites_(x, y, n_rounds=em_rounds, m_steps=em_steps, newton_iters=newton_iters, start='prior',
+                                              n_f=site_samples)
             gp.to(home)
         return gp
 
