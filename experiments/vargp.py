@@ -28,7 +28,8 @@ from torch.utils.data import ConcatDataset, DataLoader  # noqa: E402
 import vargp_amd  # noqa: E402
 from vargp_amd.datasets import PermutedMNIST, SplitMNIST, ToyDataset  # noqa: E402
 from vargp_amd.train import ElboTrainer  # noqa: E402
-from vargp_amd.train_utils import DeviceBatches, EarlyStopper, compute_accuracy, compute_lpd, compute_uncertainty, set_seeds  # noqa: E402
+from vargp_amd.train_utils import (DeviceBatches, EarlyStopper, compute_accuracy, compute_loo, compute_lpd,  # noqa: E402
+                                   compute_uncertainty, set_seeds)
 from vargp_amd.vargp import VARGP  # noqa: E402
 
 
@@ -54,7 +55,7 @@ def train(task_id, train_set, val_set, test_set, ep_var_mean=True, map_est_hyper
           retrain=False, eval_shared_hypers=False, dataloader=False, kernel='rbf', native_kernel=False,
           likelihood='softmax', link='probit', lpd=False, z_init='random', kmeans_iters=20, lengthscale_init='default',
           uncertainty=False, greedy_candidates=4096, q_init='default', newton_iters=20, em_rounds=5, em_steps=20,
-          site_samples=32):
+          site_samples=32, loo=False):
     if retrain:      # the variant of experiments/vargp_retrain.py:14-19 (earlier tasks' inducing parameters re-optimised)
         from vargp_amd.vargp_retrain import VARGPRetrain
         assert kernel == 'rbf', '--retrain builds its model with the RBF kernel'
@@ -169,6 +170,14 @@ def train(task_id, train_set, val_set, test_set, ep_var_mean=True, map_est_hyper
             if stopper.is_done():
                 break
 
+    if loo:      # --loo: mean leave-one-out log predictive density of THIS task's training set under the trained q(u) (VARGP.loo)
+        kw = dict(n_f=site_samples) if likelihood == 'softmax' else {}
+        loo_lpd, n_unstable = compute_loo(train_set, gp, device=device, **kw)
+        print(f'task {task_id}: mean LOO lpd {loo_lpd:.4f} over {N - n_unstable} of {N} training points ({n_unstable} unstable)')
+        if logger is not None:
+            logger.add_scalar(f'task{task_id}/train/loo_lpd', loo_lpd, global_step=n_steps)
+            logger.add_scalar(f'task{task_id}/train/loo_unstable', n_unstable, global_step=n_steps)
+
     info = stopper.info() or dict(state_dict=gp.state_dict(), acc_summary={}, step=epochs)
     if logger is not None and n_steps:
         # end-to-end training rate of this task: steps / wall time of the epochs' training loops (evaluation excluded)
@@ -207,7 +216,7 @@ def toy(args):
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
                    lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init, q_init=args.q_init,
                    newton_iters=args.newton_iters, em_rounds=args.em_rounds, em_steps=args.em_steps, site_samples=args.site_samples,
-                   uncertainty=args.uncertainty, greedy_candidates=args.greedy_candidates)
+                   uncertainty=args.uncertainty, greedy_candidates=args.greedy_candidates, loo=args.loo)
         prev_params.append(sd)
     logger.close()
 
@@ -236,7 +245,7 @@ def split_mnist(args):
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
                    lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init, q_init=args.q_init,
                    newton_iters=args.newton_iters, em_rounds=args.em_rounds, em_steps=args.em_steps, site_samples=args.site_samples,
-                   uncertainty=args.uncertainty, greedy_candidates=args.greedy_candidates)
+                   uncertainty=args.uncertainty, greedy_candidates=args.greedy_candidates, loo=args.loo)
         prev_params.append(sd)
     logger.close()
 
@@ -268,7 +277,7 @@ def permuted_mnist(args):
                    eval_shared_hypers=args.eval_shared_hypers, n_var_samples=args.n_var_samples, dataloader=args.dataloader,
                    lpd=args.lpd, z_init=args.z_init, kmeans_iters=args.kmeans_iters, lengthscale_init=args.lengthscale_init, q_init=args.q_init,
                    newton_iters=args.newton_iters, em_rounds=args.em_rounds, em_steps=args.em_steps, site_samples=args.site_samples,
-                   uncertainty=args.uncertainty, greedy_candidates=args.greedy_candidates)
+                   uncertainty=args.uncertainty, greedy_candidates=args.greedy_candidates, loo=args.loo)
         prev_params.append(sd)
     logger.close()
 
@@ -344,6 +353,12 @@ def parse_args(argv=None):
                         help='also log test/entropy and test/mi at every evaluation: the mean predictive entropy per point of '
                              'the test set of the tasks seen so far and its epistemic part, the mutual information of the '
                              'label and the model (VARGP.uncertainty; nats)')
+        sp.add_argument('--loo', action='store_true',
+                        help="after each task's training, print (and log as train/loo_lpd) the mean leave-one-out log predictive "
+                             "density of the task's training set under the trained q(u) (VARGP.loo: the cavity of the Gaussian "
+                             'sites at theta = log_mean, no refits; exact only at a fixed point of the site iteration, so the '
+                             'points whose cavity is improper after minibatch training are counted as unstable and left out '
+                             'of the mean); needs --ep_var_mean true and no --retrain')
         if name == 'toy':
             sp.add_argument('--retrain', action='store_true',
                             help='VARGPRetrain (reference: experiments/vargp_retrain.py toy): re-optimise the earlier '
@@ -354,6 +369,8 @@ def parse_args(argv=None):
     if args.native_kernel and (args.kernel == 'rbf' or args.dkl or getattr(args, 'retrain', False)):
         ap.error('--native_kernel selects the native route of a Matern kernel: it needs --kernel matern12 / matern32 / matern52 '
                  'and neither --dkl nor --retrain')
+    if args.loo and (not args.ep_var_mean or getattr(args, 'retrain', False)):
+        ap.error('--loo reads q(u_t) as prior x Gaussian sites: it needs --ep_var_mean true and no --retrain')
     if args.graph and args.likelihood == 'bernoulli':
         ap.error('--graph with --likelihood bernoulli: the epoch graphs (capture_epoch / step_graph_gather) run the softmax '
                  'likelihood inside the native program and refuse a Bernoulli model; train it without --graph')

@@ -407,6 +407,33 @@ int vargp_gram_moments_v(const float* theta, const float* Z, const float* X, con
                          float* sums, int G, int Mt, int N, int D, int nu2, void* ws, size_t ws_bytes, vargp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The leave-one-out cavity of the Gaussian sites (vargp_amd/loo.py: VARGP.loo).  Not in the reference.  vargp_site_moments'
+ * kernel with one more operand, V [G, Mv, Mt] (1 <= Mv <= Mt; for a whitened posterior V = H_t^T T[t, :], so that
+ *   s[g, n] = |V[g] k_n|^2
+ * is the variance that the new block of q(v) gives the site's direction T k_n).  Per 64 columns of K resident in LDS: alpha . k_n
+ * and k_n^T Q k_n as there; then, in the registers the accumulators of Q K had, V K on the f32 MFMA, a 64-row panel of V at a
+ * time, reduced to its column norms.  K(Z, X) and V K are never stored.
+ * kind < 0, the marginals form: writes mu, var, s [G, N] and nothing else; y, w, the Student-t arguments, the other outputs and
+ * the workspace are ignored and may be NULL.  One launch.
+ * kind = VARGP_SITE_*, the site form: the likelihood's (dmu, dvar) at (mu_n, var_n) in the same launch, with the operands and the
+ * conventions of vargp_site_moments, and with r = 1 - lam2 s, in fp64 from the fp32 moments and rounded once:
+ *   lam2 = w max(-2 dvar, 0),   lam1 = w dmu + lam2 mu
+ *   mu_c = (mu - s lam1) / r  (evaluated as mu - s w dmu / r),   var_c = var + lam2 s^2 / r
+ * all [G, N], beside mu, var and s.  A point with r <= 0 or a non-finite mu_c or var_c is UNSTABLE: mu_c = var_c = NaN, and
+ * n_unstable[g] (int64 [G]) counts them -- per-chunk partials in the workspace, added in ascending chunk order by a second launch.
+ * A point of weight 0 is not evaluated: lam1 = lam2 = 0 and (mu_c, var_c) are written as exactly (mu, var).
+ * The chunking is vargp_site_moments' (vargp_site_cavity_chunks); no atomics: two calls on the same input are bitwise equal.
+ * Workspace (site form): chunks x G x 8 bytes and padding, 8-byte aligned.  VARGP_EINVAL before any launch as
+ * vargp_site_moments, and for Mv < 1 or Mv > Mt.
+ */
+size_t vargp_site_cavity_workspace_bytes(int G, int Mt, int N, int D);
+int vargp_site_cavity_chunks(int G, int Mt, int N, int D);
+int vargp_site_cavity(const float* theta, const float* Z, const float* X, const float* alpha, const float* Q, const float* V,
+                      const float* y, int64_t ldy, const float* w, int kind, const float* log_scale, float df, float lognorm,
+                      float* mu, float* var, float* s, float* mu_c, float* var_c, float* lam1, float* lam2, long long* n_unstable,
+                      int G, int Mt, int Mv, int N, int D, int nu2, void* ws, size_t ws_bytes, vargp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The backward of the softmax site bound (vargp_amd/sites.py: softmax_site_bound, fit_softmax_sites_; ops.softmax_site_bound_diff).
  * Not in the reference.  The value is vargp_softmax_sites' sums[0] at the marginals of vargp_site_marginals; its gradient is these
  * two entries and one vargp_gram_moments call.  Both check their arguments on the host before any launch (VARGP_EINVAL,

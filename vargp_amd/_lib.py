@@ -121,6 +121,10 @@ _SIGNATURES = {
     'vargp_site_bound_bwd': (c_int, [_P] * 6 + [c_int64, _P, c_int, _P, c_float, c_float] + [_P] * 6 + [c_int] * 5
                              + [_P, c_size_t, _P]),
     'vargp_site_marginals': (c_int, [_P] * 7 + [c_int] * 5 + [_P]),
+    'vargp_site_cavity_workspace_bytes': (c_size_t, [c_int] * 4),
+    'vargp_site_cavity_chunks': (c_int, [c_int] * 4),
+    'vargp_site_cavity': (c_int, [_P] * 7 + [c_int64, _P, c_int, _P, c_float, c_float] + [_P] * 8 + [c_int] * 6
+                          + [_P, c_size_t, _P]),
     'vargp_softmax_sites_workspace_bytes': (c_size_t, [c_int, c_int]),
     'vargp_softmax_sites': (c_int, [_P] * 5 + [ctypes.c_uint64, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
     'vargp_softmax_site_noise': (c_int, [ctypes.c_uint64, _P, c_int, c_int, c_int, _P]),

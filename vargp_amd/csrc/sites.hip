@@ -20,7 +20,8 @@
 // input are bitwise equal.  The chunking depends on the shapes alone (site_plan).
 // The same kernel with LIK = SiteMarginals is vargp_site_marginals: the frame up to mu_n and var_n, which it writes out [G][N]; no
 // likelihood wave, no accumulators of c, no partials and no reduce launch (the coupled softmax sites of softmax_sites.hip need the
-// marginals of ALL outputs of a point at once).
+// marginals of ALL outputs of a point at once).  With LIK = Cavity<.> it is vargp_site_cavity: one more MFMA product per step, V K,
+// in the registers of Q K, and the leave-one-out cavity of every point's site (the comment at Cavity).
 #include "dataset_pass.h"
 #include "lik.h"
 
@@ -38,6 +39,8 @@ static constexpr size_t site_lds_floats(int nt) {
          4 * kMoT;
 }
 static_assert(site_lds_floats(kSiMaxNt) * sizeof(float) <= 160 * 1024, "the K block of kSiMaxMt rows must fit the LDS");
+// (the cavity's V K adds nothing to it: a 64 x 64 tile of V is staged where the tile of Q was, its norms leave through qred)
+static_assert(kMoT * kMoLD >= kMoT * kMoT && 4 * kMoT >= 4 * 32, "a tile of V fits the tile of Q, its column norms the pad of k^T Q k");
 
 struct SitePlan {
   int nt;                    // 64-row panels
@@ -69,6 +72,36 @@ struct SiteMarginals {
 };
 template <class LIK> constexpr bool kSiteMarginals = false;
 template <> constexpr bool kSiteMarginals<SiteMarginals> = true;
+
+// A likelihood (or SiteMarginals) with the leave-one-out cavity behind it (vargp_site_cavity; vargp_amd/loo.py).  One more operand,
+// V [G][Mv][Mt]: after the accumulators of Q K have been reduced to var, the SAME registers and the same staging tile take V K,
+// panel of 64 rows by panel, and leave only its column norms s_n = |V k_n|^2 -- the share of var_n that the new block of q owns.
+// With the site (lam1, lam2) of the point and r = 1 - lam2 s, in fp64 from the fp32 moments and rounded once:
+//   mu_c = mu - s w dmu / r  (= (mu - s lam1) / r),   var_c = var + lam2 s^2 / r
+// r <= 0 or a non-finite result: mu_c = var_c = NaN and the point is counted (per-chunk partials, added by cavity_reduce_kernel).
+// A point of weight 0 has lam = 0 and its cavity is written as exactly (mu, var).  No accumulators of c, no lam1 K.
+template <class LIK>
+struct Cavity {
+  using real = typename LIK::real;
+  using Lik = LIK;
+  struct Args {
+    typename LIK::Args lik;
+    const float* V;
+    float *mu, *var, *s, *mu_c, *var_c, *lam1, *lam2;
+    double* pu;              // partials of the unstable points [G][nch]
+    int Mv;
+  };
+};
+template <class LIK> struct SiteInner {
+  using type = LIK;
+  static __device__ __forceinline__ const typename LIK::Args& args(const typename LIK::Args& la) { return la; }
+};
+template <class LIK> struct SiteInner<Cavity<LIK>> {
+  using type = LIK;
+  static __device__ __forceinline__ const typename LIK::Args& args(const typename Cavity<LIK>::Args& la) { return la.lik; }
+};
+template <class LIK> constexpr bool kSiteCavity = false;
+template <class LIK> constexpr bool kSiteCavity<Cavity<LIK>> = true;
 
 // Not a likelihood either: site_bwd_kernel with GIVEN per-point seeds (vargp_site_transport_bwd).  Its "element" loads (dmu, dvar)
 // = (gm, gv) [G][N] of a point from memory; there are no targets, weights or parameters, and a point whose two seeds are both 0 is
@@ -106,9 +139,10 @@ struct SiteArgs {
 // grid (nch, G)
 template <class LIK, class EPI, bool DIRECT>
 __global__ __launch_bounds__(256) void site_kernel(const SiteArgs a, const typename LIK::Args la) {
-  using real = typename LIK::real;
+  using L = typename SiteInner<LIK>::type;            // the likelihood itself, also behind Cavity<>
+  using real = typename L::real;
   constexpr int T = kMoT, LD = kMoLD, BK = kMoBK;
-  constexpr bool MARG = kSiteMarginals<LIK>;
+  constexpr bool MARG = kSiteMarginals<L>, CAV = kSiteCavity<LIK>;
   extern __shared__ __attribute__((aligned(16))) float si_lds[];
   const int Mt = a.Mt, D = a.D, nt = a.p.nt, MtP = nt * T, LDK = MtP + 1;
   float* Ks = si_lds;                  // the K block: [n][m], m over all nt panels
@@ -134,12 +168,13 @@ __global__ __launch_bounds__(256) void site_kernel(const SiteArgs a, const typen
   const float* __restrict__ Qg = a.Q + g * (int64_t)Mt * Mt;
   const float* __restrict__ wg = a.w ? a.w + g * (int64_t)a.N : nullptr;
   const int Dl = D | 1;
-  const typename LIK::Cls cls = LIK::cls(la, (int)g);
+  const typename L::Args& lla = SiteInner<LIK>::args(la);
+  const typename L::Cls cls = L::cls(lla, (int)g);
 
   float cacc[kSiMaxNt];
 #pragma unroll
   for (int p = 0; p < kSiMaxNt; ++p) cacc[p] = 0.f;
-  double s_ell = 0.0, s_l2 = 0.0, s_cl = 0.0, s_w = 0.0;
+  double s_ell = 0.0, s_l2 = 0.0, s_cl = 0.0, s_w = 0.0, s_un = 0.0;
 
   for (int e = tid; e < MtP; e += 256) al[e] = e < Mt ? a.alpha[g * Mt + e] : 0.f;
   if constexpr (DIRECT) {
@@ -253,6 +288,71 @@ __global__ __launch_bounds__(256) void site_kernel(const SiteArgs a, const typen
     if (h == 0) qred[wave * 32 + l31] = qv;
     __syncthreads();
 
+    if constexpr (CAV) {
+      // ---- s_n = |V k_n|^2: the wave of the points below takes its shares of k^T Q k out of qred first; then (V K)_i = sum_j
+      // V_ij K_j in the registers (Q K)_i had (A = V_ij [row][k], read along its rows: coalesced; B = K_j [k][n]), squared and
+      // summed over the rows, and its shares go where those were
+      float quad = 0.f;
+      if (tid < T) quad = qred[(tid >> 5) * 32 + (tid & 31)] + qred[((tid >> 5) + 2) * 32 + (tid & 31)];
+      const float* __restrict__ Vg = la.V + g * (int64_t)la.Mv * Mt;
+      float sv = 0.f;
+      for (int i0 = 0; i0 < la.Mv; i0 += T) {
+        si_f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int tj = 0; tj < nt; ++tj) {
+          const int j0 = tj * T;
+          for (int e = tid; e < T * T; e += 256) {
+            const int r = e >> 6, k = e & 63;
+            Ss[k * LD + r] = (i0 + r < la.Mv && j0 + k < Mt) ? Vg[(int64_t)(i0 + r) * Mt + j0 + k] : 0.f;
+          }
+          __syncthreads();
+          acc = sk_tile(acc, Ss, Ks + j0, LDK, wr + l31, wc + l31, h);
+          __syncthreads();
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sv = fmaf(acc[r], acc[r], sv);
+      }
+      sv += __shfl_xor(sv, 32, 64);
+      if (h == 0) qred[wave * 32 + l31] = sv;
+      __syncthreads();
+
+      // ---- the points of the step: marginals, site and cavity; one wave, a point per lane
+      if (tid < T && n0 + tid < cend) {
+        const int64_t at = g * (int64_t)a.N + n0 + tid;
+        const float mu = wave4_sum(cred, tid);
+        const float var = fmaxf(g2 - quad, 0.f);
+        const float s = qred[(tid >> 5) * 32 + (tid & 31)] + qred[((tid >> 5) + 2) * 32 + (tid & 31)];
+        la.mu[at] = mu;
+        la.var[at] = var;
+        la.s[at] = s;
+        if constexpr (!MARG) {
+          const float wv = wg ? wg[n0 + tid] : 1.f;
+          float l1 = 0.f, l2 = 0.f, mc = mu, vc = var;
+          if (wv != 0.f) {
+            real dmu = 0, dvar = 0, dpar = 0;
+            L::template element<true>(cls, (real)mu, (real)var, L::template target<real>(lla, (int)g, (size_t)(n0 + tid)), dmu, dvar,
+                                      dpar);
+            l2 = dvar > (real)0 ? 0.f : wv * (float)((real)-2 * dvar);
+            l1 = fmaf(l2, mu, wv * (float)dmu);
+            const double sd = (double)s, r = 1.0 - (double)l2 * sd;
+            mc = (float)((double)mu - sd * ((double)wv * (double)dmu) / r);
+            vc = (float)((double)var + (double)l2 * sd * sd / r);
+            if (!(r > 0.0) || !isfinite(mc) || !isfinite(vc)) {
+              mc = vc = __builtin_nanf("");
+              s_un += 1.0;
+            }
+          }
+          la.mu_c[at] = mc;
+          la.var_c[at] = vc;
+          la.lam1[at] = l1;
+          la.lam2[at] = l2;
+        }
+      }
+      __syncthreads();
+      continue;
+    }
+
     // ---- the likelihood of the step's points: one wave, a point per lane
     if (tid < T) {
       const int64_t n = n0 + tid;
@@ -262,16 +362,16 @@ __global__ __launch_bounds__(256) void site_kernel(const SiteArgs a, const typen
       float l1 = 0.f;
       if constexpr (MARG) {
         if (n < cend) {
-          la.mu[g * (int64_t)a.N + n] = mu;
-          la.var[g * (int64_t)a.N + n] = var;
+          lla.mu[g * (int64_t)a.N + n] = mu;
+          lla.var[g * (int64_t)a.N + n] = var;
         }
       } else if (n < cend) {
         const float wv = wg ? wg[n] : 1.f;
         float l2 = 0.f;
         if (wv != 0.f) {
           real dmu = 0, dvar = 0, dpar = 0;
-          const real ell = LIK::template element<true>(cls, (real)mu, (real)var, LIK::template target<real>(la, (int)g, (size_t)n),
-                                                       dmu, dvar, dpar);
+          const real ell = L::template element<true>(cls, (real)mu, (real)var, L::template target<real>(lla, (int)g, (size_t)n),
+                                                     dmu, dvar, dpar);
           const bool clamp = dvar > (real)0;
           l2 = clamp ? 0.f : wv * (float)((real)-2 * dvar);
           l1 = fmaf(l2, mu, wv * (float)dmu);
@@ -302,6 +402,13 @@ __global__ __launch_bounds__(256) void site_kernel(const SiteArgs a, const typen
   if constexpr (MARG) return;
 
   const int64_t part = g * a.p.ch.nch + chunk;
+  if constexpr (CAV) {
+    if (wave == 0) {
+      s_un = wave_sum(s_un);
+      if (lane == 0) la.pu[part] = s_un;
+    }
+    return;
+  }
 #pragma unroll
   for (int p = 0; p < kSiMaxNt; ++p) {
     if (p < nt) {
@@ -347,10 +454,20 @@ __global__ __launch_bounds__(256) void site_reduce_kernel(const SiteArgs a) {
 template <class LIK, class EPI, bool DIRECT>
 static int site_launch_form(const SiteArgs& a, const typename LIK::Args& la, hipStream_t st) {
   constexpr auto kernel = site_kernel<LIK, EPI, DIRECT>;
-  if (int rc = reserve_dynamic_lds<kernel>(site_lds_floats(kSiMaxNt) * sizeof(float), kSiteMarginals<LIK> ? "site_marginals" : "site_moments"))
+  if (int rc = reserve_dynamic_lds<kernel>(site_lds_floats(kSiMaxNt) * sizeof(float),
+                                           kSiteCavity<LIK> ? "site_cavity" : kSiteMarginals<LIK> ? "site_marginals" : "site_moments"))
     return rc;
   hipLaunchKernelGGL(kernel, dim3(a.p.ch.nch, a.G), dim3(256), site_lds_floats(a.p.nt) * sizeof(float), st, a, la);
   return VARGP_OK;
+}
+
+// The chunks' counts of unstable points in ascending chunk order.  grid (cdiv(G, 256)): an output per thread
+__global__ __launch_bounds__(256) void cavity_reduce_kernel(const double* pu, long long* n_unstable, int G, int nch) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= G) return;
+  double s = 0.0;
+  for (int q = 0; q < nch; ++q) s += pu[(int64_t)g * nch + q];
+  n_unstable[g] = (long long)s;
 }
 
 template <class LIK>
@@ -962,4 +1079,48 @@ extern "C" int vargp_site_marginals(const float* theta, const float* Z, const fl
   ProfScope whole("site_marginals", st);
   if (int rc = site_launch<SiteMarginals>(a, SiteMarginals::Args{mu, var}, nu2, st)) return rc;
   return check_launch("site_marginals");
+}
+
+extern "C" int vargp_site_cavity_chunks(int G, int Mt, int N, int D) { return vargp_site_moments_chunks(G, Mt, N, D); }
+
+extern "C" size_t vargp_site_cavity_workspace_bytes(int G, int Mt, int N, int D) {
+  if (G <= 0 || Mt <= 0 || N <= 0 || D <= 0) return 0;
+  return (size_t)round_up((int64_t)G * site_plan(nullptr, G, Mt, N).ch.nch * (int64_t)sizeof(double), 256) + 256;
+}
+
+extern "C" int vargp_site_cavity(const float* theta, const float* Z, const float* X, const float* alpha, const float* Q,
+                                 const float* V, const float* y, int64_t ldy, const float* w, int kind, const float* log_scale,
+                                 float df, float lognorm, float* mu, float* var, float* s, float* mu_c, float* var_c, float* lam1,
+                                 float* lam2, long long* n_unstable, int G, int Mt, int Mv, int N, int D, int nu2, void* ws,
+                                 size_t ws_bytes, vargp_stream_t stream) {
+  const bool marg = kind < 0;
+  // (the marginals form has no targets, no likelihood and no partials: the checks of the site form with a shared row of targets
+  // and a kind without parameters)
+  if (int rc = site_check_args("site_cavity",
+                               theta && Z && X && alpha && Q && V && mu && var && s &&
+                                   (marg || (y && mu_c && var_c && lam1 && lam2 && n_unstable && ws)),
+                               marg ? 0 : ldy, marg ? VARGP_SITE_BERNOULLI_PROBIT : kind, log_scale && df > 0.f, "log_scale and df > 0", G,
+                               Mt, N, D, nu2, marg ? nullptr : ws, marg ? 0 : ws_bytes,
+                               marg ? 0 : vargp_site_cavity_workspace_bytes(G, Mt, N, D)))
+    return rc;
+  VARGP_REQUIRE(Mv > 0 && Mv <= Mt, "site_cavity: Mv = %d (1 to Mt = %d rows of V)", Mv, Mt);
+  SiteArgs a{};
+  a.theta = theta; a.Z = Z; a.X = X; a.alpha = alpha; a.Q = Q; a.w = w;
+  a.p = site_plan(nullptr, G, Mt, N);          // the chunking alone: the partials are the counts at ws
+  a.G = G; a.Mt = Mt; a.N = N; a.D = D;
+  hipStream_t st = as_stream(stream);
+  ProfScope whole("site_cavity", st);
+  if (marg) {
+    using C = Cavity<SiteMarginals>;
+    if (int rc = site_launch<C>(a, C::Args{{}, V, mu, var, s, nullptr, nullptr, nullptr, nullptr, nullptr, Mv}, nu2, st)) return rc;
+    return check_launch("site_cavity");
+  }
+  double* pu = reinterpret_cast<double*>(ws);
+  const int rc = with_site_lik(kind, y, ldy, log_scale, df, lognorm, [&](auto lik, const auto& la) {
+    using C = Cavity<decltype(lik)>;
+    return site_launch<C>(a, typename C::Args{la, V, mu, var, s, mu_c, var_c, lam1, lam2, pu, Mv}, nu2, st);
+  });
+  if (rc != VARGP_OK) return rc;
+  hipLaunchKernelGGL(cavity_reduce_kernel, dim3(cdiv(G, 256)), dim3(256), 0, st, pu, n_unstable, G, a.p.ch.nch);
+  return check_launch("site_cavity");
 }

@@ -2,6 +2,7 @@
 libvargp_hip.so (hand-written HIP), torch only owns the memory and the stream.
 """
 import math
+from collections import namedtuple
 
 import torch
 from torch.autograd import Function
@@ -835,6 +836,57 @@ def site_marginals(theta, Z, X, alpha, Q, nu2=0):
     check(lib().vargp_site_marginals(ptr(theta), ptr(Z), ptr(X), ptr(alpha), ptr(Q), ptr(mu), ptr(var), G, Mt, N, D, int(nu2),
                                      stream_ptr()), 'vargp_site_marginals')
     return mu, var
+
+
+# The leave-one-out cavity of the Gaussian sites (csrc/sites.hip: vargp_site_cavity -- not in the reference).  No autograd.
+SiteCavity = namedtuple('SiteCavity', 'mu_c var_c lam1 lam2 n_unstable mu var s')
+SiteCavity.__doc__ = """mu_c, var_c (G, N): the cavity moments, NaN at an unstable point; lam1, lam2 (G, N): the sites; n_unstable
+(G,) int64; mu, var, s (G, N): the marginals of q(f) and s_n = |V k_n|^2, as the same launch wrote them."""
+
+
+def _cavity_V(V, G, Mt):
+    V = V.detach().contiguous()
+    assert V.dim() == 3 and V.shape[0] == G and V.shape[2] == Mt and 1 <= V.shape[1] <= Mt and V.dtype == torch.float32, \
+        (V.shape, V.dtype, G, Mt)
+    return V
+
+
+def site_cavity_chunks(G, Mt, N, D):
+    """The number of chunks ops.site_cavity cuts N points into for this shape: site_moments'."""
+    return int(lib().vargp_site_cavity_chunks(int(G), int(Mt), int(N), int(D)))
+
+
+def site_marginals_s(theta, Z, X, alpha, Q, V, nu2=0):
+    """site_marginals, and the share of the variance that one block of q owns: V (G, Mv, Mt), Mv <= Mt -> (mu (G, N), var (G, N),
+    s (G, N) = |V k_n|^2).  The marginals form of vargp_site_cavity: V K runs on the MFMA in the registers of Q K and only its
+    column norms leave the kernel; no workspace, bitwise reproducible."""
+    require_device(theta, Z, X, alpha, Q, V)
+    theta, Z, X, alpha, Q, (G, Mt, N, D) = _data_operands(theta, Z, X, alpha, Q)
+    V = _cavity_V(V, G, Mt)
+    mu, var, s = (torch.empty(G, N, dtype=torch.float32, device=X.device) for _ in range(3))
+    check(lib().vargp_site_cavity(ptr(theta), ptr(Z), ptr(X), ptr(alpha), ptr(Q), ptr(V), None, 0, None, -1, None, 0.0, 0.0,
+                                  ptr(mu), ptr(var), ptr(s), None, None, None, None, None, G, Mt, V.shape[1], N, D, int(nu2),
+                                  None, 0, stream_ptr()), 'vargp_site_cavity')
+    return mu, var, s
+
+
+def site_cavity(theta, Z, X, alpha, Q, V, y, w, kind, extra=(), nu2=0):
+    """The Gaussian sites of site_moments at q(f_n) = N(alpha . k_n, max(gamma^2 - k_n^T Q k_n, 0)) and the cavity each leaves when it
+    is divided out of the block of q that V (G, Mv, Mt) describes; the other operands as site_moments takes them.  With s_n =
+    |V k_n|^2 and r_n = 1 - lam2_n s_n: mu_c = (mu - s lam1) / r, var_c = var + lam2 s^2 / r, in fp64 from the fp32 moments.  A
+    point with r <= 0 or a non-finite result is unstable: NaN, and counted; a point of weight 0 has lam = 0 and the cavity
+    (mu, var) exactly.  -> SiteCavity(mu_c, var_c, lam1, lam2, n_unstable (G,) int64, mu, var, s).  One fused launch plus the
+    reduce of the counts; K(Z, X) and V K are never stored; bitwise reproducible."""
+    require_device(theta, Z, X, alpha, Q, V, y, w)
+    theta, Z, X, alpha, Q, yt, ldy, w, code, log_scale, df, lognorm, (G, Mt, N, D) = _site_operands(theta, Z, X, alpha, Q, y, w, kind, extra)
+    V = _cavity_V(V, G, Mt)
+    mu, var, s, mu_c, var_c, lam1, lam2 = (torch.empty(G, N, dtype=torch.float32, device=X.device) for _ in range(7))
+    n_unstable = torch.empty(G, dtype=torch.int64, device=X.device)
+    ws = scratch(lib().vargp_site_cavity_workspace_bytes(G, Mt, N, D), X.device)
+    check(lib().vargp_site_cavity(ptr(theta), ptr(Z), ptr(X), ptr(alpha), ptr(Q), ptr(V), ptr(yt), ldy, ptr(w), code, ptr(log_scale),
+                                  df, lognorm, ptr(mu), ptr(var), ptr(s), ptr(mu_c), ptr(var_c), ptr(lam1), ptr(lam2), ptr(n_unstable),
+                                  G, Mt, V.shape[1], N, D, int(nu2), ptr(ws), ws.numel() * 4, stream_ptr()), 'vargp_site_cavity')
+    return SiteCavity(mu_c, var_c, lam1, lam2, n_unstable, mu, var, s)
 
 
 def _seed64(seed):

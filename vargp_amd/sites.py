@@ -285,6 +285,15 @@ def _check_loop_args(who, damping, n_iters, start):
     return damping, n_iters
 
 
+def precision(fr, L_u):
+    """P = (H_t H_t^T)^-1 (C, M, M) float64, symmetrised, of the model's q(u_t) = N(., L_u L_u^T) in whitened coordinates:
+    H_t^-1 = L_u^-1 L_tt."""
+    T_u = ops.chol_inv(ops.bgemm(L_u, L_u.mT), 0.0)[1]
+    H_inv = ops.bgemm(T_u, fr.L_tt, triA=LOWER, triB=LOWER).tril()
+    P = ops.bgemm(H_inv.mT, H_inv).double()
+    return 0.5 * (P + P.mT)
+
+
 def _fit(gp, pr, n_iters, damping, tol, start):
     """The iteration of the module docstring on the problem `pr` (its passes over the data, its form of the bound), from `start`
     with backtracking; writes the last accepted q(u_t) into gp.  Under no_grad.  -> SiteFit"""
@@ -296,10 +305,7 @@ def _fit(gp, pr, n_iters, damping, tol, start):
     else:
         # the model's q(u_t) in whitened coordinates and natural parameters: H_t^-1 = L_u^-1 L_tt
         a_t, H_t, L_u = read_q(gp, pr.fr.T_tt)
-        T_u = ops.chol_inv(ops.bgemm(L_u, L_u.mT), 0.0)[1]
-        H_inv = ops.bgemm(T_u, pr.fr.L_tt, triA=LOWER, triB=LOWER).tril()
-        P = ops.bgemm(H_inv.mT, H_inv).double()
-        P = 0.5 * (P + P.mT)
+        P = precision(pr.fr, L_u)
         h = mv(P, a_t)
         kl = kl_standard(a_t, H_t)
 

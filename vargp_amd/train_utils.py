@@ -117,6 +117,18 @@ def compute_lpd(dataset, gp, batch_size=512, device=None, shared_hypers=False):
     return total / len(dataset)
 
 
+def compute_loo(dataset, gp, device=None, **kwargs):
+    """(mean leave-one-out log predictive density per point, number of unstable points) of gp.loo(x, y, **kwargs) over the WHOLE
+    training set `dataset` of the current task (not in the reference): compute_lpd's number without held-out data, at theta =
+    kernel.log_mean and under the fixed-point assumption of VARGP.loo.  The mean runs over the stable points (NaN if there is
+    none); the unstable ones (loo.py) are counted, not hidden.  dataset[i] -> (x, y) as compute_lpd takes it.  ONE host sync."""
+    x, y = materialize(dataset, device)
+    res = gp.loo(x, y.t().contiguous() if y.dim() == 2 else y, **kwargs)
+    ok = torch.isfinite(res.lpd)
+    total, n_ok = torch.stack([torch.where(ok, res.lpd, torch.zeros_like(res.lpd)).double().sum(), ok.double().sum()]).tolist()
+    return (total / n_ok if n_ok else float('nan')), len(dataset) - int(n_ok)
+
+
 def compute_uncertainty(dataset, gp, batch_size=512, device=None, shared_hypers=False):
     """(mean total, mean aleatoric, mean epistemic) predictive entropy per point in nats, the means of gp.uncertainty(x) over
     `dataset` (not in the reference), alongside compute_lpd: how unsure the model is about the set, and how much of that is

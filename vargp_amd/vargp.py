@@ -19,7 +19,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import collapsed, fused, gp_utils, init, noise, ops, sites
+from . import collapsed, fused, gp_utils, init, loo, noise, ops, sites
 from .gp_utils import vec2tril, mat2trilvec, cholesky, rev_cholesky, gp_cond, block_joint, linear_marginal_diag
 from .kernels import RBFKernel, DeepRBFKernel, MaternKernel, native_code
 from .likelihoods import (BernoulliLikelihood, GaussianLikelihood, MulticlassSoftmax, PoissonLikelihood, StudentTLikelihood,
@@ -666,6 +666,23 @@ class VARGP(nn.Module):
         return sites.fit_softmax_sites_(self, x, y, n_rounds=n_rounds, m_steps=m_steps, lr=lr, params=params,
                                         newton_iters=newton_iters, damping=damping, tol=tol, weights=weights, route=route,
                                         start=start, n_f=n_f, seed=seed)
+
+    def loo(self, x, y, weights=None, route=None, check=False, n_f=32, seed=0, tile=sites.COMPOSED_TILE):
+        """Leave-one-out log predictive density of the current task's TRAINING data x (N, D), y (as this model's q(u) fit takes
+        it) per point, without refits and without held-out data (loo.loo, not in the reference): q(v_t) is read as "prior x one
+        Gaussian site per (output, point)", the site of each point is divided out in closed form (the EP / CVI cavity) and the
+        likelihood's own log predictive density is taken at the cavity moments -- the units of log_prob.  ASSUMES that q(u_t) is
+        a fixed point of the site iteration: exact LOO of the sparse model after fit_q_ (Gaussian), the standard approximation
+        after fit_q_newton_ / fit_q_softmax_; after minibatch training the cavity of a point can be improper (r_n <= 0): such
+        points come back NaN and are counted in n_unstable, and check=True adds `stationarity`, the relative distance of q's
+        precision from "prior + sites" (small at a fixed point).  Evaluated at ONE hyper vector, theta = kernel.log_mean --
+        unlike log_prob, which mixes over hyper-samples.  Every likelihood, first-task models and models with prev_params;
+        ep_var_mean=True; RBF, Matern and deep-RBF kernels.  About the cost of one site pass over the data: one fused launch up
+        to ops.SITE_MAX_MT inducing points over all tasks, composed from per-op kernels above it (route).  weights: those the fit
+        used; n_f, seed: the draws of the softmax sites.
+        -> loo.Loo(lpd (N,), lpd_out (C, N) or None for the softmax, mu, var (C, N): the cavity moments, n_unstable (C,),
+        stationarity (C,) or None, route)."""
+        return loo.loo(self, x, y, weights=weights, route=route, check=check, n_f=n_f, seed=seed, tile=tile)
 
     def collapsed_bound(self, x, y, weights=None, temper=1.0):
         """The bound fit_q_ returns -- the variational bound of x (N, D), y (N,) or (C, N) at the optimal q(u) of the current
