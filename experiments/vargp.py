@@ -30,7 +30,7 @@ from vargp_amd.datasets import PermutedMNIST, SplitMNIST, ToyDataset  # noqa: E4
 from vargp_amd.train import ElboTrainer  # noqa: E402
 from vargp_amd.train_utils import (DeviceBatches, EarlyStopper, compute_accuracy, compute_loo, compute_lpd,  # noqa: E402
                                    compute_uncertainty, set_seeds)
-from vargp_amd.vargp import VARGP  # noqa: E402
+from vargp_amd.vargp import VARGP, _CLF_Q_INITS  # noqa: E402
 
 
 class JsonlLogger:
@@ -321,7 +321,7 @@ def parse_args(argv=None):
         sp.add_argument('--lengthscale_init', choices=('default', 'median'), default='default',
                         help="lengthscales of the first task: 0.5 (the reference's), or the median distance between pairs of "
                              'its points (not with --dkl)')
-        sp.add_argument('--q_init', choices=('default', 'newton', 'em', 'newton_softmax', 'em_softmax'), default='default',
+        sp.add_argument('--q_init', choices=_CLF_Q_INITS, default='default',
                         help="q(u) of each task: the reference's start, fit_q_newton_ on the task's whole training set, or "
                              'fit_sites_ (variational EM: inducing points and kernel hyper-parameters move too) '
                              '(--likelihood bernoulli only), or fit_q_softmax_ / fit_softmax_sites_ (its variational EM) '

@@ -33,7 +33,7 @@ import torch
 
 from . import ops, sites
 from .likelihoods import GaussianLikelihood, MulticlassSoftmax
-from .whitened import alpha_Q, check_model, read_q, rows
+from .whitened import alpha_Q, check_model, read_q
 
 Loo = namedtuple('Loo', 'lpd lpd_out mu var n_unstable stationarity route')
 Loo.__doc__ = """lpd (N,): the leave-one-out log predictive density per point (nats; NaN at an unstable point); lpd_out (C, N): each
@@ -121,30 +121,6 @@ def composed_site_cavity(theta, Z, X, alpha, Q, V, y, w, kind, extra=(), nu2=0, 
     return out
 
 
-class _SiteProblem(sites._Problem):
-    who = 'loo'
-
-
-class _GaussProblem(sites._Problem):
-    """_Problem with the sites of a Gaussian likelihood, which do not depend on q: lam2 = w / sigma^2, lam1 = lam2 y."""
-    who = 'loo'
-
-    def gauss_sites(self):
-        beta = (-self.extra[0].double()).exp().unsqueeze(-1)
-        lam2 = beta.expand(self.C, self.N) if self.w is None else self.w.double() * beta
-        return lam2 * rows(self.y, self.C, self.N).double(), lam2
-
-    def _passes(self, alpha, Q):
-        lam1, lam2 = (t.float().contiguous() for t in self.gauss_sites())
-        Phi, c, _ = ops.gram_moments_v(self.fr.theta, self.zf, self.xf, lam2, lam1, self.fr.nu2)
-        zero = torch.zeros(self.C, dtype=torch.float64, device=lam2.device)
-        return Phi, c, zero, zero
-
-
-class _SoftmaxProblem(sites._SoftmaxProblem):
-    who = 'loo'
-
-
 def loo(gp, x, y, weights=None, route=None, check=False, n_f=32, seed=0, tile=sites.COMPOSED_TILE):
     """The leave-one-out log predictive density of the training data x (N, D), y (as the model's fit takes it: fit_q_,
     fit_q_newton_ or fit_q_softmax_) of the current task under the model's CURRENT q(u_t), by the cavity of the module docstring;
@@ -160,12 +136,8 @@ def loo(gp, x, y, weights=None, route=None, check=False, n_f=32, seed=0, tile=si
     if tile < 1:
         raise ValueError(f'loo: tile must be >= 1, got {tile}')
     softmax, gauss = isinstance(lik, MulticlassSoftmax), isinstance(lik, GaussianLikelihood)
-    if softmax:
-        n_f = sites._check_softmax_data('loo', x, y, weights, n_f)
-    ops.require_device(gp.z, x, y, weights)
     with torch.no_grad():
-        pr = _SoftmaxProblem(gp, x, y, weights, route, n_f, int(seed)) if softmax else (_GaussProblem if gauss else _SiteProblem)(
-            gp, x, y, weights, route)
+        pr = sites.problem_for(gp, x, y, weights, route, 'loo', n_f, seed)
         fr, fused = pr.fr, pr.route == 'fused'
         a_t, H_t, L_u = read_q(gp, fr.T_tt)
         alpha, Q = alpha_Q(fr, a_t, H_t)

@@ -906,14 +906,8 @@ def softmax_site_noise(seed, n_f, C, N, device=None):
     return eps
 
 
-def softmax_sites(mu, var, y, w, n_f, seed=0, eps=None):
-    """The Gaussian sites of the softmax likelihood at the marginals mu, var (C, N) fp32 of q(f): y (N,) int64 class indices, w
-    (N,) or None = 1, n_f Monte-Carlo draws per point -- eps (n_f, C, N) if given, else generated in the kernel from `seed` (the
-    draws softmax_site_noise(seed, n_f, C, N) returns; bitwise the same result).  With p = softmax(mu + sqrt(var) eps):
-    -> (lam1 (C, N) = w ([y = c] - E p_c) + lam2 mu, lam2 (C, N) = w E p_c (1 - p_c) >= 0, sums (4,) = (sum_n w ell, sum lam2,
-    #{w != 0}, sum w)), ell_n = mu[y_n, n] - E logsumexp(f).  2 <= C <= SOFTMAX_SITE_MAX_C; a point of weight 0 is not evaluated
-    and adds exactly nothing; bitwise reproducible."""
-    require_device(mu, var, y, w, eps)
+def _softmax_operands(mu, var, y, w, eps, n_f):
+    """The operands of the two softmax site entries, detached, contiguous and checked -> (mu, var, y, w, eps, C, N, F)."""
     det = lambda t: t.detach().contiguous()
     mu, var, y = det(mu), det(var), det(y)
     assert mu.dim() == 2 and mu.shape == var.shape and mu.dtype == var.dtype == torch.float32, (mu.shape, var.shape, mu.dtype, var.dtype)
@@ -926,6 +920,18 @@ def softmax_sites(mu, var, y, w, n_f, seed=0, eps=None):
     if eps is not None:
         eps = det(eps)
         assert tuple(eps.shape) == (F, C, N) and eps.dtype == torch.float32, (eps.shape, eps.dtype, (F, C, N))
+    return mu, var, y, w, eps, C, N, F
+
+
+def softmax_sites(mu, var, y, w, n_f, seed=0, eps=None):
+    """The Gaussian sites of the softmax likelihood at the marginals mu, var (C, N) fp32 of q(f): y (N,) int64 class indices, w
+    (N,) or None = 1, n_f Monte-Carlo draws per point -- eps (n_f, C, N) if given, else generated in the kernel from `seed` (the
+    draws softmax_site_noise(seed, n_f, C, N) returns; bitwise the same result).  With p = softmax(mu + sqrt(var) eps):
+    -> (lam1 (C, N) = w ([y = c] - E p_c) + lam2 mu, lam2 (C, N) = w E p_c (1 - p_c) >= 0, sums (4,) = (sum_n w ell, sum lam2,
+    #{w != 0}, sum w)), ell_n = mu[y_n, n] - E logsumexp(f).  2 <= C <= SOFTMAX_SITE_MAX_C; a point of weight 0 is not evaluated
+    and adds exactly nothing; bitwise reproducible."""
+    require_device(mu, var, y, w, eps)
+    mu, var, y, w, eps, C, N, F = _softmax_operands(mu, var, y, w, eps, n_f)
     lam1, lam2 = torch.empty_like(mu), torch.empty_like(mu)
     sums = torch.empty(4, dtype=torch.float32, device=mu.device)
     ws = scratch(lib().vargp_softmax_sites_workspace_bytes(C, N), mu.device)
@@ -946,6 +952,16 @@ def site_bound_bwd_chunks(G, Mt, N, D):
     return int(lib().vargp_site_bound_bwd_chunks(int(G), int(Mt), int(N), int(D)))
 
 
+def _site_bwd_outputs(workspace_bytes, Z, N):
+    """What the two fused backward entries of the site passes write: -> (gZ (G, Mt, D), gtheta (D + 1,), galpha (G, Mt), gv (G, N),
+    the entry's workspace)."""
+    G, Mt, D = Z.shape
+    gtheta = torch.empty(D + 1, dtype=torch.float32, device=Z.device)
+    galpha = torch.empty(G, Mt, dtype=torch.float32, device=Z.device)
+    gv = torch.empty(G, N, dtype=torch.float32, device=Z.device)
+    return torch.empty_like(Z), gtheta, galpha, gv, scratch(workspace_bytes(G, Mt, N, D), Z.device)
+
+
 def site_bound_bwd(theta, Z, X, alpha, Q, y, w, kind, extra, gout, nu2=0):
     """The fused backward of site_moments' sums[:, 0] (csrc/sites.hip, vargp_site_bound_bwd); operands as site_moments takes them
     and gout (G,), the seed of every output.  -> (gZ (G, Mt, D), gtheta (D + 1,), complete; galpha (G, Mt); gv (G, N) = seed x w x
@@ -956,15 +972,18 @@ def site_bound_bwd(theta, Z, X, alpha, Q, y, w, kind, extra, gout, nu2=0):
     gout = gout.detach().contiguous()
     assert tuple(gout.shape) == (G,) and gout.dtype == torch.float32, (gout.shape, gout.dtype)
     gls = None if log_scale is None else torch.empty(G, dtype=torch.float32, device=X.device)
-    gZ = torch.empty_like(Z)
-    gtheta = torch.empty(D + 1, dtype=torch.float32, device=X.device)
-    galpha = torch.empty(G, Mt, dtype=torch.float32, device=X.device)
-    gv = torch.empty(G, N, dtype=torch.float32, device=X.device)
-    ws = scratch(lib().vargp_site_bound_bwd_workspace_bytes(G, Mt, N, D), X.device)
+    gZ, gtheta, galpha, gv, ws = _site_bwd_outputs(lib().vargp_site_bound_bwd_workspace_bytes, Z, N)
     check(lib().vargp_site_bound_bwd(ptr(theta), ptr(Z), ptr(X), ptr(alpha), ptr(Q), ptr(yt), ldy, ptr(w), code, ptr(log_scale), df,
                                      lognorm, ptr(gout), ptr(gZ), ptr(gtheta), ptr(galpha), ptr(gv), ptr(gls), G, Mt, N, D,
                                      int(nu2), ptr(ws), ws.numel() * 4, stream_ptr()), 'vargp_site_bound_bwd')
     return gZ, gtheta, galpha, gv, gls
+
+
+def _bound_grads(ctx, theta, Z, X, gZ, gtheta, galpha, gv, gown=None):
+    """The tail of both bound nodes' backward: gQ = -gram_moments(w = gv).Phi, and the gradients of the eleven forward arguments
+    (theta, Z, X, alpha, Q, y, w, the eighth -- log_scale, with gradient gown, or eps --, three constants)."""
+    gQ = -gram_moments(theta, Z, X, gv, gv, ctx.nu2)[0]
+    return gtheta.view(ctx.theta_shape), gZ, None, galpha, gQ, None, None, gown, None, None, None
 
 
 class _SiteBound(Function):
@@ -982,9 +1001,7 @@ class _SiteBound(Function):
     def backward(ctx, gout):
         theta, Z, X, alpha, Q, y, w, log_scale = ctx.saved_tensors
         gout = gout.to(torch.float32).contiguous()
-        gZ, gtheta, galpha, gv, gls = site_bound_bwd(theta, Z, X, alpha, Q, y, w, ctx.kind, ctx.extra, gout, ctx.nu2)
-        gQ = -gram_moments(theta, Z, X, gv, gv, ctx.nu2)[0]
-        return gtheta.view(ctx.theta_shape), gZ, None, galpha, gQ, None, None, gls, None, None, None
+        return _bound_grads(ctx, theta, Z, X, *site_bound_bwd(theta, Z, X, alpha, Q, y, w, ctx.kind, ctx.extra, gout, ctx.nu2))
 
 
 def site_bound_diff(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0):
@@ -1010,19 +1027,9 @@ def softmax_site_grads(mu, var, y, w, n_f, gout, seed=0, eps=None):
     == 0).  The pathwise derivative for var, not the Price estimate behind lam2.  The same draws as softmax_sites (eps or seed,
     bitwise alike); a point of weight 0 is not evaluated and gets exact zeros; no workspace; bitwise reproducible."""
     require_device(mu, var, y, w, eps, gout)
-    det = lambda t: t.detach().contiguous()
-    mu, var, y, gout = det(mu), det(var), det(y), det(gout).view(-1)
-    assert mu.dim() == 2 and mu.shape == var.shape and mu.dtype == var.dtype == torch.float32, (mu.shape, var.shape, mu.dtype, var.dtype)
-    C, N = mu.shape
-    F = int(n_f)
-    assert tuple(y.shape) == (N,) and y.dtype == torch.int64, (y.shape, y.dtype)
+    mu, var, y, w, eps, C, N, F = _softmax_operands(mu, var, y, w, eps, n_f)
+    gout = gout.detach().contiguous().view(-1)
     assert gout.numel() == 1 and gout.dtype == torch.float32, (gout.shape, gout.dtype)
-    if w is not None:
-        w = det(w)
-        assert tuple(w.shape) == (N,) and w.dtype == torch.float32, (w.shape, w.dtype)
-    if eps is not None:
-        eps = det(eps)
-        assert tuple(eps.shape) == (F, C, N) and eps.dtype == torch.float32, (eps.shape, eps.dtype, (F, C, N))
     gmu, gvar = torch.empty_like(mu), torch.empty_like(mu)
     check(lib().vargp_softmax_site_grads(ptr(mu), ptr(var), ptr(y), ptr(w), ptr(eps), _seed64(seed), ptr(gout), ptr(gmu), ptr(gvar),
                                          C, N, F, stream_ptr()), 'vargp_softmax_site_grads')
@@ -1044,11 +1051,7 @@ def site_transport_bwd(theta, Z, X, alpha, Q, gm, gv, nu2=0):
     theta, Z, X, alpha, Q, (G, Mt, N, D) = _data_operands(theta, Z, X, alpha, Q)
     gm, gv = gm.detach().contiguous(), gv.detach().contiguous()
     assert tuple(gm.shape) == tuple(gv.shape) == (G, N) and gm.dtype == gv.dtype == torch.float32, (gm.shape, gv.shape, gm.dtype)
-    gZ = torch.empty_like(Z)
-    gtheta = torch.empty(D + 1, dtype=torch.float32, device=X.device)
-    galpha = torch.empty(G, Mt, dtype=torch.float32, device=X.device)
-    gv_out = torch.empty(G, N, dtype=torch.float32, device=X.device)
-    ws = scratch(lib().vargp_site_transport_bwd_workspace_bytes(G, Mt, N, D), X.device)
+    gZ, gtheta, galpha, gv_out, ws = _site_bwd_outputs(lib().vargp_site_transport_bwd_workspace_bytes, Z, N)
     check(lib().vargp_site_transport_bwd(ptr(theta), ptr(Z), ptr(X), ptr(alpha), ptr(Q), ptr(gm), ptr(gv), ptr(gZ), ptr(gtheta),
                                          ptr(galpha), ptr(gv_out), G, Mt, N, D, int(nu2), ptr(ws), ws.numel() * 4, stream_ptr()),
           'vargp_site_transport_bwd')
@@ -1070,9 +1073,7 @@ class _SoftmaxSiteBound(Function):
     def backward(ctx, gout):
         theta, Z, X, alpha, Q, y, w, eps, mu, var = ctx.saved_tensors
         gmu, gvar = softmax_site_grads(mu, var, y, w, ctx.n_f, gout.to(torch.float32).contiguous(), ctx.seed, eps)
-        gZ, gtheta, galpha, gv = site_transport_bwd(theta, Z, X, alpha, Q, gmu, gvar, ctx.nu2)
-        gQ = -gram_moments(theta, Z, X, gv, gv, ctx.nu2)[0]
-        return gtheta.view(ctx.theta_shape), gZ, None, galpha, gQ, None, None, None, None, None, None
+        return _bound_grads(ctx, theta, Z, X, *site_transport_bwd(theta, Z, X, alpha, Q, gmu, gvar, ctx.nu2))
 
 
 def softmax_site_bound_diff(theta, Z, X, alpha, Q, y, w, n_f, seed=0, eps=None, nu2=0):

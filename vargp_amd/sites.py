@@ -81,7 +81,7 @@ def _check_likelihood(lik, who):
 def check_supported(gp, who='fit_q_newton_'):
     """ValueError unless the site iteration applies to the model: a Bernoulli, Poisson or Student-t likelihood, ep_var_mean=True,
     an RBF / Matern / deep-RBF kernel.  Needs no device."""
-    check_model(gp, who, _check_likelihood)
+    _Problem.check(gp, who)
 
 
 def check_damping(damping, who='fit_q_newton_'):
@@ -147,11 +147,11 @@ def _tile_marginals(K, alpha, Q, g2):
 
 
 def _tiles(X, tile, y=None, w=None):
-    """The tiles of N points: (n0, n1, X[n0:n1], the tile's columns of y (N,) or (G, N) and of w (G, N), or None), contiguous."""
+    """The tiles of N points: (n0, n1, X[n0:n1], the tile's columns of y and of w, each (N,) or (G, N), or None), contiguous."""
+    cols = lambda t, n0, n1: None if t is None else (t[n0:n1] if t.dim() == 1 else t[:, n0:n1]).contiguous()
     for n0 in range(0, X.size(0), tile):
         n1 = min(n0 + tile, X.size(0))
-        yield (n0, n1, X[n0:n1].contiguous(), None if y is None else (y[n0:n1] if y.dim() == 1 else y[:, n0:n1]).contiguous(),
-               None if w is None else w[:, n0:n1].contiguous())
+        yield n0, n1, X[n0:n1].contiguous(), cols(y, n0, n1), cols(w, n0, n1)
 
 
 def composed_site_moments(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0, tile=COMPOSED_TILE):
@@ -188,11 +188,51 @@ def composed_site_moments(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0, ti
 
 class _Problem:
     """What the iteration needs of the model and the data, gathered once: theta, the (featurised) inducing points of all tasks
-    and inputs, the whitening factors, the frozen tasks' whitened posterior, targets, weights and the likelihood's arguments."""
+    and inputs, the whitening factors, the frozen tasks' whitened posterior, targets, weights and the likelihood's arguments.
+    The class is also the FAMILY -- independent outputs here, the softmax in _SoftmaxProblem: the class attributes and class
+    methods are everything in which the two differ, and _bound, _fit_q and _fit_em below are written over a family."""
 
-    who = 'fit_q_newton_'
+    who, bound_who, em_who = 'fit_q_newton_', 'site_bound', 'fit_sites_'          # the entry points: fit, bound, EM
+    check_likelihood = staticmethod(_check_likelihood)
+    max_classes = None
+    param_names = ('z', 'kernel', 'lik')                   # what the EM may train; 'lik' where the likelihood has a parameter
 
-    def __init__(self, gp, x, y, weights, route):
+    @classmethod
+    def check(cls, gp, who, differentiable=False):
+        """ValueError unless the family's fit (differentiable: its bound, which refuses a DeepRBFKernel) applies to the model."""
+        check_model(gp, who, cls.check_likelihood, deep=f'the feature map needs the gradient of the site pass for its inputs X, '
+                    f'which the fused backward does not produce); {cls.who} supports it' if differentiable else None)
+        if cls.max_classes is not None and gp.z.size(0) > cls.max_classes:
+            raise ValueError(f'{who}: at most {cls.max_classes} classes, got {gp.z.size(0)}')
+
+    @classmethod
+    def check_data(cls, who, x, y, weights, fit=False, **draws):
+        """The checks of the data and the draws that need no device -> the draws as the problem takes them (here: none)."""
+        return {}
+
+    @classmethod
+    def operands(cls, lik, y, weights, C, N, who, graph=False):
+        """What follows (alpha, Q) in the argument list of the family's passes: (targets, weights, kind, extra).  graph: the
+        likelihood's own parameter stays on the autograd graph (the bound); else everything is detached (the fit)."""
+        if graph:
+            own = lik.ext_param()
+            extra = (() if own is None else (own.to(torch.float32),)) + tuple(lik._consts())
+        else:
+            extra = tuple(t.detach() if torch.is_tensor(t) else t for t in lik._extra())
+        return site_target(lik.kind, y.detach(), C, N), None if weights is None else rows(weights, C, N), lik.kind, extra
+
+    @staticmethod
+    def diff_pass(route):
+        """The data term of the bound on the autograd graph: (theta, Z, X, alpha, Q, *operands, nu2) -> value."""
+        return ops.site_bound_diff if route == 'fused' else composed_site_bound
+
+    @staticmethod
+    def reduce_kl(kl):
+        """KL(q(v_t) || N(0, I)) (C,) as the bound holds it: one entry per output."""
+        return kl
+
+    def __init__(self, gp, x, y, weights, route, who=None):
+        self.who = who or self.who
         self.fr = fr = Frame(gp)
         self.C, self.M, self.N = fr.C, fr.M, x.size(0)
         self.route = pick_route(route, fr.Mt, self.who)
@@ -202,10 +242,7 @@ class _Problem:
 
     def _targets(self, lik, y, weights):
         """The likelihood's arguments, the targets and the weights as the data passes take them."""
-        C, N = self.C, self.N
-        self.kind, self.extra = lik.kind, tuple(t.detach() if torch.is_tensor(t) else t for t in lik._extra())
-        self.y = site_target(self.kind, y.detach(), C, N)
-        self.w = None if weights is None else rows(weights, C, N)
+        self.y, self.w, self.kind, self.extra = self.operands(lik, y, weights, self.C, self.N, self.who)
 
     def _passes(self, alpha, Q):
         """The passes over the data at q(f_n) = N(alpha . k_n, gamma^2 - k_n^T Q k_n): -> (Phi (C, Mt, Mt), c (C, Mt), the data
@@ -216,8 +253,8 @@ class _Problem:
         return Phi, c, sums[:, 0].double(), sums[:, 2]
 
     def bound(self, data, kl):
-        """The bound as the trace holds it, from the data term and KL(q(v_t) || N(0, I)) (C,): one entry per output."""
-        return data - kl
+        """The bound as the trace holds it, from the data term and KL(q(v_t) || N(0, I)) (C,)."""
+        return data - self.reduce_kl(kl)
 
     def sites(self, a_t, H_t):
         """The passes over the data at q(v_t) = N(a_t, H_t H_t^T): -> (the data term of the bound, float64, I + A_tt,
@@ -268,11 +305,17 @@ def fit_q_newton_(gp, x, y, n_iters=20, damping=1.0, tol=1e-6, weights=None, rou
     the model's q(u_t) is then not read).  The default start of a VARGP model (u_tril = 1.31 I in the space of u) is a WIDE q in
     function space; a Poisson likelihood, whose expected log-likelihood holds exp(mu + var / 2), can be far too steep there for
     any damped step to be accepted -- start such a model at the prior.  -> SiteFit(bound (n_iters + 1, C) float64 on the host, n_iters, n_rejected, n_clamped, route)."""
-    check_supported(gp)
-    damping, n_iters = _check_loop_args('fit_q_newton_', damping, n_iters, start)
+    return _fit_q(_Problem, gp, x, y, n_iters, damping, tol, weights, route, start)
+
+
+def _fit_q(family, gp, x, y, n_iters, damping, tol, weights, route, start, **draws):
+    """The prologue of the family's fit: the model, the loop arguments, the data and the draws, the device; then _fit."""
+    family.check(gp, family.who)
+    damping, n_iters = _check_loop_args(family.who, damping, n_iters, start)
+    draws = family.check_data(family.who, x, y, weights, fit=True, **draws)
     ops.require_device(gp.z, x, y, weights)
     with torch.no_grad():
-        return _fit(gp, _Problem(gp, x, y, weights, route), n_iters, damping, tol, start)
+        return _fit(gp, family(gp, x, y, weights, route, **draws), n_iters, damping, tol, start)
 
 
 def _check_loop_args(who, damping, n_iters, start):
@@ -364,12 +407,16 @@ def _check_softmax_likelihood(lik, who):
                          'independent outputs have fit_q_newton_ (q_init="newton"), GaussianLikelihood has fit_q_')
 
 
+def _class_indices(who, y, N):
+    if y.dtype != torch.int64 or tuple(y.shape) != (N,):
+        raise ValueError(f'{who}: y must be int64 class indices of shape ({N},), got {y.dtype} {tuple(y.shape)}')
+    return y
+
+
 def check_softmax_supported(gp, who='fit_q_softmax_'):
     """ValueError unless the softmax site iteration applies to the model: MulticlassSoftmax, ep_var_mean=True, an RBF / Matern /
     deep-RBF kernel.  Needs no device."""
-    check_model(gp, who, _check_softmax_likelihood)
-    if gp.z.size(0) > ops.SOFTMAX_SITE_MAX_C:
-        raise ValueError(f'{who}: at most {ops.SOFTMAX_SITE_MAX_C} classes, got {gp.z.size(0)}')
+    _SoftmaxProblem.check(gp, who)
 
 
 def composed_softmax_marginals(theta, Z, X, alpha, Q, nu2=0, tile=COMPOSED_TILE):
@@ -410,20 +457,46 @@ def composed_softmax_sites(mu, var, y, w, eps):
 
 
 class _SoftmaxProblem(_Problem):
-    """_Problem with the softmax's three passes and its joint data term."""
-    who = 'fit_q_softmax_'
+    """_Problem with the softmax's three passes and its joint data term: the softmax family."""
+    who, bound_who, em_who = 'fit_q_softmax_', 'softmax_site_bound', 'fit_softmax_sites_'
+    check_likelihood = staticmethod(_check_softmax_likelihood)
+    max_classes = ops.SOFTMAX_SITE_MAX_C
+    param_names = ('z', 'kernel')                          # the softmax has no parameter
 
-    def __init__(self, gp, x, y, weights, route, n_f, seed):
-        self.n_f, self.seed = n_f, seed
-        super().__init__(gp, x, y, weights, route)
+    @classmethod
+    def check_data(cls, who, x, y, weights, fit=False, n_f=32, seed=0):
+        """n_f in [1, 65535], y int64 (N,), weights None or (N,).  fit: fit_q_softmax_, which checks y with its targets (on the
+        device) and words the weights' refusal at more length."""
+        N, n_f = x.size(0), int(n_f)
+        if not 1 <= n_f <= 65535:
+            raise ValueError(f'{who}: n_f must be in [1, 65535], got {n_f}')
+        if not fit:
+            _class_indices(who, y, N)
+        if weights is not None and tuple(weights.shape) != (N,):
+            shared = ' (the classes of a point share one likelihood term)' if fit else ''
+            raise ValueError(f'{who}: weights must have shape ({N},): one weight per point{shared}, got {tuple(weights.shape)}')
+        return dict(n_f=n_f, seed=seed)
+
+    @classmethod
+    def operands(cls, lik, y, weights, C, N, who, graph=False):
+        """(class indices, weights (N,)): what follows (alpha, Q) in the softmax passes, before the draws."""
+        return _class_indices(who, y.detach(), N).contiguous(), None if weights is None else weights.detach().to(torch.float32).contiguous()
+
+    @staticmethod
+    def diff_pass(route):
+        return ops.softmax_site_bound_diff if route == 'fused' else composed_softmax_site_bound
+
+    @staticmethod
+    def reduce_kl(kl):
+        """Summed over the classes: the data term is joint."""
+        return kl.sum(-1, keepdim=True)
+
+    def __init__(self, gp, x, y, weights, route, n_f=32, seed=0, who=None):
+        self.n_f, self.seed = n_f, int(seed)
+        super().__init__(gp, x, y, weights, route, who)
 
     def _targets(self, lik, y, weights):
-        N = self.N
-        y = y.detach()
-        if y.dtype != torch.int64 or tuple(y.shape) != (N,):
-            raise ValueError(f'fit_q_softmax_: y must be int64 class indices of shape ({N},), got {y.dtype} {tuple(y.shape)}')
-        self.y = y.contiguous()
-        self.w = None if weights is None else weights.detach().to(torch.float32).contiguous()
+        self.y, self.w = self.operands(lik, y, weights, self.C, self.N, self.who)
 
     def _passes(self, alpha, Q):
         marginals = ops.site_marginals if self.route == 'fused' else composed_softmax_marginals
@@ -431,9 +504,6 @@ class _SoftmaxProblem(_Problem):
         lam1, lam2, sums = ops.softmax_sites(mu, var, self.y, self.w, self.n_f, self.seed)
         Phi, c, _ = ops.gram_moments_v(self.fr.theta, self.zf, self.xf, lam2, lam1, self.fr.nu2)
         return Phi, c, sums[:1].double(), torch.zeros((), device=mu.device)
-
-    def bound(self, data, kl):
-        return data - kl.sum(-1, keepdim=True)
 
 
 def fit_q_softmax_(gp, x, y, n_iters=20, damping=1.0, tol=1e-6, weights=None, route=None, start='current', n_f=32, seed=0):
@@ -451,17 +521,33 @@ def fit_q_softmax_(gp, x, y, n_iters=20, damping=1.0, tol=1e-6, weights=None, ro
     ends by rejection rather than by tol, at the last accepted q.
     -> SiteFit(bound (n_iters + 1, 1) float64 on the host: the summed bound, non-decreasing; n_iters; n_rejected; n_clamped = 0
     always (d ell / d var <= 0); route)."""
-    check_softmax_supported(gp)
-    damping, n_iters = _check_loop_args('fit_q_softmax_', damping, n_iters, start)
-    n_f = int(n_f)
-    if not 1 <= n_f <= 65535:
-        raise ValueError(f'fit_q_softmax_: n_f must be in [1, 65535], got {n_f}')
-    if weights is not None and tuple(weights.shape) != (x.size(0),):
-        raise ValueError(f'fit_q_softmax_: weights must have shape ({x.size(0)},): one weight per point (the classes of a point '
-                         f'share one likelihood term), got {tuple(weights.shape)}')
+    return _fit_q(_SoftmaxProblem, gp, x, y, n_iters, damping, tol, weights, route, start, n_f=n_f, seed=seed)
+
+
+class _GaussProblem(_Problem):
+    """_Problem with the sites of a Gaussian likelihood, which do not depend on q: lam2 = w / sigma^2, lam1 = lam2 y.  Its fit is
+    collapsed.fit_q_; the problem serves loo.py."""
+
+    def gauss_sites(self):
+        beta = (-self.extra[0].double()).exp().unsqueeze(-1)
+        lam2 = beta.expand(self.C, self.N) if self.w is None else self.w.double() * beta
+        return lam2 * rows(self.y, self.C, self.N).double(), lam2
+
+    def _passes(self, alpha, Q):
+        lam1, lam2 = (t.float().contiguous() for t in self.gauss_sites())
+        Phi, c, _ = ops.gram_moments_v(self.fr.theta, self.zf, self.xf, lam2, lam1, self.fr.nu2)
+        zero = torch.zeros(self.C, dtype=torch.float64, device=lam2.device)
+        return Phi, c, zero, zero
+
+
+def problem_for(gp, x, y, weights, route, who, n_f=32, seed=0):
+    """The problem of the model's family -- softmax, Gaussian or independent non-Gaussian outputs -- for the caller `who`, with
+    the family's checks of the data and the draws (n_f, seed: the softmax's) made first and the operands required on a device."""
+    lik = gp.likelihood
+    family = _SoftmaxProblem if isinstance(lik, MulticlassSoftmax) else _GaussProblem if isinstance(lik, GaussianLikelihood) else _Problem
+    draws = family.check_data(who, x, y, weights, n_f=n_f, seed=seed)
     ops.require_device(gp.z, x, y, weights)
-    with torch.no_grad():
-        return _fit(gp, _SoftmaxProblem(gp, x, y, weights, route, n_f, int(seed)), n_iters, damping, tol, start)
+    return family(gp, x, y, weights, route, who=who, **draws)
 
 
 # -- the site bound on the autograd graph: variational EM ----------------------------------------------------------------------------
@@ -484,48 +570,47 @@ is non-decreasing); n_rounds: completed rounds (M-step + E-step); n_newton: acce
 def check_differentiable(gp, who):
     """check_supported, and exactly RBFKernel or MaternKernel: the bound's gradient for a DeepRBFKernel needs the gradient of the
     site pass for its inputs X (the feature map), which the fused backward does not produce."""
-    check_model(gp, who, _check_likelihood, deep='the feature map needs the gradient of the site pass for its inputs X, which the '
-                                                 'fused backward does not produce); fit_q_newton_ supports it')
+    _Problem.check(gp, who, differentiable=True)
 
 
-def _tile_value(theta, Z, alpha, Q, log_scale, Xt, yt, wt, kind, extra, nu2):
+def _tile_value(leaves, Xt, yt, wt, kind, extra, nu2):
     """sum_n w_n ell_n (G,) float64 of one tile of points from the differentiable per-op nodes: the gram op, ops.matmul, and
-    ell_torch in fp64."""
+    ell_torch in fp64.  leaves: theta, Z, alpha, Q and, for Student-t, log_scale."""
+    theta, Z, alpha, Q, *log_scale = leaves
     mu, var = _tile_marginals(_gram_tile(theta.view(1, -1), Z, Xt, nu2), alpha, 0.5 * (Q + Q.mT), (2.0 * theta[-1]).exp())
-    ex = extra if log_scale is None else (log_scale,) + tuple(extra[1:])
-    ell = ell_torch(kind, ex, mu, var, yt)
+    ell = ell_torch(kind, tuple(log_scale) + tuple(extra[1:]) if log_scale else extra, mu, var, yt)
     if wt is None:
         return ell.sum(-1)
     return torch.where(wt != 0, wt.double() * ell, torch.zeros_like(ell)).sum(-1)
 
 
-class _ComposedSiteBound(torch.autograd.Function):
-    """ops.site_bound_diff for any Mt, a tile of N at a time: the forward adds the tiles' values in fp64 under no_grad; the
-    backward revisits the same tiles, rebuilds each tile's graph from the per-op nodes and accumulates the gradients in fp64 --
-    memory O(Mt x tile)."""
+class _ComposedBound(torch.autograd.Function):
+    """The composed route of both differentiable bounds, for any Mt, a tile of N at a time: the forward adds the tiles' values
+    tile_value(leaves, Xt, yt, wt, *per_tile(n0, n1)) in fp64 under no_grad; the backward revisits the same tiles, rebuilds each
+    tile's graph from the per-op nodes and accumulates the gradients of the leaves in fp64 -- memory O(Mt x tile).  per_tile: the
+    tile's further arguments (the likelihood's constants; the tile's slice of the softmax noise); n_out: the size of the value."""
     @staticmethod
-    def forward(ctx, theta, Z, alpha, Q, log_scale, X, y, w, kind, extra, nu2, tile):
-        ctx.save_for_backward(theta, Z, alpha, Q, log_scale, X, y, w)
-        ctx.cfg = (kind, extra, nu2, tile)
-        value = torch.zeros(Z.size(0), dtype=torch.float64, device=X.device)
-        for _, _, Xt, yt, wt in _tiles(X, tile, y, w):
-            value += _tile_value(theta, Z, alpha, Q, log_scale, Xt, yt, wt, kind, extra, nu2)
+    def forward(ctx, tile_value, per_tile, n_out, tile, X, y, w, *leaves):
+        ctx.save_for_backward(X, y, w, *leaves)
+        ctx.cfg = (tile_value, per_tile, tile)
+        value = torch.zeros(n_out, dtype=torch.float64, device=X.device)
+        for n0, n1, Xt, yt, wt in _tiles(X, tile, y, w):
+            value += tile_value(leaves, Xt, yt, wt, *per_tile(n0, n1))
         return value
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout):
-        theta, Z, alpha, Q, log_scale, X, y, w = ctx.saved_tensors
-        kind, extra, nu2, tile = ctx.cfg
-        leaves = [t.detach().clone().requires_grad_(True) for t in (theta, Z, alpha, Q) + (() if log_scale is None else (log_scale,))]
+        X, y, w, *saved = ctx.saved_tensors
+        tile_value, per_tile, tile = ctx.cfg
+        leaves = [t.detach().clone().requires_grad_(True) for t in saved]
         acc = [torch.zeros(t.shape, dtype=torch.float64, device=t.device) for t in leaves]
         with torch.enable_grad():
-            for _, _, Xt, yt, wt in _tiles(X, tile, y, w):
-                val = _tile_value(*leaves[:4], leaves[4] if log_scale is not None else None, Xt, yt, wt, kind, extra, nu2)
+            for n0, n1, Xt, yt, wt in _tiles(X, tile, y, w):
+                val = tile_value(leaves, Xt, yt, wt, *per_tile(n0, n1))
                 for a, g in zip(acc, torch.autograd.grad((val * gout.double()).sum(), leaves)):
                     a += g.double()
-        out = [a.to(t.dtype) for a, t in zip(acc, leaves)]
-        return (*out[:4], out[4] if log_scale is not None else None, None, None, None, None, None, None, None)
+        return (None,) * 7 + tuple(a.to(t.dtype) for a, t in zip(acc, leaves))
 
 
 def composed_site_bound(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0, tile=COMPOSED_TILE):
@@ -533,8 +618,23 @@ def composed_site_bound(theta, Z, X, alpha, Q, y, w, kind, extra=(), nu2=0, tile
     ops.SITE_MAX_MT inducing points and the on-device yardstick of the fused backward."""
     ops.require_device(theta, Z, X, alpha, Q, y, w)
     ops.refuse_grad('composed_site_bound', ops.SITE_BOUND_GRADS, X=X, y=y, w=w)
-    log_scale = extra[0] if kind == 'studentt' else None
-    return _ComposedSiteBound.apply(theta, Z, alpha, Q, log_scale, X, y, w, kind, tuple(extra), int(nu2), int(tile))
+    consts = (kind, tuple(extra), int(nu2))
+    return _ComposedBound.apply(_tile_value, lambda n0, n1: consts, Z.size(0), int(tile), X, y, w, theta, Z, alpha, Q,
+                                *((extra[0],) if kind == 'studentt' else ()))
+
+
+def _bound(family, gp, x, y, weights, q, route, who, **draws):
+    """The family's bound on the autograd graph: data term - KL.  The nodes are created in this order -- Frame, whitened_q, the
+    likelihood's operands, alpha_Q, the data pass, kl_standard -- and autograd adds gradients in the reverse of it (whitened.py)."""
+    family.check(gp, who, differentiable=True)
+    draws = family.check_data(who, x, y, weights, **draws)
+    ops.require_device(gp.z, x, y, weights)
+    fr = Frame(gp)
+    route = pick_route(route, fr.Mt, who)
+    a_t, H_t = whitened_q(gp) if q is None else (q[0].detach().double(), q[1].detach().float())
+    operands = family.operands(gp.likelihood, y, weights, fr.C, x.size(0), who, graph=True)
+    data = family.diff_pass(route)(fr.theta, fr.z_all, x.detach().contiguous(), *alpha_Q(fr, a_t, H_t), *operands, nu2=fr.nu2, **draws)
+    return data.double() - family.reduce_kl(kl_standard(a_t, H_t))
 
 
 def site_bound(gp, x, y, weights=None, q=None, route=None):
@@ -547,18 +647,7 @@ def site_bound(gp, x, y, weights=None, q=None, route=None):
     ops.SITE_MAX_MT inducing points over all tasks; 'composed' above it or on request: per-op kernels, a tile of N at a time).
     Bernoulli, Poisson or Student-t likelihood, ep_var_mean=True, exactly RBFKernel or MaternKernel; a DeepRBFKernel is refused
     (ValueError).  The hyper-prior (kl_hypers) is NOT part of the bound."""
-    check_differentiable(gp, 'site_bound')
-    ops.require_device(gp.z, x, y, weights)
-    lik, fr = gp.likelihood, Frame(gp)
-    route = pick_route(route, fr.Mt, 'site_bound')
-    a_t, H_t = whitened_q(gp) if q is None else (q[0].detach().double(), q[1].detach().float())
-    own = lik.ext_param()
-    extra = (() if own is None else (own.to(torch.float32),)) + tuple(lik._consts())
-    yt = site_target(lik.kind, y.detach(), fr.C, x.size(0))
-    w = None if weights is None else rows(weights, fr.C, x.size(0))
-    pass_ = ops.site_bound_diff if route == 'fused' else composed_site_bound
-    data = pass_(fr.theta, fr.z_all, x.detach().contiguous(), *alpha_Q(fr, a_t, H_t), yt, w, lik.kind, extra, fr.nu2)
-    return data.double() - kl_standard(a_t, H_t)
+    return _bound(_Problem, gp, x, y, weights, q, route, 'site_bound')
 
 
 def fit_sites_(gp, x, y, n_rounds=5, m_steps=20, lr=1e-2, params=None, newton_iters=20, damping=1.0, tol=1e-6, weights=None,
@@ -573,18 +662,30 @@ def fit_sites_(gp, x, y, n_rounds=5, m_steps=20, lr=1e-2, params=None, newton_it
     objective is the bound alone: the hyper-prior (kl_hypers) is NOT in it, so this is maximum likelihood (type II) for the
     hyper-parameters, not the MAP / variational treatment of VARGP.loss.  -> EMFit(bound (n_rounds + 1, C) float64 on the
     host, n_rounds, n_newton, stopped)."""
-    check_differentiable(gp, 'fit_sites_')
-    own = gp.likelihood.ext_param()
-    named = dict(z=gp.z, kernel=gp.kernel.log_mean, lik=own)
-    if params is None:
-        params = ('z', 'kernel') + (('lik',) if own is not None else ())
-    chosen = choose_params('fit_sites_', named, params)
-    if 'lik' in params and own is None:
-        raise ValueError(f"fit_sites_: params names 'lik', but {type(gp.likelihood).__name__} has no parameter")
-    damping, n_rounds, m_steps = _check_em_args('fit_sites_', damping, n_rounds, m_steps)
+    return _fit_em(_Problem, gp, x, y, n_rounds, m_steps, lr, params, newton_iters, damping, tol, weights, route, start)
+
+
+def _fit_em(family, gp, x, y, n_rounds, m_steps, lr, params, newton_iters, damping, tol, weights, route, start, **draws):
+    """The prologue of the family's EM: the model, the trainable subset, the loop arguments, the data and the draws, the device;
+    then _em on the family's fit and bound.  A family whose param_names hold 'lik' refuses it after the subset is chosen, where
+    the likelihood has no parameter; one without 'lik' refuses it at once."""
+    who, lik = family.em_who, gp.likelihood
+    family.check(gp, who, differentiable=True)
+    named = dict(z=gp.z, kernel=gp.kernel.log_mean, lik=lik.ext_param() if 'lik' in family.param_names else None)
+    params = tuple(k for k, t in named.items() if t is not None) if params is None else tuple(params)
+    named = {k: named[k] for k in family.param_names}
+    no_lik = 'lik' in params and named.get('lik') is None and ValueError(f"{who}: params names 'lik', but {type(lik).__name__} has "
+                                                                         'no parameter')
+    if no_lik and 'lik' not in named:
+        raise no_lik
+    chosen = choose_params(who, named, params)
+    if no_lik:
+        raise no_lik
+    damping, n_rounds, m_steps = _check_em_args(who, damping, n_rounds, m_steps)
+    draws = family.check_data(who, x, y, weights, **draws)
     ops.require_device(gp.z, x, y, weights)
-    e_step = lambda st: fit_q_newton_(gp, x, y, n_iters=newton_iters, damping=damping, tol=tol, weights=weights, route=route, start=st)
-    bound_at = lambda q: site_bound(gp, x, y, weights=weights, q=q, route=route)
+    e_step = lambda st: _fit_q(family, gp, x, y, newton_iters, damping, tol, weights, route, st, **draws)
+    bound_at = lambda q: _bound(family, gp, x, y, weights, q, route, family.bound_who, **draws)
     return _em(gp, chosen, e_step, bound_at, start, n_rounds, m_steps, lr)
 
 
@@ -649,9 +750,7 @@ def _em(gp, chosen, e_step, bound_at, start, n_rounds, m_steps, lr):
 def check_softmax_differentiable(gp, who):
     """check_softmax_supported, and exactly RBFKernel or MaternKernel: a DeepRBFKernel is refused for check_differentiable's
     reason.  Needs no device."""
-    check_model(gp, who, _check_softmax_likelihood, deep='the feature map needs the gradient of the site pass for its inputs X, which '
-                                                         'the fused backward does not produce); fit_q_softmax_ supports it')
-    check_softmax_supported(gp, who)
+    _SoftmaxProblem.check(gp, who, differentiable=True)
 
 
 def softmax_value_torch(mu, var, y, w, eps):
@@ -668,38 +767,12 @@ def softmax_value_torch(mu, var, y, w, eps):
     return torch.where(w != 0, w.double() * ell, torch.zeros_like(ell)).sum()
 
 
-def _softmax_tile_value(theta, Z, alpha, Q, Xt, yt, wt, eps_t, nu2):
+def _softmax_tile_value(leaves, Xt, yt, wt, eps_t, nu2):
     """sum_n w_n ell_n () float64 of one tile of points from the differentiable per-op nodes (the gram op, ops.matmul) and
-    softmax_value_torch on the tile's noise eps_t (F, C, B)."""
+    softmax_value_torch on the tile's noise eps_t (F, C, B).  leaves: theta, Z, alpha, Q."""
+    theta, Z, alpha, Q = leaves
     mu, var = _tile_marginals(_gram_tile(theta.view(1, -1), Z, Xt, nu2), alpha, 0.5 * (Q + Q.mT), (2.0 * theta[-1]).exp())
     return softmax_value_torch(mu, var, yt, wt, eps_t)
-
-
-class _ComposedSoftmaxSiteBound(torch.autograd.Function):
-    """ops.softmax_site_bound_diff for any Mt, a tile of N at a time, in the shape of _ComposedSiteBound: values added in fp64
-    under no_grad; the backward rebuilds each tile's graph and accumulates the gradients in fp64."""
-    @staticmethod
-    def forward(ctx, theta, Z, alpha, Q, X, y, w, eps, nu2, tile):
-        ctx.save_for_backward(theta, Z, alpha, Q, X, y, w, eps)
-        ctx.cfg = (nu2, tile)
-        value = torch.zeros(1, dtype=torch.float64, device=X.device)
-        for n0, n1, Xt, yt, _ in _tiles(X, tile, y):
-            value += _softmax_tile_value(theta, Z, alpha, Q, Xt, yt, None if w is None else w[n0:n1], eps[:, :, n0:n1], nu2)
-        return value
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gout):
-        theta, Z, alpha, Q, X, y, w, eps = ctx.saved_tensors
-        nu2, tile = ctx.cfg
-        leaves = [t.detach().clone().requires_grad_(True) for t in (theta, Z, alpha, Q)]
-        acc = [torch.zeros(t.shape, dtype=torch.float64, device=t.device) for t in leaves]
-        with torch.enable_grad():
-            for n0, n1, Xt, yt, _ in _tiles(X, tile, y):
-                val = _softmax_tile_value(*leaves, Xt, yt, None if w is None else w[n0:n1], eps[:, :, n0:n1], nu2)
-                for a, g in zip(acc, torch.autograd.grad((val * gout.double()).sum(), leaves)):
-                    a += g.double()
-        return (*[a.to(t.dtype) for a, t in zip(acc, leaves)], None, None, None, None, None, None)
 
 
 def composed_softmax_site_bound(theta, Z, X, alpha, Q, y, w, n_f, seed=0, eps=None, nu2=0, tile=COMPOSED_TILE):
@@ -711,18 +784,7 @@ def composed_softmax_site_bound(theta, Z, X, alpha, Q, y, w, n_f, seed=0, eps=No
     if eps is None:
         eps = ops.softmax_site_noise(seed, n_f, Z.size(0), X.size(0), device=X.device)
     assert tuple(eps.shape) == (int(n_f), Z.size(0), X.size(0)), (eps.shape, n_f, Z.shape, X.shape)
-    return _ComposedSoftmaxSiteBound.apply(theta, Z, alpha, Q, X, y, w, eps, int(nu2), int(tile))
-
-
-def _check_softmax_data(who, x, y, weights, n_f):
-    n_f = int(n_f)
-    if not 1 <= n_f <= 65535:
-        raise ValueError(f'{who}: n_f must be in [1, 65535], got {n_f}')
-    if y.dtype != torch.int64 or tuple(y.shape) != (x.size(0),):
-        raise ValueError(f'{who}: y must be int64 class indices of shape ({x.size(0)},), got {y.dtype} {tuple(y.shape)}')
-    if weights is not None and tuple(weights.shape) != (x.size(0),):
-        raise ValueError(f'{who}: weights must have shape ({x.size(0)},): one weight per point, got {tuple(weights.shape)}')
-    return n_f
+    return _ComposedBound.apply(_softmax_tile_value, lambda n0, n1: (eps[:, :, n0:n1], int(nu2)), 1, int(tile), X, y, w, theta, Z, alpha, Q)
 
 
 def softmax_site_bound(gp, x, y, weights=None, q=None, route=None, n_f=32, seed=0):
@@ -735,17 +797,7 @@ def softmax_site_bound(gp, x, y, weights=None, q=None, route=None, n_f=32, seed=
     (above it or on request: per-op kernels, a tile of N at a time, on an explicit noise tensor of n_f C N floats).
     MulticlassSoftmax, ep_var_mean=True, exactly RBFKernel or MaternKernel, at most ops.SOFTMAX_SITE_MAX_C classes.  The
     hyper-prior (kl_hypers) is NOT part of the bound."""
-    check_softmax_differentiable(gp, 'softmax_site_bound')
-    n_f = _check_softmax_data('softmax_site_bound', x, y, weights, n_f)
-    ops.require_device(gp.z, x, y, weights)
-    fr = Frame(gp)
-    route = pick_route(route, fr.Mt, 'softmax_site_bound')
-    a_t, H_t = whitened_q(gp) if q is None else (q[0].detach().double(), q[1].detach().float())
-    w = None if weights is None else weights.detach().to(torch.float32).contiguous()
-    pass_ = ops.softmax_site_bound_diff if route == 'fused' else composed_softmax_site_bound
-    data = pass_(fr.theta, fr.z_all, x.detach().contiguous(), *alpha_Q(fr, a_t, H_t), y.detach().contiguous(), w, n_f, int(seed),
-                 None, fr.nu2)
-    return data.double() - kl_standard(a_t, H_t).sum(-1, keepdim=True)
+    return _bound(_SoftmaxProblem, gp, x, y, weights, q, route, 'softmax_site_bound', n_f=n_f, seed=seed)
 
 
 def fit_softmax_sites_(gp, x, y, n_rounds=5, m_steps=20, lr=1e-2, params=None, newton_iters=20, damping=1.0, tol=1e-6, weights=None,
@@ -758,15 +810,5 @@ def fit_softmax_sites_(gp, x, y, n_rounds=5, m_steps=20, lr=1e-2, params=None, n
     are Bonnet / Price estimates, not the stationarity condition of the sampled bound, so the M-step's partial gradient is the
     re-converged bound's only approximately; the undo rule is what guarantees monotonicity.  The hyper-prior is NOT in the
     objective.  -> EMFit(bound (n_rounds + 1, 1) float64 on the host, n_rounds, n_newton, stopped)."""
-    check_softmax_differentiable(gp, 'fit_softmax_sites_')
-    params = ('z', 'kernel') if params is None else tuple(params)
-    if 'lik' in params:
-        raise ValueError("fit_softmax_sites_: params names 'lik', but MulticlassSoftmax has no parameter")
-    chosen = choose_params('fit_softmax_sites_', dict(z=gp.z, kernel=gp.kernel.log_mean), params)
-    damping, n_rounds, m_steps = _check_em_args('fit_softmax_sites_', damping, n_rounds, m_steps)
-    n_f = _check_softmax_data('fit_softmax_sites_', x, y, weights, n_f)
-    ops.require_device(gp.z, x, y, weights)
-    e_step = lambda st: fit_q_softmax_(gp, x, y, n_iters=newton_iters, damping=damping, tol=tol, weights=weights, route=route,
-                                       start=st, n_f=n_f, seed=seed)
-    bound_at = lambda q: softmax_site_bound(gp, x, y, weights=weights, q=q, route=route, n_f=n_f, seed=seed)
-    return _em(gp, chosen, e_step, bound_at, start, n_rounds, m_steps, lr)
+    return _fit_em(_SoftmaxProblem, gp, x, y, n_rounds, m_steps, lr, params, newton_iters, damping, tol, weights, route, start,
+                   n_f=n_f, seed=seed)

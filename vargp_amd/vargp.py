@@ -51,22 +51,87 @@ def make_reg_likelihood(likelihood, out_size, df=4.0):
     raise ValueError(f"create_reg: likelihood must be 'gaussian', 'studentt' or 'poisson', got {likelihood!r}")
 
 
-def _hand_over_hyper_prior(prev_params):
+def _hand_over_hyper_prior(prev_params, dkl=False):
     """The hyper-prior of the next task = the last task's hyper-posterior: popped from prev_params, which is mutated like the
-    reference does (vargp.py:213-222).  -> (prior_log_mean, prior_log_logvar)"""
+    reference does (vargp.py:213-222).  dkl: the feature map starts from the last task's too (vargp.py:218-219).
+    -> (prior_log_mean, prior_log_logvar, phi_params or None)"""
     if not prev_params:
-        return None, None
-    prior = prev_params[-1].get('kernel.log_mean'), prev_params[-1].get('kernel.log_logvar')
+        return None, None, None
+    last = prev_params[-1]
+    prior = last.get('kernel.log_mean'), last.get('kernel.log_logvar')
+    phi_params = {k[11:]: v for k, v in last.items() if k.startswith('kernel.phi.')} if dkl else None
     for p in prev_params:
         for k in [k for k in p if k.startswith('kernel')]:
             p.pop(k)
-    return prior
+    return (*prior, phi_params)
+
+
+def _make_kernel(in_size, kernel, dkl, native_kernel, prior_log_mean, prior_log_logvar, map_est_hypers, phi_params):
+    """The kernel module of a factory's (kernel=, dkl=, native_kernel=) with the handed-over hyper-prior."""
+    prior = dict(prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar, map_est=map_est_hypers)
+    if dkl:
+        kern = DeepRBFKernel(in_size, **prior)
+        if phi_params:
+            kern.phi.load_state_dict(phi_params)
+        return kern
+    if kernel != 'rbf':
+        return MaternKernel(in_size, nu=_KERNEL_NU[kernel], native=bool(native_kernel), **prior)
+    return RBFKernel(in_size, **prior)
 
 
 _Z_INITS = ('greedy', 'kmeans', 'random')                  # create_clf / create_reg (z_init=)
 _LENGTHSCALE_INITS = ('default', 'median')        # (lengthscale_init=)
-_Q_INITS = ('default', 'optimal', 'collapsed', 'newton', 'em')      # create_reg (q_init=)
-_CLF_Q_INITS = ('default', 'newton', 'em', 'newton_softmax', 'em_softmax')        # create_clf (q_init=)
+
+# q_init= of the factories.  name: ({factory that accepts it: (the likelihoods it applies to, the refusal of another) or None},
+# the model checker, the fit as a function of (gp, x, y, o), o the factory's options by name).
+_CLOSED_FORM = (lambda lik: lik == 'gaussian', "q_init={q!r} is the closed form of likelihood='gaussian', got {lik!r}")
+_REG_SITES = (lambda lik: lik != 'gaussian', "q_init={q!r} iterates Gaussian sites of a non-Gaussian likelihood ('poisson', "
+              "'studentt'); likelihood='gaussian' has the closed form q_init='optimal'")
+_CLF_SITES = (lambda lik: lik == 'bernoulli', 'q_init={q!r} fits independent Gaussian sites, which likelihood={lik!r} does not have '
+              "(its outputs are coupled); use likelihood='bernoulli'")
+_Q_INIT = {
+    'default': (dict(create_reg=None, create_clf=None), None, None),
+    'optimal': (dict(create_reg=_CLOSED_FORM), collapsed.check_supported, lambda gp, x, y, o: gp.fit_q_(x, y)),
+    'collapsed': (dict(create_reg=_CLOSED_FORM), collapsed.check_differentiable,
+                  lambda gp, x, y, o: gp.fit_collapsed_(x, y, n_steps=o['collapsed_steps'])),
+    'newton': (dict(create_reg=_REG_SITES, create_clf=_CLF_SITES), sites.check_supported,
+               lambda gp, x, y, o: gp.fit_q_newton_(x, y, n_iters=o['newton_iters'], start='prior')),
+    'em': (dict(create_reg=_REG_SITES, create_clf=_CLF_SITES), sites.check_differentiable,
+           lambda gp, x, y, o: gp.fit_sites_(x, y, n_rounds=o['em_rounds'], m_steps=o['em_steps'], newton_iters=o['newton_iters'],
+                                             start='prior')),
+    'newton_softmax': (dict(create_clf=(lambda lik: lik == 'softmax', "q_init={q!r} fits the coupled sites of likelihood='softmax', "
+                                        "got {lik!r}; the likelihoods with independent outputs have q_init='newton'")),
+                       sites.check_softmax_supported,
+                       lambda gp, x, y, o: gp.fit_q_softmax_(x, y, n_iters=o['newton_iters'], start='prior', n_f=o['site_samples'])),
+    'em_softmax': (dict(create_clf=(lambda lik: lik == 'softmax', 'q_init={q!r} is variational EM on the coupled sites of '
+                                    "likelihood='softmax', got {lik!r}; the likelihoods with independent outputs have q_init='em'")),
+                   sites.check_softmax_differentiable,
+                   lambda gp, x, y, o: gp.fit_softmax_sites_(x, y, n_rounds=o['em_rounds'], m_steps=o['em_steps'],
+                                                             newton_iters=o['newton_iters'], start='prior', n_f=o['site_samples'])),
+}
+_Q_INITS = tuple(q for q, entry in _Q_INIT.items() if 'create_reg' in entry[0])      # create_reg (q_init=)
+_CLF_Q_INITS = tuple(q for q, entry in _Q_INIT.items() if 'create_clf' in entry[0])        # create_clf (q_init=)
+
+
+def _check_q_init(who, q_init, likelihood):
+    """ValueError for a q_init the factory `who` does not accept, or one that does not apply to the likelihood's name."""
+    accepted = _Q_INITS if who == 'create_reg' else _CLF_Q_INITS
+    if q_init not in accepted:
+        raise ValueError(f'{who}: q_init must be one of {sorted(accepted)}, got {q_init!r}')
+    rule = _Q_INIT[q_init][0][who]
+    if rule is not None and not rule[0](likelihood):
+        raise ValueError(f'{who}: ' + rule[1].format(q=q_init, lik=likelihood))
+
+
+def _fit_whole_dataset(gp, dataset, y, check, fit, who):
+    """A factory's q_init: check the model, then on the current CUDA device load the whole data set (y: its targets as the fit
+    takes them), run fit(gp, x, y) and bring the model home."""
+    check(gp, who)
+    home, dev = gp.z.device, torch.device('cuda', torch.cuda.current_device())
+    x = dataset[torch.arange(len(dataset))][0].to(device=dev, dtype=torch.float32)
+    y = y.to(dev)
+    fit(gp.to(dev), x, y)
+    gp.to(home)
 
 
 def _check_init_names(who, z_init, lengthscale_init):
@@ -754,17 +819,7 @@ class VARGP(nn.Module):
         (likelihood='softmax' only, RBF / Matern kernel): fit_softmax_sites_(n_rounds=em_rounds, m_steps=em_steps,
         newton_iters=newton_iters, start='prior', n_f=site_samples) instead -- variational EM that also moves the inducing points
         and kernel.log_mean up the sampled bound (without the hyper-prior)."""
-        if q_init not in _CLF_Q_INITS:
-            raise ValueError(f'create_clf: q_init must be one of {sorted(_CLF_Q_INITS)}, got {q_init!r}')
-        if q_init == 'newton_softmax' and likelihood != 'softmax':
-            raise ValueError(f"create_clf: q_init='newton_softmax' fits the coupled sites of likelihood='softmax', got "
-                             f"{likelihood!r}; the likelihoods with independent outputs have q_init='newton'")
-        if q_init == 'em_softmax' and likelihood != 'softmax':
-            raise ValueError(f"create_clf: q_init='em_softmax' is variational EM on the coupled sites of likelihood='softmax', got "
-                             f"{likelihood!r}; the likelihoods with independent outputs have q_init='em'")
-        if q_init in ('newton', 'em') and likelihood != 'bernoulli':
-            raise ValueError(f"create_clf: q_init={q_init!r} fits independent Gaussian sites, which likelihood={likelihood!r} does "
-                             "not have (its outputs are coupled); use likelihood='bernoulli'")
+        _check_q_init('create_clf', q_init, likelihood)
         lik = make_clf_likelihood(likelihood, n_f, link)
         _check_init_names('create_clf', z_init, lengthscale_init)
         if dkl and lengthscale_init == 'median':
@@ -789,53 +844,17 @@ class VARGP(nn.Module):
             in_size = z.size(-1)
 
         first_task = not prev_params
-        prior_log_mean, prior_log_logvar, phi_params = None, None, None
-        if prev_params:
-            prior_log_mean = prev_params[-1].get('kernel.log_mean')
-            prior_log_logvar = prev_params[-1].get('kernel.log_logvar')
-            if dkl:      # the feature map starts from the last task's (vargp.py:218-219)
-                phi_params = {k[11:]: v for k, v in prev_params[-1].items() if k.startswith('kernel.phi.')}
-            for p in prev_params:
-                for k in [k for k in p if k.startswith('kernel')]:
-                    p.pop(k)
-        if dkl:
-            kern = DeepRBFKernel(in_size, prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
-                                 map_est=map_est_hypers)
-            if phi_params:
-                kern.phi.load_state_dict(phi_params)
-        elif kernel != 'rbf':
-            kern = MaternKernel(in_size, nu=_KERNEL_NU[kernel], prior_log_mean=prior_log_mean,
-                                prior_log_logvar=prior_log_logvar, map_est=map_est_hypers, native=bool(native_kernel))
-        else:
-            kern = RBFKernel(in_size, prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
-                             map_est=map_est_hypers)
+        prior_log_mean, prior_log_logvar, phi_params = _hand_over_hyper_prior(prev_params, dkl)
+        kern = _make_kernel(in_size, kernel, dkl, native_kernel, prior_log_mean, prior_log_logvar, map_est_hypers, phi_params)
         _init_lengthscale(kern, dataset, lengthscale_init, first_task)
         if z_init == 'greedy':
             z = _greedy_inducing(x_all, cand, M, kern, prior_log_mean, prev_params)
         gp = VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean,
                    prev_params=prev_params)
-        if q_init in ('newton', 'em'):
-            (sites.check_supported if q_init == 'newton' else sites.check_differentiable)(gp, f'create_clf(q_init="{q_init}")')
-            home, dev = gp.z.device, torch.device('cuda', torch.cuda.current_device())
-            x = dataset[torch.arange(len(dataset))][0].to(device=dev, dtype=torch.float32)
-            y = torch.as_tensor(dataset.targets).to(device=dev, dtype=torch.int64)
-            if q_init == 'newton':
-                gp.to(dev).fit_q_newton_(x, y, n_iters=newton_iters, start='prior')
-            else:
-                gp.to(dev).fit_sites_(x, y, n_rounds=em_rounds, m_steps=em_steps, newton_iters=newton_iters, start='prior')
-            gp.to(home)
-        elif q_init in ('newton_softmax', 'em_softmax'):
-            check = sites.check_softmax_supported if q_init == 'newton_softmax' else sites.check_softmax_differentiable
-            check(gp, f'create_clf(q_init="{q_init}")')
-            home, dev = gp.z.device, torch.device('cuda', torch.cuda.current_device())
-            x = dataset[torch.arange(len(dataset))][0].to(device=dev, dtype=torch.float32)
-            y = torch.as_tensor(dataset.targets).to(device=dev, dtype=torch.int64)
-            if q_init == 'newton_softmax':
-                gp.to(dev).fit_q_softmax_(x, y, n_iters=newton_iters, start='prior', n_f=site_samples)
-            else:
-                gp.to(dev).fit_softmax_sites_(x, y, n_rounds=em_rounds, m_steps=em_steps, newton_iters=newton_iters, start='prior',
-                                              n_f=site_samples)
-            gp.to(home)
+        if q_init != 'default':
+            o = dict(newton_iters=newton_iters, em_rounds=em_rounds, em_steps=em_steps, site_samples=site_samples)
+            _fit_whole_dataset(gp, dataset, torch.as_tensor(dataset.targets).to(torch.int64), _Q_INIT[q_init][1],
+                               lambda gp, x, y: _Q_INIT[q_init][2](gp, x, y, o), f'create_clf(q_init="{q_init}")')
         return gp
 
     @staticmethod
@@ -861,13 +880,7 @@ class VARGP(nn.Module):
         Student-t log_scale up the bound (without the hyper-prior); the prior start for the reason 'newton' uses it.
         None of likelihood, df, kernel and native_kernel is part of a checkpoint: give them again on reload.  A minibatch's
         targets go to loss() as (C, B) -- y.t() of a (B, C) batch -- or (B,)."""
-        if q_init not in _Q_INITS:
-            raise ValueError(f'create_reg: q_init must be one of {sorted(_Q_INITS)}, got {q_init!r}')
-        if q_init in ('optimal', 'collapsed') and likelihood != 'gaussian':
-            raise ValueError(f"create_reg: q_init={q_init!r} is the closed form of likelihood='gaussian', got {likelihood!r}")
-        if q_init in ('newton', 'em') and likelihood == 'gaussian':
-            raise ValueError(f"create_reg: q_init={q_init!r} iterates Gaussian sites of a non-Gaussian likelihood ('poisson', "
-                             "'studentt'); likelihood='gaussian' has the closed form q_init='optimal'")
+        _check_q_init('create_reg', q_init, likelihood)
         if kernel not in _KERNEL_NU:
             raise ValueError(f'create_reg: kernel must be one of {sorted(_KERNEL_NU)}, got {kernel!r}')
         if native_kernel and kernel == 'rbf':
@@ -886,32 +899,14 @@ class VARGP(nn.Module):
             z = _init_inducing(dataset, out_size, M, z_init, kmeans_iters)
             in_size = z.size(-1)
         first_task = not prev_params
-        prior_log_mean, prior_log_logvar = _hand_over_hyper_prior(prev_params)
-        if kernel != 'rbf':
-            kern = MaternKernel(in_size, nu=_KERNEL_NU[kernel], prior_log_mean=prior_log_mean,
-                                prior_log_logvar=prior_log_logvar, map_est=map_est_hypers, native=bool(native_kernel))
-        else:
-            kern = RBFKernel(in_size, prior_log_mean=prior_log_mean, prior_log_logvar=prior_log_logvar,
-                             map_est=map_est_hypers)
+        prior_log_mean, prior_log_logvar, _ = _hand_over_hyper_prior(prev_params)
+        kern = _make_kernel(in_size, kernel, False, native_kernel, prior_log_mean, prior_log_logvar, map_est_hypers, None)
         _init_lengthscale(kern, dataset, lengthscale_init, first_task)
         if z_init == 'greedy':
             z = _greedy_inducing(x_all, cand, M, kern, prior_log_mean, prev_params)
         gp = VARGP(z, kern, lik, n_var_samples=n_var_samples, ep_var_mean=ep_var_mean, prev_params=prev_params)
         if q_init != 'default':
-            check = {'optimal': collapsed.check_supported, 'collapsed': collapsed.check_differentiable,
-                     'newton': sites.check_supported, 'em': sites.check_differentiable}[q_init]
-            check(gp, f'create_reg(q_init="{q_init}")')
-            home, dev = gp.z.device, torch.device('cuda', torch.cuda.current_device())
-            x = dataset[torch.arange(len(dataset))][0]
-            y = targets if targets.dim() == 1 else targets.t()
-            x, y = x.to(device=dev, dtype=torch.float32), y.to(device=dev, dtype=torch.float32)
-            if q_init == 'optimal':
-                gp.to(dev).fit_q_(x, y)
-            elif q_init == 'newton':
-                gp.to(dev).fit_q_newton_(x, y, n_iters=newton_iters, start='prior')
-            elif q_init == 'em':
-                gp.to(dev).fit_sites_(x, y, n_rounds=em_rounds, m_steps=em_steps, newton_iters=newton_iters, start='prior')
-            else:
-                gp.to(dev).fit_collapsed_(x, y, n_steps=collapsed_steps)
-            gp.to(home)
+            o = dict(collapsed_steps=collapsed_steps, newton_iters=newton_iters, em_rounds=em_rounds, em_steps=em_steps)
+            _fit_whole_dataset(gp, dataset, (targets if targets.dim() == 1 else targets.t()).to(torch.float32), _Q_INIT[q_init][1],
+                               lambda gp, x, y: _Q_INIT[q_init][2](gp, x, y, o), f'create_reg(q_init="{q_init}")')
         return gp
