@@ -30,15 +30,21 @@ namespace vargp {
 __device__ unsigned long long g_cb16_stamps[4][8][4];
 extern "C" void vargp_debug_cb16_stamps(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_cb16_stamps), sizeof(g_cb16_stamps)); }
 #define CB_STAMP(step, i) do { if (lane == 0 && blockIdx.x == 0) g_cb16_stamps[WV][step][i] = __builtin_amdgcn_s_memtime(); } while (0)
+// ... and inside S1, the owner wave only: the block is in column layout, the pivots are done, E / ED are issued
+__device__ unsigned long long g_cb16_s1_stamps[8][4];
+extern "C" void vargp_debug_cb16_s1_stamps(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_cb16_s1_stamps), sizeof(g_cb16_s1_stamps)); }
+#define CB_S1_STAMP(step, i) do { if (lane == 0 && blockIdx.x == 0) g_cb16_s1_stamps[step][i] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define CB_STAMP(step, i) do { } while (0)
+#define CB_S1_STAMP(step, i) do { } while (0)
 #endif
 typedef float cb_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kCbNB = 7;                      // 16-row blocks (112 rows)
 // exchange areas inside the caller's staging matrix (floats); all dead before the results are written there
 constexpr int kCbRD = 0;                      // [7][256]  panel blocks R_k,j of the current step, dumped lane by lane
-constexpr int kCbWB = kCbRD + kCbNB * 256;    // [16][20]  E[i][c] = entry (i, c) of the eliminated diagonal block / sqrt(d_i): W below the diagonal,
-                                              //           L_kk^T above it (the diagonal entry itself is not used)
+constexpr int kCbWB = kCbRD + kCbNB * 256;    // [16][20]  WB[c][i] = entry (i, c) of the eliminated diagonal block, a column per row of WB; the readers
+                                              //           scale: E[i][c] = entry (i, c) / sqrt(d_i) is W below the diagonal, L_kk^T above it (the
+                                              //           diagonal entry itself is not used)
 constexpr int kCbDD = kCbWB + 16 * 20;        // [256]     the diagonal block on its way into the factorising wave's column layout
 constexpr int kCbED = kCbDD + 256;            // [16]      1 / sqrt(d_i) = W_ii = 1 / L_ii
 constexpr int kCbLdsFloats = kCbED + 16;      // (the failure flag -- first failing pivot + 1 -- is a word of the caller's)
@@ -77,6 +83,7 @@ __device__ __forceinline__ void cb16_wave(float* __restrict__ stage, const int L
   using O = CbOwn<WV>;
   const int c = lane & 15, q = lane >> 4;
   cb_f32x4 accU[kCbNB], accX[kCbNB];
+  float pvq[kCbNB], pvd[kCbNB];                          // lane c: L_ii and 1 / L_ii of row c of the blocks this wave factorised
   // ---- the wave's blocks of the (symmetric) matrix: U_ki = block (k, i), rows / columns >= n an identity, eps on the diagonal
   cb_for<0, kCbNB>([&](auto ii) {
     constexpr int i = decltype(ii)::value;
@@ -122,39 +129,62 @@ __device__ __forceinline__ void cb16_wave(float* __restrict__ stage, const int L
       // forward elimination in place (chol_small3.h's scheme on a 16 x 16 block): entry (i, e) ends as  e < i: W_ie sqrt(d_i),
       // e == i: d_i,  e > i: L_ei sqrt(d_i);  the multiplier of row i for pivot j is p_i by symmetry (lane i of row j).
       // This is the serial part of a step (the other three waves wait at B1): nothing but the pivots' dependent chain and
-      // one readlane + one FMA per remaining row in it; lane c keeps the pivot of ITS row (dmine) for the scaling below
+      // one readlane + one FMA per remaining row in it; lane c keeps the pivot of ITS row (dmine) for the scaling below.
+      // The ORDER of the source matters: written pivot by pivot (readlane, FMA, readlane, FMA, ...) it compiles to that, every
+      // multiplier through one SGPR with the two wait states of a VALU-written SGPR behind each readlane, and the pivot's dependent
+      // chain (readlane d, rcp, two FMAs, multiply, the FMA that makes the next d) with nothing beside it.  So pivot j's chain
+      // is written with the work that does not depend on it in its gaps: the FMAs that pivot j - 1 still owes to rows j + 1 .. 15
+      // and the readlanes of pivot j's own multipliers (row j is final), each into an SGPR of its own (two sets, alternating).
+      // Every entry sees the operations of the plain loop in the plain loop's order: the results are bit for bit the same.
+      CB_S1_STAMP(k, 0);
       float dmine = 1.f;
+      float m[2][16];
+      float d = cb_lane(v[0], 0), qp = 0.f;
       cb_for<0, 16>([&](auto ji) {
         constexpr int j = decltype(ji)::value;
-        const float d = cb_lane(v[j], j);
+        constexpr int P = j & 1, N = P ^ 1, R = 15 - j, NF = j > 0 ? 2 * R : R;      // NF fillers: R FMAs of pivot j - 1, R readlanes
+        auto fill = [&](auto gi) {                      // the fillers of gap g of 4
+          constexpr int g = decltype(gi)::value;
+          cb_for<NF * g / 4, NF * (g + 1) / 4>([&](auto fi) {
+            constexpr int f = decltype(fi)::value;
+            if constexpr (j > 0 && f % 2 == 0) { constexpr int r = j + 1 + f / 2; v[r] = fmaf(m[N][r], qp, v[r]); }
+            else { constexpr int r = j + 1 + (j > 0 ? f / 2 : f); m[P][r] = cb_lane(v[j], r); }
+          });
+        };
         dmine = c == j ? d : dmine;
         float x = __builtin_amdgcn_rcpf(d);
-        x = fmaf(x, fmaf(-d, x, 1.f), x);
+        fill(std::integral_constant<int, 0>{});
+        const float e = fmaf(-d, x, 1.f);
+        fill(std::integral_constant<int, 1>{});
+        x = fmaf(x, e, x);
+        fill(std::integral_constant<int, 2>{});
         const float ndi = -x;
         float qv = v[j] * ndi;
         qv = c == j ? ndi * (1.f + d) : qv;              // column j counts as 1 + d: the inverse's entry restarts as the multiplier
-        cb_for<j + 1, 16>([&](auto ri) {
-          constexpr int r = decltype(ri)::value;
-          const float m = cb_lane(v[j], r);
-          v[r] = fmaf(m, qv, v[r]);
-        });
+        fill(std::integral_constant<int, 3>{});
+        if constexpr (j < 15) {
+          v[j + 1] = fmaf(m[P][j + 1], qv, v[j + 1]);
+          d = cb_lane(v[j + 1], j + 1);
+        }
+        qp = qv;
       });
-      // 1 / sqrt(d) per lane (its own row's pivot), rows scaled by their pivot's: E[i][c] = entry (i, c) / sqrt(d_i) -- W below the
-      // diagonal, L_kk^T above it; the readers mask the triangle they want and take the diagonals from ED = 1 / sqrt(d)
+      CB_S1_STAMP(k, 1);
+      // 1 / sqrt(d) per lane (its own row's pivot) -> ED; E[i][c] = entry (i, c) / sqrt(d_i) is W below the diagonal and L_kk^T
+      // above it: the readers scale, mask the triangle they want and take the diagonals from ED = 1 / sqrt(d)
       float rsm = __builtin_amdgcn_rsqf(dmine);
       rsm = rsm * fmaf(-0.5f * dmine * rsm, rsm, 1.5f);
       const bool good = dmine > 0.f;                     // (NaN: false)
+      if (lane < 16) ED[c] = rsm;
+      pvq[k] = dmine * rsm; pvd[k] = rsm;                // (to sq / sd behind the chain)
+      // the block goes out as it stands, a column per lane (four b128 stores of sixteen lanes): WB[c][i] = entry (i, c); the
+      // readers scale by ED -- the same multiplication, done by the lane that uses the product
       if (lane < 16) {
-        ED[c] = rsm;
-        if (16 * k + c < n) { sq[16 * k + c] = (double)(dmine * rsm); sd[16 * k + c] = (double)rsm; }
-      }
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const float ri = cb_lane(rsm, i);
-        if (lane < 16) WB[i * 20 + c] = v[i] * ri;
+        for (int g = 0; g < 4; ++g) *reinterpret_cast<float4*>(&WB[c * 20 + 4 * g]) = make_float4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
       }
       const unsigned long long okm = __ballot(good || lane >= 16);
       if (okm != ~0ull && lane == 0) flag[0] = 16 * k + (int)__builtin_ctzll(~okm) + 1;      // first failing pivot + 1
+      CB_S1_STAMP(k, 2);
     }
     cb_barrier();                                        // B1: W (and a failure) is out
     fail = flag[0];
@@ -162,9 +192,13 @@ __device__ __forceinline__ void cb16_wave(float* __restrict__ stage, const int L
     CB_STAMP(k, 1);
     // ---- S2: panel R_ki = W U_ki (dumped for everybody), block row k of the inverse T_kj = W X_kj ---------------------------------
     // A fragment of W: row c, k = 4 q .. 4 q + 3 (lower triangle of E, 1 / sqrt(d) on the diagonal)
-    float4 wf = *reinterpret_cast<const float4*>(&WB[c * 20 + 4 * q]);
+    const float dg = ED[c];
+    float4 wf = make_float4(WB[(4 * q) * 20 + c], WB[(4 * q + 1) * 20 + c], WB[(4 * q + 2) * 20 + c], WB[(4 * q + 3) * 20 + c]);
+    wf = make_float4(wf.x * dg, wf.y * dg, wf.z * dg, wf.w * dg);
+    const float4 eq = *reinterpret_cast<const float4*>(&WB[c * 20 + 4 * q]);      // entries (4 q + r, c), for the diagonal block's places
+    const float4 dq = *reinterpret_cast<const float4*>(&ED[4 * q]);
+    const float ekk[4] = {eq.x * dq.x, eq.y * dq.y, eq.z * dq.z, eq.w * dq.w}, dkk[4] = {dq.x, dq.y, dq.z, dq.w};
     {
-      const float dg = ED[c];
       const int k0 = 4 * q;
       wf.x = k0 < c ? wf.x : (k0 == c ? dg : 0.f);
       wf.y = k0 + 1 < c ? wf.y : (k0 + 1 == c ? dg : 0.f);
@@ -184,7 +218,7 @@ __device__ __forceinline__ void cb16_wave(float* __restrict__ stage, const int L
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = 4 * q + r;
-        const float e = WB[i * 20 + c];
+        const float e = ekk[r];
         accU[O::ui(k, k)][r] = c > i ? e : 0.f;          // (the diagonal L_ii leaves through sq)
       }
     }
@@ -200,8 +234,8 @@ __device__ __forceinline__ void cb16_wave(float* __restrict__ stage, const int L
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = 4 * q + r;
-        const float e = WB[i * 20 + c];
-        accX[O::xi(k, k)][r] = c < i ? e : (c == i ? ED[i] : 0.f);
+        const float e = ekk[r], di = dkk[r];
+        accX[O::xi(k, k)][r] = c < i ? e : (c == i ? di : 0.f);
       }
     }
     cb_barrier();                                        // B2: the panel blocks are out
@@ -234,7 +268,13 @@ __device__ __forceinline__ void cb16_wave(float* __restrict__ stage, const int L
   CB_STAMP(7, 0);
   cb_barrier();                                          // the exchange areas are dead
   if (fail) return;
-  float* const mine = dump + lane;                       // where the entries that do not exist go (64 floats nobody reads)
+  cb_for<0, kCbNB>([&](auto kk) {                        // the pivots, off the chain: fp64 conversions and stores once, beside the result stores
+    constexpr int k = decltype(kk)::value;
+    if constexpr (cb_owner(k) == WV) {
+      if (k < nblk && lane < 16 && 16 * k + c < n) { sq[16 * k + c] = (double)pvq[k]; sd[16 * k + c] = (double)pvd[k]; }
+    }
+  });
+  float* const mine = dump + lane;                      // where the entries that do not exist go (64 floats nobody reads)
   // ---- the factors into `stage`: L below the diagonal (R_ki[4 q + r][c] = L[16 i + c][16 k + 4 q + r]), T transposed above it
   //      (T_ij[4 q + r][c] = T[16 i + 4 q + r][16 j + c] -> stage[16 j + c][16 i + 4 q + r])
   cb_for<0, kCbNB>([&](auto ii) {
